@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- fp64 supernodal Cholesky factorisation throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--case lapl_3375x3375]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--case lapl_3375x3375] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one numeric factorisation (the level loop of mmat.rg:1227-1355) of the workload, on an
@@ -16,6 +16,12 @@ rank factors the top levels -- one C-ABI call per rank and step (cholamd_factor_
 `--gpus N` without a launcher (WORLD_SIZE unset) starts the N rank processes itself, as children,
 before anything touches the GPU; a world size that differs from --gpus is an error, never a silent
 single-GPU run.
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the headline line
+(metric, value, unit, ms_per_step, dtype, config).  --full adds what is measured beside the metric: the
+cross-step identity check of the factors, one solve (fp64) or the iterative refinement (mixed),
+independent factorisations in flight, the sustained rate, the dominant-kernel roofline (a HIP-event
+pass of its own), the CPU baseline (the oracle) and, for the metric's configuration, the large fronts.
 
 Prints ONE JSON line (rank 0).
 """
@@ -44,6 +50,8 @@ PROFILE_ROUND = "r4" if os.path.exists(os.path.join(ROOT, "profiles", "r4", "sum
 PROFILE_SUMMARY = os.path.join(ROOT, "profiles", PROFILE_ROUND, "summary.json")  # scripts/profile_summary.py over the rocprofv3 passes of this command
 # the large-front regime reported beside the metric in the default single-GPU run: key -> (N, levels, tile, mixed)
 LARGE_FRONT = (("gen_60_8", (60, 8, 64, False)), ("gen_100_10", (100, 10, 64, False)), ("gen_100_10_mixed", (100, 10, 64, True)))
+DUMP_BYTES = 64_000_000  # --dump-outputs: at most this much in all
+DUMP_SAMPLE = 4 << 20    # arena entries in the seeded sample of a factor too large to write whole
 
 
 def stored_rows(plan, r, c, rows):
@@ -214,6 +222,27 @@ def large_front(ca, torch, stream, specs=LARGE_FRONT, steps=2, warmup=1):
     return out
 
 
+def dump_outputs(out_dir, plan, arena, mixed):
+    """--dump-outputs: the factor the last timed step left in its arena, as its caller receives it, in out_dir/*.npy (float64; float32 for
+    the fp32 factor).  L.npy = the lower triangle of L (P A P^T = L L^T) row by row, through plan.arena_to_dense, when it fits in
+    DUMP_BYTES (the fixtures: 45.6 MB at n = 3375); otherwise (generated problems, GB arenas) arena_sample.npy = the arena's entries at
+    DUMP_SAMPLE positions drawn with a fixed seed, in increasing order.  fill clears the whole arena first, so every entry is defined."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    dt = np.float32 if mixed else np.float64
+    n = plan.n
+    if n * (n + 1) // 2 * np.dtype(dt).itemsize <= DUMP_BYTES:
+        L = plan.arena_to_dense(arena.cpu().numpy())
+        np.save(os.path.join(out_dir, "L.npy"), L[np.tril_indices(n)].astype(dt))
+    else:
+        size = arena.numel()
+        idx = np.unique(np.random.default_rng(0).integers(0, size, size=min(DUMP_SAMPLE, size), dtype=np.int64))
+        vals = arena[torch.from_numpy(idx).to(arena.device)].cpu().numpy()
+        np.save(os.path.join(out_dir, "arena_sample.npy"), vals.astype(dt))
+
+
 def launch_ranks(n):
     """--gpus n without a launcher: start n fresh rank processes (torch.distributed.run, one per GPU) as children of
     this process, which has not touched the GPU, and return their exit code."""
@@ -235,18 +264,26 @@ def main():
                     help="a reference fixture (default: the metric's configuration) or gen:N:levels[:tile] = a generated N^3 7-point "
                          "Laplacian with geometric nested dissection (e.g. gen:100:10, BASELINE config 5's matrix; no cpu_baseline)")
     ap.add_argument("--precision", default="fp64", choices=["fp64", "mixed"],
-                    help="mixed = fp32 factor (the timed step) + fp64 iterative refinement of one solve (reported in config), BASELINE config 5")
+                    help="mixed = fp32 factor (the timed step) + fp64 iterative refinement of one solve (reported in config with --full), BASELINE config 5")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="cholamd_device_set_option switch for this run (e.g. program=0: level-by-level launches), repeatable; recorded in config")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what is reported beside the metric (see the module docstring); off: the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the factor of the last one to DIR/*.npy (one GPU; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
     ap.add_argument("--rank-arenas", type=int, default=0, help="--gpus N > 1: 1 = every rank's arenas by cholamd_device_alloc_arena (memory only under the rank's own "
                                                                "panels and the shared top: 7.5 of 34.8 GB per rank at 100^3 / world 8); default 0 = plain allocations "
                                                                "(no box with two GPUs has run the VMM arenas under RCCL yet: the driver's multi-GPU run keeps the plain ones)")
-    ap.add_argument("--large-front", type=int, default=None, help="1: add the `large_front` object (60^3 fp64, 100^3 fp64 + mixed on this GPU) to the line; "
+    ap.add_argument("--large-front", type=int, default=None, help="--full, 1: add the `large_front` object (60^3 fp64, 100^3 fp64 + mixed on this GPU) to the line; "
                                                                    "default: on for the metric's own configuration (no --case / --precision / --option, one GPU), else off")
-    ap.add_argument("--sustained", type=int, default=2000, help="extra figure beside the metric: the same step for this many factorisations (0 = skip)")
-    ap.add_argument("--in-flight", type=int, default=4, help="extra figure (not the metric): independent factorisations kept this many at a time on device objects / streams of their own; 0 or 1 = skip")
+    ap.add_argument("--sustained", type=int, default=2000, help="--full: extra figure beside the metric: the same step for this many factorisations (0 = skip)")
+    ap.add_argument("--in-flight", type=int, default=4, help="--full: extra figure (not the metric): independent factorisations kept this many at a time on device objects / streams of their own; 0 or 1 = skip")
     args = ap.parse_args()
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be at least 1")
+    if args.dump_outputs and args.gpus > 1:
+        sys.exit("bench.py: --dump-outputs writes the factor of one GPU's run; every rank of a sharded run holds only its part of it")
     if args.large_front is None:
         args.large_front = int(args.case is None and args.gpus == 1 and args.precision == "fp64" and not args.option)
     if args.case is None:
@@ -375,10 +412,6 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     info = dev.info()  # raises on a negative (internal) code: no line is printed for a failed factorisation
-    # every factorisation of the timed region factored the same matrix: the arenas must be bit-identical (a stalled or corrupted launch in the
-    # middle of the run would otherwise go unseen: info is the last launch's)
-    if world == 1 and K <= n_arenas and not all(bool(torch.equal(arenas[(done + i) % n_arenas], arenas[done % n_arenas])) for i in range(1, K)):
-        sys.exit("bench.py: the factors of the timed steps differ from each other (a launch failed or is not deterministic)")
     if world > 1:
         bad = torch.tensor([1.0 if info[0] != 0 else 0.0], device="cuda")
         dist.all_reduce(bad, op=dist.ReduceOp.MAX)
@@ -386,13 +419,42 @@ def main():
             sys.exit(f"bench.py: factorisation failed on some rank (rank {rank}: info {info})")
     elif info[0] != 0:
         sys.exit(f"bench.py: factorisation failed: info {info}")
+    last = arenas[(done + K - 1) % n_arenas] if K <= n_arenas else arenas[(K - 1) % n_arenas]  # the arena of the last timed step
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, plan, last, mixed)
+    rccl_ranks = comm.count() if comm is not None else None
+    xvol, eb_x = dev.exchange_volume(), (4 if mixed else 8)
+    rec = {
+        "world": world, "steps": K, "warmup": W, "dt_s": dt, "case": args.case, "generated": generated, "mixed": mixed,
+        "options": args.option + (["rank_arenas=1"] if rank_arenas else []), "info": list(info),
+        "plan": {"n": plan.n, "levels": plan.levels, "nsep": plan.nsep, "flops": plan.flops, "alg_bytes": plan.alg_bytes},
+        "workload": (f"generated {gn}^3 7-point Laplacian, geometric nested dissection ({glv} levels, tile {gtile}), cholamd_generate_laplacian" if generated else
+                     f"tests/{args.case} (reference fixture: 7-point Laplacian, nested-dissection ordering from the fixture files)"),
+        "data": "synthetic (generated Laplacian, ordering and clusters)" if generated else "reference fixture (matrix, ordering and cluster files from the reference's tests/, copied as data); no random data anywhere",
+        "rccl_ranks": rccl_ranks,
+        "exchange": (None if world == 1 else
+                     f"owner-directed exchange of the arena tail: {xvol[3]} column blocks, grouped ncclSend / ncclRecv to their owners + rank-ordered sum "
+                     f"(rank 0 receives {xvol[0] * eb_x / 1e6:.2f} MB, sends {xvol[1] * eb_x / 1e6:.2f} MB of a {xvol[2] * eb_x / 1e6:.2f} MB tail)" if xvol[3] > 0 else
+                     f"one in-place ncclAllReduce of the {xvol[2] * eb_x / 1e6:.2f} MB arena tail (top levels replicated)"),
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(benchline.headline(rec)))
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # every factorisation of the timed region factored the same matrix: the arenas must be bit-identical (a stalled or corrupted launch in the
+    # middle of the run would otherwise go unseen: info is the last launch's)
+    if world == 1 and K <= n_arenas and not all(bool(torch.equal(arenas[(done + i) % n_arenas], arenas[done % n_arenas])) for i in range(1, K)):
+        sys.exit("bench.py: the factors of the timed steps differ from each other (a launch failed or is not deterministic)")
 
     # dominant-kernel roofline: HIP events recorded by the library around every launch, on the
     # stream the kernels run on, in a separate pass over pre-filled arenas
     refine = None
     if mixed and world > 1:  # the other half of the configuration, distributed like the factorisation: the fp32 factor stays on the ranks, every rank
         # sweeps its own subtrees and solves the shared top redundantly, only vectors travel (cholamd_solve_refine_sharded; no gather to rank 0)
-        last = arenas[(done + K - 1) % n_arenas] if K <= n_arenas else arenas[(K - 1) % n_arenas]
         if generated:
             bvec = torch.from_numpy(ca.Problem(gn, gn, gn, glv, gtile).rhs()).cuda()
         else:
@@ -411,10 +473,10 @@ def main():
         else:
             bvec = torch.from_numpy(ca.plan.read_vector(os.path.join(os.path.dirname(files[0]), f"B_{plan.n}x1.mtx"), plan.n)).cuda()
         xvec = torch.empty_like(bvec)
-        dev.solve_refine(arenas[(done + K - 1) % n_arenas] if K <= n_arenas else arenas[(K - 1) % n_arenas], bvec, xvec, 30, 1e-11, stream)  # warm-up (work lists, CSR upload)
+        dev.solve_refine(last, bvec, xvec, 30, 1e-11, stream)  # warm-up (work lists, CSR upload)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        it, rel = dev.solve_refine(arenas[(done + K - 1) % n_arenas] if K <= n_arenas else arenas[(K - 1) % n_arenas], bvec, xvec, 30, 1e-11, stream)
+        it, rel = dev.solve_refine(last, bvec, xvec, 30, 1e-11, stream)
         torch.cuda.synchronize()
         refine = {"corrections": it, "relres": rel, "ms": round((time.perf_counter() - t0) * 1e3, 3), "tol": 1e-11}
     solve = None
@@ -424,7 +486,6 @@ def main():
         else:
             bvec = torch.from_numpy(ca.plan.read_vector(os.path.join(os.path.dirname(files[0]), f"B_{plan.n}x1.mtx"), plan.n)).cuda()
         xvec = torch.empty_like(bvec)
-        last = arenas[(done + K - 1) % n_arenas] if K <= n_arenas else arenas[(K - 1) % n_arenas]
         dev.solve(last, bvec, xvec, stream)  # warm-up (work lists)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -495,8 +556,6 @@ def main():
     timing = dev.get_timing_ex()
     dev.set_timing(0)
     ev_ms = dev.event_overhead_ms(stream)  # what an empty (record, record) pair reads on this stream
-    rccl_ranks = comm.count() if comm is not None else None
-    xvol, eb_x = dev.exchange_volume(), (4 if mixed else 8)
     timing_all = [timing]
     if world > 1:
         timing_all = [None] * world
@@ -507,27 +566,16 @@ def main():
         blocks = plan.blocks
         sizes = {int(b[1]): int(b[4] - b[2] + 1) for b in blocks if b[0] == b[1]}
         kernel0 = benchline.kernel_names(mixed, generated, all(t["trsm"][1] == 0 for t in timing_all))[benchline.dominant(timing_all)[0]].split(" + ")[0]
-        rec = {
-            "world": world, "steps": K, "warmup": W, "dt_s": dt, "case": args.case, "generated": generated, "mixed": mixed,
-            "options": args.option + (["rank_arenas=1"] if rank_arenas else []), "info": list(info),
-            "plan": {"n": plan.n, "levels": plan.levels, "nsep": plan.nsep, "flops": plan.flops, "alg_bytes": plan.alg_bytes,
-                     "flops_by_kind": {"potrf": float(flops[0]), "trsm": float(flops[1]), "update": float(flops[2] + flops[3])},
-                     "piv_entries": sum(n * (n + 1) // 2 for n in sizes.values()),
-                     "anc_entries": sum(stored_rows(plan, int(b[0]), int(b[1]), int(b[4] - b[2] + 1)) * sizes[int(b[1])] for b in blocks if b[0] != b[1])},
-            "workload": (f"generated {gn}^3 7-point Laplacian, geometric nested dissection ({glv} levels, tile {gtile}), cholamd_generate_laplacian" if generated else
-                         f"tests/{args.case} (reference fixture: 7-point Laplacian, nested-dissection ordering from the fixture files)"),
-            "data": "synthetic (generated Laplacian, ordering and clusters)" if generated else "reference fixture (matrix, ordering and cluster files from the reference's tests/, copied as data); no random data anywhere",
+        rec["plan"].update({"flops_by_kind": {"potrf": float(flops[0]), "trsm": float(flops[1]), "update": float(flops[2] + flops[3])},
+                            "piv_entries": sum(n * (n + 1) // 2 for n in sizes.values()),
+                            "anc_entries": sum(stored_rows(plan, int(b[0]), int(b[1]), int(b[4] - b[2] + 1)) * sizes[int(b[1])] for b in blocks if b[0] != b[1])})
+        rec.update({
             "timing": [{k: list(v) for k, v in t.items()} for t in timing_all], "reps": reps, "event_pair_ms": ev_ms,
-            "rccl_ranks": rccl_ranks,
-            "exchange": (None if world == 1 else
-                         f"owner-directed exchange of the arena tail: {xvol[3]} column blocks, grouped ncclSend / ncclRecv to their owners + rank-ordered sum "
-                         f"(rank 0 receives {xvol[0] * eb_x / 1e6:.2f} MB, sends {xvol[1] * eb_x / 1e6:.2f} MB of a {xvol[2] * eb_x / 1e6:.2f} MB tail)" if xvol[3] > 0 else
-                         f"one in-place ncclAllReduce of the {xvol[2] * eb_x / 1e6:.2f} MB arena tail (top levels replicated)"),
             "profile": profile_numbers(kernel0, args.case, mixed, args.option) if world == 1 else {},
             "refinement": refine, "solve": solve, "concurrent": concurrent, "sustained": sustained,
             "fp64_mfma_sustained_measured": SUSTAINED_FP64_MFMA_TFLOPS,
             "fp64_mfma_sustained_note": SUSTAINED_NOTE,
-        }
+        })
         if not args.no_cpu_baseline and not generated:  # rank 0's host, at every world size
             rec["cpu_baseline"] = cpu_baseline(files, plan.flops)
         if args.large_front and world == 1:

@@ -84,6 +84,31 @@ def large_front_entry(rec):
     return out
 
 
+def headline(rec):
+    """The line of a plain bench.py run (no --full): the metric and the configuration it was measured in.  Needs of the record
+    world, steps, warmup, dt_s, mixed, plan = {n, levels, nsep, flops, alg_bytes}, workload, data, options, info, rccl_ranks, exchange;
+    assemble() adds the rest of a --full run's line to it."""
+    world, K, W, dt = int(rec["world"]), int(rec["steps"]), int(rec["warmup"]), float(rec["dt_s"])
+    plan, mixed = rec["plan"], bool(rec.get("mixed"))
+    if world > 1:
+        par = (f"subtree-sharded x{world}: levels below tree level log2({world}) per rank, {rec.get('exchange', 'RCCL exchange of the arena tail')}, "
+               "then the top levels (replicated, or distributed by column blocks with ncclBroadcast: option dist_top)")
+    else:
+        par = "single GPU"
+    value = float(plan["flops"]) * K / dt * 1e-9
+    return {
+        "metric": "fp64 factorization GF/s (numeric level loop, F_ref flops) on 3-D Laplacian" if not mixed else
+                  "fp32 factorization GF/s (numeric level loop, F_ref flops) on 3-D Laplacian; solution refined to fp64 accuracy",
+        "value": round(value, 3), "unit": "GF/s", "n_gpus": world, "steps": K, "warmup": W,
+        "ms_per_step": round(dt / K * 1e3, 5), "higher_is_better": True,
+        "scaling": "strong", "vs_baseline": None, "dtype": "f32 factor + f64 iterative refinement" if mixed else "f64",
+        "data": rec["data"],
+        "config": {"workload": rec["workload"], "n": plan["n"], "levels": plan["levels"], "separators": plan["nsep"], "F_ref_flops": plan["flops"],
+                   "B_alg_bytes": plan["alg_bytes"], "parallelism": par, "rccl_ranks": rec.get("rccl_ranks"),
+                   "precision": "mixed" if mixed else "fp64", "options": list(rec.get("options", [])), "factor_info": list(rec.get("info", (0, 0)))},
+    }
+
+
 def assemble(rec):
     world, K, W, dt = int(rec["world"]), int(rec["steps"]), int(rec["warmup"]), float(rec["dt_s"])
     plan, timing, reps = rec["plan"], rec["timing"], max(int(rec["reps"]), 1)
@@ -125,46 +150,33 @@ def assemble(rec):
     if world > 1:
         traffic, traffic_note = None, ("no counter pass exists for an N-GPU run (rocprofv3 --pmc is collected on the 1-GPU box; the driver "
                                        "owns the multi-GPU node): HBM bytes per launch are reported for n_gpus = 1 only")
-        par = (f"subtree-sharded x{world}: levels below tree level log2({world}) per rank, {rec.get('exchange', 'RCCL exchange of the arena tail')}, "
-               "then the top levels (replicated, or distributed by column blocks with ncclBroadcast: option dist_top)")
     else:
         traffic = prof.get("hbm_bytes_per_launch")
         traffic_note = ("HBM bytes per launch of that kernel, (2*FETCH_SIZE + WRITE_SIZE)*1024 from the committed rocprofv3 --pmc passes of this command ("
                         + prof.get("source", "no profile committed for this case") + "); to compare with alg_bytes_per_launch")
-        par = "single GPU"
-    out = {
-        "metric": "fp64 factorization GF/s (numeric level loop, F_ref flops) on 3-D Laplacian" if not mixed else
-                  "fp32 factorization GF/s (numeric level loop, F_ref flops) on 3-D Laplacian; solution refined to fp64 accuracy",
-        "value": round(value, 3), "unit": "GF/s", "n_gpus": world, "steps": K, "warmup": W,
-        "ms_per_step": round(dt / K * 1e3, 5), "higher_is_better": True,
-        "scaling": "strong", "vs_baseline": None, "dtype": "f32 factor + f64 iterative refinement" if mixed else "f64",
-        "data": rec["data"],
-        "config": {"workload": rec["workload"], "n": plan["n"], "levels": plan["levels"], "separators": plan["nsep"], "F_ref_flops": plan["flops"],
-                   "B_alg_bytes": plan["alg_bytes"], "parallelism": par, "rccl_ranks": rec.get("rccl_ranks"),
-                   "precision": "mixed" if mixed else "fp64", "options": list(rec.get("options", [])), "factor_info": list(rec.get("info", (0, 0)))},
-        "roofline": {"bound": "mfma", "kernel": names[dom], "achieved": round(achieved, 5),
-                     "peak": peak, "unit": "TFLOP/s", "frac": round(achieved / peak, 6),
-                     "peak_note": f"{world} x {peak1} TFLOP/s" if world > 1 else None,
-                     "traffic": traffic, "traffic_note": traffic_note,
-                     "alg_bytes_per_launch": plan["alg_bytes"] / max(launches_per_step, 1e-9),
-                     "alg_bytes_note": "SURVEY 8(d): B_alg = 8 (nnz(tril A) + nnz(L)) per factorisation / launches of the kernel per factorisation; dense_panel_bytes_per_launch = what the stored panels (row-compacted; the structural zeros inside the kept tiles included) make those launches move",
-                     "dense_panel_bytes_per_launch": (panel_bytes[dom] / max(launches_per_step, 1e-9)) if panel_bytes[dom] else None,
-                     "avg_launch_us": round(avg_s * 1e6, 2), "avg_launch_us_events_raw": round(avg_s_raw * 1e6, 2), "event_pair_overhead_us": round(ev_ms * 1e3, 2),
-                     "slowest_rank": dom_rank,
-                     "avg_launch_us_rocprof": prof.get("avg_launch_us") if world == 1 else None,
-                     "mfma_busy_frac_rocprof": prof.get("mfma_busy_frac") if world == 1 else None,
-                     "launches_per_step": launches_per_step,
-                     "alg_flops_per_launch": flops_per_launch,
-                     "exchange_ms": round(exchange_ms, 5) if world > 1 else None,
-                     "bcast_ms": round(bcast_ms, 5) if world > 1 else None,
-                     "exchange_note": ("HIP events on the launch stream around the RCCL extend-add exchange (reduce of the arena tail) and around the grouped "
-                                       "ncclBroadcasts of the distributed top levels; per step, max over ranks (a rank that arrives early waits inside the collective)") if world > 1 else None,
-                     "whole_step_frac_of_peak": round(value * 1e-3 / peak, 6),
-                     "whole_step_alg_GBs": round(plan["alg_bytes"] * K / dt * 1e-9, 3), "hbm_peak_GBs": PEAK_HBM_GBS * world,
-                     "kernel_ms_per_step_events_raw": {k: round(per_step_max(k), 5) for k in KINDS},
-                     "launch_structure": "one program launch per factorisation (resident workgroups, job queue, followers)" if program else
-                                         "per level and column-block step: fused POTRF+TRSM launch + update launch(es)"},
-    }
+    out = headline(rec)
+    out["roofline"] = {"bound": "mfma", "kernel": names[dom], "achieved": round(achieved, 5),
+                       "peak": peak, "unit": "TFLOP/s", "frac": round(achieved / peak, 6),
+                       "peak_note": f"{world} x {peak1} TFLOP/s" if world > 1 else None,
+                       "traffic": traffic, "traffic_note": traffic_note,
+                       "alg_bytes_per_launch": plan["alg_bytes"] / max(launches_per_step, 1e-9),
+                       "alg_bytes_note": "SURVEY 8(d): B_alg = 8 (nnz(tril A) + nnz(L)) per factorisation / launches of the kernel per factorisation; dense_panel_bytes_per_launch = what the stored panels (row-compacted; the structural zeros inside the kept tiles included) make those launches move",
+                       "dense_panel_bytes_per_launch": (panel_bytes[dom] / max(launches_per_step, 1e-9)) if panel_bytes[dom] else None,
+                       "avg_launch_us": round(avg_s * 1e6, 2), "avg_launch_us_events_raw": round(avg_s_raw * 1e6, 2), "event_pair_overhead_us": round(ev_ms * 1e3, 2),
+                       "slowest_rank": dom_rank,
+                       "avg_launch_us_rocprof": prof.get("avg_launch_us") if world == 1 else None,
+                       "mfma_busy_frac_rocprof": prof.get("mfma_busy_frac") if world == 1 else None,
+                       "launches_per_step": launches_per_step,
+                       "alg_flops_per_launch": flops_per_launch,
+                       "exchange_ms": round(exchange_ms, 5) if world > 1 else None,
+                       "bcast_ms": round(bcast_ms, 5) if world > 1 else None,
+                       "exchange_note": ("HIP events on the launch stream around the RCCL extend-add exchange (reduce of the arena tail) and around the grouped "
+                                         "ncclBroadcasts of the distributed top levels; per step, max over ranks (a rank that arrives early waits inside the collective)") if world > 1 else None,
+                       "whole_step_frac_of_peak": round(value * 1e-3 / peak, 6),
+                       "whole_step_alg_GBs": round(plan["alg_bytes"] * K / dt * 1e-9, 3), "hbm_peak_GBs": PEAK_HBM_GBS * world,
+                       "kernel_ms_per_step_events_raw": {k: round(per_step_max(k), 5) for k in KINDS},
+                       "launch_structure": "one program launch per factorisation (resident workgroups, job queue, followers)" if program else
+                                           "per level and column-block step: fused POTRF+TRSM launch + update launch(es)"}
     for key in ("fp64_mfma_sustained_measured", "fp64_mfma_sustained_note"):
         if rec.get(key) is not None and not mixed:
             out["roofline"][key] = rec[key]

@@ -32,6 +32,39 @@ def case_paths(case):
     return os.path.join(d, m), os.path.join(d, o), os.path.join(d, c), os.path.join(d, b)
 
 
+# what the reference's own mmio.c (compiled into oracle/_ref) reads from every fixture's matrix and right-hand side:
+# {path under tests/golden: [mm_read_banner rc, typecode, mm_read_mtx_crd_size rc, M, N, NZ]} (tests/golden/make_golden.py)
+MMIO_GOLDEN = os.path.join(GOLDEN, "mmio_ref.json")
+
+
+def mm_read(lib, path):
+    """(mm_read_banner rc, typecode, mm_read_mtx_crd_size rc, M, N, NZ) of a Matrix-Market file through `lib`'s mmio entry
+    points; the size line is read for coordinate files only."""
+    import ctypes as C
+
+    libc = C.CDLL(None)
+    libc.fopen.restype = C.c_void_p
+    libc.fopen.argtypes = [C.c_char_p, C.c_char_p]
+    libc.fclose.argtypes = [C.c_void_p]
+    lib.mm_read_banner.argtypes = [C.c_void_p, C.c_char_p]
+    lib.mm_read_mtx_crd_size.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 3
+    fp = libc.fopen(path.encode(), b"r")
+    assert fp, path
+    tc = C.create_string_buffer(4)
+    rc = lib.mm_read_banner(fp, tc)
+    M, N, NZ = C.c_int(), C.c_int(), C.c_int()
+    rc2 = lib.mm_read_mtx_crd_size(fp, C.byref(M), C.byref(N), C.byref(NZ)) if tc.raw[1:2] == b"C" else 0
+    libc.fclose(fp)
+    return (rc, tc.raw.decode("latin-1"), rc2, M.value, N.value, NZ.value)
+
+
+def mmio_golden():
+    import json
+
+    with open(MMIO_GOLDEN) as f:
+        return {os.path.join(GOLDEN, k): tuple(v) for k, v in json.load(f).items()}
+
+
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
 

@@ -3,13 +3,16 @@
 
 Run ONLY in the authoring container, where /root/reference exists:
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py          # golden.npz of every fixture, then mmio_ref.json
+    python tests/golden/make_golden.py mmio     # mmio_ref.json only
 
 For every fixture of the reference's test-suite (test_matrices.py:51-142) it calls
   * verify.permute_matrix (verify.py:127-213)  -> permuted lower matrix PAP^T
   * scipy.linalg.cholesky(lower=True)          -> L     (what verify.check_matrix compares, verify.py:278-287)
   * scipy.linalg.solve(A, b)                   -> x     (what verify.check_solution compares, verify.py:290-302)
 and stores them as compressed COO / dense vectors in  tests/golden/<case>/golden.npz.
+It also records what the reference's mmio.c (compiled into oracle/_ref) reads from every fixture's
+Matrix-Market files in tests/golden/mmio_ref.json.
 
 Only DATA is written (inputs are the reference's fixture files copied verbatim next to
 this script; outputs are numbers).  No reference source text is copied.
@@ -72,7 +75,34 @@ def main():
         print(f"{case}: n={A.shape[0]} nnz(pmat)={pv.size} nnz(L)={lv.size} "
               f"resid={resid:.2e} -> {out} ({os.path.getsize(out)} bytes)")
     os.chdir(cwd)
+    write_mmio_golden()
+
+
+def write_mmio_golden():
+    """mmio_ref.json: what the reference's own mmio.c (oracle/_ref/libmmio_ref.so, built by `make -C oracle` where the
+    reference tree is present) reads from every fixture's matrix and right-hand side file."""
+    import ctypes
+    import json
+
+    sys.path.insert(0, os.path.dirname(HERE))
+    from conftest import MMIO_GOLDEN, mm_read
+
+    so = os.path.join(os.path.dirname(os.path.dirname(HERE)), "oracle", "_ref", "libmmio_ref.so")
+    if not os.path.exists(so):
+        sys.exit("oracle/_ref/libmmio_ref.so not built; run `make -C oracle` where the reference tree is present")
+    ref = ctypes.CDLL(so)
+    out = {}
+    for case, (mtx, _, _, bfile) in CASES.items():
+        for name in (mtx, bfile):
+            out[f"{case}/{name}"] = list(mm_read(ref, os.path.join(HERE, case, name)))
+    with open(MMIO_GOLDEN, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(f"mmio: {len(out)} files -> {MMIO_GOLDEN}")
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["mmio"]:
+        write_mmio_golden()
+    else:
+        main()

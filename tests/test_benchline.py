@@ -101,3 +101,17 @@ def test_line_carries_large_front():
     assert lf["gen_100_10"]["dtype"] == "f64" and lf["gen_100_10_mixed"]["refinement"]["relres"] < 1e-10
     assert out["value"] == pytest.approx(1.48552e8 / 2.1e-4 * 1e-9, rel=1e-6)  # the metric is untouched
     assert "large_front" not in benchline.assemble(record(1, program=True))
+
+
+@pytest.mark.parametrize("world", [1, 2, 8])
+def test_plain_line_is_the_head_of_the_full_line(world):
+    """A plain bench.py run prints benchline.headline(rec): the metric's keys, exactly as they lead the --full line, and nothing the
+    headline does not need (no roofline, baselines or extra figures)."""
+    rec = record(world)
+    head, full = benchline.headline(rec), benchline.assemble(rec)
+    assert list(full)[:len(head)] == list(head) and all(full[k] == v for k, v in head.items())
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in head
+    assert head["ms_per_step"] == round(rec["dt_s"] / rec["steps"] * 1e3, 5)
+    assert not {"roofline", "cpu_baseline", "sustained", "concurrent", "large_front"} & set(head)
+    json.dumps(head)

@@ -8,7 +8,7 @@ import re
 import numpy as np
 import pytest
 
-from conftest import CASES, KNOWN, ROOT, case_paths
+from conftest import CASES, KNOWN, ROOT, case_paths, mm_read, mmio_golden
 from oracle import oracle as orc
 
 
@@ -196,31 +196,20 @@ def test_ingest_errors_are_reported(tmp_path, ca):
 
 
 def test_mm_reader_matches_reference_build(ca):
-    """The library's mm_read_banner / mm_read_mtx_crd_size agree with the reference's own mmio.c
-    (compiled where it lies into oracle/_ref) on every fixture."""
-    so = os.path.join(ROOT, "oracle", "_ref", "libmmio_ref.so")
-    if not os.path.exists(so):
-        pytest.skip("oracle/_ref not built (reference tree absent)")
+    """The library's mm_read_banner / mm_read_mtx_crd_size agree with the reference's own mmio.c on every fixture: with its
+    results stored in tests/golden/mmio_ref.json, and with the build in oracle/_ref (compiled where the reference lies) when
+    that is present."""
     from cholesky_amd import _lib
-    ref, mine, libc = C.CDLL(so), C.CDLL(_lib.LIB_PATH), C.CDLL(None)
-    libc.fopen.restype = C.c_void_p
-    libc.fopen.argtypes = [C.c_char_p, C.c_char_p]
-    libc.fclose.argtypes = [C.c_void_p]
-    for lib in (ref, mine):
-        lib.mm_read_banner.argtypes = [C.c_void_p, C.c_char_p]
-        lib.mm_read_mtx_crd_size.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 3
-    for case in CASES:
-        for path in (case_paths(case)[0], case_paths(case)[3]):
-            res = []
-            for lib in (ref, mine):
-                fp = libc.fopen(path.encode(), b"r")
-                tc = C.create_string_buffer(4)
-                rc = lib.mm_read_banner(fp, tc)
-                M, N, NZ = C.c_int(), C.c_int(), C.c_int()
-                rc2 = lib.mm_read_mtx_crd_size(fp, C.byref(M), C.byref(N), C.byref(NZ)) if tc.raw[1:2] == b"C" else 0
-                libc.fclose(fp)
-                res.append((rc, tc.raw, rc2, M.value, N.value, NZ.value))
-            assert res[0] == res[1], path
+    libs = [C.CDLL(_lib.LIB_PATH)]
+    so = os.path.join(ROOT, "oracle", "_ref", "libmmio_ref.so")
+    if os.path.exists(so):
+        libs.append(C.CDLL(so))
+    want = mmio_golden()
+    paths = [p for case in CASES for p in (case_paths(case)[0], case_paths(case)[3])]
+    assert sorted(want) == sorted(paths)
+    for path in paths:
+        for lib in libs:
+            assert mm_read(lib, path) == want[path], path
 
 
 def test_partition_work_lists(ca, plans):

@@ -9,7 +9,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import CASES, KNOWN, case_paths
+from conftest import CASES, KNOWN, case_paths, mm_read, mmio_golden
 from oracle import oracle as orc
 
 
@@ -117,31 +117,22 @@ def test_factor_writer_roundtrip(tmp_path, oracles, golden):
 
 
 def test_mmio_reference_build_agrees():
-    """oracle/_ref/libmmio_ref.so is the reference's own mmio.c compiled where it lies; the oracle's
-    banner/size reader must agree with it on every fixture."""
+    """The oracle's banner/size reader agrees with the reference's own mmio.c on every fixture: with its results stored in
+    tests/golden/mmio_ref.json, and with oracle/_ref/libmmio_ref.so (that mmio.c compiled where it lies) when it is present."""
     import ctypes as C
 
     so = os.path.join(os.path.dirname(orc.__file__), "_ref", "libmmio_ref.so")
-    if not os.path.exists(so):
-        pytest.skip("oracle/_ref not built (reference tree absent)")
-    ref = C.CDLL(so)
-    libc = C.CDLL(None)
-    libc.fopen.restype = C.c_void_p
-    libc.fopen.argtypes = [C.c_char_p, C.c_char_p]
-    libc.fclose.argtypes = [C.c_void_p]
-    ref.mm_read_banner.argtypes = [C.c_void_p, C.c_char_p]
-    ref.mm_read_mtx_crd_size.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    ref = C.CDLL(so) if os.path.exists(so) else None
+    want = mmio_golden()
     for case in CASES:
         m, o, c, _ = case_paths(case)
-        fp = libc.fopen(m.encode(), b"r")
-        tc = C.create_string_buffer(4)
-        assert ref.mm_read_banner(fp, tc) == 0
-        M, N, NZ = C.c_int(), C.c_int(), C.c_int()
-        assert ref.mm_read_mtx_crd_size(fp, C.byref(M), C.byref(N), C.byref(NZ)) == 0
-        libc.fclose(fp)
+        if ref is not None:
+            assert mm_read(ref, m) == want[m]
+        rc, tc, rc2, M, N, NZ = want[m]
+        assert rc == 0 and rc2 == 0
         O = orc.Oracle(m, o, c)
-        assert (O.N, O.NZ) == (N.value, NZ.value) and M.value == N.value
-        assert tc.raw == b"MCRH"  # matrix coordinate real hermitian
+        assert (O.N, O.NZ) == (N, NZ) and M == N
+        assert tc == "MCRH"  # matrix coordinate real hermitian
 
 
 def test_level_parallel_oracle_is_bit_identical():
