@@ -151,6 +151,9 @@ def load():
     L.cholamd_solve_f32.argtypes = [vp, vp, vp, vp, vp]
     L.cholamd_solve_refine.argtypes = [vp, vp, vp, vp, ci, cd, C.POINTER(ci), C.POINTER(cd), vp]
     L.cholamd_residual.argtypes = [vp, vp, vp, vp, C.POINTER(cd), vp]
+    L.cholamd_solve_nrhs.argtypes = [vp, vp, vp, i64, vp, i64, ci, vp]
+    L.cholamd_solve_nrhs_f32.argtypes = [vp, vp, vp, i64, vp, i64, ci, vp]
+    L.cholamd_solve_refine_nrhs.argtypes = [vp, vp, vp, i64, vp, i64, ci, ci, cd, C.POINTER(ci), vp, vp]
     L.cholamd_device_alloc_arena.argtypes = [vp, ci, C.POINTER(vp), C.POINTER(C.c_int64)]
     L.cholamd_device_free_arena.argtypes = [vp, vp]
     L.cholamd_device_set_timing.argtypes = [vp, ci]

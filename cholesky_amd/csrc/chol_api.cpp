@@ -93,6 +93,9 @@ struct cholamd_device {
   // switches, read from the environment once at cholamd_device_create (cholamd_device_set_option changes them later)
   chol_sched_opts opt;
   bool solve_reference_shape = false; // cholamd_solve with the per-call (deterministic) kernels of the BLAS-level entry points
+  // block solve (cholamd_solve_nrhs): the permuted block of one chunk (n x CHOL_NRHS_W, row-major); refinement: the chunk's right-hand sides, residual and
+  // correction (n x CHOL_NRHS_W, column-major) and the per-column partial sums of the residual kernel
+  double *ynrhs = nullptr, *bnrhs = nullptr, *rnrhs = nullptr, *dxnrhs = nullptr, *pnrhs = nullptr;
 };
 
 static int no_device_error()
@@ -273,6 +276,7 @@ extern "C" void cholamd_device_destroy(cholamd_device *d)
   (void)hipFree(d->ws32); (void)hipFree(d->csr_ptr); (void)hipFree(d->csr_col); (void)hipFree(d->csr_val); (void)hipFree(d->rvec); (void)hipFree(d->dxvec); (void)hipFree(d->partial);
   (void)hipFree(d->xstage); (void)hipFree(d->xdesc);
   (void)hipFree(d->ws); (void)hipFree(d->ws_solve); (void)hipFree(d->step_flags); (void)hipFree(d->w256); (void)hipFree(d->step_xt); (void)hipFree(d->info); (void)hipFree(d->progress); (void)hipFree(d->a_dst); (void)hipFree(d->a_val); (void)hipFree(d->perm); (void)hipFree(d->ytmp);
+  (void)hipFree(d->ynrhs); (void)hipFree(d->bnrhs); (void)hipFree(d->rnrhs); (void)hipFree(d->dxnrhs); (void)hipFree(d->pnrhs);
   for (int q = 0; q < 2; q++) { (void)hipFree(d->top_dst[q]); (void)hipFree(d->top_val[q]); }
   for (auto &t : d->tl) { d->pool.push_back(t.a); d->pool.push_back(t.b); }
   for (auto e : d->pool) (void)hipEventDestroy(e);
@@ -1004,6 +1008,160 @@ extern "C" int cholamd_solve_refine(cholamd_device *d, const float *d_arena32, c
   if (iters_out) *iters_out = it;
   if (relres_out) *relres_out = rel;
   if (rel != rel) { chol_set_error("iterative refinement produced NaN (fp32 factorisation broke down)"); return CHOLAMD_ERR_ARG; }
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Block solve (not in the reference, whose mmat.rg -b solves one vector): nrhs right-hand sides in chunks of CHOL_NRHS_W columns, each chunk one forward
+// and one backward sweep over the solve lists of the whole tree (chol_solve_nrhs.hip), so the factor is read once per sweep per chunk.
+// ---------------------------------------------------------------------------------------------
+static int lnrhs_trsv(const double *a, const chol_trsv_desc *t, int n, int mx, int mu, const double *W, const double *W256, double *Y, int bw, hipStream_t st) { return chol_nrhs_launch_trsv(a, t, n, mx, mu, W, W256, Y, bw, st); }
+static int lnrhs_trsv(const float *a, const chol_trsv_desc *t, int n, int mx, int mu, const double *W, const double *W256, double *Y, int bw, hipStream_t st) { return chol32_nrhs_launch_trsv(a, t, n, mx, mu, W, W256, Y, bw, st); }
+static int lnrhs_off(const double *a, const chol_gemv_desc *g, const int *it, int n, double *Y, int bw, hipStream_t st) { return chol_nrhs_launch_offdiag(a, g, it, n, Y, bw, st); }
+static int lnrhs_off(const float *a, const chol_gemv_desc *g, const int *it, int n, double *Y, int bw, hipStream_t st) { return chol32_nrhs_launch_offdiag(a, g, it, n, Y, bw, st); }
+static int nrhs_check(cholamd_device *d, const void *arena, const double *B, int64_t ldb, const double *X, int64_t ldx, int nrhs, const char *what)
+{ // 1: nothing to do
+  if (!d) { chol_set_error("%s: NULL device", what); return CHOLAMD_ERR_ARG; }
+  const int n = d->plan->n;
+  if (nrhs < 0) { chol_set_error("%s: nrhs = %d < 0", what, nrhs); return CHOLAMD_ERR_ARG; }
+  if (ldb < n || ldx < n) { chol_set_error("%s: leading dimensions ldb = %lld, ldx = %lld must be at least n = %d", what, (long long)ldb, (long long)ldx, n); return CHOLAMD_ERR_ARG; }
+  if (nrhs == 0) return 1;
+  if (!arena || !B || !X) { chol_set_error("%s: NULL %s", what, !arena ? "arena" : !B ? "B" : "X"); return CHOLAMD_ERR_ARG; }
+  return 0;
+}
+// A chunk's sweeps cost the same for 1 and for 32 columns (the launches of the span chain and the factor's bytes, not the MFMA work, set their time), so a
+// chunk of fewer columns than this is solved column by column with the single-vector path.  Measured on one MI355X: a block chunk
+// takes 3.0 - 3.3 single fp64 solves and 5.0 single fp32-factor solves.
+template <class TL> static constexpr int nrhs_min_block() { return sizeof(TL) == sizeof(double) ? 4 : 6; }
+struct keep_restore { // keep_inverses for the chunks of one call, the caller's value back on every way out
+  cholamd_device *d; bool old;
+  explicit keep_restore(cholamd_device *d_) : d(d_), old(d_->keep_inverses) {}
+  ~keep_restore() { d->keep_inverses = old; }
+};
+template <class TL> static int solve_nrhs_t(cholamd_device *d, const TL *d_arena, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int nrhs, hipStream_t st)
+{
+  { int rc = build_solve(d); if (rc) return rc; }
+  const int L = d->plan->levels, n = d->plan->n;
+  for (int lvl = 0; lvl < L && !d->keep_inverses; lvl++) { // the diagonal inverses once per call, as solve_phase
+    const solve_dev &s = d->sv[lvl];
+    HIPCHK((hipError_t)lsolve_dinv(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, st));
+    if (s.w256_off >= 0 && d->w256) HIPCHK((hipError_t)lsolve_inv256(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, d->w256 + s.w256_off, st));
+  }
+  keep_restore kr(d);
+  d->keep_inverses = true; // (the column-by-column chunks: solve_streamed reuses them)
+  for (int c0 = 0; c0 < nrhs; c0 += CHOL_NRHS_W) {
+    const int cols = std::min(CHOL_NRHS_W, nrhs - c0);
+    if (cols < nrhs_min_block<TL>()) {
+      for (int j = c0; j < c0 + cols; j++) { int rc = solve_streamed(d, d_arena, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, st); if (rc) return rc; }
+      continue;
+    }
+    if (!d->ynrhs) HIPCHK(hipMalloc((void **)&d->ynrhs, (size_t)n * CHOL_NRHS_W * sizeof(double)));
+    double *Y = d->ynrhs;
+    HIPCHK((hipError_t)chol_nrhs_launch_permute(d_B, ldb, d->perm, Y, nullptr, 0, n, c0, cols, 0, st));
+    for (int lvl = L - 1; lvl >= 0; lvl--) { // forward: the separators' triangles, then their panels into the ancestors
+      const solve_dev &s = d->sv[lvl];
+      const double *W256 = s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr;
+      HIPCHK((hipError_t)lnrhs_trsv(d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, W256, Y, 0, st));
+      HIPCHK((hipError_t)lnrhs_off(d_arena, s.bw, s.ifw, s.n_ifw, Y, 0, st));
+    }
+    for (int lvl = 0; lvl < L; lvl++) { // backward: gather from the ancestors, then the transposed triangles
+      const solve_dev &s = d->sv[lvl];
+      const double *W256 = s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr;
+      HIPCHK((hipError_t)lnrhs_off(d_arena, s.bw, s.ibw, s.n_ibw, Y, 1, st));
+      HIPCHK((hipError_t)lnrhs_trsv(d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, W256, Y, 1, st));
+    }
+    HIPCHK((hipError_t)chol_nrhs_launch_permute(nullptr, 0, d->perm, Y, d_X, ldx, n, c0, cols, 1, st));
+  }
+  return 0;
+}
+extern "C" int cholamd_solve_nrhs(cholamd_device *d, const double *d_arena, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int nrhs, void *stream)
+{
+  { int rc = nrhs_check(d, d_arena, d_B, ldb, d_X, ldx, nrhs, "cholamd_solve_nrhs"); if (rc) return rc > 0 ? 0 : rc; }
+  HIPCHK(hipSetDevice(d->dev));
+  if (d->solve_reference_shape) { // the deterministic per-call kernels, column by column
+    for (int j = 0; j < nrhs; j++) { int rc = cholamd_solve(d, d_arena, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, stream); if (rc) return rc; }
+    return 0;
+  }
+  return solve_nrhs_t(d, d_arena, d_B, ldb, d_X, ldx, nrhs, (hipStream_t)stream);
+}
+extern "C" int cholamd_solve_nrhs_f32(cholamd_device *d, const float *d_arena32, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int nrhs, void *stream)
+{
+  { int rc = nrhs_check(d, d_arena32, d_B, ldb, d_X, ldx, nrhs, "cholamd_solve_nrhs_f32"); if (rc) return rc > 0 ? 0 : rc; }
+  HIPCHK(hipSetDevice(d->dev));
+  if (d->solve_reference_shape) {
+    for (int j = 0; j < nrhs; j++) { int rc = cholamd_solve_f32(d, d_arena32, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, stream); if (rc) return rc; }
+    return 0;
+  }
+  return solve_nrhs_t(d, d_arena32, d_B, ldb, d_X, ldx, nrhs, (hipStream_t)stream);
+}
+// one chunk's residuals: R = B - A X (column-major, ld n), rel[j] = ||r_j|| / ||b_j||
+static int residual_nrhs(cholamd_device *d, const double *d_B, int64_t ldb, const double *d_X, int64_t ldx, int cols, double *rel, hipStream_t st)
+{
+  const int n = d->plan->n, nb = (n + 255) / 256;
+  HIPCHK((hipError_t)chol_nrhs_launch_residual(d->csr_ptr, d->csr_col, d->csr_val, d_B, ldb, d_X, ldx, d->rnrhs, n, n, cols, d->pnrhs, st));
+  std::vector<double> h((size_t)2 * nb * cols);
+  HIPCHK(hipMemcpyAsync(h.data(), d->pnrhs, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (int j = 0; j < cols; j++) {
+    double r2 = 0.0, b2 = 0.0;
+    for (int i = 0; i < nb; i++) { r2 += h[2 * ((size_t)j * nb + i)]; b2 += h[2 * ((size_t)j * nb + i) + 1]; }
+    rel[j] = b2 > 0.0 ? std::sqrt(r2 / b2) : std::sqrt(r2);
+  }
+  return 0;
+}
+// M^-1 B for `cols` columns with M = L32 L32^T: the block solve, or column by column under option solve_reference_shape
+static int refine_solve(cholamd_device *d, const float *d_arena32, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int cols, hipStream_t st)
+{
+  if (!d->solve_reference_shape) return solve_nrhs_t(d, d_arena32, d_B, ldb, d_X, ldx, cols, st);
+  for (int j = 0; j < cols; j++) { int rc = solve_streamed(d, d_arena32, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, st); if (rc) return rc; }
+  return 0;
+}
+extern "C" int cholamd_solve_refine_nrhs(cholamd_device *d, const float *d_arena32, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int nrhs, int max_iter,
+                                         double tol, int *iters_out, double *relres_out, void *stream)
+{
+  { int rc = nrhs_check(d, d_arena32, d_B, ldb, d_X, ldx, nrhs, "cholamd_solve_refine_nrhs"); if (rc) { if (rc > 0 && iters_out) *iters_out = 0; return rc > 0 ? 0 : rc; } }
+  HIPCHK(hipSetDevice(d->dev));
+  int rc = ensure_refine(d);
+  if (!rc) rc = build_solve(d);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int n = d->plan->n, nb = (n + 255) / 256;
+  if (!d->bnrhs) HIPCHK(hipMalloc((void **)&d->bnrhs, (size_t)n * CHOL_NRHS_W * sizeof(double)));
+  if (!d->rnrhs) HIPCHK(hipMalloc((void **)&d->rnrhs, (size_t)n * CHOL_NRHS_W * sizeof(double)));
+  if (!d->dxnrhs) HIPCHK(hipMalloc((void **)&d->dxnrhs, (size_t)n * CHOL_NRHS_W * sizeof(double)));
+  if (!d->pnrhs) HIPCHK(hipMalloc((void **)&d->pnrhs, (size_t)2 * nb * CHOL_NRHS_W * sizeof(double)));
+  if (max_iter < 0) max_iter = 0;
+  // chunk by chunk: the chunk's columns of B are copied first (X may be B: in place), x0 = M^-1 b with M = L32 L32^T, then X += M^-1 (B - A X) on ALL the
+  // chunk's columns until every one of them has ||b_j - A x_j|| <= tol ||b_j|| or max_iter corrections have been applied.  The inverses are formed once.
+  keep_inverses_scope keep(&d, 1);
+  d->keep_inverses = false; // (until the first solve has formed them)
+  int it_max = 0;
+  bool nan = false;
+  std::vector<double> rel(CHOL_NRHS_W);
+  int c0 = 0;
+  for (; c0 < nrhs; c0 += CHOL_NRHS_W) {
+    const int cols = std::min(CHOL_NRHS_W, nrhs - c0);
+    double *X = d_X + (int64_t)c0 * ldx;
+    HIPCHK(hipMemcpy2DAsync(d->bnrhs, (size_t)n * sizeof(double), d_B + (int64_t)c0 * ldb, (size_t)ldb * sizeof(double), (size_t)n * sizeof(double), (size_t)cols,
+                            hipMemcpyDeviceToDevice, st));
+    if ((rc = refine_solve(d, d_arena32, d->bnrhs, n, X, ldx, cols, st))) return rc;
+    d->keep_inverses = true;
+    int it = 0;
+    for (;; ++it) {
+      if ((rc = residual_nrhs(d, d->bnrhs, n, X, ldx, cols, rel.data(), st))) return rc;
+      bool done = true;
+      for (int j = 0; j < cols; j++) { if (rel[j] != rel[j]) nan = true; if (rel[j] > tol) done = false; }
+      if (done || nan || it >= max_iter) break;
+      if ((rc = refine_solve(d, d_arena32, d->rnrhs, n, d->dxnrhs, n, cols, st))) return rc;
+      HIPCHK((hipError_t)chol_nrhs_launch_axpy(X, ldx, d->dxnrhs, n, n, cols, st));
+    }
+    if (it > it_max) it_max = it;
+    if (relres_out) for (int j = 0; j < cols; j++) relres_out[c0 + j] = rel[j];
+    if (nan) { c0 += cols; break; }
+  }
+  if (relres_out) for (int j = c0; j < nrhs; j++) relres_out[j] = std::nan(""); // (after a NaN: the chunks not reached)
+  if (iters_out) *iters_out = it_max;
+  if (nan) { chol_set_error("iterative refinement produced NaN (fp32 factorisation broke down)"); return CHOLAMD_ERR_ARG; }
   return 0;
 }
 

@@ -50,6 +50,18 @@ int chol32_launch_solve_trsv(const float *base, const chol_trsv_desc *descs, int
 int chol32_launch_solve_offdiag(const float *base, const chol_gemv_desc *blocks, const int *items, int n_items, double *y, int backward, hipStream_t st);
 int chol_launch_residual(const int64_t *ptr, const int *col, const double *val, const double *b, const double *x, double *r, int n, double *partial, hipStream_t st);
 int chol_launch_axpy1(double *x, const double *dx, int n, hipStream_t st);
+/* block solve (chol_solve_nrhs.hip): right-hand sides in chunks of CHOL_NRHS_W columns in a permuted block Y (n x CHOL_NRHS_W, row-major); W16 / W256 as for
+ * chol_launch_solve_trsv (W256 NULL: the substitution chain of the 16x16 inverses) */
+#define CHOL_NRHS_W 32
+int chol_nrhs_launch_permute(const double *B, int64_t ldb, const int *perm, double *Y, double *X, int64_t ldx, int n, int c0, int cols, int inverse, hipStream_t st);
+int chol_nrhs_launch_trsv(const double *base, const chol_trsv_desc *descs, int n, int max_n, int max_under, const double *W16, const double *W256, double *Y, int backward, hipStream_t st);
+int chol32_nrhs_launch_trsv(const float *base, const chol_trsv_desc *descs, int n, int max_n, int max_under, const double *W16, const double *W256, double *Y, int backward, hipStream_t st);
+int chol_nrhs_launch_offdiag(const double *base, const chol_gemv_desc *blocks, const int *items, int n_items, double *Y, int backward, hipStream_t st);
+int chol32_nrhs_launch_offdiag(const float *base, const chol_gemv_desc *blocks, const int *items, int n_items, double *Y, int backward, hipStream_t st);
+/* R(:, j) = B(:, j) - A X(:, j), j < cols; partial[2 (j * nb + blk) + {0, 1}] = the row block's sum of r^2 / b^2, nb = (n + 255) / 256 */
+int chol_nrhs_launch_residual(const int64_t *ptr, const int *col, const double *val, const double *B, int64_t ldb, const double *X, int64_t ldx, double *R, int64_t ldr,
+                              int n, int cols, double *partial, hipStream_t st);
+int chol_nrhs_launch_axpy(double *X, int64_t ldx, const double *D, int64_t ldd, int n, int cols, hipStream_t st);
 /* diagnostic instance of the program launch (k_program<true>): 4 stamps per job, then CHOL_TRACE_X per job -- [0] follower: own tiles' wait over,
  * [1] its items, [2 + i] round of item i begun; [48 + k] POTRF job: column k published / TRSM job (first strip): column tile k on its channel;
  * [72 + k] POTRF job: the factor wave starts column k / TRSM job: the POTRF's column k seen */

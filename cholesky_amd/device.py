@@ -203,6 +203,45 @@ class Device:
                                                   comm.h if comm is not None else None, _stream_ptr(stream)), "cholamd_solve_refine_sharded")
         return int(it.value), float(rel.value)
 
+    @staticmethod
+    def _block(t, what, n):
+        """(ld, nrhs) of a 2-D column-major float64 CUDA tensor of n rows (stride(0) == 1, ld = stride(1)); ValueError otherwise."""
+        import torch
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or not t.is_cuda or t.dtype != torch.float64:
+            raise ValueError(f"{what} must be a 2-D CUDA float64 tensor, e.g. torch.empty(k, n).T")
+        if t.shape[0] != n:
+            raise ValueError(f"{what} has {t.shape[0]} rows, the system has n = {n}")
+        if t.shape[1] > 0 and t.stride(0) != 1:
+            raise ValueError(f"{what} must be column-major (stride(0) == 1), e.g. torch.empty(k, n).T; got strides {t.stride()}")
+        if t.shape[1] > 1 and t.stride(1) < n:  # overlapping columns (expand, as_strided): the library would read / write k * ld doubles
+            raise ValueError(f"{what} has column stride {t.stride(1)} < n = {n}: its columns overlap")
+        return (int(t.stride(1)) if t.shape[1] > 1 else n), int(t.shape[1])
+
+    def _blocks(self, B, X):
+        ldb, k = self._block(B, "B", self.plan.n)
+        ldx, kx = self._block(X, "X", self.plan.n)
+        if kx != k:
+            raise ValueError(f"B has {k} columns, X has {kx}")
+        return ldb, ldx, k
+
+    def solve_nrhs(self, arena, B, X, stream=None):
+        """X = A^-1 B for the k columns of B (n x k, column-major: stride(0) == 1) in one pass over the factor per 32 columns
+        (cholamd_solve_nrhs / _f32 by the arena's element type); asynchronous on `stream`."""
+        import torch
+        ldb, ldx, k = self._blocks(B, X)
+        f32 = arena.elem_bytes == 4 if isinstance(arena, RankArena) else arena.dtype == torch.float32
+        fn = self.L.cholamd_solve_nrhs_f32 if f32 else self.L.cholamd_solve_nrhs
+        check(fn(self.h, self.ptr(arena), self.ptr(B), ldb, self.ptr(X), ldx, k, _stream_ptr(stream)), "cholamd_solve_nrhs")
+
+    def solve_refine_nrhs(self, arena32, B, X, max_iter=20, tol=1e-12, stream=None):
+        """cholamd_solve_refine_nrhs: every column of X = A^-1 B by iterative refinement on the fp32 factor; returns (corrections applied, relres per column)."""
+        ldb, ldx, k = self._blocks(B, X)
+        it = C.c_int(0)
+        rel = np.zeros(max(k, 1), dtype=np.float64)
+        check(self.L.cholamd_solve_refine_nrhs(self.h, self.ptr(arena32), self.ptr(B), ldb, self.ptr(X), ldx, k, int(max_iter), float(tol),
+                                               C.byref(it), rel.ctypes.data, _stream_ptr(stream)), "cholamd_solve_refine_nrhs")
+        return int(it.value), rel[:k]
+
     def residual(self, b, x, r=None, stream=None):
         """||b - A x|| / ||b|| in fp64 on the device (A = the matrix file's entries)."""
         rel = C.c_double(0.0)

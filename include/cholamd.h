@@ -365,6 +365,25 @@ int cholamd_solve_f32(cholamd_device *d, const float *d_arena32, const double *d
 int cholamd_solve_refine(cholamd_device *d, const float *d_arena32, const double *d_b, double *d_x, int max_iter, double tol,
                          int *iters_out, double *relres_out, void *stream);
 int cholamd_residual(cholamd_device *d, const double *d_b, const double *d_x, double *d_r, double *relres_out, void *stream);
+/* ---- block solve (not in the reference, whose mmat.rg -b solves one vector): nrhs right-hand sides per pass over the factor.  B and X are column-major
+ * n x nrhs fp64 device arrays in ORIGINAL dof order (column j at d_B + j * ldb / d_X + j * ldx, ldb, ldx >= n); rows n .. ld - 1 of X are never written.
+ * X == B with ldx == ldb (in place) is allowed; any other overlap of X and B is undefined.  The right-hand sides are solved in chunks of 32 columns, each
+ * one forward and one backward sweep over the solve lists of cholamd_solve (every stored entry of L read once per sweep per chunk, 16 x 32 fp64 MFMA tiles;
+ * the off-diagonal blocks accumulate by fp64 atomics, so X agrees with cholamd_solve per column to rounding, not bit for bit); the 16x16 and span inverses are
+ * formed once per call.  A chunk costs about the same for any number of columns up to 32: ~3 single solves with an fp64 factor, ~5 with an fp32 one, so
+ * a chunk of fewer than 4 (fp64) / 6 (fp32) columns -- nrhs == 1 among them -- is solved column by column with the single-vector path instead.  Option
+ * "solve_reference_shape" solves every column through cholamd_solve / cholamd_solve_f32.
+ * nrhs == 0 returns 0 and touches nothing; nrhs < 0, ldb < n, ldx < n or a NULL pointer with nrhs > 0: CHOLAMD_ERR_ARG.
+ * cholamd_solve_nrhs / _f32 (fp64 / fp32 factor; vectors and arithmetic fp64) are asynchronous on `stream`.  cholamd_solve_refine_nrhs is
+ * cholamd_solve_refine for every column (fp32 factor, residual in fp64 against the matrix file's A) and synchronises: chunk by chunk (the chunk's columns
+ * of B are copied to a workspace first, so in-place use is allowed here too), corrections are applied to ALL columns of a chunk (converged columns are not
+ * masked out) until every column has ||b_j - A x_j|| <= tol ||b_j|| or max_iter corrections have been applied; *iters_out = the most corrections any chunk
+ * applied, relres_out[j] (nrhs doubles, may be NULL) = column j's final relative residual.  A NaN in any column fails as cholamd_solve_refine does
+ * (CHOLAMD_ERR_ARG): the chunks after the failing one are not solved, their relres_out entries are NaN, *iters_out counts the chunks up to the failing one. */
+int cholamd_solve_nrhs(cholamd_device *d, const double *d_arena, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int nrhs, void *stream);
+int cholamd_solve_nrhs_f32(cholamd_device *d, const float *d_arena32, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int nrhs, void *stream);
+int cholamd_solve_refine_nrhs(cholamd_device *d, const float *d_arena32, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int nrhs, int max_iter,
+                              double tol, int *iters_out, double *relres_out /* nrhs doubles, may be NULL */, void *stream);
 /* average device time (ms) of the three kernel families of the last cholamd_factor call measured
  * with HIP events on its stream; valid after cholamd_device_sync.  Enable with set_timing(1). */
 int cholamd_device_set_timing(cholamd_device *d, int on);
