@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <algorithm>
 #include <cstdlib>
+#include <cfloat>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -86,6 +87,7 @@ struct cholamd_device {
   // mixed precision (fp32 factor + fp64 refinement): work lists of the fp32 kernels, their workspace, A as a device CSR
   std::vector<level_dev> lv32;
   float *ws32 = nullptr;
+  int f32_range = -1; int64_t f32_bad = -1; // A's entries all zero or normal floats (1), or not (0: f32_bad = the first entry that is not); -1: not checked yet
   int64_t *csr_ptr = nullptr; int *csr_col = nullptr; double *csr_val = nullptr;
   double *rvec = nullptr, *dxvec = nullptr, *partial = nullptr;
   // extend-add exchange under the distributed top levels: staging of the copies received for the owned column blocks, descriptors of the sum
@@ -870,8 +872,26 @@ extern "C" int cholamd_solve(cholamd_device *d, const double *d_arena, const dou
 // Mixed precision (BASELINE config 5): fp32 factor, fp64 iterative refinement of the solve.
 // The fp32 arena has the element layout of the fp64 one (cholamd_plan_arena_doubles() floats).
 // ---------------------------------------------------------------------------------------------
+// the fp32 factor converts A to float: an entry beyond FLT_MAX would become inf, one below FLT_MIN a denormal or zero, and the pivot checks do not see
+// what that does to the factor.  Such a matrix is refused (include/cholamd.h); checked once per device object.
+static int f32_range_ok(cholamd_device *d)
+{
+  const cholamd_plan *p = d->plan;
+  if (d->f32_range < 0) {
+    d->f32_range = 1;
+    for (int64_t e = 0; e < p->nnz_a; e++) {
+      const double a = std::fabs(p->a_val[e]);
+      if (a > (double)FLT_MAX || a < (double)FLT_MIN) { d->f32_range = 0; d->f32_bad = e; break; } // (explicit zeros are not in a_val)
+    }
+  }
+  if (d->f32_range) return 0;
+  chol_set_error("fp32 factor: entry %lld of A (%.17g) is outside the normal range of float [%g, %g]; use the fp64 factor", (long long)d->f32_bad,
+                 p->a_val[d->f32_bad], (double)FLT_MIN, (double)FLT_MAX);
+  return CHOLAMD_ERR_ARG;
+}
 static int ensure_f32(cholamd_device *d)
 {
+  { int rc = f32_range_ok(d); if (rc) return rc; }
   if (!d->lv32.empty()) return 0;
   const int L = d->plan->levels;
   chol_sched_opts o = d->opt;
@@ -891,8 +911,8 @@ extern "C" int cholamd_device_fill_f32(cholamd_device *d, float *d_arena32, void
 {
   HIPCHK(hipSetDevice(d->dev));
   hipStream_t st = (hipStream_t)stream;
-  { int rc = clear_owned(d, d_arena32, sizeof(float), st); if (rc) return rc; }
   { int rc = ensure_f32(d); if (rc) return rc; } // the fp32 schedule's column blocks decide which entries of the shared top are this rank's
+  { int rc = clear_owned(d, d_arena32, sizeof(float), st); if (rc) return rc; }
   int64_t below = 0, ntop = 0; const int64_t *tdst = nullptr; const double *tval = nullptr;
   { int rc = top_entries(d, 1, &below, &tdst, &tval, &ntop); if (rc) return rc; }
   HIPCHK((hipError_t)chol32_launch_scatter(d_arena32, d->a_dst, d->a_val, below, st));

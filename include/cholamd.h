@@ -357,7 +357,11 @@ int cholamd_solve(cholamd_device *d, const double *d_arena, const double *d_b, d
  * arithmetic fp64, L converted on load); cholamd_solve_refine iterates x += (L32 L32^T)^-1 (b - A x) with the residual
  * in fp64 against the matrix file's A until ||b - A x|| / ||b|| <= tol or max_iter corrections have been applied, and
  * returns the corrections used and the final relative residual.  cholamd_residual computes that residual for any x
- * (d_r may be NULL); both synchronise the stream. */
+ * (d_r may be NULL); both synchronise the stream.
+ * fp32 range: every non-zero entry of A must be a normal float in magnitude (FLT_MIN <= |a| <= FLT_MAX); otherwise cholamd_device_fill_f32, the fp32
+ * factorisations (cholamd_factor_f32, _levels_f32, _sharded_f32, _multi_f32) return CHOLAMD_ERR_ARG and say which
+ * entry (cholamd_last_error) -- the conversion would turn it into inf or a denormal, which the pivot checks cannot be relied on to report.  Scale such a
+ * matrix or use the fp64 factor, which has no such limit. */
 int cholamd_device_fill_f32(cholamd_device *d, float *d_arena32, void *stream);
 int cholamd_factor_f32(cholamd_device *d, float *d_arena32, void *stream);
 int cholamd_factor_levels_f32(cholamd_device *d, float *d_arena32, int level_hi, int level_lo, void *stream);

@@ -259,7 +259,8 @@ def _ntiles_table(case):
     return table
 
 
-@pytest.mark.parametrize("opts", [
+# every schedule / launch variant selectable through cholamd_device_set_option (tests/test_gpu_general_spd.py runs them on general SPD inputs)
+LAUNCH_PATHS = [
     {"follow": 0},                                     # the one-launch program without followers (update jobs carry every contribution)
     {"follow_tail": 0},                                # followers take every column tile of their sources themselves (no early update jobs)
     {"follow_tail": 2},                                # ... only the last two (most of the contribution through early jobs)
@@ -282,7 +283,10 @@ def _ntiles_table(case):
     {"cells": 0},                                      # extend-add by the reference's cluster tiles instead of grid cells (no followers)
     {"program": 0, "cells": 0},
     {"solve_reference_shape": 1},                      # the per-call (deterministic) solve kernels
-], ids=lambda o: "+".join(f"{k}={v}" for k, v in o.items()))
+]
+
+
+@pytest.mark.parametrize("opts", LAUNCH_PATHS, ids=lambda o: "+".join(f"{k}={v}" for k, v in o.items()))
 def test_alternative_launch_paths_keep_parity(opts, ca, golden):
     """Every schedule / launch variant selectable through cholamd_device_set_option factors lapl_3375 to the same L
     (reference golden, 1e-12) and solves to the same x."""
