@@ -11,6 +11,7 @@
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "chol_kernels.h"
@@ -120,6 +121,28 @@ template <class T> static int upload_vec(T **dptr, const T *h, size_t n)
   HIPCHK(hipMalloc((void **)dptr, n * sizeof(T)));
   HIPCHK(hipMemcpy(*dptr, h, n * sizeof(T), hipMemcpyHostToDevice));
   return 0;
+}
+
+// Every allocation of floating-point data goes through fp_malloc.  With CHOLAMD_POISON set and non-zero (read at each allocation) it takes a
+// guard tail of CHOL_POISON_GUARD bytes more and fills the whole allocation with 0xFF bytes -- a NaN in fp64 and fp32 -- before any clearing the
+// caller does: a kernel that reads a value it does not own, even to multiply it by zero, then produces NaN.  Integer, flag and descriptor
+// buffers are never poisoned (bounded spin-waits read some of them).  Unset: a plain hipMalloc.
+#define CHOL_POISON_GUARD ((size_t)64 << 10)
+static bool poison_on()
+{
+  const char *e = std::getenv("CHOLAMD_POISON");
+  return e && *e && atoi(e) != 0;
+}
+static hipError_t poison_fill(void *p, size_t bytes)
+{
+  hipError_t e = hipMemset(p, 0xFF, bytes);
+  return e == hipSuccess ? hipDeviceSynchronize() : e; // ordered before work on any stream
+}
+static hipError_t fp_malloc(void **dptr, size_t bytes)
+{
+  if (!poison_on()) return hipMalloc(dptr, bytes);
+  hipError_t e = hipMalloc(dptr, bytes + CHOL_POISON_GUARD);
+  return e == hipSuccess ? poison_fill(*dptr, bytes + CHOL_POISON_GUARD) : e;
 }
 
 static void free_level(level_dev &l)
@@ -248,7 +271,7 @@ extern "C" int cholamd_device_create(const cholamd_plan *plan, int device_id, ch
   { const char *e = getenv("CHOLAMD_SOLVE_REFERENCE_SHAPE"); d->solve_reference_shape = e && *e && atoi(e) != 0; }
   int rc = build_levels(d);
   if (!rc) {
-    hipError_t e = hipMalloc((void **)&d->ws, (size_t)(plan->ws_doubles > 0 ? plan->ws_doubles : 1) * sizeof(double));
+    hipError_t e = fp_malloc((void **)&d->ws, (size_t)(plan->ws_doubles > 0 ? plan->ws_doubles : 1) * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void **)&d->info, 4 * sizeof(int));
     if (e == hipSuccess) e = hipMemset(d->info, 0, 4 * sizeof(int));
     if (e == hipSuccess) e = hipMalloc((void **)&d->progress, (size_t)(plan->nsep + 2) * sizeof(int));
@@ -336,7 +359,7 @@ extern "C" int cholamd_device_set_option(cholamd_device *d, const char *name, in
 extern "C" int cholamd_device_alloc(cholamd_device *d, int64_t doubles, double **dptr)
 {
   HIPCHK(hipSetDevice(d->dev));
-  HIPCHK(hipMalloc((void **)dptr, (size_t)doubles * sizeof(double)));
+  HIPCHK(fp_malloc((void **)dptr, (size_t)doubles * sizeof(double)));
   return 0;
 }
 extern "C" int cholamd_device_free(cholamd_device *d, double *dptr)
@@ -407,7 +430,7 @@ extern "C" int cholamd_device_alloc_arena(cholamd_device *d, int elem_bytes, voi
   if (elem_bytes != 4 && elem_bytes != 8) { chol_set_error("alloc_arena: element size %d", elem_bytes); return CHOLAMD_ERR_ARG; }
   const size_t full = (size_t)d->plan->arena * (size_t)elem_bytes;
   if (d->world <= 1 || d->rank == 0) {
-    HIPCHK(hipMalloc(dptr, full > 0 ? full : 1));
+    HIPCHK(fp_malloc(dptr, full > 0 ? full : 1));
     if (backed_bytes) *backed_bytes = (int64_t)full;
     return 0;
   }
@@ -436,12 +459,13 @@ extern "C" int cholamd_device_alloc_arena(cholamd_device *d, int elem_bytes, voi
   hipError_t e = hipMemCreate(&hs, scratch, &prop, 0);
   if (e != hipSuccess) { (void)hipMemAddressFree(A.va, total); chol_set_error("alloc_arena: hipMemCreate: %s", hipGetErrorString(e)); return CHOLAMD_ERR_HIP; }
   A.handles.push_back(hs);
-  size_t backed = scratch, pos = 0;
+  size_t backed = scratch, pos = 0, alias_at = 0, alias_len = 0; // (alias_at, alias_len): the longest view of the scratch chunk
   auto alias = [&](size_t lo, size_t hi) { // [lo, hi) onto the scratch chunk, piece by piece
     for (size_t o = lo; o < hi;) {
       const size_t n = std::min(scratch, hi - o);
       hipError_t e2 = hipMemMap((char *)A.va + o, n, 0, hs, 0);
       if (e2 != hipSuccess) return e2;
+      if (n > alias_len) { alias_at = o; alias_len = n; }
       o += n;
     }
     return hipSuccess;
@@ -471,6 +495,11 @@ extern "C" int cholamd_device_alloc_arena(cholamd_device *d, int elem_bytes, voi
     acc.push_back(a1);
   }
   if ((e = hipMemSetAccess(A.va, total, acc.data(), acc.size())) != hipSuccess) return fail(e, "hipMemSetAccess");
+  if (poison_on()) { // as fp_malloc: the owned ranges (their widening to the chunk size is the guard) and the scratch chunk once
+    for (auto &b : back)
+      if ((e = poison_fill((char *)A.va + b.first, b.second - b.first)) != hipSuccess) return fail(e, "hipMemset (poison)");
+    if (alias_len > 0 && (e = poison_fill((char *)A.va + alias_at, alias_len)) != hipSuccess) return fail(e, "hipMemset (poison)");
+  }
   d->vmm.push_back(A);
   *dptr = A.va;
   if (backed_bytes) *backed_bytes = (int64_t)backed;
@@ -763,10 +792,10 @@ static int build_solve(cholamd_device *d, int rank = 0, int world = 1)
     chol_solve_level_free(&w);
     if (rc) return rc;
   }
-  if (!d->ytmp) HIPCHK(hipMalloc((void **)&d->ytmp, (size_t)d->plan->n * sizeof(double)));
-  if (!d->ws_solve) HIPCHK(hipMalloc((void **)&d->ws_solve, (size_t)(d->plan->ws_doubles > 0 ? d->plan->ws_doubles : 1) * sizeof(double)));
+  if (!d->ytmp) HIPCHK(fp_malloc((void **)&d->ytmp, (size_t)d->plan->n * sizeof(double)));
+  if (!d->ws_solve) HIPCHK(fp_malloc((void **)&d->ws_solve, (size_t)(d->plan->ws_doubles > 0 ? d->plan->ws_doubles : 1) * sizeof(double)));
   if (!d->step_flags) { HIPCHK(hipMalloc((void **)&d->step_flags, CHOL_STEPW_MAX_SEPS * 16 * sizeof(int))); HIPCHK(hipMemset(d->step_flags, 0, CHOL_STEPW_MAX_SEPS * 16 * sizeof(int))); }
-  if (!d->step_xt) { HIPCHK(hipMalloc((void **)&d->step_xt, CHOL_STEPW_MAX_SEPS * 256 * sizeof(double))); HIPCHK(hipMemset(d->step_xt, 0, CHOL_STEPW_MAX_SEPS * 256 * sizeof(double))); }
+  if (!d->step_xt) { HIPCHK(fp_malloc((void **)&d->step_xt, CHOL_STEPW_MAX_SEPS * 256 * sizeof(double))); HIPCHK(hipMemset(d->step_xt, 0, CHOL_STEPW_MAX_SEPS * 256 * sizeof(double))); }
   int64_t w256 = 0; // explicit inverses of the diagonal spans where the span chain is the solve's critical path: the levels of at most 8 separators
   if (!std::getenv("CHOLAMD_SOLVE_NO_INV256"))
     for (int lvl = 0; lvl < L; lvl++) {
@@ -775,7 +804,7 @@ static int build_solve(cholamd_device *d, int rank = 0, int world = 1)
       s.w256_off = w256;
       w256 += (int64_t)s.n_trsv * ((s.max_n + 255) / 256) * 65536;
     }
-  if (w256 > 0) HIPCHK(hipMalloc((void **)&d->w256, (size_t)w256 * sizeof(double)));
+  if (w256 > 0) HIPCHK(fp_malloc((void **)&d->w256, (size_t)w256 * sizeof(double)));
   d->solve_ready = true;
   return 0;
 }
@@ -904,7 +933,7 @@ static int ensure_f32(cholamd_device *d)
     chol_level_work_free(&w);
     if (rc) { for (auto &l : d->lv32) free_level(l); d->lv32.clear(); return rc; }
   }
-  if (!d->ws32) HIPCHK(hipMalloc((void **)&d->ws32, (size_t)(d->plan->ws_doubles > 0 ? d->plan->ws_doubles : 1) * sizeof(float)));
+  if (!d->ws32) HIPCHK(fp_malloc((void **)&d->ws32, (size_t)(d->plan->ws_doubles > 0 ? d->plan->ws_doubles : 1) * sizeof(float)));
   return 0;
 }
 extern "C" int cholamd_device_fill_f32(cholamd_device *d, float *d_arena32, void *stream)
@@ -978,9 +1007,9 @@ static int ensure_refine(cholamd_device *d)
   if (!rc) rc = upload_vec(&d->csr_col, p->csr_col, (size_t)(p->csr_ptr[n] > 0 ? p->csr_ptr[n] : 1));
   if (!rc) rc = upload_vec(&d->csr_val, p->csr_val, (size_t)(p->csr_ptr[n] > 0 ? p->csr_ptr[n] : 1));
   if (rc) return rc;
-  HIPCHK(hipMalloc((void **)&d->rvec, (size_t)n * sizeof(double)));
-  HIPCHK(hipMalloc((void **)&d->dxvec, (size_t)n * sizeof(double)));
-  HIPCHK(hipMalloc((void **)&d->partial, (size_t)2 * ((n + 255) / 256) * sizeof(double)));
+  HIPCHK(fp_malloc((void **)&d->rvec, (size_t)n * sizeof(double)));
+  HIPCHK(fp_malloc((void **)&d->dxvec, (size_t)n * sizeof(double)));
+  HIPCHK(fp_malloc((void **)&d->partial, (size_t)2 * ((n + 255) / 256) * sizeof(double)));
   return 0;
 }
 // r = b - A x on the device (fp64, A = the matrix file's entries, both triangles), ||r|| / ||b|| back on the host
@@ -1075,7 +1104,7 @@ template <class TL> static int solve_nrhs_t(cholamd_device *d, const TL *d_arena
       for (int j = c0; j < c0 + cols; j++) { int rc = solve_streamed(d, d_arena, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, st); if (rc) return rc; }
       continue;
     }
-    if (!d->ynrhs) HIPCHK(hipMalloc((void **)&d->ynrhs, (size_t)n * CHOL_NRHS_W * sizeof(double)));
+    if (!d->ynrhs) HIPCHK(fp_malloc((void **)&d->ynrhs, (size_t)n * CHOL_NRHS_W * sizeof(double)));
     double *Y = d->ynrhs;
     HIPCHK((hipError_t)chol_nrhs_launch_permute(d_B, ldb, d->perm, Y, nullptr, 0, n, c0, cols, 0, st));
     for (int lvl = L - 1; lvl >= 0; lvl--) { // forward: the separators' triangles, then their panels into the ancestors
@@ -1146,10 +1175,10 @@ extern "C" int cholamd_solve_refine_nrhs(cholamd_device *d, const float *d_arena
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int n = d->plan->n, nb = (n + 255) / 256;
-  if (!d->bnrhs) HIPCHK(hipMalloc((void **)&d->bnrhs, (size_t)n * CHOL_NRHS_W * sizeof(double)));
-  if (!d->rnrhs) HIPCHK(hipMalloc((void **)&d->rnrhs, (size_t)n * CHOL_NRHS_W * sizeof(double)));
-  if (!d->dxnrhs) HIPCHK(hipMalloc((void **)&d->dxnrhs, (size_t)n * CHOL_NRHS_W * sizeof(double)));
-  if (!d->pnrhs) HIPCHK(hipMalloc((void **)&d->pnrhs, (size_t)2 * nb * CHOL_NRHS_W * sizeof(double)));
+  if (!d->bnrhs) HIPCHK(fp_malloc((void **)&d->bnrhs, (size_t)n * CHOL_NRHS_W * sizeof(double)));
+  if (!d->rnrhs) HIPCHK(fp_malloc((void **)&d->rnrhs, (size_t)n * CHOL_NRHS_W * sizeof(double)));
+  if (!d->dxnrhs) HIPCHK(fp_malloc((void **)&d->dxnrhs, (size_t)n * CHOL_NRHS_W * sizeof(double)));
+  if (!d->pnrhs) HIPCHK(fp_malloc((void **)&d->pnrhs, (size_t)2 * nb * CHOL_NRHS_W * sizeof(double)));
   if (max_iter < 0) max_iter = 0;
   // chunk by chunk: the chunk's columns of B are copied first (X may be B: in place), x0 = M^-1 b with M = L32 L32^T, then X += M^-1 (B - A X) on ALL the
   // chunk's columns until every one of them has ||b_j - A x_j|| <= tol ||b_j|| or max_iter corrections have been applied.  The inverses are formed once.
@@ -1204,7 +1233,8 @@ struct scratch { // per-call device scratch, freed at scope exit after the strea
   }
   template <class T> int get(T **dptr, size_t n)
   {
-    HIPCHK(hipMalloc((void **)dptr, (n ? n : 1) * sizeof(T)));
+    if (std::is_floating_point<T>::value) HIPCHK(fp_malloc((void **)dptr, (n ? n : 1) * sizeof(T)));
+    else HIPCHK(hipMalloc((void **)dptr, (n ? n : 1) * sizeof(T)));
     ptrs.push_back(*dptr);
     return 0;
   }
@@ -1649,7 +1679,7 @@ struct host_mat { // a host matrix mirrored on the device for the duration of on
   {
     h = const_cast<double *>(hp); rows = r; cols = c; ld = ldh; writeback = wb;
     if (r == 0 || c == 0) return 0;
-    HIPCHK(hipMalloc((void **)&d, (size_t)ld * cols * sizeof(double)));
+    HIPCHK(fp_malloc((void **)&d, (size_t)ld * cols * sizeof(double)));
     HIPCHK(hipMemcpy(d, h, ((size_t)ld * (cols - 1) + rows) * sizeof(double), hipMemcpyHostToDevice));
     return 0;
   }
@@ -1744,7 +1774,7 @@ extern "C" void cholamd_cblas_dgemv(int layout, int trans, int m, int n, double 
   if (m == 0 || n == 0) return;
   // x and y share one device buffer so that 32-bit relative offsets always suffice
   double *xy = nullptr;
-  if (hipMalloc((void **)&xy, (size_t)(lx + ly) * sizeof(double)) != hipSuccess) { g_blas_status = CHOLAMD_ERR_HIP; return; }
+  if (fp_malloc((void **)&xy, (size_t)(lx + ly) * sizeof(double)) != hipSuccess) { g_blas_status = CHOLAMD_ERR_HIP; return; }
   host_mat A;
   rc = A.up(a, m, n, lda, false);
   if (!rc && hipMemcpy(xy, x, (size_t)lx * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = CHOLAMD_ERR_HIP;
@@ -1989,7 +2019,7 @@ template <class T> static int exchange_owned(cholamd_device *d, T *arena, const 
   if ((size_t)need * sizeof(T) > d->xstage_bytes) {
     HIPCHK(hipStreamSynchronize(st));
     (void)hipFree(d->xstage); d->xstage = nullptr; d->xstage_bytes = 0;
-    HIPCHK(hipMalloc(&d->xstage, (size_t)need * sizeof(T)));
+    HIPCHK(fp_malloc(&d->xstage, (size_t)need * sizeof(T)));
     d->xstage_bytes = (size_t)need * sizeof(T);
   }
   if (d->xdesc_gen != d->sched_gen || d->xdesc_elem != (int)sizeof(T)) { // the descriptors of the sum kernel, once per schedule

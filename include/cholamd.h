@@ -264,7 +264,12 @@ int cholamd_device_count(void);
 int cholamd_device_create(const cholamd_plan *plan, int device_id, cholamd_device **out);
 void cholamd_device_destroy(cholamd_device *d);
 /* device memory owned by the library (hipMalloc); callers may instead pass their own buffers
- * (e.g. torch tensors) of cholamd_plan_arena_doubles() doubles to the calls below */
+ * (e.g. torch tensors) of cholamd_plan_arena_doubles() doubles to the calls below.
+ * CHOLAMD_POISON=1 in the environment (a test switch, read at every allocation): every buffer of floating-point data the library
+ * allocates -- these, cholamd_device_alloc_arena's (owned ranges and scratch chunk), the work and solve vectors, the per-call BLAS
+ * buffers -- gets a guard tail and starts as 0xFF bytes (NaN in fp64 and fp32) instead of whatever the allocator returns.  A read of
+ * memory a kernel does not own then shows up as NaN.  Integer, flag and descriptor buffers are never poisoned.  Unset or 0: plain
+ * hipMalloc, nothing else changes. */
 int cholamd_device_alloc(cholamd_device *d, int64_t doubles, double **dptr);
 int cholamd_device_free(cholamd_device *d, double *dptr);
 int cholamd_device_upload(cholamd_device *d, double *d_dst, const double *h_src, int64_t doubles, void *stream);
