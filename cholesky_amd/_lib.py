@@ -90,6 +90,11 @@ def load():
     L.cholamd_plan_flops.restype = cd
     L.cholamd_plan_fill_host.argtypes = [vp, vp]
     L.cholamd_plan_arena_to_dense.argtypes = [vp, vp, vp]
+    L.cholamd_plan_entries.argtypes = [vp, vp, vp]
+    L.cholamd_plan_value_map.argtypes = [vp, vp]
+    L.cholamd_plan_fill_host_values.argtypes = [vp, vp, i64, vp]
+    L.cholamd_device_set_values.argtypes = [vp, vp, i64, ci, vp]
+    L.cholamd_device_values_status.argtypes = [vp, vp, vp]
     L.cholamd_plan_fill_host_part.argtypes = [vp, vp, ci, ci, C.POINTER(i64)]
     L.cholamd_plan_level_work_counts.argtypes = [vp, ci, ci, ci, vp]
     L.cholamd_plan_level_work_volume.argtypes = [vp, ci, ci, ci, ci, vp]

@@ -73,7 +73,16 @@ struct cholamd_device {
   int epoch = 0, done_total = 0;
   int64_t *a_dst = nullptr; double *a_val = nullptr; int *perm = nullptr; double *ytmp = nullptr;
   // distributed top levels: the entries of A in the column blocks of the shared top THIS rank owns ([0]: by the fp64 schedule's blocks, [1]: the fp32 one's)
-  int64_t *top_dst[2] = { nullptr, nullptr }; double *top_val[2] = { nullptr, nullptr }; int64_t top_n[2] = { 0, 0 }; int top_gen[2] = { -1, -1 };
+  // top_val is gathered on the device from a_val through top_e (the entries' positions in the scatter list), so that it follows cholamd_device_set_values
+  int64_t *top_dst[2] = { nullptr, nullptr }; double *top_val[2] = { nullptr, nullptr }; int *top_e[2] = { nullptr, nullptr }; int64_t top_n[2] = { 0, 0 }; int top_gen[2] = { -1, -1 };
+  // new values of A (cholamd_device_set_values): the index lists of the gather and the entries' classes (uploaded at the first call), the status words of
+  // the last call on the device ([4]), their start values ([4], device) and where they are read back to (pinned host, two slots of four)
+  int *a_src = nullptr, *csr_src = nullptr; unsigned char *e_cls = nullptr;
+  int64_t *vs_dev = nullptr, *vs_init = nullptr, *vs_host = nullptr;
+  int64_t vs_last[4] = { 0, 0, 0, 0 };  // the last call's status words as read back
+  bool vs_called = false, vs_last_valid = false;
+  bool vs_in_force = false; // the values in force come from set_values: the fp32 range verdict comes from the status words, not from the plan's values
+  bool f32_pending = false; // ... and has not been read back yet (the last call was asynchronous)
   bool timing = false;
   std::vector<timed_launch> tl;
   std::vector<hipEvent_t> pool;
@@ -302,7 +311,8 @@ extern "C" void cholamd_device_destroy(cholamd_device *d)
   (void)hipFree(d->xstage); (void)hipFree(d->xdesc);
   (void)hipFree(d->ws); (void)hipFree(d->ws_solve); (void)hipFree(d->step_flags); (void)hipFree(d->w256); (void)hipFree(d->step_xt); (void)hipFree(d->info); (void)hipFree(d->progress); (void)hipFree(d->a_dst); (void)hipFree(d->a_val); (void)hipFree(d->perm); (void)hipFree(d->ytmp);
   (void)hipFree(d->ynrhs); (void)hipFree(d->bnrhs); (void)hipFree(d->rnrhs); (void)hipFree(d->dxnrhs); (void)hipFree(d->pnrhs);
-  for (int q = 0; q < 2; q++) { (void)hipFree(d->top_dst[q]); (void)hipFree(d->top_val[q]); }
+  for (int q = 0; q < 2; q++) { (void)hipFree(d->top_dst[q]); (void)hipFree(d->top_val[q]); (void)hipFree(d->top_e[q]); }
+  (void)hipFree(d->a_src); (void)hipFree(d->csr_src); (void)hipFree(d->e_cls); (void)hipFree(d->vs_dev); (void)hipFree(d->vs_init); (void)hipHostFree(d->vs_host);
   for (auto &t : d->tl) { d->pool.push_back(t.a); d->pool.push_back(t.b); }
   for (auto e : d->pool) (void)hipEventDestroy(e);
   delete d;
@@ -528,14 +538,14 @@ extern "C" int cholamd_device_free_arena(cholamd_device *d, void *dptr)
 // subtrees reach it (chol_top_contributors), and rank 0 sends no more than any other rank.  `*below` = leading entries of (a_dst, a_val) to
 // scatter; (*tdst, *tval, *ntop) = further entries (device arrays).  f32: the fp32 schedule's column blocks.
 static void exchange_pieces(const cholamd_device *d, const std::vector<level_dev> &lv, std::vector<struct xpiece> &out);
-static int top_entries(cholamd_device *d, int f32, int64_t *below, const int64_t **tdst, const double **tval, int64_t *ntop);
+static int top_entries(cholamd_device *d, int f32, int64_t *below, const int64_t **tdst, const double **tval, int64_t *ntop, hipStream_t st);
 extern "C" int cholamd_device_fill(cholamd_device *d, double *d_arena, void *stream)
 {
   HIPCHK(hipSetDevice(d->dev));
   hipStream_t st = (hipStream_t)stream;
   { int rc = clear_owned(d, d_arena, sizeof(double), st); if (rc) return rc; }
   int64_t below = 0, ntop = 0; const int64_t *tdst = nullptr; const double *tval = nullptr;
-  { int rc = top_entries(d, 0, &below, &tdst, &tval, &ntop); if (rc) return rc; }
+  { int rc = top_entries(d, 0, &below, &tdst, &tval, &ntop, st); if (rc) return rc; }
   HIPCHK((hipError_t)chol_launch_scatter(d_arena, d->a_dst, d->a_val, below, st));
   if (ntop > 0) HIPCHK((hipError_t)chol_launch_scatter(d_arena, tdst, tval, ntop, st));
   return 0;
@@ -903,9 +913,20 @@ extern "C" int cholamd_solve(cholamd_device *d, const double *d_arena, const dou
 // ---------------------------------------------------------------------------------------------
 // the fp32 factor converts A to float: an entry beyond FLT_MAX would become inf, one below FLT_MIN a denormal or zero, and the pivot checks do not see
 // what that does to the factor.  Such a matrix is refused (include/cholamd.h); checked once per device object.
-static int f32_range_ok(cholamd_device *d)
+static int read_values_status(cholamd_device *d, hipStream_t st);
+static int f32_range_ok(cholamd_device *d, hipStream_t st)
 {
   const cholamd_plan *p = d->plan;
+  if (d->vs_in_force) { // the values of cholamd_device_set_values: the verdict is in the status words of that call, read back once
+    if (d->f32_pending) { int rc = read_values_status(d, st); if (rc) return rc; }
+    if (d->f32_range) return 0;
+    double v = 0.0; // the message names the value-array index; the value itself sits in the scatter list
+    for (int64_t e = 0; e < p->nnz_a; e++)
+      if (p->a_src[e] == d->f32_bad) { HIPCHK(hipMemcpy(&v, d->a_val + e, sizeof v, hipMemcpyDeviceToHost)); break; }
+    chol_set_error("fp32 factor: entry %lld of A (%.17g) is outside the normal range of float [%g, %g]; use the fp64 factor", (long long)d->f32_bad,
+                   v, (double)FLT_MIN, (double)FLT_MAX);
+    return CHOLAMD_ERR_ARG;
+  }
   if (d->f32_range < 0) {
     d->f32_range = 1;
     for (int64_t e = 0; e < p->nnz_a; e++) {
@@ -918,9 +939,9 @@ static int f32_range_ok(cholamd_device *d)
                  p->a_val[d->f32_bad], (double)FLT_MIN, (double)FLT_MAX);
   return CHOLAMD_ERR_ARG;
 }
-static int ensure_f32(cholamd_device *d)
+static int ensure_f32(cholamd_device *d, hipStream_t st)
 {
-  { int rc = f32_range_ok(d); if (rc) return rc; }
+  { int rc = f32_range_ok(d, st); if (rc) return rc; }
   if (!d->lv32.empty()) return 0;
   const int L = d->plan->levels;
   chol_sched_opts o = d->opt;
@@ -940,10 +961,10 @@ extern "C" int cholamd_device_fill_f32(cholamd_device *d, float *d_arena32, void
 {
   HIPCHK(hipSetDevice(d->dev));
   hipStream_t st = (hipStream_t)stream;
-  { int rc = ensure_f32(d); if (rc) return rc; } // the fp32 schedule's column blocks decide which entries of the shared top are this rank's
+  { int rc = ensure_f32(d, st); if (rc) return rc; } // the fp32 schedule's column blocks decide which entries of the shared top are this rank's
   { int rc = clear_owned(d, d_arena32, sizeof(float), st); if (rc) return rc; }
   int64_t below = 0, ntop = 0; const int64_t *tdst = nullptr; const double *tval = nullptr;
-  { int rc = top_entries(d, 1, &below, &tdst, &tval, &ntop); if (rc) return rc; }
+  { int rc = top_entries(d, 1, &below, &tdst, &tval, &ntop, st); if (rc) return rc; }
   HIPCHK((hipError_t)chol32_launch_scatter(d_arena32, d->a_dst, d->a_val, below, st));
   if (ntop > 0) HIPCHK((hipError_t)chol32_launch_scatter(d_arena32, tdst, tval, ntop, st));
   return 0;
@@ -967,7 +988,7 @@ extern "C" int cholamd_factor_levels_f32(cholamd_device *d, float *d_arena32, in
 static int factor_levels_f32_comm(cholamd_device *d, float *d_arena32, int level_hi, int level_lo, cholamd_comm *c, hipStream_t st)
 {
   HIPCHK(hipSetDevice(d->dev));
-  int rc = ensure_f32(d);
+  int rc = ensure_f32(d, st);
   if (rc) return rc;
   const int L = d->plan->levels;
   if (level_hi >= L) level_hi = L - 1;
@@ -1010,6 +1031,93 @@ static int ensure_refine(cholamd_device *d)
   HIPCHK(fp_malloc((void **)&d->rvec, (size_t)n * sizeof(double)));
   HIPCHK(fp_malloc((void **)&d->dxvec, (size_t)n * sizeof(double)));
   HIPCHK(fp_malloc((void **)&d->partial, (size_t)2 * ((n + 255) / 256) * sizeof(double)));
+  return 0;
+}
+// ---------------------------------------------------------------------------------------------
+// New values of A on the same pattern (include/cholamd.h at cholamd_device_set_values).  The copies of A's values a device object holds are the
+// scatter list a_val (with the owned-top copies top_val cut from it) and the residual operator csr_val; k_set_values gathers both from the caller's
+// value array through the plan's index lists, and counts what the values are.  No schedule, work list or solve list is touched (sched_gen stays).
+// ---------------------------------------------------------------------------------------------
+static int ensure_values(cholamd_device *d)
+{
+  if (d->vs_dev) return 0;
+  const cholamd_plan *p = d->plan;
+  int rc = ensure_refine(d); // the residual operator follows the values from now on
+  if (rc) return rc;
+  const size_t ncsr = (size_t)p->csr_ptr[p->n];
+  if (!d->a_src) rc = upload_vec(&d->a_src, p->a_src, (size_t)p->nnz_a);
+  if (!rc && !d->csr_src) rc = upload_vec(&d->csr_src, p->csr_src, ncsr);
+  if (!rc && !d->e_cls) rc = upload_vec(&d->e_cls, p->e_cls, (size_t)p->nz_file);
+  const int64_t init[4] = { 0, INT64_MAX, 0, INT64_MAX };
+  if (!rc && !d->vs_init) rc = upload_vec(&d->vs_init, init, (size_t)4);
+  if (rc) return rc;
+  if (!d->vs_host) HIPCHK(hipHostMalloc((void **)&d->vs_host, 8 * sizeof(int64_t)));
+  HIPCHK(hipMalloc((void **)&d->vs_dev, 4 * sizeof(int64_t)));
+  return 0;
+}
+static void take_f32_verdict(cholamd_device *d, const int64_t *status)
+{
+  d->f32_range = status[0] == 0; d->f32_bad = status[0] ? status[1] : -1; d->f32_pending = false;
+}
+// the status words of the last (asynchronous) call, which are those of the values in force: one synchronisation of `st`
+static int read_values_status(cholamd_device *d, hipStream_t st)
+{
+  HIPCHK(hipMemcpyAsync(d->vs_host, d->vs_dev, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  std::memcpy(d->vs_last, d->vs_host, sizeof d->vs_last);
+  d->vs_last_valid = true;
+  take_f32_verdict(d, d->vs_last);
+  return 0;
+}
+extern "C" int cholamd_device_set_values(cholamd_device *d, const double *d_vals, int64_t count, int flags, void *stream)
+{
+  const cholamd_plan *p = d->plan;
+  if (!d_vals) { chol_set_error("cholamd_device_set_values: null value array"); return CHOLAMD_ERR_ARG; }
+  if (count != p->nz_file) { chol_set_error("cholamd_device_set_values: value array of %lld entries, the plan has %d", (long long)count, p->nz_file); return CHOLAMD_ERR_ARG; }
+  if (flags < 0 || (flags & ~CHOLAMD_VALUES_NOCHECK)) { chol_set_error("cholamd_device_set_values: bad flags %d", flags); return CHOLAMD_ERR_ARG; }
+  HIPCHK(hipSetDevice(d->dev));
+  { int rc = ensure_values(d); if (rc) return rc; }
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t nz = p->nz_file, ncsr = p->csr_ptr[p->n];
+  auto launch = [&](int parts) {
+    return (hipError_t)chol_launch_set_values(d_vals, nz, d->e_cls, d->a_val, d->a_src, p->nnz_a, d->csr_val, d->csr_src, ncsr, parts, d->vs_dev, st);
+  };
+  if (flags & CHOLAMD_VALUES_NOCHECK) {
+    HIPCHK(hipMemcpyAsync(d->vs_dev, d->vs_init, 4 * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    HIPCHK(launch(CHOL_VALUES_STATUS | CHOL_VALUES_GATHER));
+    d->vs_last_valid = false; d->f32_range = -1; d->f32_pending = true;
+  } else {
+    // look first, gather afterwards: a refused array leaves every copy as it was.  The verdict on the values in force, if nobody has read it yet, is
+    // taken along in the same synchronisation (the status words are about to be overwritten)
+    const bool pending = d->f32_pending;
+    if (pending) HIPCHK(hipMemcpyAsync(d->vs_host + 4, d->vs_dev, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(d->vs_dev, d->vs_init, 4 * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    HIPCHK(launch(CHOL_VALUES_STATUS));
+    HIPCHK(hipMemcpyAsync(d->vs_host, d->vs_dev, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (pending) take_f32_verdict(d, d->vs_host + 4);
+    std::memcpy(d->vs_last, d->vs_host, sizeof d->vs_last);
+    d->vs_called = true; d->vs_last_valid = true;
+    if (d->vs_last[2] > 0) {
+      chol_set_error("cholamd_device_set_values: entry %lld of the value array is outside the pattern (0.0 when the plan was made) and %lld such entr%s not zero now; "
+                     "the previous values stay in force (a new pattern needs a new plan)", (long long)d->vs_last[3], (long long)d->vs_last[2], d->vs_last[2] == 1 ? "y is" : "ies are");
+      return CHOLAMD_ERR_ARG;
+    }
+    HIPCHK(launch(CHOL_VALUES_GATHER));
+    take_f32_verdict(d, d->vs_last);
+  }
+  d->vs_called = true; d->vs_in_force = true;
+  for (int q = 0; q < 2; q++) // the owned-top copies of the current schedule; a later rebuild (top_entries) gathers from a_val itself
+    if (d->top_gen[q] == d->sched_gen && d->top_n[q] > 0) HIPCHK((hipError_t)chol_launch_gather(d->top_val[q], d->a_val, d->top_e[q], d->top_n[q], st));
+  return 0;
+}
+extern "C" int cholamd_device_values_status(cholamd_device *d, void *stream, int64_t out[4])
+{
+  if (!d->vs_called) { chol_set_error("cholamd_device_values_status: no cholamd_device_set_values call on this device object yet"); return CHOLAMD_ERR_ARG; }
+  HIPCHK(hipSetDevice(d->dev));
+  if (!d->vs_last_valid) { int rc = read_values_status(d, (hipStream_t)stream); if (rc) return rc; }
+  out[0] = d->vs_last[0]; out[1] = d->vs_last[0] ? d->vs_last[1] : -1;
+  out[2] = d->vs_last[2]; out[3] = d->vs_last[2] ? d->vs_last[3] : -1;
   return 0;
 }
 // r = b - A x on the device (fp64, A = the matrix file's entries, both triangles), ||r|| / ||b|| back on the host
@@ -1946,7 +2054,7 @@ static void exchange_pieces(const cholamd_device *d, const std::vector<level_dev
   int64_t st = 0; // staging slots of the pieces this rank owns: one copy per contributing rank other than itself, senders in rank order
   for (xpiece &x : out) if (x.owner == d->rank) { x.stage = st; st += x.count * __builtin_popcount(x.contrib & ~(1u << d->rank)); }
 }
-static int top_entries(cholamd_device *d, int f32, int64_t *below, const int64_t **tdst, const double **tval, int64_t *ntop)
+static int top_entries(cholamd_device *d, int f32, int64_t *below, const int64_t **tdst, const double **tval, int64_t *ntop, hipStream_t st)
 {
   const cholamd_plan *p = d->plan;
   *tdst = nullptr; *tval = nullptr; *ntop = 0;
@@ -1956,7 +2064,8 @@ static int top_entries(cholamd_device *d, int f32, int64_t *below, const int64_t
   while (lo < hi) { int64_t mid = (lo + hi) / 2; if (p->a_dst[mid] < tail) lo = mid + 1; else hi = mid; }
   *below = lo;
   if (d->top_gen[f32] != d->sched_gen) { // once per schedule
-    (void)hipFree(d->top_dst[f32]); (void)hipFree(d->top_val[f32]); d->top_dst[f32] = nullptr; d->top_val[f32] = nullptr; d->top_n[f32] = 0;
+    (void)hipFree(d->top_dst[f32]); (void)hipFree(d->top_val[f32]); (void)hipFree(d->top_e[f32]);
+    d->top_dst[f32] = nullptr; d->top_val[f32] = nullptr; d->top_e[f32] = nullptr; d->top_n[f32] = 0;
     std::vector<xpiece> px;
     exchange_pieces(d, f32 ? d->lv32 : d->lv, px);
     if (px.empty()) d->top_n[f32] = d->rank == 0 ? -1 : 0; // replicated top levels: rank 0 scatters the whole tail
@@ -1964,16 +2073,19 @@ static int top_entries(cholamd_device *d, int f32, int64_t *below, const int64_t
       std::vector<xpiece> mine;
       for (const xpiece &x : px) if (x.owner == d->rank) mine.push_back(x);
       std::sort(mine.begin(), mine.end(), [](const xpiece &a, const xpiece &b) { return a.off < b.off; });
-      std::vector<int64_t> td; std::vector<double> tv;
+      std::vector<int64_t> td; std::vector<int> te;
       size_t q = 0;
       for (int64_t e = lo; e < p->nnz_a; e++) { // a_dst ascends: one merge pass over the owned blocks
         while (q < mine.size() && mine[q].off + mine[q].count <= p->a_dst[e]) q++;
-        if (q < mine.size() && p->a_dst[e] >= mine[q].off) { td.push_back(p->a_dst[e]); tv.push_back(p->a_val[e]); }
+        if (q < mine.size() && p->a_dst[e] >= mine[q].off) { td.push_back(p->a_dst[e]); te.push_back((int)e); }
       }
       if (!td.empty()) {
         int rc = upload_vec(&d->top_dst[f32], td.data(), td.size());
-        if (!rc) rc = upload_vec(&d->top_val[f32], tv.data(), tv.size());
+        if (!rc) rc = upload_vec(&d->top_e[f32], te.data(), te.size());
         if (rc) return rc;
+        // the values: the device object's CURRENT ones (the plan's, or those of the last cholamd_device_set_values)
+        HIPCHK(fp_malloc((void **)&d->top_val[f32], td.size() * sizeof(double)));
+        HIPCHK((hipError_t)chol_launch_gather(d->top_val[f32], d->a_val, d->top_e[f32], (int64_t)td.size(), st));
       }
       d->top_n[f32] = (int64_t)td.size();
     }
@@ -2120,7 +2232,7 @@ extern "C" int cholamd_factor_sharded_f32(cholamd_device *d, float *d_arena32, c
 {
   const int L = d->plan->levels, split = chol_split_level(d->world);
   if (d->world == 1) return cholamd_factor_f32(d, d_arena32, stream);
-  int rc = ensure_f32(d);
+  int rc = ensure_f32(d, (hipStream_t)stream);
   if (!rc) rc = factor_levels_f32_comm(d, d_arena32, L - 1, split, nullptr, (hipStream_t)stream);
   if (!rc) {
     scoped_timer t(d, (hipStream_t)stream, CHOL_TK_EXCHANGE, true);
@@ -2223,7 +2335,7 @@ template <class T> static int factor_multi_t(cholamd_device *const *devs, T *con
     if (comm_matches(devs[g], comms[g])) return CHOLAMD_ERR_ARG;
     if (comms[g]->local != G || (!G && !comms[g]->comm)) { chol_set_error("the %d communicators are not of one kind", n); return CHOLAMD_ERR_ARG; }
     int rc;
-    if (F32) { rc = ensure_f32(devs[g]); if (!rc) rc = factor_levels_f32_comm(devs[g], (float *)arenas[g], L - 1, split, nullptr, stream_of(streams, g)); }
+    if (F32) { rc = ensure_f32(devs[g], stream_of(streams, g)); if (!rc) rc = factor_levels_f32_comm(devs[g], (float *)arenas[g], L - 1, split, nullptr, stream_of(streams, g)); }
     else rc = cholamd_factor_levels(devs[g], (double *)arenas[g], L - 1, split, stream_of(streams, g));
     if (rc) return rc;
   }

@@ -8,6 +8,13 @@
 extern "C" {
 #endif
 int chol_launch_scatter(double *arena, const int64_t *dst, const double *val, int64_t nnz, hipStream_t st);
+/* new values of A (cholamd_device_set_values): `parts` = CHOL_VALUES_STATUS (the four status words of the value array, which start at
+ * { 0, INT64_MAX, 0, INT64_MAX }) | CHOL_VALUES_GATHER (a_val[e] = vals[a_src[e]], csr_val[k] = vals[csr_src[k]]) in one launch */
+#define CHOL_VALUES_STATUS 1
+#define CHOL_VALUES_GATHER 2
+int chol_launch_set_values(const double *vals, int64_t nz, const unsigned char *cls, double *a_val, const int *a_src, int64_t nnz_a,
+                           double *csr_val, const int *csr_src, int64_t ncsr, int parts, int64_t *status, hipStream_t st);
+int chol_launch_gather(double *out, const double *in, const int *idx, int64_t n, hipStream_t st); /* out[i] = in[idx[i]] */
 int chol_launch_potrf(double *base, double *ws, const chol_potrf_desc *descs, int n, int *info, hipStream_t st);
 int chol_launch_potrf_big(double *base, double *ws, const chol_potrf_desc *descs, int n, int *info, hipStream_t st);
 int chol_launch_potrf_trsm(double *base, double *ws, const chol_potrf_desc *pdescs, int n_potrf, const chol_trsm_desc *tdescs, int n_trsm,

@@ -13,6 +13,7 @@
 // hold 16 consecutive rows of one column and the read-modify-write of the column-major target is
 // made of 128-byte segments.
 #include <hip/hip_runtime.h>
+#include <float.h>
 #include <stdint.h>
 
 #include "chol_plan.h"
@@ -146,6 +147,53 @@ __global__ void k_scatter(double *__restrict__ arena, const int64_t *__restrict_
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (; i < nnz; i += stride) arena[dst[i]] = val[i];
+}
+
+// ------------------------------------------------------------------------------------------------
+// New values of A on the same pattern (cholamd_device_set_values).  Three index spaces laid end to end, [i0, i1) of them per launch:
+//   [0, nz)                    the value array itself: the status words (what the values are, by the entry's class chol_plan.e_cls)
+//   [nz, nz + nnz_a)           a_val[e] = vals[a_src[e]]: the scatter list of the fills
+//   [nz + nnz_a, ... + ncsr)   csr_val[k] = vals[csr_src[k]]: the residual operator (both triangles point at the same index)
+// The destination side is coalesced, vals[...] an 8-byte gather through int indices.  status[0] / [2] count the in-pattern values that are
+// non-zero and not a normal float in magnitude (NaN and inf included: every comparison with them is false) / the out-of-pattern entries
+// that are not +-0.0; status[1] / [3] = the smallest index of one (they start at INT64_MAX).  Every lane keeps its own counts and minimum,
+// the wave reduces them, lane 0 issues one atomic add and one 64-bit atomic minimum per word pair the wave has something for: the
+// first offender does not depend on the order the waves arrive in.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_set_values(const double *__restrict__ vals, int64_t nz, const unsigned char *__restrict__ cls,
+                                                    double *__restrict__ a_val, const int *__restrict__ a_src, int64_t nnz_a,
+                                                    double *__restrict__ csr_val, const int *__restrict__ csr_src, int64_t i0, int64_t i1,
+                                                    int64_t *__restrict__ status)
+{
+  const long long none = 0x7fffffffffffffffLL;
+  long long nbad = 0, fbad = none, nout = 0, fout = none;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = i0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < i1; i += stride) {
+    if (i < nz) {
+      const double v = vals[i], a = fabs(v);
+      const int c = cls[i];
+      if (c == CHOL_ENTRY_IN && v != 0.0 && !(a <= (double)FLT_MAX && a >= (double)FLT_MIN)) { nbad++; fbad = i < fbad ? i : fbad; }
+      if (c == CHOL_ENTRY_OUT && v != 0.0) { nout++; fout = i < fout ? i : fout; }
+    } else if (i < nz + nnz_a) a_val[i - nz] = vals[a_src[i - nz]];
+    else csr_val[i - nz - nnz_a] = vals[csr_src[i - nz - nnz_a]];
+  }
+  if (i0 >= nz) return; // (launch-uniform) no part of the value array in this launch
+  for (int o = 32; o > 0; o >>= 1) {
+    nbad += __shfl_down(nbad, o, 64); nout += __shfl_down(nout, o, 64);
+    const long long b = __shfl_down(fbad, o, 64), u = __shfl_down(fout, o, 64);
+    fbad = b < fbad ? b : fbad; fout = u < fout ? u : fout;
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (nbad) { atomicAdd((unsigned long long *)&status[0], (unsigned long long)nbad); atomicMin((long long *)&status[1], fbad); }
+    if (nout) { atomicAdd((unsigned long long *)&status[2], (unsigned long long)nout); atomicMin((long long *)&status[3], fout); }
+  }
+}
+// out[i] = in[idx[i]]: the owned-top copies of a partitioned device follow the scatter list (top_entries)
+__global__ void k_gather(double *__restrict__ out, const double *__restrict__ in, const int *__restrict__ idx, int64_t n)
+{
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (; i < n; i += stride) out[i] = in[idx[i]];
 }
 
 // Staged waits of an extend-add job of the program launch (chol_upd_src.stage): the job's sources become readable one source pivot
@@ -3442,6 +3490,24 @@ int chol_launch_scatter(double *arena, const int64_t *dst, const double *val, in
   int blocks = (int)((nnz + 255) / 256);
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(k_scatter, dim3(blocks), dim3(256), 0, st, arena, dst, val, nnz);
+  return (int)hipGetLastError();
+}
+int chol_launch_set_values(const double *vals, int64_t nz, const unsigned char *cls, double *a_val, const int *a_src, int64_t nnz_a,
+                           double *csr_val, const int *csr_src, int64_t ncsr, int parts, int64_t *status, hipStream_t st)
+{
+  const int64_t i0 = (parts & CHOL_VALUES_STATUS) ? 0 : nz, i1 = (parts & CHOL_VALUES_GATHER) ? nz + nnz_a + ncsr : nz;
+  if (i1 <= i0) return 0;
+  int blocks = (int)((i1 - i0 + 255) / 256);
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(k_set_values, dim3(blocks), dim3(256), 0, st, vals, nz, cls, a_val, a_src, nnz_a, csr_val, csr_src, i0, i1, status);
+  return (int)hipGetLastError();
+}
+int chol_launch_gather(double *out, const double *in, const int *idx, int64_t n, hipStream_t st)
+{
+  if (n <= 0) return 0;
+  int blocks = (int)((n + 255) / 256);
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(k_gather, dim3(blocks), dim3(256), 0, st, out, in, idx, n);
   return (int)hipGetLastError();
 }
 int chol_launch_potrf(double *base, double *ws, const chol_potrf_desc *descs, int n, int *info, hipStream_t st)

@@ -24,6 +24,9 @@
 extern "C" {
 #endif
 
+#define CHOL_ENTRY_OUT 0     /* chol_plan.e_cls */
+#define CHOL_ENTRY_IN 1
+#define CHOL_ENTRY_DROPPED 2
 #define CHOL_NB 16        /* diagonal-block width of the POTRF/TRSM kernels = one fp64 MFMA tile */
 #define CHOL_RR_MAXN 272  /* largest pivot the register-resident kernels take (17 tiles) */
 #ifndef CHOL_FOLLOW_ALL_MAXT
@@ -335,6 +338,11 @@ struct cholamd_plan {
   int64_t nnz_a, dropped; int64_t *a_dst; double *a_val;
   /* A, both triangles, CSR over ORIGINAL dof indices (residual of the iterative refinement) */
   int64_t *csr_ptr; int *csr_col; double *csr_val;
+  /* the VALUE ARRAY: nz_file doubles in the order plan creation received the entries (cholamd_device_set_values).  e_row / e_col: the entry
+   * list itself (original 0-based coordinates); a_src[e] / csr_src[k]: index in the value array of scatter entry e / CSR entry k (both
+   * triangles point at the same index); e_cls[k]: what became of entry k -- outside the pattern (0.0 at creation: in neither list), in the
+   * scatter list and the CSR, or dropped by the ordering (CSR only) */
+  int *e_row, *e_col, *a_src, *csr_src; unsigned char *e_cls;
   /* fill snapshots per interval label */
   int64_t *snap_n; cholamd_filled **snap;
   /* reference-order BLAS call list */

@@ -251,6 +251,11 @@ int chol_plan_finish(plan_t *p, int nz, const int *a_row, const int *a_col, cons
   for (int b = 0; b < p->nblk; b++) { F[b].f = NULL; fill_resize(&F[b], 0, chol_ntiles(p, p->blk[b].r, 0), chol_ntiles(p, p->blk[b].c, 0)); }
   p->a_dst = malloc((size_t)(nz > 0 ? nz : 1) * sizeof(int64_t));
   p->a_val = malloc((size_t)(nz > 0 ? nz : 1) * sizeof(double));
+  p->a_src = malloc((size_t)(nz > 0 ? nz : 1) * sizeof(int));
+  p->e_row = malloc((size_t)(nz > 0 ? nz : 1) * sizeof(int));
+  p->e_col = malloc((size_t)(nz > 0 ? nz : 1) * sizeof(int));
+  p->e_cls = calloc((size_t)(nz > 0 ? nz : 1), 1); /* CHOL_ENTRY_OUT */
+  if (nz > 0) { memcpy(p->e_row, a_row, (size_t)nz * sizeof(int)); memcpy(p->e_col, a_col, (size_t)nz * sizeof(int)); }
   p->nnz_a = 0; p->dropped = 0;
   int *px = malloc((size_t)(nz > 0 ? nz : 1) * sizeof(int)), *py = malloc((size_t)(nz > 0 ? nz : 1) * sizeof(int));
   unsigned char **keep = calloc(p->nblk, sizeof(unsigned char *)); /* per block: the 16-row tiles the panel must store */
@@ -259,17 +264,18 @@ int chol_plan_finish(plan_t *p, int nz, const int *a_row, const int *a_col, cons
     if (i < 0 || j < 0 || i >= n || j >= n) {
       chol_set_error("matrix entry %d out of range", e);
       for (int b = 0; b < p->nblk; b++) free(F[b].f);
-      free(F); free(px); free(py); free(keep); /* a_dst / a_val belong to the plan: cholamd_plan_destroy frees them */
+      free(F); free(px); free(py); free(keep); /* a_dst / a_val / a_src belong to the plan: cholamd_plan_destroy frees them */
       return CHOLAMD_ERR_FORMAT;
     }
     if (a_val[e] == 0.0) continue; /* explicit zeros are invisible to the reference (mnd.c:168-195) */
     int pi = p->iperm[i], pj = p->iperm[j];
     int x = pi > pj ? pi : pj, y = pi > pj ? pj : pi;
     int bi = BIDX(p, p->sep_of_pos[x], p->sep_of_pos[y]);
-    if (bi < 0) { p->dropped++; continue; } /* not in an ancestor/descendant block: the ordering is not a valid ND */
+    if (bi < 0) { p->dropped++; p->e_cls[e] = CHOL_ENTRY_DROPPED; continue; } /* not in an ancestor/descendant block: the ordering is not a valid ND */
     const chol_block *b = &p->blk[bi];
     p->a_dst[p->nnz_a] = bi; /* the block for now: the arena offset once the panels are laid out */
     p->a_val[p->nnz_a] = a_val[e];
+    p->a_src[p->nnz_a] = e; p->e_cls[e] = CHOL_ENTRY_IN;
     px[p->nnz_a] = x; py[p->nnz_a] = y;
     p->nnz_a++;
     int tr = tile_of(&p->cl[b->r], 0, x - b->lo_x), tc = tile_of(&p->cl[b->c], 0, y - b->lo_y);
@@ -287,13 +293,14 @@ int chol_plan_finish(plan_t *p, int nz, const int *a_row, const int *a_col, cons
     for (int i = 0; i < n; i++) ptr[i + 1] += ptr[i];
     p->csr_col = malloc((size_t)(ptr[n] > 0 ? ptr[n] : 1) * sizeof(int));
     p->csr_val = malloc((size_t)(ptr[n] > 0 ? ptr[n] : 1) * sizeof(double));
+    p->csr_src = malloc((size_t)(ptr[n] > 0 ? ptr[n] : 1) * sizeof(int));
     int64_t *fillp = malloc((size_t)(n > 0 ? n : 1) * sizeof(int64_t));
     memcpy(fillp, ptr, (size_t)n * sizeof(int64_t));
     for (int e = 0; e < nz; e++) {
       if (a_val[e] == 0.0) continue;
       const int i = a_row[e], j = a_col[e];
-      p->csr_col[fillp[i]] = j; p->csr_val[fillp[i]++] = a_val[e];
-      if (i != j) { p->csr_col[fillp[j]] = i; p->csr_val[fillp[j]++] = a_val[e]; }
+      p->csr_col[fillp[i]] = j; p->csr_src[fillp[i]] = e; p->csr_val[fillp[i]++] = a_val[e];
+      if (i != j) { p->csr_col[fillp[j]] = i; p->csr_src[fillp[j]] = e; p->csr_val[fillp[j]++] = a_val[e]; }
     }
     free(fillp);
     p->csr_ptr = ptr;
@@ -459,11 +466,11 @@ int chol_plan_finish(plan_t *p, int nz, const int *a_row, const int *a_col, cons
   free(px); free(py);
   { /* ascending arena offsets: coalesced device scatter, and the entries of the shared top of the
      * tree (the tail of the arena) form a suffix that non-root ranks skip (multi-GPU fill) */
-    typedef struct { int64_t d; double v; } dv_t;
+    typedef struct { int64_t d; double v; int s; } dv_t;
     dv_t *t = malloc((size_t)(p->nnz_a > 0 ? p->nnz_a : 1) * sizeof(dv_t));
-    for (int64_t e = 0; e < p->nnz_a; e++) { t[e].d = p->a_dst[e]; t[e].v = p->a_val[e]; }
+    for (int64_t e = 0; e < p->nnz_a; e++) { t[e].d = p->a_dst[e]; t[e].v = p->a_val[e]; t[e].s = p->a_src[e]; }
     qsort(t, (size_t)p->nnz_a, sizeof(dv_t), cmp_dv);
-    for (int64_t e = 0; e < p->nnz_a; e++) { p->a_dst[e] = t[e].d; p->a_val[e] = t[e].v; }
+    for (int64_t e = 0; e < p->nnz_a; e++) { p->a_dst[e] = t[e].d; p->a_val[e] = t[e].v; p->a_src[e] = t[e].s; }
     free(t);
   }
   return 0;
@@ -615,6 +622,7 @@ void cholamd_plan_destroy(cholamd_plan *p)
   free(p->sep_off); free(p->tree); free(p->heap_of); free(p->level_of); free(p->blk); free(p->blk_index);
   free(p->panel_off); free(p->panel_ld); free(p->panel_rows); free(p->dinv_off); free(p->a_dst); free(p->a_val); free(p->ops);
   free(p->csr_ptr); free(p->csr_col); free(p->csr_val);
+  free(p->e_row); free(p->e_col); free(p->a_src); free(p->csr_src); free(p->e_cls);
   free(p);
 }
 
@@ -682,6 +690,24 @@ int cholamd_plan_fill_host(const cholamd_plan *p, double *arena)
 {
   memset(arena, 0, (size_t)p->arena * sizeof(double));
   for (int64_t e = 0; e < p->nnz_a; e++) arena[p->a_dst[e]] = p->a_val[e];
+  return 0;
+}
+
+int cholamd_plan_entries(const cholamd_plan *p, int *row, int *col)
+{
+  if (p->nz_file > 0) { memcpy(row, p->e_row, (size_t)p->nz_file * sizeof(int)); memcpy(col, p->e_col, (size_t)p->nz_file * sizeof(int)); }
+  return 0;
+}
+int cholamd_plan_value_map(const cholamd_plan *p, int64_t *src_out)
+{
+  for (int64_t e = 0; e < p->nnz_a; e++) src_out[e] = p->a_src[e];
+  return 0;
+}
+int cholamd_plan_fill_host_values(const cholamd_plan *p, const double *vals, int64_t count, double *arena)
+{
+  if (!vals || count != p->nz_file) { chol_set_error("value array of %lld entries, the plan has %d", (long long)count, p->nz_file); return CHOLAMD_ERR_ARG; }
+  memset(arena, 0, (size_t)p->arena * sizeof(double));
+  for (int64_t e = 0; e < p->nnz_a; e++) arena[p->a_dst[e]] = vals[p->a_src[e]];
   return 0;
 }
 

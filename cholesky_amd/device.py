@@ -8,6 +8,8 @@ import numpy as np
 
 from ._lib import check, load
 
+_check = check  # Device.set_values has a parameter of that name
+
 
 def _stream_ptr(stream):
     if stream is None:
@@ -51,6 +53,7 @@ class Device:
         check(self.L.cholamd_device_create(plan.h, device_id, C.byref(h)), "cholamd_device_create")
         self.h = h
         self._owned = []
+        self._values_buf = None  # set_values: the device copy of a host value array
 
     def __del__(self):
         try:
@@ -102,6 +105,41 @@ class Device:
     def fill(self, arena, stream=None):
         """A scatter on the device: fill_block for every block (mmat.rg:1216-1224)."""
         check(self.L.cholamd_device_fill(self.h, self.ptr(arena), _stream_ptr(stream)), "cholamd_device_fill")
+
+    VALUES_NOCHECK = 1  # CHOLAMD_VALUES_NOCHECK
+
+    def set_values(self, values, check=True, stream=None):
+        """New values of A on the plan's pattern (cholamd_device_set_values): `values` is the value array of plan.nz doubles in the order of
+        plan.entries() -- a contiguous 1-D float64 tensor on this device is read where it is, a 1-D float64 numpy array is uploaded through a
+        buffer this object keeps.  Anything else raises ValueError.  Fill and factor afterwards; residuals and refinements measure against the
+        new A.  check=True synchronises once and refuses (CholamdError, previous values kept) an array that gives an out-of-pattern entry a
+        non-zero value; check=False is asynchronous on `stream` and ignores such values (values_status() reports them)."""
+        import torch
+        nz = self.plan.nz
+        if isinstance(values, np.ndarray):
+            if values.dtype != np.float64 or values.ndim != 1 or values.size != nz or not values.flags.c_contiguous:
+                raise ValueError(f"values must be a contiguous 1-D float64 array of plan.nz = {nz} elements; got {values.dtype} {values.shape}")
+            if self._values_buf is None:
+                self._values_buf = torch.empty(max(nz, 1), dtype=torch.float64, device=f"cuda:{self.device_id}")
+            self.upload(self._values_buf, values, stream)
+            ptr = self._values_buf.data_ptr()
+        elif isinstance(values, torch.Tensor):
+            if values.dtype != torch.float64 or values.dim() != 1 or values.numel() != nz or not values.is_contiguous():
+                raise ValueError(f"values must be a contiguous 1-D float64 tensor of plan.nz = {nz} elements; got {values.dtype} {tuple(values.shape)} strides {values.stride()}")
+            if not values.is_cuda or values.device.index != self.device_id:
+                raise ValueError(f"values must live on cuda:{self.device_id}; got {values.device}")
+            ptr = values.data_ptr()
+        else:
+            raise ValueError("values must be a float64 numpy array or CUDA tensor")
+        _check(self.L.cholamd_device_set_values(self.h, C.c_void_p(ptr), nz, 0 if check else self.VALUES_NOCHECK, _stream_ptr(stream)),
+               "cholamd_device_set_values")
+
+    def values_status(self, stream=None):
+        """(in-pattern values that are non-zero and not a normal float in magnitude, the first one's value-array index or -1, out-of-pattern
+        entries whose value is not zero, the first one's index or -1) of the last set_values call (cholamd_device_values_status)."""
+        out = np.zeros(4, dtype=np.int64)
+        _check(self.L.cholamd_device_values_status(self.h, _stream_ptr(stream), out.ctypes.data), "cholamd_device_values_status")
+        return tuple(int(v) for v in out)
 
     def factor(self, arena, stream=None):
         """The level loop (mmat.rg:1227-1355), asynchronous on `stream`."""

@@ -131,10 +131,29 @@ class Plan:
         self.L.cholamd_plan_counts(self.h, level, c.ctypes.data, f.ctypes.data)
         return c, f
 
-    def fill_host(self):
-        """fill_block for every block: the arena holding P A P^T (host array)."""
+    def entries(self):
+        """(row, col) of the entry list in value-array order: original 0-based coordinates, in the order plan creation received them
+        (cholamd_plan_entries).  Entry k of a value array (fill_host(values), Device.set_values) is the value of entry k of this list."""
+        row, col = np.zeros(self.nz, dtype=np.int32), np.zeros(self.nz, dtype=np.int32)
+        check(self.L.cholamd_plan_entries(self.h, row.ctypes.data, col.ctypes.data), "cholamd_plan_entries")
+        return row, col
+
+    def value_map(self):
+        """Index in the value array of every scatter entry (nnz_a of them, ascending arena offset): cholamd_plan_value_map.  The indices that
+        do not occur are outside the pattern (0.0 at creation) or were dropped by the ordering."""
+        out = np.zeros(self.nnz_a, dtype=np.int64)
+        check(self.L.cholamd_plan_value_map(self.h, out.ctypes.data), "cholamd_plan_value_map")
+        return out
+
+    def fill_host(self, values=None):
+        """fill_block for every block: the arena holding P A P^T (host array).  `values`: a value array of `nz` doubles (see entries()) to
+        scatter instead of the plan's own values."""
         a = np.zeros(self.arena_doubles, dtype=np.float64)
-        check(self.L.cholamd_plan_fill_host(self.h, a.ctypes.data), "cholamd_plan_fill_host")
+        if values is None:
+            check(self.L.cholamd_plan_fill_host(self.h, a.ctypes.data), "cholamd_plan_fill_host")
+        else:
+            v = np.ascontiguousarray(values, dtype=np.float64)
+            check(self.L.cholamd_plan_fill_host_values(self.h, v.ctypes.data, v.size, a.ctypes.data), "cholamd_plan_fill_host_values")
         return a
 
     def fill_host_part(self, rank, world):

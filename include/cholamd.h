@@ -175,6 +175,22 @@ int64_t cholamd_plan_alg_bytes(const cholamd_plan *p);      /* B_alg = 8 (nnz(tr
 
 /* fill_block for every block (mmat.rg:529-633, 1216-1224): zero the arena and scatter A. */
 int cholamd_plan_fill_host(const cholamd_plan *p, double *arena);
+/* ---- the VALUE ARRAY: cholamd_plan_nz() doubles in the order in which plan creation received the entries (file order for cholamd_plan_create,
+ * array order for _from_arrays, the generator's own order for _from_problem); entry k of the array is the value of entry k of that list.  It is how
+ * new values of A on the same pattern reach a plan's consumers (here on the host; cholamd_device_set_values on the device).  The plan itself is
+ * immutable: its own values, the writers and cholamd_plan_fill_host are what they were at creation.
+ * Entries that were exactly 0.0 at creation are OUTSIDE THE PATTERN: invisible to the reference (mnd.c:168-195), they have no place in the scatter
+ * list or the residual operator, and no later value can give them one (that is a new plan).
+ * cholamd_plan_entries: the entry list in value-array order (original 0-based coordinates, as stored: a symmetric file's entry stays on its side of
+ * the diagonal), so a caller need not re-read the file to know the order.
+ * cholamd_plan_value_map: src_out[e] = index in the value array of scatter entry e, cholamd_plan_nnz_a() of them in the order of the scatter
+ * (ascending arena offset); the value-array indices that do not occur are out of the pattern or were dropped by the ordering
+ * (cholamd_plan_dropped_entries; those stay in the residual operator).
+ * cholamd_plan_fill_host_values: cholamd_plan_fill_host with the value array `vals` instead of the plan's own values; count != cholamd_plan_nz()
+ * or a NULL array: CHOLAMD_ERR_ARG, nothing written. */
+int cholamd_plan_entries(const cholamd_plan *p, int *row, int *col);
+int cholamd_plan_value_map(const cholamd_plan *p, int64_t *src_out);
+int cholamd_plan_fill_host_values(const cholamd_plan *p, const double *vals, int64_t count, double *arena);
 /* Multi-GPU view of the same: with `world` ranks the shared top of the tree (the tail of
  * the arena starting at *tail_offset_out) receives A's entries on rank 0 only, so that the sum over
  * ranks of the tails after the local levels equals A_top minus every contribution. */
@@ -280,6 +296,31 @@ int cholamd_device_sync(cholamd_device *d, void *stream);
  * top levels are replicated, those of the column blocks the rank OWNS when they are distributed (option dist_top) -- fill after set_partition /
  * set_option, with the schedule the factorisation will use. */
 int cholamd_device_fill(cholamd_device *d, double *d_arena, void *stream);
+/* ---- new values of A on the same pattern, from DEVICE memory, without a new plan (Newton / interior-point steps, time stepping, shifted systems).
+ * d_vals: a device array of count = cholamd_plan_nz() doubles, the value array described at cholamd_plan_entries.  One gather pass on `stream`
+ * replaces every copy of A's values the device object holds: the scatter list of cholamd_device_fill / _fill_f32 (the column blocks a partitioned
+ * device owns included, also when cholamd_device_set_option / _set_partition rebuild them later), and the operator of cholamd_residual and of every
+ * refinement.  After it every entry point that takes the device object behaves as that of a device object on a plan created from the same entries
+ * with these values.  Schedules, work lists, the program, the solve lists and the plan are NOT touched, arenas already filled neither: fill again,
+ * then factor.  The values belong to the device object: two objects on one plan hold independent values, and every rank object of a multi-rank run
+ * needs the call.  d_vals is read during the call's kernels only.  The first call on a device object uploads the index lists (and the residual
+ * operator, if no refinement has done so); later calls allocate nothing.
+ * Zeros: an in-pattern entry may become 0.0 -- it is stored and factored as an explicit zero.  An entry OUTSIDE the pattern (0.0 at creation) cannot
+ * become non-zero: envelope, skylines and solve bands were derived from the creation-time pattern.
+ * flags = 0: the call looks at the values first (one synchronisation of `stream`, 32 bytes read back); an out-of-pattern entry that is not +-0.0 makes
+ * it return CHOLAMD_ERR_ARG naming the first such entry, and the device object's PREVIOUS values stay in force.
+ * flags = CHOLAMD_VALUES_NOCHECK: asynchronous on `stream`, no synchronisation; such values are ignored (they have no slot anywhere).
+ * count != cholamd_plan_nz(), a NULL pointer, a negative or unknown flag: CHOLAMD_ERR_ARG, nothing written.
+ * NaN / inf / values outside float's range are not refused here: the fp64 path takes them as a plan created with them would (the pivot checks report
+ * what they do), and the fp32 range rule (at cholamd_device_fill_f32) follows the CURRENT values: it names the value-array index of the first
+ * in-pattern value that is non-zero and not a normal float in magnitude (read back lazily, once per set_values, by the first fp32 entry point).
+ * cholamd_device_values_status: the counts of the most recent cholamd_device_set_values call, accepted or refused (synchronises `stream` if they have
+ * not been read yet): out[0] in-pattern values that are non-zero and not a normal float in magnitude (|v| > FLT_MAX or < FLT_MIN, NaN and inf
+ * included), out[1] the smallest value-array index of one (-1: none), out[2] out-of-pattern entries whose value is not +-0.0, out[3] the smallest
+ * index of one (-1: none).  Before the first call: CHOLAMD_ERR_ARG. */
+#define CHOLAMD_VALUES_NOCHECK 1
+int cholamd_device_set_values(cholamd_device *d, const double *d_vals, int64_t count, int flags, void *stream);
+int cholamd_device_values_status(cholamd_device *d, void *stream, int64_t out[4]);
 /* The hot path: the whole level loop of mmat.rg:1227-1355 on d_arena, asynchronously on stream.  Small problems (every
  * pivot block <= 192 columns, no macro-tile phase: the reference's fixtures) run as ONE launch of resident workgroups that
  * draw POTRF / TRSM / update jobs from a queue and hand data to each other through counters (option "program"); otherwise,
@@ -449,7 +490,8 @@ int cholamd_exchange_tail(cholamd_device *d, double *d_arena, cholamd_comm *c, v
 /* elements this rank receives / sends in that exchange, elements of the tail, column-block pieces (0 pieces: the all-reduce) */
 int cholamd_exchange_volume(const cholamd_device *d, int64_t out[4]);
 /* one rank's part of a sharded factorisation: local levels, exchange, top levels; asynchronous on `stream`.
- * The arena must have been filled by cholamd_device_fill AFTER cholamd_device_set_partition (rank-aware fill). */
+ * The arena must have been filled by cholamd_device_fill AFTER cholamd_device_set_partition (rank-aware fill).  New values of A
+ * (cholamd_device_set_values) belong to a device object: every rank's object needs the call, with the same value array, before its fill. */
 int cholamd_factor_sharded(cholamd_device *d, double *d_arena, cholamd_comm *c, void *stream);
 /* the same with the fp32 factor (mixed precision x multi-GPU, BASELINE config 5): fp32 arena (cholamd_device_fill_f32 after
  * set_partition), the fp32 schedule partitioned like the fp64 one, exchange and broadcasts on floats */
