@@ -159,6 +159,15 @@ def load():
     L.cholamd_solve_nrhs.argtypes = [vp, vp, vp, i64, vp, i64, ci, vp]
     L.cholamd_solve_nrhs_f32.argtypes = [vp, vp, vp, i64, vp, i64, ci, vp]
     L.cholamd_solve_refine_nrhs.argtypes = [vp, vp, vp, i64, vp, i64, ci, ci, cd, C.POINTER(ci), vp, vp]
+    L.cholamd_solve_half.argtypes = [vp, vp, vp, vp, ci, vp]
+    L.cholamd_solve_half_f32.argtypes = [vp, vp, vp, vp, ci, vp]
+    L.cholamd_solve_half_nrhs.argtypes = [vp, vp, vp, i64, vp, i64, ci, ci, vp]
+    L.cholamd_solve_half_nrhs_f32.argtypes = [vp, vp, vp, i64, vp, i64, ci, ci, vp]
+    L.cholamd_factor_logdet.argtypes = [vp, vp, C.POINTER(cd), vp]
+    L.cholamd_factor_logdet_f32.argtypes = [vp, vp, C.POINTER(cd), vp]
+    L.cholamd_factor_diag.argtypes = [vp, vp, vp, vp]
+    L.cholamd_factor_diag_f32.argtypes = [vp, vp, vp, vp]
+    L.cholamd_plan_diag_list.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.cholamd_device_alloc_arena.argtypes = [vp, ci, C.POINTER(vp), C.POINTER(C.c_int64)]
     L.cholamd_device_free_arena.argtypes = [vp, vp]
     L.cholamd_device_set_timing.argtypes = [vp, ci]

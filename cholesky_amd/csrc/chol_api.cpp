@@ -108,6 +108,10 @@ struct cholamd_device {
   // block solve (cholamd_solve_nrhs): the permuted block of one chunk (n x CHOL_NRHS_W, row-major); refinement: the chunk's right-hand sides, residual and
   // correction (n x CHOL_NRHS_W, column-major) and the per-column partial sums of the residual kernel
   double *ynrhs = nullptr, *bnrhs = nullptr, *rnrhs = nullptr, *dxnrhs = nullptr, *pnrhs = nullptr;
+  // factor queries (cholamd_factor_diag / _logdet): the TRSV descriptors of the whole tree in one list ordered by permuted position and the prefix of their
+  // column counts (built with the solve lists of rank 0 of 1); the logdet's per-workgroup partial sums, their integer companions and the three result words
+  chol_trsv_desc *dg_desc = nullptr; int *dg_prefix = nullptr; int n_dg = 0;
+  double *ld_part = nullptr; int64_t *ld_ipart = nullptr, *ld_res = nullptr;
 };
 
 static int no_device_error()
@@ -175,6 +179,7 @@ static void free_solve_lists(cholamd_device *d)
   for (auto &s : d->sv) { (void)hipFree(s.trsv); (void)hipFree(s.fw); (void)hipFree(s.bw); (void)hipFree(s.grp_start); (void)hipFree(s.grp_rows); (void)hipFree(s.bw_start); (void)hipFree(s.ifw); (void)hipFree(s.ibw); }
   d->sv.clear();
   (void)hipFree(d->w256); d->w256 = nullptr;
+  (void)hipFree(d->dg_desc); d->dg_desc = nullptr; (void)hipFree(d->dg_prefix); d->dg_prefix = nullptr; d->n_dg = 0;
   (void)hipFree(d->zr_sub); d->zr_sub = nullptr; d->n_zr_sub = 0;
   d->solve_ready = false;
 }
@@ -310,6 +315,7 @@ extern "C" void cholamd_device_destroy(cholamd_device *d)
   (void)hipFree(d->ws32); (void)hipFree(d->csr_ptr); (void)hipFree(d->csr_col); (void)hipFree(d->csr_val); (void)hipFree(d->rvec); (void)hipFree(d->dxvec); (void)hipFree(d->partial);
   (void)hipFree(d->xstage); (void)hipFree(d->xdesc);
   (void)hipFree(d->ws); (void)hipFree(d->ws_solve); (void)hipFree(d->step_flags); (void)hipFree(d->w256); (void)hipFree(d->step_xt); (void)hipFree(d->info); (void)hipFree(d->progress); (void)hipFree(d->a_dst); (void)hipFree(d->a_val); (void)hipFree(d->perm); (void)hipFree(d->ytmp);
+  (void)hipFree(d->ld_part); (void)hipFree(d->ld_ipart); (void)hipFree(d->ld_res);
   (void)hipFree(d->ynrhs); (void)hipFree(d->bnrhs); (void)hipFree(d->rnrhs); (void)hipFree(d->dxnrhs); (void)hipFree(d->pnrhs);
   for (int q = 0; q < 2; q++) { (void)hipFree(d->top_dst[q]); (void)hipFree(d->top_val[q]); (void)hipFree(d->top_e[q]); }
   (void)hipFree(d->a_src); (void)hipFree(d->csr_src); (void)hipFree(d->e_cls); (void)hipFree(d->vs_dev); (void)hipFree(d->vs_init); (void)hipHostFree(d->vs_host);
@@ -784,10 +790,12 @@ static int build_solve(cholamd_device *d, int rank = 0, int world = 1)
     d->n_zr_sub = (int)zr.size() / 2;
     if (!zr.empty()) { int rc = upload_vec(&d->zr_sub, zr.data(), zr.size()); if (rc) return rc; }
   }
+  std::vector<chol_trsv_desc> diag; // the whole tree's lists only: the diagonal walk of the factor queries
   for (int lvl = 0; lvl < L; lvl++) {
     chol_solve_level w;
     int rc = chol_build_solve_level_part(d->plan, lvl, rank, world, &w);
     if (rc) return rc;
+    if (world == 1) diag.insert(diag.end(), w.trsv, w.trsv + w.n_trsv);
     solve_dev &s = d->sv[lvl];
     s.n_trsv = w.n_trsv; s.n_grp = w.n_grp; s.n_fw = w.n_fw; s.n_bw = w.n_bw;
     rc = upload_vec(&s.trsv, w.trsv, (size_t)w.n_trsv);
@@ -801,6 +809,14 @@ static int build_solve(cholamd_device *d, int rank = 0, int world = 1)
     if (!rc) rc = upload_vec(&s.ibw, w.ibw, (size_t)4 * w.n_ibw);
     chol_solve_level_free(&w);
     if (rc) return rc;
+  }
+  if (!diag.empty()) {
+    std::vector<int> prefix(diag.size() + 1);
+    int rc = chol_diag_list(d->plan, diag.data(), (int)diag.size(), prefix.data());
+    if (!rc) rc = upload_vec(&d->dg_desc, diag.data(), diag.size());
+    if (!rc) rc = upload_vec(&d->dg_prefix, prefix.data(), prefix.size());
+    if (rc) return rc;
+    d->n_dg = (int)diag.size();
   }
   if (!d->ytmp) HIPCHK(fp_malloc((void **)&d->ytmp, (size_t)d->plan->n * sizeof(double)));
   if (!d->ws_solve) HIPCHK(fp_malloc((void **)&d->ws_solve, (size_t)(d->plan->ws_doubles > 0 ? d->plan->ws_doubles : 1) * sizeof(double)));
@@ -1190,12 +1206,45 @@ static int nrhs_check(cholamd_device *d, const void *arena, const double *B, int
 // chunk of fewer columns than this is solved column by column with the single-vector path.  Measured on one MI355X: a block chunk
 // takes 3.0 - 3.3 single fp64 solves and 5.0 single fp32-factor solves.
 template <class TL> static constexpr int nrhs_min_block() { return sizeof(TL) == sizeof(double) ? 4 : 6; }
+// The same rule for one triangular half (cholamd_solve_half_nrhs): a half chunk and a half single solve both drop one of the two sweeps.  DESIGN.md section 10
+// records the measurement behind the value.
+template <class TL> static constexpr int half_nrhs_min_block() { return sizeof(TL) == sizeof(double) ? 4 : 6; }
+// One triangular half of the streamed solve on the whole tree, x = P^T L^-1 P b (CHOLAMD_HALF_FORWARD) or P^T L^-T P b (CHOLAMD_HALF_BACKWARD): the
+// launches of that sweep of solve_phase between the two permutes, the diagonal inverses of THIS arena first unless the caller keeps them.
+template <class TL> static int solve_half_streamed(cholamd_device *d, const TL *d_arena, const double *d_b, double *d_x, int which, hipStream_t st)
+{
+  { int rc = build_solve(d); if (rc) return rc; }
+  const int L = d->plan->levels, n = d->plan->n;
+  double *y = d->ytmp;
+  HIPCHK((hipError_t)chol_launch_permute(d_b, d->perm, y, n, 0, st));
+  for (int lvl = 0; lvl < L && !d->keep_inverses; lvl++) {
+    const solve_dev &s = d->sv[lvl];
+    HIPCHK((hipError_t)lsolve_dinv(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, st));
+    if (s.w256_off >= 0 && d->w256) HIPCHK((hipError_t)lsolve_inv256(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, d->w256 + s.w256_off, st));
+  }
+  if (which == CHOLAMD_HALF_FORWARD)
+    for (int lvl = L - 1; lvl >= 0; lvl--) {
+      const solve_dev &s = d->sv[lvl];
+      HIPCHK((hipError_t)lsolve_trsv(d, d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, y, 0, s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr, st));
+      HIPCHK((hipError_t)lsolve_off(d_arena, s.bw, s.ifw, s.n_ifw, y, 0, st));
+    }
+  else
+    for (int lvl = 0; lvl < L; lvl++) {
+      const solve_dev &s = d->sv[lvl];
+      HIPCHK((hipError_t)lsolve_off(d_arena, s.bw, s.ibw, s.n_ibw, y, 1, st));
+      HIPCHK((hipError_t)lsolve_trsv(d, d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, y, 1, s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr, st));
+    }
+  HIPCHK((hipError_t)chol_launch_permute(y, d->perm, d_x, n, 1, st));
+  return 0;
+}
 struct keep_restore { // keep_inverses for the chunks of one call, the caller's value back on every way out
   cholamd_device *d; bool old;
   explicit keep_restore(cholamd_device *d_) : d(d_), old(d_->keep_inverses) {}
   ~keep_restore() { d->keep_inverses = old; }
 };
-template <class TL> static int solve_nrhs_t(cholamd_device *d, const TL *d_arena, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int nrhs, hipStream_t st)
+// which: CHOL_BOTH_SWEEPS (the solve), or one CHOLAMD_HALF_* sweep alone (cholamd_solve_half_nrhs)
+#define CHOL_BOTH_SWEEPS (-1)
+template <class TL> static int solve_nrhs_t(cholamd_device *d, const TL *d_arena, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int nrhs, hipStream_t st, int which = CHOL_BOTH_SWEEPS)
 {
   { int rc = build_solve(d); if (rc) return rc; }
   const int L = d->plan->levels, n = d->plan->n;
@@ -1208,20 +1257,24 @@ template <class TL> static int solve_nrhs_t(cholamd_device *d, const TL *d_arena
   d->keep_inverses = true; // (the column-by-column chunks: solve_streamed reuses them)
   for (int c0 = 0; c0 < nrhs; c0 += CHOL_NRHS_W) {
     const int cols = std::min(CHOL_NRHS_W, nrhs - c0);
-    if (cols < nrhs_min_block<TL>()) {
-      for (int j = c0; j < c0 + cols; j++) { int rc = solve_streamed(d, d_arena, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, st); if (rc) return rc; }
+    if (cols < (which == CHOL_BOTH_SWEEPS ? nrhs_min_block<TL>() : half_nrhs_min_block<TL>())) {
+      for (int j = c0; j < c0 + cols; j++) {
+        int rc = which == CHOL_BOTH_SWEEPS ? solve_streamed(d, d_arena, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, st)
+                                           : solve_half_streamed(d, d_arena, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, which, st);
+        if (rc) return rc;
+      }
       continue;
     }
     if (!d->ynrhs) HIPCHK(fp_malloc((void **)&d->ynrhs, (size_t)n * CHOL_NRHS_W * sizeof(double)));
     double *Y = d->ynrhs;
     HIPCHK((hipError_t)chol_nrhs_launch_permute(d_B, ldb, d->perm, Y, nullptr, 0, n, c0, cols, 0, st));
-    for (int lvl = L - 1; lvl >= 0; lvl--) { // forward: the separators' triangles, then their panels into the ancestors
+    for (int lvl = L - 1; lvl >= 0 && which != CHOLAMD_HALF_BACKWARD; lvl--) { // forward: the separators' triangles, then their panels into the ancestors
       const solve_dev &s = d->sv[lvl];
       const double *W256 = s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr;
       HIPCHK((hipError_t)lnrhs_trsv(d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, W256, Y, 0, st));
       HIPCHK((hipError_t)lnrhs_off(d_arena, s.bw, s.ifw, s.n_ifw, Y, 0, st));
     }
-    for (int lvl = 0; lvl < L; lvl++) { // backward: gather from the ancestors, then the transposed triangles
+    for (int lvl = 0; lvl < L && which != CHOLAMD_HALF_FORWARD; lvl++) { // backward: gather from the ancestors, then the transposed triangles
       const solve_dev &s = d->sv[lvl];
       const double *W256 = s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr;
       HIPCHK((hipError_t)lnrhs_off(d_arena, s.bw, s.ibw, s.n_ibw, Y, 1, st));
@@ -1251,6 +1304,116 @@ extern "C" int cholamd_solve_nrhs_f32(cholamd_device *d, const float *d_arena32,
   }
   return solve_nrhs_t(d, d_arena32, d_B, ldb, d_X, ldx, nrhs, (hipStream_t)stream);
 }
+// ---------------------------------------------------------------------------------------------
+// One triangular half of the solve, and the factor's diagonal (include/cholamd.h at cholamd_solve_half): M = P^T L P, so M M^T = A in original dof order.
+// ---------------------------------------------------------------------------------------------
+static int half_which_ok(int which, const char *what)
+{
+  if (which == CHOLAMD_HALF_FORWARD || which == CHOLAMD_HALF_BACKWARD) return 0;
+  chol_set_error("%s: which = %d is neither CHOLAMD_HALF_FORWARD (0) nor CHOLAMD_HALF_BACKWARD (1)", what, which);
+  return CHOLAMD_ERR_ARG;
+}
+// the deterministic per-call kernels of cholamd_solve under option solve_reference_shape, one sweep of them (fp64 factor)
+static int solve_half_reference(cholamd_device *d, const double *d_arena, const double *d_b, double *d_x, int which, hipStream_t st)
+{
+  { int rc = build_solve(d); if (rc) return rc; }
+  const int L = d->plan->levels, n = d->plan->n;
+  double *y = d->ytmp;
+  HIPCHK((hipError_t)chol_launch_permute(d_b, d->perm, y, n, 0, st));
+  if (which == CHOLAMD_HALF_FORWARD)
+    for (int lvl = L - 1; lvl >= 0; lvl--) {
+      const solve_dev &s = d->sv[lvl];
+      HIPCHK((hipError_t)chol_launch_trsv_fwd(d_arena, s.trsv, s.n_trsv, y, st));
+      HIPCHK((hipError_t)chol_launch_gemv_fwd(d_arena, s.fw, s.grp_start, s.grp_rows, s.n_grp, y, st));
+    }
+  else
+    for (int lvl = 0; lvl < L; lvl++) {
+      const solve_dev &s = d->sv[lvl];
+      HIPCHK((hipError_t)chol_launch_bwd(d_arena, s.trsv, s.bw, s.bw_start, s.n_trsv, y, st));
+    }
+  HIPCHK((hipError_t)chol_launch_permute(y, d->perm, d_x, n, 1, st));
+  return 0;
+}
+static int half_check(cholamd_device *d, const void *arena, const double *b, const double *x, int which, const char *what)
+{
+  if (!d) { chol_set_error("%s: NULL device", what); return CHOLAMD_ERR_ARG; }
+  { int rc = half_which_ok(which, what); if (rc) return rc; }
+  if (!arena || !b || !x) { chol_set_error("%s: NULL %s", what, !arena ? "arena" : !b ? "b" : "x"); return CHOLAMD_ERR_ARG; }
+  return 0;
+}
+extern "C" int cholamd_solve_half(cholamd_device *d, const double *d_arena, const double *d_b, double *d_x, int which, void *stream)
+{
+  { int rc = half_check(d, d_arena, d_b, d_x, which, "cholamd_solve_half"); if (rc) return rc; }
+  HIPCHK(hipSetDevice(d->dev));
+  if (d->solve_reference_shape) return solve_half_reference(d, d_arena, d_b, d_x, which, (hipStream_t)stream);
+  return solve_half_streamed(d, d_arena, d_b, d_x, which, (hipStream_t)stream);
+}
+extern "C" int cholamd_solve_half_f32(cholamd_device *d, const float *d_arena32, const double *d_b, double *d_x, int which, void *stream)
+{
+  { int rc = half_check(d, d_arena32, d_b, d_x, which, "cholamd_solve_half_f32"); if (rc) return rc; }
+  HIPCHK(hipSetDevice(d->dev));
+  return solve_half_streamed(d, d_arena32, d_b, d_x, which, (hipStream_t)stream); // (as cholamd_solve_f32: the per-call kernels exist for the fp64 factor only)
+}
+extern "C" int cholamd_solve_half_nrhs(cholamd_device *d, const double *d_arena, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int nrhs, int which, void *stream)
+{
+  if (d) { int rc = half_which_ok(which, "cholamd_solve_half_nrhs"); if (rc) return rc; }
+  { int rc = nrhs_check(d, d_arena, d_B, ldb, d_X, ldx, nrhs, "cholamd_solve_half_nrhs"); if (rc) return rc > 0 ? 0 : rc; }
+  HIPCHK(hipSetDevice(d->dev));
+  if (d->solve_reference_shape) {
+    for (int j = 0; j < nrhs; j++) { int rc = solve_half_reference(d, d_arena, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, which, (hipStream_t)stream); if (rc) return rc; }
+    return 0;
+  }
+  return solve_nrhs_t(d, d_arena, d_B, ldb, d_X, ldx, nrhs, (hipStream_t)stream, which);
+}
+extern "C" int cholamd_solve_half_nrhs_f32(cholamd_device *d, const float *d_arena32, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int nrhs, int which, void *stream)
+{
+  if (d) { int rc = half_which_ok(which, "cholamd_solve_half_nrhs_f32"); if (rc) return rc; }
+  { int rc = nrhs_check(d, d_arena32, d_B, ldb, d_X, ldx, nrhs, "cholamd_solve_half_nrhs_f32"); if (rc) return rc > 0 ? 0 : rc; }
+  HIPCHK(hipSetDevice(d->dev));
+  return solve_nrhs_t(d, d_arena32, d_B, ldb, d_X, ldx, nrhs, (hipStream_t)stream, which);
+}
+static int lfactor_diag(const double *a, const chol_trsv_desc *t, const int *pre, int nd, int n, const int *perm, double *dg, hipStream_t st) { return chol_launch_factor_diag(a, t, pre, nd, n, perm, dg, st); }
+static int lfactor_diag(const float *a, const chol_trsv_desc *t, const int *pre, int nd, int n, const int *perm, double *dg, hipStream_t st) { return chol32_launch_factor_diag(a, t, pre, nd, n, perm, dg, st); }
+static int lfactor_logdet(const double *a, const chol_trsv_desc *t, const int *pre, int nd, int n, double *part, int64_t *ipart, int64_t *res, hipStream_t st) { return chol_launch_factor_logdet(a, t, pre, nd, n, part, ipart, res, st); }
+static int lfactor_logdet(const float *a, const chol_trsv_desc *t, const int *pre, int nd, int n, double *part, int64_t *ipart, int64_t *res, hipStream_t st) { return chol32_launch_factor_logdet(a, t, pre, nd, n, part, ipart, res, st); }
+template <class TL> static int factor_diag_t(cholamd_device *d, const TL *d_arena, double *d_diag, hipStream_t st, const char *what)
+{
+  if (!d) { chol_set_error("%s: NULL device", what); return CHOLAMD_ERR_ARG; }
+  if (!d_arena || !d_diag) { chol_set_error("%s: NULL %s", what, !d_arena ? "arena" : "d_diag"); return CHOLAMD_ERR_ARG; }
+  HIPCHK(hipSetDevice(d->dev));
+  { int rc = build_solve(d); if (rc) return rc; }
+  HIPCHK((hipError_t)lfactor_diag(d_arena, d->dg_desc, d->dg_prefix, d->n_dg, d->plan->n, d->perm, d_diag, st));
+  return 0;
+}
+template <class TL> static int factor_logdet_t(cholamd_device *d, const TL *d_arena, double *logdet_out, hipStream_t st, const char *what)
+{
+  if (logdet_out) *logdet_out = std::nan("");
+  if (!d) { chol_set_error("%s: NULL device", what); return CHOLAMD_ERR_ARG; }
+  if (!d_arena || !logdet_out) { chol_set_error("%s: NULL %s", what, !d_arena ? "arena" : "logdet_out"); return CHOLAMD_ERR_ARG; }
+  HIPCHK(hipSetDevice(d->dev));
+  { int rc = build_solve(d); if (rc) return rc; }
+  if (!d->ld_part) HIPCHK(fp_malloc((void **)&d->ld_part, 2 * CHOL_LOGDET_MAX_BLOCKS * sizeof(double)));
+  if (!d->ld_ipart) HIPCHK(hipMalloc((void **)&d->ld_ipart, 2 * CHOL_LOGDET_MAX_BLOCKS * sizeof(int64_t)));
+  if (!d->ld_res) HIPCHK(hipMalloc((void **)&d->ld_res, 3 * sizeof(int64_t)));
+  HIPCHK((hipError_t)lfactor_logdet(d_arena, d->dg_desc, d->dg_prefix, d->n_dg, d->plan->n, d->ld_part, d->ld_ipart, d->ld_res, st));
+  int64_t res[3] = { 0, 0, 0 };
+  HIPCHK(hipMemcpyAsync(res, d->ld_res, sizeof res, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (res[1] > 0) {
+    const cholamd_plan *p = d->plan;
+    const int pos = (int)res[2], sep = p->sep_of_pos[pos];
+    chol_set_error("%s: %lld of the factor's diagonal entries %s not positive and finite, the first in column %d of separator %d (permuted position %d): "
+                   "the arena holds no valid factor", what, (long long)res[1], res[1] == 1 ? "is" : "are", pos - p->sep_off[sep] + 1, sep, pos);
+    return CHOLAMD_ERR_ARG;
+  }
+  std::memcpy(logdet_out, &res[0], sizeof(double));
+  return 0;
+}
+extern "C" int cholamd_factor_diag(cholamd_device *d, const double *d_arena, double *d_diag, void *stream) { return factor_diag_t(d, d_arena, d_diag, (hipStream_t)stream, "cholamd_factor_diag"); }
+extern "C" int cholamd_factor_diag_f32(cholamd_device *d, const float *d_arena32, double *d_diag, void *stream) { return factor_diag_t(d, d_arena32, d_diag, (hipStream_t)stream, "cholamd_factor_diag_f32"); }
+extern "C" int cholamd_factor_logdet(cholamd_device *d, const double *d_arena, double *logdet_out, void *stream) { return factor_logdet_t(d, d_arena, logdet_out, (hipStream_t)stream, "cholamd_factor_logdet"); }
+extern "C" int cholamd_factor_logdet_f32(cholamd_device *d, const float *d_arena32, double *logdet_out, void *stream) { return factor_logdet_t(d, d_arena32, logdet_out, (hipStream_t)stream, "cholamd_factor_logdet_f32"); }
+
 // one chunk's residuals: R = B - A X (column-major, ld n), rel[j] = ||r_j|| / ||b_j||
 static int residual_nrhs(cholamd_device *d, const double *d_B, int64_t ldb, const double *d_X, int64_t ldx, int cols, double *rel, hipStream_t st)
 {

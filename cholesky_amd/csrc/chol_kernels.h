@@ -69,6 +69,16 @@ int chol32_nrhs_launch_offdiag(const float *base, const chol_gemv_desc *blocks, 
 int chol_nrhs_launch_residual(const int64_t *ptr, const int *col, const double *val, const double *B, int64_t ldb, const double *X, int64_t ldx, double *R, int64_t ldr,
                               int n, int cols, double *partial, hipStream_t st);
 int chol_nrhs_launch_axpy(double *X, int64_t ldx, const double *D, int64_t ldd, int n, int cols, hipStream_t st);
+/* factor queries (chol_factor_query.hip): one walk over the factor's diagonal for the whole tree.  descs / prefix: the list of chol_diag_list (nd descriptors,
+ * prefix[nd] = n).  diag: d_diag[perm[pos]] = L(pos, pos).  logdet: stage 1 writes one partial sum of log L_ii per workgroup (an unevaluated pair hi + lo) to part[2 b], part[2 b + 1] and the workgroup's
+ * (entries that are not positive and finite, smallest permuted position of one or INT64_MAX) to ipart[2 b], ipart[2 b + 1]; stage 2 (one workgroup, the
+ * partials in a fixed order, as pairs) writes res[0] = the bits of the fp64 sum, res[1] = bad entries, res[2] = the first one's position.  No atomics.
+ * part: 2 * CHOL_LOGDET_MAX_BLOCKS doubles, ipart: 2 * CHOL_LOGDET_MAX_BLOCKS int64, res: 3 int64. */
+#define CHOL_LOGDET_MAX_BLOCKS 1024
+int chol_launch_factor_diag(const double *base, const chol_trsv_desc *descs, const int *prefix, int nd, int n, const int *perm, double *diag, hipStream_t st);
+int chol32_launch_factor_diag(const float *base, const chol_trsv_desc *descs, const int *prefix, int nd, int n, const int *perm, double *diag, hipStream_t st);
+int chol_launch_factor_logdet(const double *base, const chol_trsv_desc *descs, const int *prefix, int nd, int n, double *part, int64_t *ipart, int64_t *res, hipStream_t st);
+int chol32_launch_factor_logdet(const float *base, const chol_trsv_desc *descs, const int *prefix, int nd, int n, double *part, int64_t *ipart, int64_t *res, hipStream_t st);
 /* diagnostic instance of the program launch (k_program<true>): 4 stamps per job, then CHOL_TRACE_X per job -- [0] follower: own tiles' wait over,
  * [1] its items, [2 + i] round of item i begun; [48 + k] POTRF job: column k published / TRSM job (first strip): column tile k on its channel;
  * [72 + k] POTRF job: the factor wave starts column k / TRSM job: the POTRF's column k seen */

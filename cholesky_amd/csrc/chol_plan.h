@@ -396,6 +396,9 @@ typedef struct {
 int chol_build_solve_level(const struct cholamd_plan *p, int level, chol_solve_level *out);
 int chol_build_solve_level_part(const struct cholamd_plan *p, int level, int rank, int world, chol_solve_level *out);
 void chol_solve_level_free(chol_solve_level *w);
+/* the TRSV descriptors of all levels (count of them, sorted in place by x_off) as the diagonal walk of cholamd_factor_diag / _logdet: prefix[count + 1] =
+ * columns before each descriptor; an error unless they tile the permuted vector exactly once inside the arena */
+int chol_diag_list(const struct cholamd_plan *p, chol_trsv_desc *list, int count, int *prefix);
 void chol_set_error(const char *fmt, ...);
 
 #ifdef __cplusplus

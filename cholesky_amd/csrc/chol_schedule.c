@@ -2174,6 +2174,56 @@ void chol_solve_level_free(chol_solve_level *w)
   memset(w, 0, sizeof *w);
 }
 
+/* The diagonal of the factor (cholamd_factor_diag / _logdet): the TRSV descriptors of every level in ONE list, ordered by their position in the permuted
+ * vector, with prefix[i] = columns before descriptor i (prefix[count] = n).  Element j of descriptor i is arena[a_off + j (lda + 1)] and belongs to
+ * permuted position x_off + j.  Sorts `list` in place; fails unless the descriptors tile [0, n) exactly once. */
+static int diag_by_pos(const void *a, const void *b)
+{
+  const chol_trsv_desc *x = a, *y = b;
+  return x->x_off < y->x_off ? -1 : x->x_off > y->x_off;
+}
+int chol_diag_list(const plan_t *p, chol_trsv_desc *list, int count, int *prefix)
+{
+  qsort(list, (size_t)count, sizeof *list, diag_by_pos);
+  int at = 0;
+  for (int i = 0; i < count; i++) {
+    if (list[i].x_off != at || list[i].n < 0 || list[i].lda < list[i].n || list[i].a_off < 0 || list[i].a_off + (int64_t)list[i].n * list[i].lda > p->arena) {
+      chol_set_error("internal: the diagonal descriptors do not tile the permuted vector (descriptor %d of separator %d at %d, expected %d)", i, list[i].sep, list[i].x_off, at);
+      return CHOLAMD_ERR_INVARIANT;
+    }
+    prefix[i] = at;
+    at += list[i].n;
+  }
+  prefix[count] = at;
+  if (at != p->n) { chol_set_error("internal: the diagonal descriptors cover %d of %d positions", at, p->n); return CHOLAMD_ERR_INVARIANT; }
+  return 0;
+}
+int cholamd_plan_diag_list(const cholamd_plan *p, int64_t *a_off, int *cols, int *lda, int *x_off, int *sep, int *prefix)
+{
+  if (!p) { chol_set_error("cholamd_plan_diag_list: NULL plan"); return CHOLAMD_ERR_ARG; }
+  chol_trsv_desc *list = malloc((size_t)p->nsep * sizeof *list);
+  int *pre = malloc(((size_t)p->nsep + 1) * sizeof(int)), count = 0, rc = 0;
+  for (int lvl = 0; lvl < p->levels && !rc; lvl++) {
+    chol_solve_level w;
+    rc = chol_build_solve_level(p, lvl, &w);
+    if (rc) break;
+    if (count + w.n_trsv > p->nsep) { chol_set_error("internal: more diagonal descriptors than separators"); rc = CHOLAMD_ERR_INVARIANT; }
+    else { memcpy(list + count, w.trsv, (size_t)w.n_trsv * sizeof *list); count += w.n_trsv; }
+    chol_solve_level_free(&w);
+  }
+  if (!rc) rc = chol_diag_list(p, list, count, pre);
+  for (int i = 0; i < count && !rc; i++) {
+    if (a_off) a_off[i] = list[i].a_off;
+    if (cols) cols[i] = list[i].n;
+    if (lda) lda[i] = list[i].lda;
+    if (x_off) x_off[i] = list[i].x_off;
+    if (sep) sep[i] = list[i].sep;
+  }
+  if (!rc && prefix) memcpy(prefix, pre, ((size_t)count + 1) * sizeof(int));
+  free(list); free(pre);
+  return rc ? rc : count;
+}
+
 /* ---------------------------------------------------------------------------------------- */
 /* host-side views of the multi-GPU partition (testable without a device)                     */
 /* ---------------------------------------------------------------------------------------- */

@@ -4,7 +4,9 @@
  *   [-p permuted.mtx] [-d debug_dir] [--iterations n]
  * plus:  --gpu id (first device, default 0), --gpus n (subtree-sharded over n devices of this node, one RCCL all-reduce;
  *        n a power of two), --repeat n (= --iterations), --full-precision (write %.17g instead of the reference's
- *        %0.8g), --precision fp64|mixed (mixed: fp32 factor + fp64 iterative refinement of the solve).
+ *        %0.8g), --precision fp64|mixed (mixed: fp32 factor + fp64 iterative refinement of the solve),
+ *        --logdet (one line "logdet: %.17g" after the factorisation: log det A = 2 sum log L_ii from the factor on the device;
+ *        "logdet(fp32 factor): ..." under --precision mixed).
  * Unknown flags (the reference passes -fflow/-ll:cpu/-fcuda/-ll:csize through to Legion) are ignored.
  *
  * Flow = main() of mmat.rg:1056-1496 with the numeric phase on the GPU.  Progress lines keep the
@@ -30,7 +32,7 @@ int main(int argc, char **argv)
 {
   const char *matrix_file = "", *separator_file = "", *clusters_file = "", *b_file = "", *solution_file = "", *factor_file = "",
              *permuted_file = "", *debug_path = "";
-  int debug = 0, iterations = 1, gpu = 0, full = 0, gpus = 1;
+  int debug = 0, iterations = 1, gpu = 0, full = 0, gpus = 1, want_logdet = 0;
   const char *precision = "fp64";
   for (int i = 0; i < argc; i++) {
     const char *next = i + 1 < argc ? argv[i + 1] : "";
@@ -48,6 +50,7 @@ int main(int argc, char **argv)
     else if (!strcmp(argv[i], "--gpus")) gpus = atoi(next);
     else if (!strcmp(argv[i], "--precision")) precision = next;
     else if (!strcmp(argv[i], "--full-precision")) full = 1;
+    else if (!strcmp(argv[i], "--logdet")) want_logdet = 1;
   }
   printf("Iterations: %d\n", iterations);
   if (!*matrix_file || !*separator_file || !*clusters_file) DIE("usage: %s -i A.mtx -s ord.txt -c clust.txt [-b B.mtx -o x.txt] [-m L.mtx] [-p PAPt.mtx] [-d dir] [--iterations n]", argv[0]);
@@ -123,6 +126,11 @@ int main(int argc, char **argv)
   fprintf(stderr, "[cholamd] %d GPU(s), symbolic %.3f ms, numeric factorisation %.3f ms, F_ref %.6g flop, %.3f GF/s, B_alg %ld bytes\n",
           gpus, 1e3 * t_sym, 1e3 * t_factor, flops, flops / t_factor * 1e-9, (long)cholamd_plan_alg_bytes(plan));
 
+  if (want_logdet) { /* the complete factor is on device 0 */
+    double logdet = 0.0;
+    if (mixed ? cholamd_factor_logdet_f32(dev, (const float *)d_arena, &logdet, NULL) : cholamd_factor_logdet(dev, d_arena, &logdet, NULL)) DIE("logdet: %s", cholamd_last_error());
+    printf(mixed ? "logdet(fp32 factor): %.17g\n" : "logdet: %.17g\n", logdet);
+  }
   if (*factor_file) { /* mmat.rg:1360-1362 */
     if (cholamd_device_download(dev, h_arena, d_arena, na, NULL)) DIE("download: %s", cholamd_last_error());
     if (mixed) { /* the device arena holds na floats (in the first half of the buffer): widen in place, back to front */

@@ -10,6 +10,8 @@ from ._lib import check, load
 
 _check = check  # Device.set_values has a parameter of that name
 
+HALF_FORWARD, HALF_BACKWARD = 0, 1  # CHOLAMD_HALF_FORWARD (x = M^-1 b), CHOLAMD_HALF_BACKWARD (x = M^-T b); M = P^T L P
+
 
 def _stream_ptr(stream):
     if stream is None:
@@ -107,6 +109,7 @@ class Device:
         check(self.L.cholamd_device_fill(self.h, self.ptr(arena), _stream_ptr(stream)), "cholamd_device_fill")
 
     VALUES_NOCHECK = 1  # CHOLAMD_VALUES_NOCHECK
+    HALF_FORWARD, HALF_BACKWARD = 0, 1  # CHOLAMD_HALF_FORWARD / CHOLAMD_HALF_BACKWARD
 
     def set_values(self, values, check=True, stream=None):
         """New values of A on the plan's pattern (cholamd_device_set_values): `values` is the value array of plan.nz doubles in the order of
@@ -270,6 +273,43 @@ class Device:
         f32 = arena.elem_bytes == 4 if isinstance(arena, RankArena) else arena.dtype == torch.float32
         fn = self.L.cholamd_solve_nrhs_f32 if f32 else self.L.cholamd_solve_nrhs
         check(fn(self.h, self.ptr(arena), self.ptr(B), ldb, self.ptr(X), ldx, k, _stream_ptr(stream)), "cholamd_solve_nrhs")
+
+    # -- one triangular half of the solve, the factor's diagonal, log det A (M = P^T L P, M M^T = A in original dof order) ------------
+    @staticmethod
+    def _is_f32(arena):
+        import torch
+        return arena.elem_bytes == 4 if isinstance(arena, RankArena) else arena.dtype == torch.float32
+
+    def solve_half(self, arena, b, x, which, stream=None):
+        """x = M^-1 b (which = HALF_FORWARD) or x = M^-T b (HALF_BACKWARD): cholamd_solve_half / _f32 by the arena's element type; x may be b."""
+        fn = self.L.cholamd_solve_half_f32 if self._is_f32(arena) else self.L.cholamd_solve_half
+        check(fn(self.h, self.ptr(arena), self.ptr(b), self.ptr(x), int(which), _stream_ptr(stream)), "cholamd_solve_half")
+
+    def solve_half_nrhs(self, arena, B, X, which, stream=None):
+        """The same for the k columns of B (n x k, column-major, as solve_nrhs takes them): cholamd_solve_half_nrhs / _f32."""
+        ldb, ldx, k = self._blocks(B, X)
+        fn = self.L.cholamd_solve_half_nrhs_f32 if self._is_f32(arena) else self.L.cholamd_solve_half_nrhs
+        check(fn(self.h, self.ptr(arena), self.ptr(B), ldb, self.ptr(X), ldx, k, int(which), _stream_ptr(stream)), "cholamd_solve_half_nrhs")
+
+    def logdet(self, arena, stream=None):
+        """log det A = 2 sum log L_ii from the factor in `arena` (cholamd_factor_logdet / _f32); synchronises `stream`; deterministic."""
+        out = C.c_double(float("nan"))
+        fn = self.L.cholamd_factor_logdet_f32 if self._is_f32(arena) else self.L.cholamd_factor_logdet
+        check(fn(self.h, self.ptr(arena), C.byref(out), _stream_ptr(stream)), "cholamd_factor_logdet")
+        return float(out.value)
+
+    def factor_diag(self, arena, out=None, stream=None):
+        """diag(M): out[dof] = L(p, p), p the permuted position of dof (cholamd_factor_diag / _f32), a float64 CUDA tensor of n elements;
+        asynchronous on `stream`."""
+        import torch
+        n = self.plan.n
+        if out is None:
+            out = torch.empty(n, dtype=torch.float64, device=f"cuda:{self.device_id}")
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or not out.is_cuda or out.dim() != 1 or out.numel() != n or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous 1-D CUDA float64 tensor of n = {n} elements")
+        fn = self.L.cholamd_factor_diag_f32 if self._is_f32(arena) else self.L.cholamd_factor_diag
+        check(fn(self.h, self.ptr(arena), self.ptr(out), _stream_ptr(stream)), "cholamd_factor_diag")
+        return out
 
     def solve_refine_nrhs(self, arena32, B, X, max_iter=20, tol=1e-12, stream=None):
         """cholamd_solve_refine_nrhs: every column of X = A^-1 B by iterative refinement on the fp32 factor; returns (corrections applied, relres per column)."""

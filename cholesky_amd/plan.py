@@ -190,6 +190,18 @@ class Plan:
         check(self.L.cholamd_plan_solve_skips(self.h, level, seps.ctypes.data, runs.ctypes.data), "cholamd_plan_solve_skips")
         return seps[:cnt[0]], runs[:cnt[1]]
 
+    def diag_list(self):
+        """cholamd_plan_diag_list: where the factor's diagonal lies in an arena -- (a_off int64, cols, lda, x_off, sep, prefix) with one entry per
+        separator in the order of the permuted vector (prefix: one more); element j of descriptor i is arena[a_off[i] + j * (lda[i] + 1)]."""
+        m = self.nsep
+        a_off = np.zeros(m, dtype=np.int64)
+        cols, lda, x_off, sep = (np.zeros(m, dtype=np.int32) for _ in range(4))
+        prefix = np.zeros(m + 1, dtype=np.int32)
+        n = self.L.cholamd_plan_diag_list(self.h, a_off.ctypes.data, cols.ctypes.data, lda.ctypes.data, x_off.ctypes.data, sep.ctypes.data, prefix.ctypes.data)
+        if n < 0:
+            check(n, "cholamd_plan_diag_list")
+        return a_off[:n], cols[:n], lda[:n], x_off[:n], sep[:n], prefix[:n + 1]
+
     def exchange_pieces(self, world, dist_top=2):
         """The column-block pieces of that exchange as rows (arena offset, elements, owner rank, heap index of the top separator)."""
         out = np.zeros((4096, 4), dtype=np.int64)

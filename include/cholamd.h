@@ -191,6 +191,11 @@ int cholamd_plan_fill_host(const cholamd_plan *p, double *arena);
 int cholamd_plan_entries(const cholamd_plan *p, int *row, int *col);
 int cholamd_plan_value_map(const cholamd_plan *p, int64_t *src_out);
 int cholamd_plan_fill_host_values(const cholamd_plan *p, const double *vals, int64_t count, double *arena);
+/* where the factor's diagonal lies in an arena (the walk of cholamd_factor_diag / cholamd_factor_logdet, host side): one descriptor per separator, ordered
+ * by permuted position -- element j < cols[i] of descriptor i is arena[a_off[i] + j * (lda[i] + 1)] and is L(x_off[i] + j, x_off[i] + j); prefix[i] = columns
+ * before descriptor i, prefix[count] = n.  Every array has room for cholamd_plan_num_separators() entries (prefix: one more) and may be NULL.  Returns the
+ * number of descriptors, or a negative error code if they do not cover every permuted position exactly once. */
+int cholamd_plan_diag_list(const cholamd_plan *p, int64_t *a_off, int *cols, int *lda, int *x_off, int *sep, int *prefix);
 /* Multi-GPU view of the same: with `world` ranks the shared top of the tree (the tail of
  * the arena starting at *tail_offset_out) receives A's entries on rank 0 only, so that the sum over
  * ranks of the tails after the local levels equals A_top minus every contribution. */
@@ -434,6 +439,42 @@ int cholamd_solve_nrhs(cholamd_device *d, const double *d_arena, const double *d
 int cholamd_solve_nrhs_f32(cholamd_device *d, const float *d_arena32, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int nrhs, void *stream);
 int cholamd_solve_refine_nrhs(cholamd_device *d, const float *d_arena32, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int nrhs, int max_iter,
                               double tol, int *iters_out, double *relres_out /* nrhs doubles, may be NULL */, void *stream);
+/* ---- one triangular half of the solve, the factor's diagonal and log det A (not in the reference; CHOLMOD's CHOLMOD_L / CHOLMOD_Lt systems and the logdet
+ * every sparse Cholesky offers).  THE SQUARE ROOT these calls speak about is M = P^T L P in ORIGINAL dof order (P the plan's permutation, L the factor in
+ * the arena): M M^T = A, A^-1 = M^-T M^-1, and no caller ever sees permuted coordinates.  M y = b whitens b (b^T A^-1 b = ||y||^2); M^T x = z turns white
+ * noise z into a sample x ~ N(0, A^-1).
+ * cholamd_solve_half / _f32 (fp64 / fp32 factor; vectors and arithmetic fp64): x = M^-1 b (which = CHOLAMD_HALF_FORWARD) or x = M^-T b
+ * (CHOLAMD_HALF_BACKWARD), b and x n doubles on the device in original dof order, asynchronous on `stream`; d_x == d_b is allowed (as in cholamd_solve, b is
+ * permuted into the work vector first).  Each is the permute, that sweep's launches of cholamd_solve, and the permute back: BACKWARD(FORWARD(b)) is the
+ * solve and agrees with cholamd_solve to rounding (atomics in the off-diagonal blocks: not bit for bit).  The 16x16 and 256-column span inverses are formed
+ * from d_arena at the start of EVERY half call (as at the start of a solve): a BACKWARD call does not rely on a preceding FORWARD call, whose arena may have
+ * been another.  Option "solve_reference_shape" selects the deterministic per-call kernels for the halves of an fp64 factor as it does for cholamd_solve.
+ * cholamd_solve_half_nrhs / _f32: the same for nrhs columns, with the argument rules of cholamd_solve_nrhs verbatim (column-major n x nrhs, ldb, ldx >= n,
+ * rows n .. ld - 1 of X never written, in place with X == B and ldx == ldb; nrhs == 0 returns 0 and touches nothing; nrhs < 0, ldb < n, ldx < n or a NULL
+ * pointer with nrhs > 0: CHOLAMD_ERR_ARG), the 32-column chunks and kernels of cholamd_solve_nrhs with one sweep instead of two, the inverses once per
+ * call, and the same small-chunk rule: a chunk of fewer than 4 (fp64) / 6 (fp32) columns is solved column by column; column j agrees with
+ * cholamd_solve_half of column j to rounding.
+ * `which` other than 0 / 1: CHOLAMD_ERR_ARG, nothing written.
+ * cholamd_factor_logdet / _f32: *logdet_out (HOST) = log det A = 2 sum_i log L_ii, accumulated in fp64 (an fp32 factor's diagonal is converted before the
+ * log).  Synchronises `stream` (it returns a host scalar, like cholamd_residual).  DETERMINISTIC: a fixed assignment of entries to lanes, one partial sum
+ * per workgroup, the partials summed in a fixed order by a second one-workgroup launch (every addition error-free: the sum is carried as a pair of doubles); no floating-point atomics anywhere, so two calls on
+ * the same arena return the same bits.  A diagonal entry that is not a positive finite number (a failed or never-run factorisation, a poisoned arena)
+ * makes the call return CHOLAMD_ERR_ARG with *logdet_out = NaN; cholamd_last_error() names the separator and (1-based) column of the first such entry in
+ * permuted order -- the smallest position, an integer minimum independent of the order in which workgroups finish.
+ * cholamd_factor_diag / _f32: d_diag[dof] = L(p, p) with p the permuted position of dof (n doubles on the device, asynchronous on `stream`): the diagonal
+ * of M; 2 sum log d_diag equals the logdet to summation rounding.
+ * All eight need the COMPLETE factor in the arena: a single-GPU device object, or rank 0's after cholamd_gather_to_root / cholamd_gather_factor (they use
+ * the solve lists of the whole tree, like cholamd_solve on a partitioned device).  There are no sharded variants. */
+#define CHOLAMD_HALF_FORWARD  0   /* x = M^-1 b   = P^T L^-1 P b   */
+#define CHOLAMD_HALF_BACKWARD 1   /* x = M^-T b   = P^T L^-T P b   */
+int cholamd_solve_half(cholamd_device *d, const double *d_arena, const double *d_b, double *d_x, int which, void *stream);
+int cholamd_solve_half_f32(cholamd_device *d, const float *d_arena32, const double *d_b, double *d_x, int which, void *stream);
+int cholamd_solve_half_nrhs(cholamd_device *d, const double *d_arena, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int nrhs, int which, void *stream);
+int cholamd_solve_half_nrhs_f32(cholamd_device *d, const float *d_arena32, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int nrhs, int which, void *stream);
+int cholamd_factor_logdet(cholamd_device *d, const double *d_arena, double *logdet_out, void *stream);
+int cholamd_factor_logdet_f32(cholamd_device *d, const float *d_arena32, double *logdet_out, void *stream);
+int cholamd_factor_diag(cholamd_device *d, const double *d_arena, double *d_diag, void *stream);
+int cholamd_factor_diag_f32(cholamd_device *d, const float *d_arena32, double *d_diag, void *stream);
 /* average device time (ms) of the three kernel families of the last cholamd_factor call measured
  * with HIP events on its stream; valid after cholamd_device_sync.  Enable with set_timing(1). */
 int cholamd_device_set_timing(cholamd_device *d, int on);
