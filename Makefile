@@ -13,7 +13,7 @@ HIPFLAGS:= -O3 -fPIC --offload-arch=$(ARCH) -Iinclude -I$(CSRC) -Wall
 KERNFLAGS := -mllvm -pragma-unroll-threshold=100000
 
 HOST_OBJS := $(OUT)/chol_ingest.o $(OUT)/chol_symbolic.o $(OUT)/chol_schedule.o $(OUT)/chol_generate.o
-HIP_OBJS  := $(OUT)/chol_kernels.o $(OUT)/chol_kernels_f32.o $(OUT)/chol_solve_nrhs.o $(OUT)/chol_factor_query.o $(OUT)/chol_api.o
+HIP_OBJS  := $(OUT)/chol_kernels.o $(OUT)/chol_kernels_f32.o $(OUT)/chol_solve_nrhs.o $(OUT)/chol_factor_query.o $(OUT)/chol_selinv.o $(OUT)/chol_api.o
 
 all: $(OUT)/libcholamd.so $(BIN)/cholamd_mmat oracle
 
@@ -34,6 +34,10 @@ $(OUT)/chol_solve_nrhs.o: $(CSRC)/chol_solve_nrhs.hip $(CSRC)/chol_plan.h $(CSRC
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(OUT)/chol_factor_query.o: $(CSRC)/chol_factor_query.hip $(CSRC)/chol_plan.h $(CSRC)/chol_kernels.h
+	@mkdir -p $(OUT)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(OUT)/chol_selinv.o: $(CSRC)/chol_selinv.hip $(CSRC)/chol_plan.h $(CSRC)/chol_kernels.h
 	@mkdir -p $(OUT)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -69,7 +73,7 @@ $(ASAN_OUT)/%.o: $(CSRC)/%.c $(CSRC)/chol_plan.h include/cholamd.h
 $(ASAN_OUT)/chol_api.o: $(CSRC)/chol_api.cpp $(CSRC)/chol_plan.h $(CSRC)/chol_kernels.h include/cholamd.h
 	@mkdir -p $(ASAN_OUT)
 	$(HIPCC) $(HIPFLAGS) -O1 $(SAN) -fno-sanitize=function -fno-gpu-sanitize -x hip -c $< -o $@
-$(ASAN_OUT)/libcholamd.so: $(ASAN_HOST_OBJS) $(ASAN_OUT)/chol_api.o $(OUT)/chol_kernels.o $(OUT)/chol_kernels_f32.o $(OUT)/chol_solve_nrhs.o $(OUT)/chol_factor_query.o
+$(ASAN_OUT)/libcholamd.so: $(ASAN_HOST_OBJS) $(ASAN_OUT)/chol_api.o $(OUT)/chol_kernels.o $(OUT)/chol_kernels_f32.o $(OUT)/chol_solve_nrhs.o $(OUT)/chol_factor_query.o $(OUT)/chol_selinv.o
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) $(SAN) -fno-gpu-sanitize -o $@ $^ -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 # leak detection: ON, in a process of its own without an interpreter (tests/native/host_leak.c: plans, schedules of every level and
 # world size, the program builder and its self-check, the generator, error paths); the only suppression is the HIP runtime's own

@@ -168,6 +168,11 @@ def load():
     L.cholamd_factor_diag.argtypes = [vp, vp, vp, vp]
     L.cholamd_factor_diag_f32.argtypes = [vp, vp, vp, vp]
     L.cholamd_plan_diag_list.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.cholamd_selinv.argtypes = [vp, vp, vp, vp]
+    L.cholamd_selinv_diag.argtypes = [vp, vp, vp, vp]
+    L.cholamd_selinv_entries.argtypes = [vp, vp, vp, i64, vp]
+    L.cholamd_plan_selinv_blocks.argtypes = [vp, ci]
+    L.cholamd_plan_selinv_front.argtypes = [vp, ci, ci, ci, vp, vp, vp]
     L.cholamd_device_alloc_arena.argtypes = [vp, ci, C.POINTER(vp), C.POINTER(C.c_int64)]
     L.cholamd_device_free_arena.argtypes = [vp, vp]
     L.cholamd_device_set_timing.argtypes = [vp, ci]

@@ -45,6 +45,12 @@ struct solve_dev {
   int64_t w256_off = -1; // this level's explicit span inverses in cholamd_device::w256 (levels of at most 8 separators wider than a span); -1: none
   int *ifw = nullptr, *ibw = nullptr;
 };
+struct selinv_dev { // the lists of one tree level of the selected inversion (chol_selinv_level) on the device
+  std::vector<chol_selinv_sep> host; // the separator descriptors, for the launch geometry of every step
+  chol_selinv_sep *sep = nullptr; chol_selinv_tile *tile = nullptr;
+  int *chain_ld = nullptr, *chain_pos0 = nullptr; int64_t *rowoff = nullptr;
+  int max_nblk = 0;
+};
 struct timed_launch { hipEvent_t a, b; int kind; };
 
 struct cholamd_device {
@@ -112,6 +118,8 @@ struct cholamd_device {
   // column counts (built with the solve lists of rank 0 of 1); the logdet's per-workgroup partial sums, their integer companions and the three result words
   chol_trsv_desc *dg_desc = nullptr; int *dg_prefix = nullptr; int n_dg = 0;
   double *ld_part = nullptr; int64_t *ld_ipart = nullptr, *ld_res = nullptr;
+  // selected inversion (cholamd_selinv): the gather lists of every level and the workspace of the widest level, built at the first call
+  std::vector<selinv_dev> si; double *si_ws = nullptr; bool si_ready = false;
 };
 
 static int no_device_error()
@@ -182,6 +190,13 @@ static void free_solve_lists(cholamd_device *d)
   (void)hipFree(d->dg_desc); d->dg_desc = nullptr; (void)hipFree(d->dg_prefix); d->dg_prefix = nullptr; d->n_dg = 0;
   (void)hipFree(d->zr_sub); d->zr_sub = nullptr; d->n_zr_sub = 0;
   d->solve_ready = false;
+}
+static void free_selinv(cholamd_device *d)
+{
+  for (auto &l : d->si) { (void)hipFree(l.sep); (void)hipFree(l.tile); (void)hipFree(l.chain_ld); (void)hipFree(l.chain_pos0); (void)hipFree(l.rowoff); }
+  d->si.clear();
+  (void)hipFree(d->si_ws); d->si_ws = nullptr;
+  d->si_ready = false;
 }
 static int upload_level(level_dev &l, const chol_level_work &w, bool with_tables = true)
 {
@@ -312,6 +327,7 @@ extern "C" void cholamd_device_destroy(cholamd_device *d)
     (void)hipMemAddressFree(a.va, a.total);
   }
   free_solve_lists(d);
+  free_selinv(d);
   (void)hipFree(d->ws32); (void)hipFree(d->csr_ptr); (void)hipFree(d->csr_col); (void)hipFree(d->csr_val); (void)hipFree(d->rvec); (void)hipFree(d->dxvec); (void)hipFree(d->partial);
   (void)hipFree(d->xstage); (void)hipFree(d->xdesc);
   (void)hipFree(d->ws); (void)hipFree(d->ws_solve); (void)hipFree(d->step_flags); (void)hipFree(d->w256); (void)hipFree(d->step_xt); (void)hipFree(d->info); (void)hipFree(d->progress); (void)hipFree(d->a_dst); (void)hipFree(d->a_val); (void)hipFree(d->perm); (void)hipFree(d->ytmp);
@@ -1413,6 +1429,89 @@ extern "C" int cholamd_factor_diag(cholamd_device *d, const double *d_arena, dou
 extern "C" int cholamd_factor_diag_f32(cholamd_device *d, const float *d_arena32, double *d_diag, void *stream) { return factor_diag_t(d, d_arena32, d_diag, (hipStream_t)stream, "cholamd_factor_diag_f32"); }
 extern "C" int cholamd_factor_logdet(cholamd_device *d, const double *d_arena, double *logdet_out, void *stream) { return factor_logdet_t(d, d_arena, logdet_out, (hipStream_t)stream, "cholamd_factor_logdet"); }
 extern "C" int cholamd_factor_logdet_f32(cholamd_device *d, const float *d_arena32, double *logdet_out, void *stream) { return factor_logdet_t(d, d_arena32, logdet_out, (hipStream_t)stream, "cholamd_factor_logdet_f32"); }
+
+// ---------------------------------------------------------------------------------------------
+// Selected inversion (include/cholamd.h at cholamd_selinv; kernels and launch structure in chol_selinv.hip).  The gather lists depend on the plan alone:
+// they are built at the first call on a device object, beside the solve lists, and stay until it is destroyed -- device creation and the factor path do
+// not pay for them.
+// ---------------------------------------------------------------------------------------------
+static int build_selinv(cholamd_device *d)
+{
+  if (d->si_ready) return 0;
+  free_selinv(d);
+  const int L = d->plan->levels;
+  d->si.resize(L);
+  int64_t ws = 1;
+  for (int lvl = 0; lvl < L; lvl++) {
+    chol_selinv_level w;
+    int rc = chol_build_selinv_level(d->plan, lvl, &w);
+    if (rc) return rc;
+    selinv_dev &s = d->si[lvl];
+    s.host.assign(w.sep, w.sep + w.n_sep);
+    s.max_nblk = w.max_nblk;
+    if (w.max_tiles > CHOL_SELINV_MAX_TILES) {
+      chol_set_error("cholamd_selinv: a panel of level %d stores %d 16-row tiles, the step launches take %d", lvl, w.max_tiles, CHOL_SELINV_MAX_TILES);
+      chol_selinv_level_free(&w);
+      return CHOLAMD_ERR_ARG;
+    }
+    ws = std::max(ws, w.ws_doubles);
+    rc = upload_vec(&s.sep, w.sep, (size_t)w.n_sep);
+    if (!rc) rc = upload_vec(&s.tile, w.tile, (size_t)w.n_tile);
+    if (!rc) rc = upload_vec(&s.chain_ld, w.chain_ld, (size_t)w.n_chain);
+    if (!rc) rc = upload_vec(&s.chain_pos0, w.chain_pos0, (size_t)w.n_chain);
+    if (!rc) rc = upload_vec(&s.rowoff, w.rowoff, (size_t)w.n_rowoff);
+    chol_selinv_level_free(&w);
+    if (rc) return rc;
+  }
+  HIPCHK(fp_malloc((void **)&d->si_ws, (size_t)ws * sizeof(double)));
+  d->si_ready = true;
+  return 0;
+}
+extern "C" int cholamd_selinv(cholamd_device *d, const double *d_arena, double *d_zarena, void *stream)
+{
+  if (!d) { chol_set_error("cholamd_selinv: NULL device"); return CHOLAMD_ERR_ARG; }
+  if (!d_arena || !d_zarena) { chol_set_error("cholamd_selinv: NULL %s", !d_arena ? "arena" : "Z arena"); return CHOLAMD_ERR_ARG; }
+  const int64_t na = d->plan->arena;
+  if (d_zarena < d_arena + na && d_arena < d_zarena + na) {
+    chol_set_error("cholamd_selinv: the Z arena overlaps the factor's arena (there is no in-place form)");
+    return CHOLAMD_ERR_ARG;
+  }
+  if (d->world > 1 && d->rank != 0) {
+    chol_set_error("cholamd_selinv: rank %d of %d holds its own subtrees only; the call needs the complete factor (a single-GPU object, or rank 0 after a gather)", d->rank, d->world);
+    return CHOLAMD_ERR_ARG;
+  }
+  HIPCHK(hipSetDevice(d->dev));
+  { int rc = build_selinv(d); if (rc) return rc; }
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(hipMemsetAsync(d_zarena, 0, (size_t)na * sizeof(double), st)); // padding rows, the upper triangles of the diagonal blocks: every stored position is defined
+  for (int lvl = 0; lvl < d->plan->levels; lvl++) { // root first: a separator gathers from its ancestors' finished panels
+    const selinv_dev &s = d->si[lvl];
+    for (int step = 0; step < s.max_nblk; step++) {
+      int n_act = 0, below = 0; // the separators with a block left are a prefix of the list
+      for (const chol_selinv_sep &q : s.host) {
+        if (q.nblk <= step) break;
+        const int j1 = std::min((q.nblk - step) * CHOL_SELINV_W, q.w);
+        below = std::max(below, q.ntile - (j1 == q.w ? q.nown : j1 / CHOL_NB));
+        n_act++;
+      }
+      HIPCHK((hipError_t)chol_launch_selinv_step(d_arena, d_zarena, d->si_ws, s.sep, n_act, s.tile, s.chain_ld, s.chain_pos0, s.rowoff, step, below, st));
+    }
+  }
+  return 0;
+}
+// k_factor_diag on the Z arena: the walk over the diagonal is the factor's
+extern "C" int cholamd_selinv_diag(cholamd_device *d, const double *d_zarena, double *d_diag, void *stream) { return factor_diag_t(d, d_zarena, d_diag, (hipStream_t)stream, "cholamd_selinv_diag"); }
+extern "C" int cholamd_selinv_entries(cholamd_device *d, const double *d_zarena, double *d_vals, int64_t count, void *stream)
+{
+  if (!d) { chol_set_error("cholamd_selinv_entries: NULL device"); return CHOLAMD_ERR_ARG; }
+  if (!d_zarena || !d_vals) { chol_set_error("cholamd_selinv_entries: NULL %s", !d_zarena ? "Z arena" : "d_vals"); return CHOLAMD_ERR_ARG; }
+  const cholamd_plan *p = d->plan;
+  if (count != p->nz_file) { chol_set_error("cholamd_selinv_entries: room for %lld entries, the plan has %d", (long long)count, p->nz_file); return CHOLAMD_ERR_ARG; }
+  HIPCHK(hipSetDevice(d->dev));
+  if (!d->a_src) { int rc = upload_vec(&d->a_src, p->a_src, (size_t)p->nnz_a); if (rc) return rc; } // the index list of cholamd_device_set_values
+  HIPCHK((hipError_t)chol_launch_selinv_entries(d_zarena, d->a_dst, d->a_src, p->nnz_a, d_vals, count, (hipStream_t)stream));
+  return 0;
+}
 
 // one chunk's residuals: R = B - A X (column-major, ld n), rel[j] = ||r_j|| / ||b_j||
 static int residual_nrhs(cholamd_device *d, const double *d_B, int64_t ldb, const double *d_X, int64_t ldx, int cols, double *rel, hipStream_t st)

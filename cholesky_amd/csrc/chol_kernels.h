@@ -79,6 +79,13 @@ int chol_launch_factor_diag(const double *base, const chol_trsv_desc *descs, con
 int chol32_launch_factor_diag(const float *base, const chol_trsv_desc *descs, const int *prefix, int nd, int n, const int *perm, double *diag, hipStream_t st);
 int chol_launch_factor_logdet(const double *base, const chol_trsv_desc *descs, const int *prefix, int nd, int n, double *part, int64_t *ipart, int64_t *res, hipStream_t st);
 int chol32_launch_factor_logdet(const float *base, const chol_trsv_desc *descs, const int *prefix, int nd, int n, double *part, int64_t *ipart, int64_t *res, hipStream_t st);
+/* selected inversion (chol_selinv.hip): one column-block step of one tree level -- block nblk - 1 - step of the first n_act separators of the level's list
+ * (chol_selinv_level, uploaded as it is): L_JJ^-1, Y, the gather-product Z[below, J] and the diagonal block Z[J, J], four launches, no atomics.
+ * max_below_tiles: the most 16-row tiles any of them has below the block.  ws: the level's workspace (chol_selinv_level.ws_doubles).
+ * entries: vals[k] = quiet NaN for every k < nz, then vals[a_src[e]] = Z[a_dst[e]] for the nnz entries of the scatter list */
+int chol_launch_selinv_step(const double *L, double *Z, double *ws, const chol_selinv_sep *seps, int n_act, const chol_selinv_tile *tiles, const int *chain_ld,
+                            const int *chain_pos0, const int64_t *rowoff, int step, int max_below_tiles, hipStream_t st);
+int chol_launch_selinv_entries(const double *Z, const int64_t *a_dst, const int *a_src, int64_t nnz, double *vals, int64_t nz, hipStream_t st);
 /* diagnostic instance of the program launch (k_program<true>): 4 stamps per job, then CHOL_TRACE_X per job -- [0] follower: own tiles' wait over,
  * [1] its items, [2 + i] round of item i begun; [48 + k] POTRF job: column k published / TRSM job (first strip): column tile k on its channel;
  * [72 + k] POTRF job: the factor wave starts column k / TRSM job: the POTRF's column k seen */

@@ -399,6 +399,40 @@ void chol_solve_level_free(chol_solve_level *w);
 /* the TRSV descriptors of all levels (count of them, sorted in place by x_off) as the diagonal walk of cholamd_factor_diag / _logdet: prefix[count + 1] =
  * columns before each descriptor; an error unless they tile the permuted vector exactly once inside the arena */
 int chol_diag_list(const struct cholamd_plan *p, chol_trsv_desc *list, int count, int *prefix);
+
+/* ---- selected inversion (cholamd_selinv; chol_selinv.hip): the lists of one tree level.  The unit of the recursion is a COLUMN BLOCK of at most
+ * CHOL_SELINV_W columns of a separator, last block first; its "rows below" are the rows panel(s) stores after the block's last column (the separator's
+ * own rows, then the stored rows of the ancestors).  A panel's rows are cut into TILES of at most 16 rows on the 16-row grid of the separator they belong
+ * to (the grid of chol_block.tmap), in storage order = ascending permuted position.  chain = the separator and its ancestors, bottom up (chain index 0 =
+ * the separator itself).  rowoff[tile][k] = arena offset, in column 0 of panel(chain[k]), of the tile's first row -- chol_block_row of block
+ * (tile's separator, chain[k]) -- or -1: chain[k] lies above the tile's separator (only the lower triangle is stored) or the row compaction of that panel
+ * dropped the tile.  Z(i, j), i in tile a, j in tile b, a after b (or a == b and i >= j), lives at
+ *   rowoff[a][tile[b].k] + (i - tile[a].pos0) + (j - chain_pos0[tile[b].k]) * chain_ld[tile[b].k]        (Z arena = the arena's own layout)
+ * and reads as 0.0 where rowoff is -1. */
+#define CHOL_SELINV_W 64
+#define CHOL_SELINV_MAX_TILES 65535 /* most 16-row tiles of a panel (they lie on grid.y of the step launches): a panel of 10^6 stored rows; build_selinv refuses more */
+typedef struct { int q0, nrows, pos0, k; } chol_selinv_tile; /* first row inside the panel, rows (<= 16), permuted position of the first row, chain index of its separator */
+typedef struct {
+  int64_t panel_off;           /* arena offset of panel(s) */
+  int64_t ws_off;              /* workspace of the separator: Y^T (prows x W, row-major), Z[below, J]^T (the same shape), L_JJ^-1 (W x W, column-major) */
+  int64_t rowoff_first;        /* rowoff[rowoff_first + tile * nchain + k] */
+  int ld, w, prows, nblk;      /* leading dimension, columns, stored rows, column blocks */
+  int sep;
+  int tile_first, ntile, nown; /* tiles [tile_first, tile_first + ntile) of the level's list; the first nown are the separator's own rows */
+  int chain_first, nchain;     /* chain_ld / chain_pos0 [chain_first + k] */
+  int pad;
+} chol_selinv_sep;
+typedef struct {
+  int level;
+  int n_sep; chol_selinv_sep *sep;     /* ordered by column blocks, most first: the separators that take part in step t (block nblk - 1 - t) are a prefix */
+  int n_tile; chol_selinv_tile *tile;
+  int n_chain; int *chain_ld, *chain_pos0;
+  int64_t n_rowoff; int64_t *rowoff;
+  int max_nblk, max_tiles;
+  int64_t ws_doubles;
+} chol_selinv_level;
+int chol_build_selinv_level(const struct cholamd_plan *p, int level, chol_selinv_level *out);
+void chol_selinv_level_free(chol_selinv_level *w);
 void chol_set_error(const char *fmt, ...);
 
 #ifdef __cplusplus

@@ -2298,3 +2298,133 @@ int cholamd_plan_level_work_counts(const cholamd_plan *p, int level, int rank, i
   chol_level_work_free(&w);
   return 0;
 }
+
+/* ---------------------------------------------------------------------------------------- */
+/* selected inversion: the gather lists of one tree level (chol_plan.h at chol_selinv_level)  */
+/* ---------------------------------------------------------------------------------------- */
+static int selinv_by_blocks(const void *a, const void *b)
+{
+  const chol_selinv_sep *x = a, *y = b;
+  return x->nblk != y->nblk ? (x->nblk > y->nblk ? -1 : 1) : (x->sep < y->sep ? -1 : x->sep > y->sep);
+}
+void chol_selinv_level_free(chol_selinv_level *w)
+{
+  free(w->sep); free(w->tile); free(w->chain_ld); free(w->chain_pos0); free(w->rowoff);
+  memset(w, 0, sizeof *w);
+}
+int chol_build_selinv_level(const plan_t *p, int level, chol_selinv_level *out)
+{
+  memset(out, 0, sizeof *out);
+  out->level = level;
+  if (level < 0 || level >= p->levels) { chol_set_error("selected inversion: level %d of %d", level, p->levels); return CHOLAMD_ERR_ARG; }
+  const int h_lo = 1 << level, h_hi = (2 << level) - 1 < p->nsep ? (2 << level) - 1 : p->nsep;
+  const int nchain = level + 1;
+  int ns = 0;
+  int64_t ntile = 0;
+  for (int h = h_lo; h <= h_hi; h++) {
+    const int s = p->tree[h];
+    if (p->sep_size[s] <= 0) continue;
+    ns++;
+    for (int a = h; a >= 1; a /= 2) ntile += (p->sep_size[p->tree[a]] + CHOL_NB - 1) / CHOL_NB;
+  }
+  out->sep = calloc((size_t)(ns > 0 ? ns : 1), sizeof *out->sep);
+  out->tile = calloc((size_t)(ntile > 0 ? ntile : 1), sizeof *out->tile);
+  out->chain_ld = calloc((size_t)(ns > 0 ? ns : 1) * nchain, sizeof(int));
+  out->chain_pos0 = calloc((size_t)(ns > 0 ? ns : 1) * nchain, sizeof(int));
+  out->rowoff = malloc((size_t)(ntile > 0 ? ntile : 1) * nchain * sizeof(int64_t));
+  if (!out->sep || !out->tile || !out->chain_ld || !out->chain_pos0 || !out->rowoff) { chol_selinv_level_free(out); chol_set_error("out of memory"); return CHOLAMD_ERR_NOMEM; }
+  for (int h = h_lo; h <= h_hi; h++) {
+    const int s = p->tree[h];
+    if (p->sep_size[s] <= 0) continue;
+    chol_selinv_sep *d = &out->sep[out->n_sep++];
+    d->sep = s; d->panel_off = p->panel_off[s]; d->ld = p->panel_ld[s]; d->w = p->sep_size[s]; d->prows = p->panel_rows[s];
+    d->nblk = (d->w + CHOL_SELINV_W - 1) / CHOL_SELINV_W;
+    d->nown = (d->w + CHOL_NB - 1) / CHOL_NB;
+    d->tile_first = out->n_tile; d->chain_first = out->n_chain; d->nchain = nchain; d->rowoff_first = out->n_rowoff;
+    int k = 0;
+    for (int a = h; a >= 1; a /= 2, k++) { /* the chain, bottom up: the panels Z is gathered from */
+      out->chain_ld[out->n_chain + k] = p->panel_ld[p->tree[a]];
+      out->chain_pos0[out->n_chain + k] = p->sep_off[p->tree[a]];
+    }
+    out->n_chain += nchain;
+    k = 0;
+    for (int a = h; a >= 1; a /= 2, k++) { /* the tiles of panel(s) in storage order */
+      const int anc = p->tree[a];
+      const chol_block *B = chol_plan_block(p, anc, s);
+      if (!B) { chol_selinv_level_free(out); chol_set_error("internal: no block (%d, %d)", anc, s); return CHOLAMD_ERR_INVARIANT; }
+      for (int r0 = 0; r0 < B->rows; r0 += CHOL_NB) {
+        const int64_t ro = chol_block_row(B, r0);
+        if (ro < 0) continue;
+        chol_selinv_tile *t = &out->tile[out->n_tile];
+        t->q0 = (int)(ro - p->panel_off[s]); t->nrows = B->rows - r0 < CHOL_NB ? B->rows - r0 : CHOL_NB; t->pos0 = p->sep_off[anc] + r0; t->k = k;
+        int64_t *ro_t = &out->rowoff[out->n_rowoff];
+        int k2 = 0;
+        for (int a2 = h; a2 >= 1; a2 /= 2, k2++) { /* where the tile's rows lie in the panels of the chain: the extend-add's relation, read instead of written */
+          const chol_block *B2 = k2 <= k ? chol_plan_block(p, anc, p->tree[a2]) : NULL;
+          ro_t[k2] = B2 ? chol_block_row(B2, r0) : -1;
+        }
+        out->n_tile++; out->n_rowoff += nchain;
+      }
+    }
+    d->ntile = out->n_tile - d->tile_first;
+    d->ws_off = out->ws_doubles;
+    out->ws_doubles += 2 * (int64_t)d->prows * CHOL_SELINV_W + CHOL_SELINV_W * CHOL_SELINV_W;
+    if (d->nblk > out->max_nblk) out->max_nblk = d->nblk;
+    if (d->ntile > out->max_tiles) out->max_tiles = d->ntile;
+  }
+  qsort(out->sep, (size_t)out->n_sep, sizeof *out->sep, selinv_by_blocks);
+  return 0;
+}
+
+/* the arena offset of Z(i, j) by the rule of the kernels; i, j: (tile, row inside the tile) of one separator's list */
+static int64_t selinv_offset(const chol_selinv_level *w, const chol_selinv_sep *d, int ta, int ra, int tb, int rb)
+{
+  if (ta < tb || (ta == tb && ra < rb)) { int t = ta; ta = tb; tb = t; t = ra; ra = rb; rb = t; }
+  const chol_selinv_tile *B = &w->tile[d->tile_first + tb];
+  const int64_t base = w->rowoff[d->rowoff_first + (int64_t)ta * d->nchain + B->k];
+  if (base < 0) return -1;
+  return base + ra + (int64_t)(B->pos0 + rb - w->chain_pos0[d->chain_first + B->k]) * w->chain_ld[d->chain_first + B->k];
+}
+int cholamd_plan_selinv_blocks(const cholamd_plan *p, int sep)
+{
+  if (!p || sep < 1 || sep > p->nsep) { chol_set_error("cholamd_plan_selinv_blocks: no separator %d", sep); return CHOLAMD_ERR_ARG; }
+  return (p->sep_size[sep] + CHOL_SELINV_W - 1) / CHOL_SELINV_W;
+}
+int cholamd_plan_selinv_front(const cholamd_plan *p, int sep, int block, int cap, int cols[2], int *pos, int64_t *off)
+{
+  if (!p || sep < 1 || sep > p->nsep) { chol_set_error("cholamd_plan_selinv_front: no separator %d", sep); return CHOLAMD_ERR_ARG; }
+  const int nblk = (p->sep_size[sep] + CHOL_SELINV_W - 1) / CHOL_SELINV_W;
+  if (block < 0 || block >= nblk) { chol_set_error("cholamd_plan_selinv_front: separator %d has %d column blocks, not block %d", sep, nblk, block); return CHOLAMD_ERR_ARG; }
+  chol_selinv_level w;
+  int rc = chol_build_selinv_level(p, p->level_of[sep], &w);
+  if (rc) return rc;
+  const chol_selinv_sep *d = NULL;
+  for (int i = 0; i < w.n_sep; i++) if (w.sep[i].sep == sep) d = &w.sep[i];
+  if (!d) { chol_selinv_level_free(&w); chol_set_error("internal: separator %d is not in the lists of its level", sep); return CHOLAMD_ERR_INVARIANT; }
+  const int j0 = block * CHOL_SELINV_W, j1 = j0 + CHOL_SELINV_W < d->w ? j0 + CHOL_SELINV_W : d->w;
+  const int t0 = j1 == d->w ? d->nown : j1 / CHOL_NB;
+  int m = 0;
+  for (int t = t0; t < d->ntile; t++) m += w.tile[d->tile_first + t].nrows;
+  if (cols) { cols[0] = p->sep_off[sep] + j0; cols[1] = j1 - j0; }
+  if (pos || off) {
+    if (m > cap || m > CHOLAMD_SELINV_FRONT_MAX) {
+      chol_selinv_level_free(&w);
+      chol_set_error("cholamd_plan_selinv_front: %d rows below block %d of separator %d (room for %d, at most %d)", m, block, sep, cap, CHOLAMD_SELINV_FRONT_MAX);
+      return CHOLAMD_ERR_ARG;
+    }
+    int *tl = malloc((size_t)(m > 0 ? m : 1) * 2 * sizeof(int));
+    if (!tl) { chol_selinv_level_free(&w); chol_set_error("out of memory"); return CHOLAMD_ERR_NOMEM; }
+    int i = 0;
+    for (int t = t0; t < d->ntile; t++)
+      for (int r = 0; r < w.tile[d->tile_first + t].nrows; r++, i++) {
+        tl[2 * i] = t; tl[2 * i + 1] = r;
+        if (pos) pos[i] = w.tile[d->tile_first + t].pos0 + r;
+      }
+    if (off)
+      for (int a = 0; a < m; a++)
+        for (int b = 0; b < m; b++) off[(size_t)a * m + b] = selinv_offset(&w, d, tl[2 * a], tl[2 * a + 1], tl[2 * b], tl[2 * b + 1]);
+    free(tl);
+  }
+  chol_selinv_level_free(&w);
+  return m;
+}

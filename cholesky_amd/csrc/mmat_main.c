@@ -6,7 +6,9 @@
  *        n a power of two), --repeat n (= --iterations), --full-precision (write %.17g instead of the reference's
  *        %0.8g), --precision fp64|mixed (mixed: fp32 factor + fp64 iterative refinement of the solve),
  *        --logdet (one line "logdet: %.17g" after the factorisation: log det A = 2 sum log L_ii from the factor on the device;
- *        "logdet(fp32 factor): ..." under --precision mixed).
+ *        "logdet(fp32 factor): ..." under --precision mixed),
+ *        --invdiag FILE (after the factorisation: diag(A^-1) by selected inversion -- cholamd_selinv + cholamd_selinv_diag -- in the solution
+ *        writer's format: n lines, original dof order, %0.8g or %.17g under --full-precision; fp64 factor only).
  * Unknown flags (the reference passes -fflow/-ll:cpu/-fcuda/-ll:csize through to Legion) are ignored.
  *
  * Flow = main() of mmat.rg:1056-1496 with the numeric phase on the GPU.  Progress lines keep the
@@ -31,7 +33,7 @@ static double now_s(void)
 int main(int argc, char **argv)
 {
   const char *matrix_file = "", *separator_file = "", *clusters_file = "", *b_file = "", *solution_file = "", *factor_file = "",
-             *permuted_file = "", *debug_path = "";
+             *permuted_file = "", *debug_path = "", *invdiag_file = "";
   int debug = 0, iterations = 1, gpu = 0, full = 0, gpus = 1, want_logdet = 0;
   const char *precision = "fp64";
   for (int i = 0; i < argc; i++) {
@@ -51,6 +53,7 @@ int main(int argc, char **argv)
     else if (!strcmp(argv[i], "--precision")) precision = next;
     else if (!strcmp(argv[i], "--full-precision")) full = 1;
     else if (!strcmp(argv[i], "--logdet")) want_logdet = 1;
+    else if (!strcmp(argv[i], "--invdiag")) invdiag_file = next;
   }
   printf("Iterations: %d\n", iterations);
   if (!*matrix_file || !*separator_file || !*clusters_file) DIE("usage: %s -i A.mtx -s ord.txt -c clust.txt [-b B.mtx -o x.txt] [-m L.mtx] [-p PAPt.mtx] [-d dir] [--iterations n]", argv[0]);
@@ -82,6 +85,7 @@ int main(int argc, char **argv)
   const int mixed = !strcmp(precision, "mixed");
   if (!mixed && strcmp(precision, "fp64")) DIE("--precision %s: fp64 or mixed", precision);
   if (mixed && gpus > 1) DIE("--precision mixed is a single-GPU path");
+  if (mixed && *invdiag_file) DIE("--invdiag needs the fp64 factor (--precision fp64)");
   if (gpus < 1 || gpus > 64 || (gpus & (gpus - 1))) DIE("--gpus must be a power of two");
   if (cholamd_device_count() < gpu + gpus) DIE("--gpus %d from device %d: only %d HIP devices are visible", gpus, gpu, cholamd_device_count());
   /* one device object + arena per GPU; devs[0] ends up with the complete factor */
@@ -130,6 +134,17 @@ int main(int argc, char **argv)
     double logdet = 0.0;
     if (mixed ? cholamd_factor_logdet_f32(dev, (const float *)d_arena, &logdet, NULL) : cholamd_factor_logdet(dev, d_arena, &logdet, NULL)) DIE("logdet: %s", cholamd_last_error());
     printf(mixed ? "logdet(fp32 factor): %.17g\n" : "logdet: %.17g\n", logdet);
+  }
+  if (*invdiag_file) { /* the complete factor is on device 0; the Z arena is a second arena */
+    double *d_z = NULL, *d_diag = NULL, *diag = malloc((size_t)n * sizeof(double));
+    if (!diag) DIE("out of memory");
+    if (cholamd_device_alloc(dev, na, &d_z) || cholamd_device_alloc(dev, n, &d_diag)) DIE("alloc: %s", cholamd_last_error());
+    if (cholamd_selinv(dev, d_arena, d_z, NULL) || cholamd_selinv_diag(dev, d_z, d_diag, NULL) || cholamd_device_download(dev, diag, d_diag, n, NULL))
+      DIE("invdiag: %s", cholamd_last_error());
+    printf("Saving diagonal of the inverse to: %s\n", invdiag_file);
+    if (cholamd_write_solution(invdiag_file, diag, n, full)) DIE("%s", cholamd_last_error());
+    cholamd_device_free(dev, d_z); cholamd_device_free(dev, d_diag);
+    free(diag);
   }
   if (*factor_file) { /* mmat.rg:1360-1362 */
     if (cholamd_device_download(dev, h_arena, d_arena, na, NULL)) DIE("download: %s", cholamd_last_error());

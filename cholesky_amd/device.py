@@ -311,6 +311,40 @@ class Device:
         check(fn(self.h, self.ptr(arena), self.ptr(out), _stream_ptr(stream)), "cholamd_factor_diag")
         return out
 
+    # -- selected inversion: the entries of A^-1 on the pattern of the factor ---------------------------------------------------------
+    def _f64_vec(self, t, what, count):
+        import torch
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_cuda or t.dim() != 1 or t.numel() != count or not t.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous 1-D CUDA float64 tensor of {count} elements")
+        return t
+
+    def selinv(self, arena, zarena=None, stream=None):
+        """Z = (P A P^T)^-1 on the pattern of L from the fp64 factor in `arena` (cholamd_selinv), into `zarena` (a second arena: the arena's own
+        layout, plan.arena_to_dense reads it; allocated when None) -- returned.  Asynchronous on `stream`; deterministic."""
+        if zarena is None:
+            zarena = self.new_arena()
+        check(self.L.cholamd_selinv(self.h, self.ptr(arena), self.ptr(zarena), _stream_ptr(stream)), "cholamd_selinv")
+        return zarena
+
+    def selinv_diag(self, zarena, out=None, stream=None):
+        """diag(A^-1) in original dof order from the Z arena of selinv (cholamd_selinv_diag): a float64 CUDA tensor of n elements."""
+        import torch
+        if out is None:
+            out = torch.empty(self.plan.n, dtype=torch.float64, device=f"cuda:{self.device_id}")
+        self._f64_vec(out, "out", self.plan.n)
+        check(self.L.cholamd_selinv_diag(self.h, self.ptr(zarena), self.ptr(out), _stream_ptr(stream)), "cholamd_selinv_diag")
+        return out
+
+    def selinv_entries(self, zarena, out=None, stream=None):
+        """(A^-1)(row_k, col_k) for every entry k of plan.entries() (the value-array order of set_values) from the Z arena of selinv
+        (cholamd_selinv_entries); NaN for the entries outside the pattern or dropped by the ordering.  A float64 CUDA tensor of plan.nz elements."""
+        import torch
+        if out is None:
+            out = torch.empty(self.plan.nz, dtype=torch.float64, device=f"cuda:{self.device_id}")
+        self._f64_vec(out, "out", self.plan.nz)
+        check(self.L.cholamd_selinv_entries(self.h, self.ptr(zarena), self.ptr(out), self.plan.nz, _stream_ptr(stream)), "cholamd_selinv_entries")
+        return out
+
     def solve_refine_nrhs(self, arena32, B, X, max_iter=20, tol=1e-12, stream=None):
         """cholamd_solve_refine_nrhs: every column of X = A^-1 B by iterative refinement on the fp32 factor; returns (corrections applied, relres per column)."""
         ldb, ldx, k = self._blocks(B, X)

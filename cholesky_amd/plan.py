@@ -202,6 +202,31 @@ class Plan:
             check(n, "cholamd_plan_diag_list")
         return a_off[:n], cols[:n], lda[:n], x_off[:n], sep[:n], prefix[:n + 1]
 
+    SELINV_BLOCK = 64         # CHOLAMD_SELINV_BLOCK: columns of a column block of the selected inversion
+    SELINV_FRONT_MAX = 8192   # CHOLAMD_SELINV_FRONT_MAX: most rows below a block selinv_front tabulates
+
+    def selinv_blocks(self, sep):
+        """Column blocks of separator `sep` (label) in the selected inversion (cholamd_plan_selinv_blocks)."""
+        n = self.L.cholamd_plan_selinv_blocks(self.h, int(sep))
+        if n < 0:
+            check(n, "cholamd_plan_selinv_blocks")
+        return n
+
+    def selinv_front(self, sep, block):
+        """Host view of the gather lists of Device.selinv for column block `block` of separator `sep` (cholamd_plan_selinv_front):
+        (first column's permuted position, columns, pos, off) -- pos[i] = permuted positions of the m rows below the block, off[i, j] = Z-arena offset
+        of Z(pos[i], pos[j]) (the stored side) or -1 = not stored, read as 0.0.  Quadratic in m; refuses m > SELINV_FRONT_MAX."""
+        cols = np.zeros(2, dtype=np.int32)
+        m = self.L.cholamd_plan_selinv_front(self.h, int(sep), int(block), 0, cols.ctypes.data, None, None)
+        if m < 0:
+            check(m, "cholamd_plan_selinv_front")
+        pos = np.zeros(max(m, 1), dtype=np.int32)
+        off = np.zeros((max(m, 1), max(m, 1)), dtype=np.int64)
+        m2 = self.L.cholamd_plan_selinv_front(self.h, int(sep), int(block), m, cols.ctypes.data, pos.ctypes.data, off.ctypes.data)
+        if m2 < 0:
+            check(m2, "cholamd_plan_selinv_front")
+        return int(cols[0]), int(cols[1]), pos[:m], off[:m, :m]
+
     def exchange_pieces(self, world, dist_top=2):
         """The column-block pieces of that exchange as rows (arena offset, elements, owner rank, heap index of the top separator)."""
         out = np.zeros((4096, 4), dtype=np.int64)

@@ -475,6 +475,46 @@ int cholamd_factor_logdet(cholamd_device *d, const double *d_arena, double *logd
 int cholamd_factor_logdet_f32(cholamd_device *d, const float *d_arena32, double *logdet_out, void *stream);
 int cholamd_factor_diag(cholamd_device *d, const double *d_arena, double *d_diag, void *stream);
 int cholamd_factor_diag_f32(cholamd_device *d, const float *d_arena32, double *d_diag, void *stream);
+/* ---- selected inversion (not in the reference; the Takahashi recursion every sparse Cholesky package offers): the entries of A^-1 on the pattern of the
+ * factor -- the diagonal of A^-1 (marginal variances of a Gaussian Markov random field, leverage scores), the entries on the pattern of A (the trace term
+ * tr(A^-1 dA) of a likelihood gradient) -- from the factor, in a small multiple of the factorisation's flops instead of n solves.  fp64 factor only.
+ * With Z = (P A P^T)^-1 = L^-T L^-1 and, for the columns J of a separator, "below" = the rows its panel stores after them:
+ *   Y = L[below, J] L[J, J]^-1,   Z[below, J] = -Z[below, below] Y,   Z[J, J] = L[J, J]^-T L[J, J]^-1 - Y^T Z[below, J],
+ * root first, in column blocks of CHOLAMD_SELINV_BLOCK columns, last block first; Z[below, below] is read from the panels of the ancestors (and the later
+ * blocks), which are complete by then.
+ * cholamd_selinv: d_zarena = cholamd_plan_arena_doubles() doubles in device memory with THE ARENA'S OWN LAYOUT: the element that holds L(i, j) in d_arena
+ * holds Z(i, j) in d_zarena (lower triangle in the diagonal blocks); cholamd_plan_arena_to_dense and cholamd_plan_region read it like a factor.
+ * Asynchronous on `stream`.  Every element of d_zarena is written by the call, whatever it held before (the call starts by zeroing it).
+ * WHAT IS EXACT: the positions of the structural pattern of L (every position where L can be non-zero, hence every position of tril(P A P^T)).  Stored
+ * positions outside that pattern (the rest of the 16-row tiles a panel stores, the parent's rows, the upper triangles and padding rows: zero) hold
+ * finite numbers without meaning for a finite factor.  A position of Z[below, below] no panel stores reads as 0.0: it only ever meets an exact zero of Y.
+ * DETERMINISTIC: every element has one owner and a fixed summation order, no floating-point atomics: two calls on one factor return the same bits.
+ * d_zarena overlapping d_arena (d_zarena == d_arena included): CHOLAMD_ERR_ARG, nothing written -- there is no in-place form.  A NULL pointer:
+ * CHOLAMD_ERR_ARG.  The first call on a device object builds and uploads the gather lists and allocates the workspace (two row-major strips of 64 doubles
+ * per panel row of the widest level); later calls allocate nothing.  A failed factorisation (cholamd_factor_info != 0) gives numbers without meaning (inf
+ * and NaN among them), never a hang.  Like the calls above it needs the COMPLETE factor: a single-GPU device object, or rank 0's after a gather; on
+ * another rank of a partitioned object it returns CHOLAMD_ERR_ARG (that the gather has happened on rank 0 is the caller's business, as for cholamd_solve).
+ * ONE CALL AT A TIME per device object: the workspace (and the lists, built at the first call) belong to the object, as the factorisation's and the
+ * solve's do (see cholamd_factor) -- order the cholamd_selinv calls of one object on one stream, or use one object per concurrent stream.
+ * cholamd_selinv_diag and cholamd_selinv_entries use no workspace.
+ * cholamd_selinv_diag: d_diag[dof] = (A^-1)(dof, dof), n doubles on the device in original dof order, asynchronous: cholamd_factor_diag's walk (the same
+ * kernel) over the Z arena.
+ * cholamd_selinv_entries: the mirror image of cholamd_device_set_values -- d_vals[k] = (A^-1)(row_k, col_k) for entry k of the plan's entry list
+ * (cholamd_plan_entries: the VALUE-ARRAY order), count = cholamd_plan_nz() doubles on the device, asynchronous.  Entries outside the pattern (0.0 when the
+ * plan was made) or dropped by the ordering have no position in any arena: they are written as quiet NaN.  Duplicate entries of one position all receive
+ * the value.  count != cholamd_plan_nz() or a NULL pointer: CHOLAMD_ERR_ARG, nothing written.
+ * Host view of the gather lists (tests and diagnostics, no device): cholamd_plan_selinv_blocks = column blocks of separator `sep` (label);
+ * cholamd_plan_selinv_front: for column block `block` of `sep`, cols[0] = permuted position of the block's first column, cols[1] = its columns; returns m =
+ * the rows below it; pos[i], i < m = their permuted positions (ascending); off[i * m + j] = the Z-arena offset the kernels read Z(pos[i], pos[j]) from
+ * (symmetric: the stored side) or -1 = not stored, read as 0.0.  pos and off may be NULL (the count alone).  The offset table is quadratic in m: with pos or
+ * off given, m > cap or m > CHOLAMD_SELINV_FRONT_MAX is refused (CHOLAMD_ERR_ARG) -- not a call for the fronts of a large problem. */
+#define CHOLAMD_SELINV_BLOCK 64
+#define CHOLAMD_SELINV_FRONT_MAX 8192
+int cholamd_selinv(cholamd_device *d, const double *d_arena, double *d_zarena, void *stream);
+int cholamd_selinv_diag(cholamd_device *d, const double *d_zarena, double *d_diag, void *stream);
+int cholamd_selinv_entries(cholamd_device *d, const double *d_zarena, double *d_vals, int64_t count, void *stream);
+int cholamd_plan_selinv_blocks(const cholamd_plan *p, int sep);
+int cholamd_plan_selinv_front(const cholamd_plan *p, int sep, int block, int cap, int cols[2], int *pos, int64_t *off);
 /* average device time (ms) of the three kernel families of the last cholamd_factor call measured
  * with HIP events on its stream; valid after cholamd_device_sync.  Enable with set_timing(1). */
 int cholamd_device_set_timing(cholamd_device *d, int on);
