@@ -173,6 +173,14 @@ def load():
     L.cholamd_selinv_entries.argtypes = [vp, vp, vp, i64, vp]
     L.cholamd_plan_selinv_blocks.argtypes = [vp, ci]
     L.cholamd_plan_selinv_front.argtypes = [vp, ci, ci, ci, vp, vp, vp]
+    L.cholamd_plan_schur_size.argtypes = [vp, ci]
+    L.cholamd_plan_schur_dofs.argtypes = [vp, ci, vp]
+    L.cholamd_plan_schur_list.argtypes = [vp, ci, i64, vp]
+    L.cholamd_plan_schur_host.argtypes = [vp, ci, vp, vp, i64]
+    L.cholamd_schur_factor.argtypes = [vp, vp, ci, vp]
+    L.cholamd_schur.argtypes = [vp, vp, ci, vp, i64, vp]
+    for f in (L.cholamd_schur_condense, L.cholamd_schur_condense_f32, L.cholamd_schur_expand, L.cholamd_schur_expand_f32):
+        f.argtypes = [vp, vp, ci, vp, vp, vp, vp]
     L.cholamd_device_alloc_arena.argtypes = [vp, ci, C.POINTER(vp), C.POINTER(C.c_int64)]
     L.cholamd_device_free_arena.argtypes = [vp, vp]
     L.cholamd_device_set_timing.argtypes = [vp, ci]

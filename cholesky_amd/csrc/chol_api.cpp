@@ -51,6 +51,7 @@ struct selinv_dev { // the lists of one tree level of the selected inversion (ch
   int *chain_ld = nullptr, *chain_pos0 = nullptr; int64_t *rowoff = nullptr;
   int max_nblk = 0;
 };
+struct schur_dev { chol_schur_desc *desc = nullptr; int64_t n = -1; }; // n < 0: not built yet
 struct timed_launch { hipEvent_t a, b; int kind; };
 
 struct cholamd_device {
@@ -120,6 +121,8 @@ struct cholamd_device {
   double *ld_part = nullptr; int64_t *ld_ipart = nullptr, *ld_res = nullptr;
   // selected inversion (cholamd_selinv): the gather lists of every level and the workspace of the widest level, built at the first call
   std::vector<selinv_dev> si; double *si_ws = nullptr; bool si_ready = false;
+  // Schur complement (cholamd_schur): the gather kernel's piece list per number of kept levels k (index k), uploaded at the first call with that k
+  std::vector<schur_dev> sc;
 };
 
 static int no_device_error()
@@ -197,6 +200,11 @@ static void free_selinv(cholamd_device *d)
   d->si.clear();
   (void)hipFree(d->si_ws); d->si_ws = nullptr;
   d->si_ready = false;
+}
+static void free_schur(cholamd_device *d)
+{
+  for (auto &q : d->sc) (void)hipFree(q.desc);
+  d->sc.clear();
 }
 static int upload_level(level_dev &l, const chol_level_work &w, bool with_tables = true)
 {
@@ -328,6 +336,7 @@ extern "C" void cholamd_device_destroy(cholamd_device *d)
   }
   free_solve_lists(d);
   free_selinv(d);
+  free_schur(d);
   (void)hipFree(d->ws32); (void)hipFree(d->csr_ptr); (void)hipFree(d->csr_col); (void)hipFree(d->csr_val); (void)hipFree(d->rvec); (void)hipFree(d->dxvec); (void)hipFree(d->partial);
   (void)hipFree(d->xstage); (void)hipFree(d->xdesc);
   (void)hipFree(d->ws); (void)hipFree(d->ws_solve); (void)hipFree(d->step_flags); (void)hipFree(d->w256); (void)hipFree(d->step_xt); (void)hipFree(d->info); (void)hipFree(d->progress); (void)hipFree(d->a_dst); (void)hipFree(d->a_val); (void)hipFree(d->perm); (void)hipFree(d->ytmp);
@@ -1512,6 +1521,131 @@ extern "C" int cholamd_selinv_entries(cholamd_device *d, const double *d_zarena,
   HIPCHK((hipError_t)chol_launch_selinv_entries(d_zarena, d->a_dst, d->a_src, p->nnz_a, d_vals, count, (hipStream_t)stream));
   return 0;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Schur complement on the top k levels of the tree (include/cholamd.h at cholamd_schur; the gather kernel in chol_schur.hip).  The factorisation is
+// right-looking: after the levels levels - 1 .. k every contribution of the eliminated separators sits in the blocks of the kept ones, which then hold
+// S = A_TT - A_TI A_II^-1 A_IT.  Condense and expand are the streamed solve cut at level k instead of at the partition's level: the same launches over
+// a level range, the levels above the cut never read as a factor.
+// ---------------------------------------------------------------------------------------------
+static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+  const char *pa = (const char *)a, *pb = (const char *)b;
+  return pa < pb + nb && pb < pa + na;
+}
+// the checks every Schur entry point shares; returns m (the kept dofs) and *t0 = n - m, or the error
+static int schur_args(const cholamd_device *d, int k, const char *what, int *t0)
+{
+  if (!d) { chol_set_error("%s: NULL device", what); return CHOLAMD_ERR_ARG; }
+  if (d->world > 1) { chol_set_error("%s: the device object is partitioned (rank %d of %d); there are no sharded variants", what, d->rank, d->world); return CHOLAMD_ERR_ARG; }
+  return chol_schur_range(d->plan, k, t0);
+}
+extern "C" int cholamd_schur_factor(cholamd_device *d, double *d_arena, int k, void *stream)
+{
+  const int m = schur_args(d, k, "cholamd_schur_factor", nullptr);
+  if (m < 0) return m;
+  if (!d_arena) { chol_set_error("cholamd_schur_factor: NULL arena"); return CHOLAMD_ERR_ARG; }
+  return factor_levels_comm(d, d_arena, d->plan->levels - 1, k, nullptr, (hipStream_t)stream); // the per-level launches, never the program
+}
+static int build_schur(cholamd_device *d, int k)
+{
+  if (d->sc.empty()) d->sc.resize(d->plan->levels);
+  schur_dev &q = d->sc[k];
+  if (q.n >= 0) return 0;
+  const int64_t cnt = chol_schur_pieces(d->plan, k, 1, CHOL_SCHUR_CHUNK, 0, nullptr);
+  if (cnt < 0) return (int)cnt;
+  std::vector<chol_schur_desc> h((size_t)cnt);
+  chol_schur_pieces(d->plan, k, 1, CHOL_SCHUR_CHUNK, cnt, h.data());
+  int rc = upload_vec(&q.desc, h.data(), (size_t)cnt);
+  if (rc) return rc;
+  q.n = cnt;
+  return 0;
+}
+extern "C" int cholamd_schur(cholamd_device *d, const double *d_arena, int k, double *d_S, int64_t lds, void *stream)
+{
+  const int m = schur_args(d, k, "cholamd_schur", nullptr);
+  if (m < 0) return m;
+  if (!d_arena || !d_S) { chol_set_error("cholamd_schur: NULL %s", !d_arena ? "arena" : "S"); return CHOLAMD_ERR_ARG; }
+  if (lds < m) { chol_set_error("cholamd_schur: lds = %lld < m = %d", (long long)lds, m); return CHOLAMD_ERR_ARG; }
+  if (m == 0) return 0;
+  if (ranges_overlap(d_S, ((size_t)(m - 1) * (size_t)lds + (size_t)m) * sizeof(double), d_arena, (size_t)d->plan->arena * sizeof(double))) {
+    chol_set_error("cholamd_schur: S overlaps the arena");
+    return CHOLAMD_ERR_ARG;
+  }
+  HIPCHK(hipSetDevice(d->dev));
+  { int rc = build_schur(d, k); if (rc) return rc; }
+  HIPCHK((hipError_t)chol_launch_schur_gather(d_arena, d->sc[k].desc, d->sc[k].n, d_S, lds, (hipStream_t)stream));
+  return 0;
+}
+// the 16x16 and span inverses of the levels under the cut, from this arena (the levels above it hold S, not a factor)
+template <class TL> static int schur_inverses(cholamd_device *d, const TL *d_arena, int k, hipStream_t st)
+{
+  for (int lvl = k; lvl < d->plan->levels; lvl++) {
+    const solve_dev &s = d->sv[lvl];
+    HIPCHK((hipError_t)lsolve_dinv(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, st));
+    if (s.w256_off >= 0 && d->w256) HIPCHK((hipError_t)lsolve_inv256(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, d->w256 + s.w256_off, st));
+  }
+  return 0;
+}
+template <class TL> static int schur_condense_t(cholamd_device *d, const TL *d_arena, int k, const double *d_b, double *d_w, double *d_g, hipStream_t st, const char *what)
+{
+  int t0 = 0;
+  const int m = schur_args(d, k, what, &t0);
+  if (m < 0) return m;
+  if (!d_arena || !d_b || !d_w || !d_g) { chol_set_error("%s: NULL %s", what, !d_arena ? "arena" : !d_b ? "b" : !d_w ? "w" : "g"); return CHOLAMD_ERR_ARG; }
+  const size_t nb = (size_t)d->plan->n * sizeof(double), mb = (size_t)m * sizeof(double), ab = (size_t)d->plan->arena * sizeof(TL);
+  if (ranges_overlap(d_w, nb, d_b, nb) || ranges_overlap(d_w, nb, d_g, mb) || ranges_overlap(d_g, mb, d_b, nb) || ranges_overlap(d_w, nb, d_arena, ab) ||
+      ranges_overlap(d_g, mb, d_arena, ab)) {
+    chol_set_error("%s: b, w, g and the arena must not overlap each other", what);
+    return CHOLAMD_ERR_ARG;
+  }
+  HIPCHK(hipSetDevice(d->dev));
+  { int rc = build_solve(d); if (rc) return rc; }
+  const int L = d->plan->levels, n = d->plan->n;
+  HIPCHK((hipError_t)chol_launch_permute(d_b, d->perm, d_w, n, 0, st));
+  { int rc = schur_inverses(d, d_arena, k, st); if (rc) return rc; }
+  for (int lvl = L - 1; lvl >= k; lvl--) { // forward sweep under the cut: TRSV per separator, then its panel into the ancestors (the kept ones included)
+    const solve_dev &s = d->sv[lvl];
+    HIPCHK((hipError_t)lsolve_trsv(d, d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, d_w, 0, s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr, st));
+    HIPCHK((hipError_t)lsolve_off(d_arena, s.bw, s.ifw, s.n_ifw, d_w, 0, st));
+  }
+  if (m > 0) HIPCHK(hipMemcpyAsync(d_g, d_w + t0, mb, hipMemcpyDeviceToDevice, st)); // the tail of the permuted vector is g, in Schur order
+  return 0;
+}
+template <class TL> static int schur_expand_t(cholamd_device *d, const TL *d_arena, int k, const double *d_w, const double *d_xt, double *d_x, hipStream_t st, const char *what)
+{
+  int t0 = 0;
+  const int m = schur_args(d, k, what, &t0);
+  if (m < 0) return m;
+  if (!d_arena || !d_w || !d_xt || !d_x) { chol_set_error("%s: NULL %s", what, !d_arena ? "arena" : !d_w ? "w" : !d_xt ? "xt" : "x"); return CHOLAMD_ERR_ARG; }
+  const size_t nb = (size_t)d->plan->n * sizeof(double), mb = (size_t)m * sizeof(double), ab = (size_t)d->plan->arena * sizeof(TL);
+  if (ranges_overlap(d_x, nb, d_w, nb) || ranges_overlap(d_x, nb, d_xt, mb) || ranges_overlap(d_x, nb, d_arena, ab)) {
+    chol_set_error("%s: x must not overlap w, xt or the arena", what);
+    return CHOLAMD_ERR_ARG;
+  }
+  HIPCHK(hipSetDevice(d->dev));
+  { int rc = build_solve(d); if (rc) return rc; }
+  const int L = d->plan->levels, n = d->plan->n;
+  double *y = d->ytmp; // w stays as it is: the sweep runs in the device object's work vector
+  if (t0 > 0) HIPCHK(hipMemcpyAsync(y, d_w, (size_t)t0 * sizeof(double), hipMemcpyDeviceToDevice, st));
+  if (m > 0) HIPCHK(hipMemcpyAsync(y + t0, d_xt, mb, hipMemcpyDeviceToDevice, st));
+  { int rc = schur_inverses(d, d_arena, k, st); if (rc) return rc; } // as at the start of every half solve: the arena of the call before may have been another
+  for (int lvl = k; lvl < L; lvl++) { // backward sweep under the cut: gather from the ancestors, then TRSV^T
+    const solve_dev &s = d->sv[lvl];
+    HIPCHK((hipError_t)lsolve_off(d_arena, s.bw, s.ibw, s.n_ibw, y, 1, st));
+    HIPCHK((hipError_t)lsolve_trsv(d, d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, y, 1, s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr, st));
+  }
+  HIPCHK((hipError_t)chol_launch_permute(y, d->perm, d_x, n, 1, st));
+  return 0;
+}
+extern "C" int cholamd_schur_condense(cholamd_device *d, const double *d_arena, int k, const double *d_b, double *d_w, double *d_g, void *stream)
+{ return schur_condense_t(d, d_arena, k, d_b, d_w, d_g, (hipStream_t)stream, "cholamd_schur_condense"); }
+extern "C" int cholamd_schur_condense_f32(cholamd_device *d, const float *d_arena32, int k, const double *d_b, double *d_w, double *d_g, void *stream)
+{ return schur_condense_t(d, d_arena32, k, d_b, d_w, d_g, (hipStream_t)stream, "cholamd_schur_condense_f32"); }
+extern "C" int cholamd_schur_expand(cholamd_device *d, const double *d_arena, int k, const double *d_w, const double *d_xt, double *d_x, void *stream)
+{ return schur_expand_t(d, d_arena, k, d_w, d_xt, d_x, (hipStream_t)stream, "cholamd_schur_expand"); }
+extern "C" int cholamd_schur_expand_f32(cholamd_device *d, const float *d_arena32, int k, const double *d_w, const double *d_xt, double *d_x, void *stream)
+{ return schur_expand_t(d, d_arena32, k, d_w, d_xt, d_x, (hipStream_t)stream, "cholamd_schur_expand_f32"); }
 
 // one chunk's residuals: R = B - A X (column-major, ld n), rel[j] = ||r_j|| / ||b_j||
 static int residual_nrhs(cholamd_device *d, const double *d_B, int64_t ldb, const double *d_X, int64_t ldx, int cols, double *rel, hipStream_t st)

@@ -86,6 +86,9 @@ int chol32_launch_factor_logdet(const float *base, const chol_trsv_desc *descs, 
 int chol_launch_selinv_step(const double *L, double *Z, double *ws, const chol_selinv_sep *seps, int n_act, const chol_selinv_tile *tiles, const int *chain_ld,
                             const int *chain_pos0, const int64_t *rowoff, int step, int max_below_tiles, hipStream_t st);
 int chol_launch_selinv_entries(const double *Z, const int64_t *a_dst, const int *a_src, int64_t nnz, double *vals, int64_t nz, hipStream_t st);
+/* Schur complement (chol_schur.hip): S (m x m, column-major, leading dimension lds) from the pieces of chol_schur_pieces(p, k, 1, CHOL_SCHUR_CHUNK): both
+ * triangles, the zeros of the pieces without storage included; one owner per element, no atomics */
+int chol_launch_schur_gather(const double *arena, const chol_schur_desc *descs, int64_t ndesc, double *S, int64_t lds, hipStream_t st);
 /* diagnostic instance of the program launch (k_program<true>): 4 stamps per job, then CHOL_TRACE_X per job -- [0] follower: own tiles' wait over,
  * [1] its items, [2 + i] round of item i begun; [48 + k] POTRF job: column k published / TRSM job (first strip): column tile k on its channel;
  * [72 + k] POTRF job: the factor wave starts column k / TRSM job: the POTRF's column k seen */

@@ -433,6 +433,17 @@ typedef struct {
 } chol_selinv_level;
 int chol_build_selinv_level(const struct cholamd_plan *p, int level, chol_selinv_level *out);
 void chol_selinv_level_free(chol_selinv_level *w);
+
+/* ---- Schur complement on the top k levels of the tree (cholamd_schur; chol_schur.hip).  The kept separators (heap indices 1 .. 2^k - 1) are the tail
+ * [t0, n) of the permuted order; Schur coordinate i = permuted position t0 + i.  A PIECE is one 16-row tile of a block (r, c) of two kept separators, r at or
+ * after c in the permuted order, over the block's columns (a diagonal block: the columns up to the tile's last row -- the lower triangle), optionally cut
+ * into chunks of `chunk` columns.  off = arena offset of the piece's first element, or -1: the block does not exist (r, c not ancestor and descendant) or
+ * the row compaction dropped the tile -- structurally zero; with_empty = 0 leaves those out (the host view cholamd_plan_schur_list), with_empty = 1 makes the
+ * pieces tile the lower triangle of S exactly once (the gather kernel's list: it writes the zeros too).  diag: only row0 + i >= col0 + j is meant. */
+#define CHOL_SCHUR_CHUNK 64 /* columns of a piece of the gather kernel's list: one workgroup moves 16 x 64 */
+typedef struct { int64_t off; int ld, rows, cols, row0, col0, diag; } chol_schur_desc;
+int chol_schur_range(const struct cholamd_plan *p, int k, int *t0_out); /* m (the kept dofs), *t0_out = n - m; < 0: error */
+int64_t chol_schur_pieces(const struct cholamd_plan *p, int k, int with_empty, int chunk /* 0: whole */, int64_t cap, chol_schur_desc *out); /* the count, whatever cap */
 void chol_set_error(const char *fmt, ...);
 
 #ifdef __cplusplus

@@ -2428,3 +2428,123 @@ int cholamd_plan_selinv_front(const cholamd_plan *p, int sep, int block, int cap
   chol_selinv_level_free(&w);
   return m;
 }
+
+/* ---------------------------------------------------------------------------------------- */
+/* Schur complement on the top k levels of the tree (include/cholamd.h at cholamd_schur)       */
+/* ---------------------------------------------------------------------------------------- */
+int chol_schur_range(const cholamd_plan *p, int k, int *t0_out)
+{
+  if (!p) { chol_set_error("schur: NULL plan"); return CHOLAMD_ERR_ARG; }
+  if (k < 1 || k > p->levels - 1 || (1 << k) - 1 > p->nsep) {
+    chol_set_error("schur: k = %d kept levels, the tree of %d levels allows 1 .. %d", k, p->levels, p->levels - 1);
+    return CHOLAMD_ERR_ARG;
+  }
+  const int nk = (1 << k) - 1;
+  int m = 0, lo = p->n;
+  for (int h = 1; h <= nk; h++) {
+    const int s = p->tree[h];
+    if (p->sep_size[s] <= 0) continue;
+    m += p->sep_size[s];
+    if (p->sep_off[s] < lo) lo = p->sep_off[s];
+  }
+  if (lo != p->n - m) { /* the kept separators are the last labels: a contiguous tail of the permuted order */
+    chol_set_error("schur: the top %d levels hold %d dofs but start at permuted position %d of %d", k, m, lo, p->n);
+    return CHOLAMD_ERR_INVARIANT;
+  }
+  if (t0_out) *t0_out = lo;
+  return m;
+}
+int64_t chol_schur_pieces(const cholamd_plan *p, int k, int with_empty, int chunk, int64_t cap, chol_schur_desc *out)
+{
+  int t0 = 0;
+  const int m = chol_schur_range(p, k, &t0);
+  if (m < 0) return m;
+  const int nk = (1 << k) - 1;
+  int64_t cnt = 0;
+  for (int hc = 1; hc <= nk; hc++) {
+    const int c = p->tree[hc], wc = p->sep_size[c];
+    if (wc <= 0) continue;
+    for (int hr = 1; hr <= nk; hr++) {
+      const int r = p->tree[hr], wr = p->sep_size[r];
+      if (wr <= 0 || p->sep_off[r] < p->sep_off[c]) continue; /* the lower block triangle */
+      const chol_block *B = chol_plan_block(p, r, c);
+      if (!B && !with_empty) continue; /* not ancestor and descendant: structurally zero */
+      if (B && (B->rows != wr || B->cols != wc || B->lo_x != p->sep_off[r] || B->lo_y != p->sep_off[c])) {
+        chol_set_error("internal: block (%d, %d) does not span its separators", r, c);
+        return CHOLAMD_ERR_INVARIANT;
+      }
+      const int diag = r == c;
+      for (int i0 = 0; i0 < wr; i0 += CHOL_NB) {
+        const int rows = wr - i0 < CHOL_NB ? wr - i0 : CHOL_NB;
+        const int64_t row = B ? chol_block_row(B, i0) : -1;
+        if (row < 0 && !with_empty) continue; /* a tile the row compaction dropped */
+        const int ncols = diag ? i0 + rows : wc; /* a diagonal block stores its lower triangle */
+        if (row >= 0 && (row + rows - 1 + (int64_t)(ncols - 1) * B->ld >= p->arena)) {
+          chol_set_error("internal: tile %d of block (%d, %d) leaves the arena", i0 / CHOL_NB, r, c);
+          return CHOLAMD_ERR_INVARIANT;
+        }
+        const int step = chunk > 0 ? chunk : ncols;
+        for (int j0 = 0; j0 < ncols; j0 += step, cnt++) {
+          if (cnt >= cap) continue;
+          chol_schur_desc *q = &out[cnt];
+          q->off = row < 0 ? -1 : row + (int64_t)j0 * B->ld;
+          q->ld = B ? B->ld : 0;
+          q->rows = rows; q->cols = ncols - j0 < step ? ncols - j0 : step;
+          q->row0 = p->sep_off[r] - t0 + i0; q->col0 = p->sep_off[c] - t0 + j0;
+          q->diag = diag;
+        }
+      }
+    }
+  }
+  return cnt;
+}
+int cholamd_plan_schur_size(const cholamd_plan *p, int k) { return chol_schur_range(p, k, NULL); }
+int cholamd_plan_schur_dofs(const cholamd_plan *p, int k, int *dofs_out)
+{
+  int t0 = 0;
+  const int m = chol_schur_range(p, k, &t0);
+  if (m < 0) return m;
+  if (!dofs_out) { chol_set_error("cholamd_plan_schur_dofs: NULL dofs_out"); return CHOLAMD_ERR_ARG; }
+  memcpy(dofs_out, p->perm + t0, (size_t)m * sizeof(int));
+  return m;
+}
+int cholamd_plan_schur_list(const cholamd_plan *p, int k, int64_t cap, int64_t *out)
+{
+  const int64_t cnt = chol_schur_pieces(p, k, 0, 0, 0, NULL);
+  if (cnt < 0) return (int)cnt;
+  if (cnt > INT32_MAX) { chol_set_error("cholamd_plan_schur_list: %lld records", (long long)cnt); return CHOLAMD_ERR_ARG; }
+  if (cap <= 0 || !out) return (int)cnt;
+  chol_schur_desc *q = malloc((size_t)(cnt > 0 ? cnt : 1) * sizeof *q);
+  if (!q) { chol_set_error("out of memory"); return CHOLAMD_ERR_NOMEM; }
+  chol_schur_pieces(p, k, 0, 0, cnt, q);
+  for (int64_t i = 0; i < cnt && i < cap; i++) {
+    int64_t *o = out + CHOLAMD_SCHUR_RECORD * i;
+    o[0] = q[i].off; o[1] = q[i].ld; o[2] = q[i].rows; o[3] = q[i].cols; o[4] = q[i].row0; o[5] = q[i].col0; o[6] = q[i].diag;
+  }
+  free(q);
+  return (int)cnt;
+}
+int cholamd_plan_schur_host(const cholamd_plan *p, int k, const double *arena_host, double *S, int64_t lds)
+{
+  const int m = chol_schur_range(p, k, NULL);
+  if (m < 0) return m;
+  if (!arena_host || !S) { chol_set_error("cholamd_plan_schur_host: NULL %s", !arena_host ? "arena" : "S"); return CHOLAMD_ERR_ARG; }
+  if (lds < m) { chol_set_error("cholamd_plan_schur_host: lds = %lld < m = %d", (long long)lds, m); return CHOLAMD_ERR_ARG; }
+  const int64_t cnt = chol_schur_pieces(p, k, 0, 0, 0, NULL);
+  if (cnt < 0) return (int)cnt;
+  chol_schur_desc *q = malloc((size_t)(cnt > 0 ? cnt : 1) * sizeof *q);
+  if (!q) { chol_set_error("out of memory"); return CHOLAMD_ERR_NOMEM; }
+  chol_schur_pieces(p, k, 0, 0, cnt, q);
+  for (int j = 0; j < m; j++) memset(S + (int64_t)j * lds, 0, (size_t)m * sizeof(double));
+  for (int64_t e = 0; e < cnt; e++)
+    for (int j = 0; j < q[e].cols; j++)
+      for (int i = 0; i < q[e].rows; i++) {
+        const int R = q[e].row0 + i, C = q[e].col0 + j;
+        if (q[e].diag && R < C) continue;
+        const double v = arena_host[q[e].off + i + (int64_t)j * q[e].ld];
+        S[R + (int64_t)C * lds] = v;
+        S[C + (int64_t)R * lds] = v;
+      }
+  free(q);
+  return 0;
+}

@@ -8,7 +8,10 @@
  *        --logdet (one line "logdet: %.17g" after the factorisation: log det A = 2 sum log L_ii from the factor on the device;
  *        "logdet(fp32 factor): ..." under --precision mixed),
  *        --invdiag FILE (after the factorisation: diag(A^-1) by selected inversion -- cholamd_selinv + cholamd_selinv_diag -- in the solution
- *        writer's format: n lines, original dof order, %0.8g or %.17g under --full-precision; fp64 factor only).
+ *        writer's format: n lines, original dof order, %0.8g or %.17g under --full-precision; fp64 factor only),
+ *        --schur K FILE (after the factorisation: the Schur complement of A on the K kept tree levels -- cholamd_schur_factor + cholamd_schur on a second,
+ *        freshly filled arena -- as a Matrix-Market dense `array` file, %.17g, column by column, and the Schur dofs, 1-based, one per line, as FILE.dofs;
+ *        single GPU, fp64 only).
  * Unknown flags (the reference passes -fflow/-ll:cpu/-fcuda/-ll:csize through to Legion) are ignored.
  *
  * Flow = main() of mmat.rg:1056-1496 with the numeric phase on the GPU.  Progress lines keep the
@@ -33,8 +36,8 @@ static double now_s(void)
 int main(int argc, char **argv)
 {
   const char *matrix_file = "", *separator_file = "", *clusters_file = "", *b_file = "", *solution_file = "", *factor_file = "",
-             *permuted_file = "", *debug_path = "", *invdiag_file = "";
-  int debug = 0, iterations = 1, gpu = 0, full = 0, gpus = 1, want_logdet = 0;
+             *permuted_file = "", *debug_path = "", *invdiag_file = "", *schur_file = "";
+  int debug = 0, iterations = 1, gpu = 0, full = 0, gpus = 1, want_logdet = 0, schur_k = 0;
   const char *precision = "fp64";
   for (int i = 0; i < argc; i++) {
     const char *next = i + 1 < argc ? argv[i + 1] : "";
@@ -54,6 +57,7 @@ int main(int argc, char **argv)
     else if (!strcmp(argv[i], "--full-precision")) full = 1;
     else if (!strcmp(argv[i], "--logdet")) want_logdet = 1;
     else if (!strcmp(argv[i], "--invdiag")) invdiag_file = next;
+    else if (!strcmp(argv[i], "--schur")) { schur_k = atoi(next); schur_file = i + 2 < argc ? argv[i + 2] : ""; if (!*schur_file) DIE("--schur K FILE"); }
   }
   printf("Iterations: %d\n", iterations);
   if (!*matrix_file || !*separator_file || !*clusters_file) DIE("usage: %s -i A.mtx -s ord.txt -c clust.txt [-b B.mtx -o x.txt] [-m L.mtx] [-p PAPt.mtx] [-d dir] [--iterations n]", argv[0]);
@@ -86,6 +90,8 @@ int main(int argc, char **argv)
   if (!mixed && strcmp(precision, "fp64")) DIE("--precision %s: fp64 or mixed", precision);
   if (mixed && gpus > 1) DIE("--precision mixed is a single-GPU path");
   if (mixed && *invdiag_file) DIE("--invdiag needs the fp64 factor (--precision fp64)");
+  if (*schur_file && (mixed || gpus > 1)) DIE("--schur is a single-GPU fp64 path");
+  if (*schur_file && cholamd_plan_schur_size(plan, schur_k) < 0) DIE("--schur: %s", cholamd_last_error());
   if (gpus < 1 || gpus > 64 || (gpus & (gpus - 1))) DIE("--gpus must be a power of two");
   if (cholamd_device_count() < gpu + gpus) DIE("--gpus %d from device %d: only %d HIP devices are visible", gpus, gpu, cholamd_device_count());
   /* one device object + arena per GPU; devs[0] ends up with the complete factor */
@@ -145,6 +151,34 @@ int main(int argc, char **argv)
     if (cholamd_write_solution(invdiag_file, diag, n, full)) DIE("%s", cholamd_last_error());
     cholamd_device_free(dev, d_z); cholamd_device_free(dev, d_diag);
     free(diag);
+  }
+  if (*schur_file) { /* a second arena, filled again and eliminated down to level K only: its kept blocks hold S */
+    const int m = cholamd_plan_schur_size(plan, schur_k);
+    double *d_a2 = NULL, *d_S = NULL, *S = malloc((size_t)(m > 0 ? m : 1) * (size_t)(m > 0 ? m : 1) * sizeof(double));
+    int *dofs = malloc((size_t)(m > 0 ? m : 1) * sizeof(int));
+    if (!S || !dofs) DIE("out of memory");
+    if (cholamd_device_alloc(dev, na, &d_a2) || cholamd_device_alloc(dev, (int64_t)(m > 0 ? m : 1) * (m > 0 ? m : 1), &d_S)) DIE("alloc: %s", cholamd_last_error());
+    if (cholamd_device_fill(dev, d_a2, NULL) || cholamd_schur_factor(dev, d_a2, schur_k, NULL) || cholamd_schur(dev, d_a2, schur_k, d_S, m, NULL) ||
+        cholamd_device_download(dev, S, d_S, (int64_t)m * m, NULL) || cholamd_plan_schur_dofs(plan, schur_k, dofs) < 0)
+      DIE("schur: %s", cholamd_last_error());
+    int sep = 0, info = cholamd_factor_info(dev, &sep);
+    if (info < 0) DIE("schur: %s", cholamd_last_error());
+    if (info > 0) fprintf(stderr, "warning: leading minor %d of separator %d is not positive definite\n", info, sep);
+    printf("Saving Schur complement (%d kept levels, %d dofs) to: %s\n", schur_k, m, schur_file);
+    FILE *fs = fopen(schur_file, "w");
+    if (!fs) DIE("cannot write %s", schur_file);
+    fprintf(fs, "%%%%MatrixMarket matrix array real general\n%d %d\n", m, m);
+    for (int64_t e = 0; e < (int64_t)m * m; e++) fprintf(fs, "%.17g\n", S[e]);
+    if (fclose(fs)) DIE("cannot write %s", schur_file);
+    char *dofs_name = malloc(strlen(schur_file) + 6);
+    if (!dofs_name) DIE("out of memory");
+    sprintf(dofs_name, "%s.dofs", schur_file);
+    FILE *fd = fopen(dofs_name, "w");
+    if (!fd) DIE("cannot write %s", dofs_name);
+    for (int i = 0; i < m; i++) fprintf(fd, "%d\n", dofs[i] + 1);
+    if (fclose(fd)) DIE("cannot write %s", dofs_name);
+    cholamd_device_free(dev, d_a2); cholamd_device_free(dev, d_S);
+    free(dofs_name); free(dofs); free(S);
   }
   if (*factor_file) { /* mmat.rg:1360-1362 */
     if (cholamd_device_download(dev, h_arena, d_arena, na, NULL)) DIE("download: %s", cholamd_last_error());

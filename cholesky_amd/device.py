@@ -345,6 +345,58 @@ class Device:
         check(self.L.cholamd_selinv_entries(self.h, self.ptr(zarena), self.ptr(out), self.plan.nz, _stream_ptr(stream)), "cholamd_selinv_entries")
         return out
 
+    # -- Schur complement on the top k levels of the tree: S = A_TT - A_TI A_II^-1 A_IT, condense, expand ---------------------------
+    def schur_factor(self, arena, k, stream=None):
+        """Eliminate the tree levels levels - 1 .. k of a filled fp64 arena by the per-level launches (cholamd_schur_factor): the blocks of the k kept
+        levels then hold S.  factor_levels(arena, k - 1, 0) afterwards completes the factor.  Asynchronous on `stream`."""
+        check(self.L.cholamd_schur_factor(self.h, self.ptr(arena), int(k), _stream_ptr(stream)), "cholamd_schur_factor")
+
+    def schur(self, arena, k, out=None, stream=None):
+        """S as an m x m column-major float64 CUDA tensor (stride(0) == 1), both triangles, in the Schur order of plan.schur_dofs(k) (cholamd_schur).
+        `out`: a 2-D column-major tensor of m columns and at least m rows -- the rows beyond m are never touched; allocated when None.  fp64 arena
+        only.  Asynchronous on `stream`; deterministic.  Returns the m x m view."""
+        import torch
+        if self._is_f32(arena):
+            raise ValueError("schur needs the fp64 arena (there is no fp32 form of cholamd_schur)")
+        m = self.plan.schur_size(k)
+        if out is None:
+            out = torch.empty((m, m), dtype=torch.float64, device=f"cuda:{self.device_id}").T
+        if not isinstance(out, torch.Tensor) or out.dim() != 2 or not out.is_cuda or out.dtype != torch.float64:
+            raise ValueError("out must be a 2-D CUDA float64 tensor, e.g. torch.empty(m, lds).T")
+        if out.shape[1] != m or out.shape[0] < m:
+            raise ValueError(f"out has shape {tuple(out.shape)}, S is {m} x {m}")
+        if m > 0 and out.stride(0) != 1:
+            raise ValueError(f"out must be column-major (stride(0) == 1), e.g. torch.empty(m, lds).T; got strides {out.stride()}")
+        if m > 1 and out.stride(1) < out.shape[0]:
+            raise ValueError(f"out has column stride {out.stride(1)} < its {out.shape[0]} rows: its columns overlap")
+        lds = int(out.stride(1)) if m > 1 else max(int(out.shape[0]), 1)
+        check(self.L.cholamd_schur(self.h, self.ptr(arena), int(k), self.ptr(out), lds, _stream_ptr(stream)), "cholamd_schur")
+        return out[:m, :]
+
+    def schur_condense(self, arena, k, b, w=None, g=None, stream=None):
+        """g = b_T - A_TI A_II^-1 b_I (m doubles, Schur order) and the state w of schur_expand (n doubles) from b (n doubles, original dof order):
+        cholamd_schur_condense / _f32 by the arena's element type.  w and g are allocated when None; returns (w, g).  Asynchronous on `stream`."""
+        import torch
+        n, m = self.plan.n, self.plan.schur_size(k)
+        self._f64_vec(b, "b", n)
+        w = torch.empty(n, dtype=torch.float64, device=f"cuda:{self.device_id}") if w is None else self._f64_vec(w, "w", n)
+        g = torch.empty(m, dtype=torch.float64, device=f"cuda:{self.device_id}") if g is None else self._f64_vec(g, "g", m)
+        fn = self.L.cholamd_schur_condense_f32 if self._is_f32(arena) else self.L.cholamd_schur_condense
+        check(fn(self.h, self.ptr(arena), int(k), self.ptr(b), self.ptr(w), self.ptr(g), _stream_ptr(stream)), "cholamd_schur_condense")
+        return w, g
+
+    def schur_expand(self, arena, k, w, xt, x=None, stream=None):
+        """The full solution x (n doubles, original dof order) from the state w of schur_condense and the caller's solution xt of S x_T = g (m doubles,
+        Schur order): cholamd_schur_expand / _f32 by the arena's element type.  w is not modified; x is allocated when None and returned."""
+        import torch
+        n, m = self.plan.n, self.plan.schur_size(k)
+        self._f64_vec(w, "w", n)
+        self._f64_vec(xt, "xt", m)
+        x = torch.empty(n, dtype=torch.float64, device=f"cuda:{self.device_id}") if x is None else self._f64_vec(x, "x", n)
+        fn = self.L.cholamd_schur_expand_f32 if self._is_f32(arena) else self.L.cholamd_schur_expand
+        check(fn(self.h, self.ptr(arena), int(k), self.ptr(w), self.ptr(xt), self.ptr(x), _stream_ptr(stream)), "cholamd_schur_expand")
+        return x
+
     def solve_refine_nrhs(self, arena32, B, X, max_iter=20, tol=1e-12, stream=None):
         """cholamd_solve_refine_nrhs: every column of X = A^-1 B by iterative refinement on the fp32 factor; returns (corrections applied, relres per column)."""
         ldb, ldx, k = self._blocks(B, X)

@@ -275,6 +275,44 @@ class Plan:
         nj = int(buf[-1])
         return buf[:8 * nj].reshape(nj, 8), buf[8 * nj:-1].reshape(-1, 3)
 
+    # -- Schur complement on the top k levels of the tree (the host side of Device.schur*) -----------------------------------------
+    SCHUR_RECORD = 7  # CHOLAMD_SCHUR_RECORD: int64 words per record of schur_list
+
+    def schur_size(self, k):
+        """m = the dofs of the k kept tree levels (heap indices 1 .. 2^k - 1): cholamd_plan_schur_size.  They are permuted positions [n - m, n)."""
+        m = self.L.cholamd_plan_schur_size(self.h, int(k))
+        if m < 0:
+            check(m, "cholamd_plan_schur_size")
+        return m
+
+    def schur_dofs(self, k):
+        """The m original dof ids in Schur order (entry i = perm[n - m + i]): cholamd_plan_schur_dofs."""
+        m = self.schur_size(k)
+        out = np.zeros(max(m, 1), dtype=np.int32)
+        check(min(self.L.cholamd_plan_schur_dofs(self.h, int(k), out.ctypes.data), 0), "cholamd_plan_schur_dofs")
+        return out[:m]
+
+    def schur_list(self, k):
+        """Host view of the gather of Device.schur (cholamd_plan_schur_list): int64 rows (arena offset, leading dimension, rows, columns, first row,
+        first column in Schur coordinates, 1 = in a diagonal block: lower triangle only), one per stored 16-row tile piece of a kept block."""
+        cnt = self.L.cholamd_plan_schur_list(self.h, int(k), 0, None)
+        if cnt < 0:
+            check(cnt, "cholamd_plan_schur_list")
+        out = np.zeros((max(cnt, 1), self.SCHUR_RECORD), dtype=np.int64)
+        check(min(self.L.cholamd_plan_schur_list(self.h, int(k), cnt, out.ctypes.data), 0), "cholamd_plan_schur_list")
+        return out[:cnt]
+
+    def schur_host(self, k, arena, lds=None):
+        """S (m x m, both triangles) gathered on the CPU from a host arena (cholamd_plan_schur_host): what Device.schur writes, bit for bit.  `lds`:
+        leading dimension of the column-major result (default m); the rows m .. lds - 1 are returned as NaN, untouched."""
+        arena = np.ascontiguousarray(arena, dtype=np.float64)
+        assert arena.size == self.arena_doubles
+        m = self.schur_size(k)
+        ld = m if lds is None else int(lds)
+        buf = np.full((max(m, 1), max(ld, 1)), np.nan, dtype=np.float64)  # row j of the buffer = column j of S
+        check(self.L.cholamd_plan_schur_host(self.h, int(k), arena.ctypes.data, buf.ctypes.data, ld), "cholamd_plan_schur_host")
+        return buf[:m, :].T if lds is not None else buf[:m, :m].T
+
     def arena_to_dense(self, arena):
         arena = np.ascontiguousarray(arena, dtype=np.float64)
         assert arena.size == self.arena_doubles

@@ -515,6 +515,62 @@ int cholamd_selinv_diag(cholamd_device *d, const double *d_zarena, double *d_dia
 int cholamd_selinv_entries(cholamd_device *d, const double *d_zarena, double *d_vals, int64_t count, void *stream);
 int cholamd_plan_selinv_blocks(const cholamd_plan *p, int sep);
 int cholamd_plan_selinv_front(const cholamd_plan *p, int sep, int block, int cap, int cols[2], int *pos, int64_t *off);
+/* ---- Schur complement on the top of the tree, with condense and expand (not in the reference; the "Schur complement" / "partial factorisation" option of
+ * MUMPS and PARDISO): eliminate the interior dofs I, keep the interface dofs T, and receive  S = A_TT - A_TI A_II^-1 A_IT  -- substructuring, domain
+ * decomposition, static condensation, constrained Gaussian Markov random fields.  The caller assembles or solves the interface problem, then recovers the interior.
+ * k = the number of tree levels KEPT, 1 <= k <= levels - 1: the kept separators are heap indices 1 .. 2^k - 1 (cholamd_plan_tree), m = the sum of their sizes,
+ * t0 = n - m.  They are the tail [t0, n) of the permuted order (checked: CHOLAMD_ERR_INVARIANT otherwise).
+ * THE SCHUR ORDER: entry i of every m-vector and row / column i of S is permuted position t0 + i, i.e. original dof perm[t0 + i] (cholamd_plan_schur_dofs).
+ * Why the arena holds S: the factorisation is right-looking and level by level, leaves first.  After the levels levels - 1 .. k every contribution of the
+ * eliminated separators has been extend-added into the blocks of the kept ones, and nothing else has touched them: they hold S, lower triangle, in the arena's
+ * row-compacted layout.
+ *
+ * Host side (no device):
+ * cholamd_plan_schur_size: m, or CHOLAMD_ERR_ARG for k out of range.
+ * cholamd_plan_schur_dofs: writes the m original dof ids in Schur order, returns m.
+ * cholamd_plan_schur_list (tests and diagnostics): one record of CHOLAMD_SCHUR_RECORD int64 per STORED 16-row tile piece of a block of two kept separators:
+ *   [0] arena offset of the piece's first element, [1] leading dimension, [2] rows (<= 16), [3] columns, [4] first row and [5] first column in Schur
+ *   coordinates, [6] 1 = the piece lies in a diagonal block, which stores its lower triangle: only elements with row >= column are meant (its columns end at the
+ *   tile's last row).  Element (i, j) of a piece is arena[[0] + i + j * [1]] = S([4] + i, [5] + j).  Lower-triangle positions of S no record covers are exact
+ *   zeros: the two separators are not ancestor and descendant, or the row compaction dropped the tile (cholamd_plan_block_tile_map: -1).  Returns the number of
+ *   records and writes at most cap of them; cap = 0 (out may be NULL) sizes the buffer.  The gather kernel's list is built from the same enumeration (cut into
+ *   chunks of 64 columns, the pieces without storage added as zeros).
+ * cholamd_plan_schur_host: the gather restated on the CPU over a host arena: S column-major m x m, lds >= m, both triangles, every element written, rows
+ *   m .. lds - 1 untouched.  NULL pointer or lds < m: CHOLAMD_ERR_ARG, nothing written.
+ *
+ * Device side.  Common rules -- CHOLAMD_ERR_ARG with NOTHING written for: k out of range, a NULL pointer, a partitioned device object (world > 1).  There are
+ * NO sharded variants and NO _nrhs variants of these calls.
+ * cholamd_schur_factor: eliminates the levels levels - 1 .. k of a filled arena by the per-level launches -- the launches of cholamd_factor_levels(d, a,
+ *   levels - 1, k); it never uses the one-launch program, whatever the problem's size.  Asynchronous on `stream`; cholamd_factor_info reports pivots as usual.
+ *   cholamd_factor_levels(d, a, k - 1, 0) afterwards COMPLETES the factor: the arena is then bit-identical to one factored by cholamd_factor_levels(d, a,
+ *   levels - 1, 0).
+ * cholamd_schur: d_S column-major m x m in device memory, lds >= m, BOTH triangles (the stored lower one is mirrored).  Every one of the m x m elements is
+ *   written by the call -- the exact zeros between unrelated kept separators and of tiles without storage included; rows m .. lds - 1 are never touched.  A pure
+ *   gather: one owner per element, no atomics, bit-identical from call to call.  Asynchronous.  lds < m, or d_S overlapping the arena: CHOLAMD_ERR_ARG.  The
+ *   piece list is uploaded at the first call per (device object, k); later calls allocate nothing.  fp64 arena ONLY: there is no cholamd_schur_f32 (take S from
+ *   an fp64 run).
+ * cholamd_schur_condense: d_b n doubles in ORIGINAL dof order; d_g m doubles in Schur order = b_T - A_TI A_II^-1 b_I; d_w n doubles of opaque state for the
+ *   expand (the permuted, forward-swept vector).  The call permutes, forms the 16x16 and span inverses of the levels >= k ONLY -- the levels < k hold S, not a
+ *   factor, and are never read as one -- and runs the forward sweep of the levels levels - 1 .. k with the kernels of cholamd_solve.  The off-diagonal blocks
+ *   accumulate by fp64 atomics: g agrees from run to run to rounding, not bit for bit.  Asynchronous.  b, w, g and the arena must not overlap each other:
+ *   CHOLAMD_ERR_ARG.
+ * cholamd_schur_expand: d_xt = the caller's solution of S x_T = g (m doubles, Schur order); d_x = the full solution, n doubles, original order.  Backward sweep
+ *   of the levels k .. levels - 1 and the inverse permutation.  d_w is NOT modified (the sweep runs in the device object's work vector, and the inverses are
+ *   formed again from d_arena, as at the start of every half solve), so one condense serves any number of expands.  x overlapping w, xt or the arena:
+ *   CHOLAMD_ERR_ARG.  ONE CALL AT A TIME per device object, as for the solve.  Asynchronous.
+ * _f32: the same on an fp32 arena partially factored with cholamd_factor_levels_f32(d, a32, levels - 1, k) (vectors and arithmetic fp64).
+ * A failed factorisation (cholamd_factor_info != 0) gives numbers without meaning, never a hang. */
+#define CHOLAMD_SCHUR_RECORD 7
+int cholamd_plan_schur_size(const cholamd_plan *p, int k);
+int cholamd_plan_schur_dofs(const cholamd_plan *p, int k, int *dofs_out);
+int cholamd_plan_schur_list(const cholamd_plan *p, int k, int64_t cap, int64_t *out);
+int cholamd_plan_schur_host(const cholamd_plan *p, int k, const double *arena_host, double *S, int64_t lds);
+int cholamd_schur_factor(cholamd_device *d, double *d_arena, int k, void *stream);
+int cholamd_schur(cholamd_device *d, const double *d_arena, int k, double *d_S, int64_t lds, void *stream);
+int cholamd_schur_condense(cholamd_device *d, const double *d_arena, int k, const double *d_b, double *d_w, double *d_g, void *stream);
+int cholamd_schur_expand(cholamd_device *d, const double *d_arena, int k, const double *d_w, const double *d_xt, double *d_x, void *stream);
+int cholamd_schur_condense_f32(cholamd_device *d, const float *d_arena32, int k, const double *d_b, double *d_w, double *d_g, void *stream);
+int cholamd_schur_expand_f32(cholamd_device *d, const float *d_arena32, int k, const double *d_w, const double *d_xt, double *d_x, void *stream);
 /* average device time (ms) of the three kernel families of the last cholamd_factor call measured
  * with HIP events on its stream; valid after cholamd_device_sync.  Enable with set_timing(1). */
 int cholamd_device_set_timing(cholamd_device *d, int on);
