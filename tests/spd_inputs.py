@@ -4,6 +4,8 @@ Every reference fixture and every generated problem is a constant-coefficient gr
 off-diagonal entry of L is <= 0, every update product has one sign and the values of A are nearly all equal.  `build()` keeps a
 base problem's nested-dissection ordering and cluster files and writes a new matrix file (`SPD`):
 
+  base      a reference fixture, a generated grid (nx, ny, nz, levels, tile) or a synthetic elimination tree (a spec of tests/tree_inputs.py, which
+            brings its own ordering, clusters and pattern: separator sizes no grid has)
   pattern   "own": the base's own pattern; "full": the 27-point stencil on the base's grid (9-point when nz == 1);
             "subset": each edge of that stencil kept with probability p (seeded)
   values    off-diagonal magnitudes log-uniform on [1e-2, 1e2], signs negative or mixed; diagonal sum_j |w_ij| + sigma
@@ -35,6 +37,7 @@ import os
 import numpy as np
 
 from conftest import CASES, case_paths
+from tree_inputs import NAMED as _TREE_NAMES, TREES as _TREES
 
 U64 = 2.0 ** -53
 U32 = 2.0 ** -24
@@ -85,7 +88,13 @@ class SPD:
     def __init__(self, tmp_path, base, seed, pattern="own", p=0.4, signs="mixed", sigma=1.0, scale=0.0, name="spd", oracle=True, dense=True):
         import cholesky_amd as ca
         rng = np.random.default_rng(seed)
-        if isinstance(base, str):
+        self.tree = None
+        if isinstance(base, dict):       # a synthetic elimination tree (tests/tree_inputs.py): its own ordering, clusters and pattern
+            import tree_inputs
+            assert pattern == "own", "a tree spec names its own pattern"
+            self.tree, self.ord, self.clust = tree_inputs.build(tmp_path, name, base)
+            n, lo, hi = self.tree.n, self.tree.lo, self.tree.hi
+        elif isinstance(base, str):
             m0, self.ord, self.clust, _ = case_paths(base)
             assert pattern == "own", "the fixtures are used with their own pattern"
             n, lo, hi, _ = _read_coo(m0)
@@ -120,6 +129,10 @@ class SPD:
         write_mtx(self.mtx, n, self.row, self.col, self.val)
         self.plan = ca.Plan(self.mtx, self.ord, self.clust)
         assert self.plan.dropped == 0 and self.plan.n == n
+        if self.tree is not None:        # the same arrays without the files: the same plan
+            o = np.lexsort((self.row, self.col))
+            self.plan_arrays = self.tree.plan_from_arrays(self.row[o], self.col[o], self.val[o])
+            tree_inputs.assert_same_plan(self.plan, self.plan_arrays)
         self.perm = self.plan.perm
         # the original matrix, symmetric, and P A P^T built here (not by the library): PAP[i, j] = A[perm[i], perm[j]]; dense only with `dense`
         self.A_sparse = self.sparse_a()
@@ -295,7 +308,9 @@ INPUTS = [
     ("g20_2d", (20, 20, 1, 3, 16), {"pattern": "full"}),
     ("g7_ragged", (7, 5, 3, 3, 4), {"pattern": "full"}),
 ]
-assert all(isinstance(b, tuple) or b in CASES for _, b, _ in INPUTS)
+# synthetic trees (tests/tree_inputs.py), appended: the inputs above keep their seeds
+INPUTS += [(nm, _TREES[nm], {}) for nm in _TREE_NAMES]
+assert all(isinstance(b, (tuple, dict)) or b in CASES for _, b, _ in INPUTS)
 
 
 NAMES = [nm for nm, _, _ in INPUTS]
@@ -309,8 +324,10 @@ def make(tmp_path, name, seed=None):
     return SPD(tmp_path, base, 1000 + i if seed is None else seed, name=name, **opts)
 
 
-def cached(tmp_path_factory, name):
-    """make() once per test session (the references of the larger inputs take seconds)."""
+def cached(tmp_path_factory, name, build=None):
+    """make() once per test session (the references of the larger inputs take seconds).  `build(tmp_path)`: the maker of an input that is
+    not in INPUTS (the single-purpose trees of tests/tree_inputs.py), cached under `name` in the same way."""
     if name not in _CACHE:
-        _CACHE[name] = make(tmp_path_factory.mktemp(name), name)
+        tmp_path = tmp_path_factory.mktemp(name)
+        _CACHE[name] = make(tmp_path, name) if build is None else build(tmp_path)
     return _CACHE[name]

@@ -363,11 +363,13 @@ def _assemble(plan, parts, world):
 
 @pytest.mark.parametrize("world", [2, 4])
 @pytest.mark.parametrize("f32", [False, True])
-def test_sharded_factor_of_a_general_input(world, f32, spd):
+@pytest.mark.parametrize("name", ["g16_subset", "tree_skew"])
+def test_sharded_factor_of_a_general_input(name, world, f32, spd):
+    """g16_subset: a grid's balanced subtrees; tree_skew: subtrees of very unequal weight (leaves of 1 and of 289 columns)."""
     import cholesky_amd as ca
     from cholesky_amd import parallel
     from cholesky_amd.device import factor_multi
-    S = spd("g16_subset")
+    S = spd(name)
     plan = S.plan
     _, ref_t = _factor(S, f32=f32)
     ref = ref_t.cpu().numpy().astype(np.float64)
