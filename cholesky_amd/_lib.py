@@ -163,6 +163,14 @@ def load():
     L.cholamd_solve_half_f32.argtypes = [vp, vp, vp, vp, ci, vp]
     L.cholamd_solve_half_nrhs.argtypes = [vp, vp, vp, i64, vp, i64, ci, ci, vp]
     L.cholamd_solve_half_nrhs_f32.argtypes = [vp, vp, vp, i64, vp, i64, ci, ci, vp]
+    for name in ("cholamd_multiply_half", "cholamd_multiply_half_f32"):
+        getattr(L, name).argtypes = [vp, vp, vp, vp, ci, vp]
+    for name in ("cholamd_multiply", "cholamd_multiply_f32"):
+        getattr(L, name).argtypes = [vp, vp, vp, vp, vp]
+    for name in ("cholamd_factor_residual", "cholamd_factor_residual_f32"):
+        getattr(L, name).argtypes = [vp, vp, vp, C.POINTER(cd), vp]
+    L.cholamd_plan_multiply_host.argtypes = [vp, vp, ci, vp, vp]
+    L.cholamd_plan_multiply_counts.argtypes = [vp, vp]
     L.cholamd_factor_logdet.argtypes = [vp, vp, C.POINTER(cd), vp]
     L.cholamd_factor_logdet_f32.argtypes = [vp, vp, C.POINTER(cd), vp]
     L.cholamd_factor_diag.argtypes = [vp, vp, vp, vp]

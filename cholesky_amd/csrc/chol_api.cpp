@@ -123,6 +123,10 @@ struct cholamd_device {
   std::vector<selinv_dev> si; double *si_ws = nullptr; bool si_ready = false;
   // Schur complement (cholamd_schur): the gather kernel's piece list per number of kept levels k (index k), uploaded at the first call with that k
   std::vector<schur_dev> sc;
+  // forward products (cholamd_multiply_half / cholamd_multiply / cholamd_factor_residual): the owner lists of the whole tree per direction, uploaded at the
+  // first call; the intermediate vector of cholamd_multiply (permuted coordinates); the residual's per-workgroup partial sums and result words
+  chol_mul_item *mul_item[2] = { nullptr, nullptr }; chol_mul_src *mul_src[2] = { nullptr, nullptr }; int n_mul_item[2] = { 0, 0 }; bool mul_ready = false;
+  double *mvec = nullptr, *mr_part = nullptr; int64_t *mr_ipart = nullptr, *mr_res = nullptr;
 };
 
 static int no_device_error()
@@ -341,6 +345,8 @@ extern "C" void cholamd_device_destroy(cholamd_device *d)
   (void)hipFree(d->xstage); (void)hipFree(d->xdesc);
   (void)hipFree(d->ws); (void)hipFree(d->ws_solve); (void)hipFree(d->step_flags); (void)hipFree(d->w256); (void)hipFree(d->step_xt); (void)hipFree(d->info); (void)hipFree(d->progress); (void)hipFree(d->a_dst); (void)hipFree(d->a_val); (void)hipFree(d->perm); (void)hipFree(d->ytmp);
   (void)hipFree(d->ld_part); (void)hipFree(d->ld_ipart); (void)hipFree(d->ld_res);
+  for (int q = 0; q < 2; q++) { (void)hipFree(d->mul_item[q]); (void)hipFree(d->mul_src[q]); }
+  (void)hipFree(d->mvec); (void)hipFree(d->mr_part); (void)hipFree(d->mr_ipart); (void)hipFree(d->mr_res);
   (void)hipFree(d->ynrhs); (void)hipFree(d->bnrhs); (void)hipFree(d->rnrhs); (void)hipFree(d->dxnrhs); (void)hipFree(d->pnrhs);
   for (int q = 0; q < 2; q++) { (void)hipFree(d->top_dst[q]); (void)hipFree(d->top_val[q]); (void)hipFree(d->top_e[q]); }
   (void)hipFree(d->a_src); (void)hipFree(d->csr_src); (void)hipFree(d->e_cls); (void)hipFree(d->vs_dev); (void)hipFree(d->vs_init); (void)hipHostFree(d->vs_host);
@@ -1521,6 +1527,112 @@ extern "C" int cholamd_selinv_entries(cholamd_device *d, const double *d_zarena,
   HIPCHK((hipError_t)chol_launch_selinv_entries(d_zarena, d->a_dst, d->a_src, p->nnz_a, d_vals, count, (hipStream_t)stream));
   return 0;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Forward products with the factor (include/cholamd.h at cholamd_multiply_half; kernels in chol_multiply.hip): y = M z, M^T z, M M^T z with M = P^T L P.
+// The owner lists depend on the plan alone: built and uploaded at the first call on a device object, kept until it is destroyed.  A half product is the
+// permute of z into the work vector and ONE launch over the whole tree, which writes y in original dof order; the full product puts the BACKWARD launch
+// between them, into the object's second vector (permuted coordinates throughout).
+// ---------------------------------------------------------------------------------------------
+static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb);
+static int build_multiply(cholamd_device *d)
+{
+  if (d->mul_ready) return 0;
+  chol_mul_lists w;
+  int rc = chol_build_multiply(d->plan, &w);
+  if (rc) return rc;
+  for (int q = 0; q < 2 && !rc; q++) {
+    (void)hipFree(d->mul_item[q]); (void)hipFree(d->mul_src[q]); d->mul_item[q] = nullptr; d->mul_src[q] = nullptr;
+    rc = upload_vec(&d->mul_item[q], w.item[q], (size_t)w.n_item[q]);
+    if (!rc) rc = upload_vec(&d->mul_src[q], w.src[q], (size_t)w.n_src[q]);
+    d->n_mul_item[q] = w.n_item[q];
+  }
+  chol_mul_lists_free(&w);
+  if (rc) return rc;
+  const size_t n = (size_t)(d->plan->n > 0 ? d->plan->n : 1);
+  if (!d->ytmp) HIPCHK(fp_malloc((void **)&d->ytmp, n * sizeof(double)));
+  if (!d->mvec) HIPCHK(fp_malloc((void **)&d->mvec, n * sizeof(double)));
+  d->mul_ready = true;
+  return 0;
+}
+static int lmultiply(const double *a, const chol_mul_item *it, int ni, const chol_mul_src *sr, int bw, const double *z, double *y, const int *perm, hipStream_t st) { return chol_launch_multiply(a, it, ni, sr, bw, z, y, perm, st); }
+static int lmultiply(const float *a, const chol_mul_item *it, int ni, const chol_mul_src *sr, int bw, const double *z, double *y, const int *perm, hipStream_t st) { return chol32_launch_multiply(a, it, ni, sr, bw, z, y, perm, st); }
+// the checks every product shares, after the NULL / which / nrhs rules of the half solves: the complete factor, y outside the arena
+template <class TL> static int multiply_check(cholamd_device *d, const TL *d_arena, const double *d_y, int64_t y_doubles, const char *what)
+{
+  if (d->world > 1 && d->rank != 0) {
+    chol_set_error("%s: rank %d of %d holds its own subtrees only; the call needs the complete factor (a single-GPU object, or rank 0 after a gather)", what, d->rank, d->world);
+    return CHOLAMD_ERR_ARG;
+  }
+  if (d_y && ranges_overlap(d_arena, (size_t)d->plan->arena * sizeof(TL), d_y, (size_t)y_doubles * sizeof(double))) {
+    chol_set_error("%s: the result overlaps the factor's arena", what);
+    return CHOLAMD_ERR_ARG;
+  }
+  return 0;
+}
+// which: one CHOLAMD_HALF_* product, or CHOL_BOTH_SWEEPS: y = M M^T z (BACKWARD, then FORWARD)
+template <class TL> static int multiply_t(cholamd_device *d, const TL *d_arena, const double *d_z, double *d_y, int which, hipStream_t st)
+{
+  { int rc = build_multiply(d); if (rc) return rc; }
+  const int n = d->plan->n, F = CHOLAMD_HALF_FORWARD, B = CHOLAMD_HALF_BACKWARD;
+  HIPCHK((hipError_t)chol_launch_permute(d_z, d->perm, d->ytmp, n, 0, st)); // (first: d_y may be d_z)
+  const double *in = d->ytmp;
+  if (which == CHOL_BOTH_SWEEPS) {
+    HIPCHK((hipError_t)lmultiply(d_arena, d->mul_item[B], d->n_mul_item[B], d->mul_src[B], 1, in, d->mvec, nullptr, st));
+    in = d->mvec;
+    which = F;
+  }
+  HIPCHK((hipError_t)lmultiply(d_arena, d->mul_item[which], d->n_mul_item[which], d->mul_src[which], which == B, in, d_y, d->perm, st));
+  return 0;
+}
+template <class TL> static int multiply_half_api(cholamd_device *d, const TL *d_arena, const double *d_z, double *d_y, bool half, int which, hipStream_t st, const char *what)
+{
+  if (!d) { chol_set_error("%s: NULL device", what); return CHOLAMD_ERR_ARG; }
+  if (half) { int rc = half_which_ok(which, what); if (rc) return rc; } // (a caller's which = -1 must not be taken for the full product)
+  else which = CHOL_BOTH_SWEEPS;
+  if (!d_arena || !d_z || !d_y) { chol_set_error("%s: NULL %s", what, !d_arena ? "arena" : !d_z ? "z" : "y"); return CHOLAMD_ERR_ARG; }
+  { int rc = multiply_check(d, d_arena, d_y, d->plan->n, what); if (rc) return rc; }
+  HIPCHK(hipSetDevice(d->dev));
+  return multiply_t(d, d_arena, d_z, d_y, which, st);
+}
+extern "C" int cholamd_multiply_half(cholamd_device *d, const double *d_arena, const double *d_z, double *d_y, int which, void *stream)
+{ return multiply_half_api(d, d_arena, d_z, d_y, true, which, (hipStream_t)stream, "cholamd_multiply_half"); }
+extern "C" int cholamd_multiply_half_f32(cholamd_device *d, const float *d_arena32, const double *d_z, double *d_y, int which, void *stream)
+{ return multiply_half_api(d, d_arena32, d_z, d_y, true, which, (hipStream_t)stream, "cholamd_multiply_half_f32"); }
+extern "C" int cholamd_multiply(cholamd_device *d, const double *d_arena, const double *d_z, double *d_y, void *stream)
+{ return multiply_half_api(d, d_arena, d_z, d_y, false, 0, (hipStream_t)stream, "cholamd_multiply"); }
+extern "C" int cholamd_multiply_f32(cholamd_device *d, const float *d_arena32, const double *d_z, double *d_y, void *stream)
+{ return multiply_half_api(d, d_arena32, d_z, d_y, false, 0, (hipStream_t)stream, "cholamd_multiply_f32"); }
+template <class TL> static int factor_residual_t(cholamd_device *d, const TL *d_arena, const double *d_z, double *rel_out, hipStream_t st, const char *what)
+{
+  if (rel_out) *rel_out = std::nan("");
+  if (!d) { chol_set_error("%s: NULL device", what); return CHOLAMD_ERR_ARG; }
+  if (!d_arena || !d_z || !rel_out) { chol_set_error("%s: NULL %s", what, !d_arena ? "arena" : !d_z ? "z" : "rel_out"); return CHOLAMD_ERR_ARG; }
+  { int rc = multiply_check(d, d_arena, (const double *)nullptr, 0, what); if (rc) return rc; }
+  HIPCHK(hipSetDevice(d->dev));
+  { int rc = ensure_refine(d); if (rc) return rc; } // the residual operator with the CURRENT values (cholamd_device_set_values keeps it up to date)
+  const int n = d->plan->n, nb = (n + 255) / 256;
+  if (!d->mr_part) HIPCHK(fp_malloc((void **)&d->mr_part, (size_t)2 * (nb > 0 ? nb : 1) * sizeof(double)));
+  if (!d->mr_ipart) HIPCHK(hipMalloc((void **)&d->mr_ipart, (size_t)(nb > 0 ? nb : 1) * sizeof(int64_t)));
+  if (!d->mr_res) HIPCHK(hipMalloc((void **)&d->mr_res, 3 * sizeof(int64_t)));
+  { int rc = multiply_t(d, d_arena, d_z, d->rvec, CHOL_BOTH_SWEEPS, st); if (rc) return rc; } // w = M M^T z in original dof order
+  HIPCHK((hipError_t)chol_launch_multiply_resid(d->csr_ptr, d->csr_col, d->csr_val, d_z, d->rvec, n, d->mr_part, d->mr_ipart, d->mr_res, st));
+  int64_t res[3] = { 0, 0, 0 };
+  HIPCHK(hipMemcpyAsync(res, d->mr_res, sizeof res, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  double d2, a2;
+  std::memcpy(&d2, &res[0], sizeof d2); std::memcpy(&a2, &res[1], sizeof a2);
+  if (res[2] > 0 || !(d2 <= DBL_MAX) || !(a2 <= DBL_MAX)) {
+    chol_set_error("%s: A z or M M^T z is not finite in %lld rows (a NaN or inf in z, in the values of A or in the arena)", what, (long long)res[2]);
+    return CHOLAMD_ERR_ARG;
+  }
+  *rel_out = a2 > 0.0 ? std::sqrt(d2 / a2) : std::sqrt(d2);
+  return 0;
+}
+extern "C" int cholamd_factor_residual(cholamd_device *d, const double *d_arena, const double *d_z, double *rel_out, void *stream)
+{ return factor_residual_t(d, d_arena, d_z, rel_out, (hipStream_t)stream, "cholamd_factor_residual"); }
+extern "C" int cholamd_factor_residual_f32(cholamd_device *d, const float *d_arena32, const double *d_z, double *rel_out, void *stream)
+{ return factor_residual_t(d, d_arena32, d_z, rel_out, (hipStream_t)stream, "cholamd_factor_residual_f32"); }
 
 // ---------------------------------------------------------------------------------------------
 // Schur complement on the top k levels of the tree (include/cholamd.h at cholamd_schur; the gather kernel in chol_schur.hip).  The factorisation is

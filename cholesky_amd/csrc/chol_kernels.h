@@ -89,6 +89,13 @@ int chol_launch_selinv_entries(const double *Z, const int64_t *a_dst, const int 
 /* Schur complement (chol_schur.hip): S (m x m, column-major, leading dimension lds) from the pieces of chol_schur_pieces(p, k, 1, CHOL_SCHUR_CHUNK): both
  * triangles, the zeros of the pieces without storage included; one owner per element, no atomics */
 int chol_launch_schur_gather(const double *arena, const chol_schur_desc *descs, int64_t ndesc, double *S, int64_t lds, hipStream_t st);
+/* forward products with the factor (chol_multiply.hip): one launch over the items of one direction of chol_mul_lists, y = L z (backward = 0) or L^T z (1) in
+ * permuted coordinates, z and y distinct; perm != NULL: the result goes to y[perm[pos]] (original dof order).  One owner per element, no atomics.
+ * resid: res[0], res[1] = the bits of ||A z - w||^2 and ||A z||^2 (A as CSR in original dof order), res[2] = rows where either is not finite; two stages
+ * with one partial pair per workgroup of 256 rows (part: 2 * ceil(n / 256) doubles, ipart: ceil(n / 256) int64), summed in a fixed order */
+int chol_launch_multiply(const double *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, const double *z, double *y, const int *perm, hipStream_t st);
+int chol32_launch_multiply(const float *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, const double *z, double *y, const int *perm, hipStream_t st);
+int chol_launch_multiply_resid(const int64_t *ptr, const int *col, const double *val, const double *z, const double *w, int n, double *part, int64_t *ipart, int64_t *res, hipStream_t st);
 /* diagnostic instance of the program launch (k_program<true>): 4 stamps per job, then CHOL_TRACE_X per job -- [0] follower: own tiles' wait over,
  * [1] its items, [2 + i] round of item i begun; [48 + k] POTRF job: column k published / TRSM job (first strip): column tile k on its channel;
  * [72 + k] POTRF job: the factor wave starts column k / TRSM job: the POTRF's column k seen */

@@ -446,6 +446,26 @@ int chol_schur_range(const struct cholamd_plan *p, int k, int *t0_out); /* m (th
 int64_t chol_schur_pieces(const struct cholamd_plan *p, int k, int with_empty, int chunk /* 0: whole */, int64_t cap, chol_schur_desc *out); /* the count, whatever cap */
 void chol_set_error(const char *fmt, ...);
 
+/* ---- forward product with the factor (cholamd_multiply_half; chol_multiply.hip): ONE list for the whole tree and each direction.  An ITEM owns
+ * nv <= CHOL_MUL_TILE consecutive positions y[y_off ..] of the permuted result -- a 16-row chunk of a separator on its 16-row grid (FORWARD, y = L z) or a
+ * 16-column chunk of a separator (BACKWARD, y = L^T z) -- and sums over its SOURCES [src_first, src_end) in list order; no other item writes them.
+ * A source is a strip of stored entries, the item's 16 lines wide and `len` reduction steps long, z[z_off + k] being the factor of step k:
+ *   FORWARD   line i = a row,    L(i, k) = arena[a_off + i + k * ld],  meant iff k <= tri + i  (diagonal block: the lower triangle; else tri is large)
+ *   BACKWARD  line j = a column, L(k, j) = arena[a_off + k + j * ld],  meant iff k >= tri + j  (diagonal block: tri = 0; else tri = -CHOL_MUL_TILE)
+ * FORWARD sources: the separator's own diagonal block rows (from the first column the leaf band allows), then the chunk's rows in the panel of every
+ * descendant that stores them (row compaction: chol_block_row), level by level downwards, from the first column c_lo the leaf envelope allows.
+ * BACKWARD sources: the diagonal block's rows from the chunk's first column (down to what the leaf band allows), then the stored row runs of the panel,
+ * parent first (the runs of the solve's `bw` list, uncut), a leaf's run left out where the chunk lies in front of its c_lo. */
+#define CHOL_MUL_TILE 16
+typedef struct { int64_t a_off; int ld, len, z_off, tri; } chol_mul_src;
+typedef struct { int src_first, src_end, y_off, nv; } chol_mul_item;
+typedef struct {
+  int n_item[2]; chol_mul_item *item[2]; /* [CHOLAMD_HALF_FORWARD], [CHOLAMD_HALF_BACKWARD] */
+  int n_src[2]; chol_mul_src *src[2];
+} chol_mul_lists;
+int chol_build_multiply(const struct cholamd_plan *p, chol_mul_lists *out);
+void chol_mul_lists_free(chol_mul_lists *w);
+
 #ifdef __cplusplus
 }
 #endif

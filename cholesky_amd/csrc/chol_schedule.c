@@ -2548,3 +2548,204 @@ int cholamd_plan_schur_host(const cholamd_plan *p, int k, const double *arena_ho
   free(q);
   return 0;
 }
+
+/* ---------------------------------------------------------------------------------------- */
+/* forward product with the factor (cholamd_multiply_half): the owner lists of the whole tree  */
+/* (chol_plan.h at chol_mul_lists) and their host restatement                                  */
+/* ---------------------------------------------------------------------------------------- */
+#define MUL_TRI_OFF (1 << 30)
+typedef struct { chol_mul_item *item; chol_mul_src *src; int n_item, cap_item, n_src, cap_src, fail; } mul_build;
+static void mul_push_src(mul_build *b, int64_t a_off, int ld, int len, int z_off, int tri)
+{
+  if (len <= 0 || b->fail) return;
+  if (b->n_src == b->cap_src) {
+    if (b->cap_src > (1 << 29)) { b->fail = 1; return; }
+    b->cap_src = b->cap_src ? 2 * b->cap_src : 256;
+    chol_mul_src *q = realloc(b->src, (size_t)b->cap_src * sizeof *q);
+    if (!q) { b->fail = 1; return; }
+    b->src = q;
+  }
+  const chol_mul_src s = { a_off, ld, len, z_off, tri };
+  b->src[b->n_src++] = s;
+}
+static void mul_open_item(mul_build *b, int y_off, int nv)
+{
+  if (b->fail) return;
+  if (b->n_item == b->cap_item) {
+    b->cap_item = b->cap_item ? 2 * b->cap_item : 256;
+    chol_mul_item *q = realloc(b->item, (size_t)b->cap_item * sizeof *q);
+    if (!q) { b->fail = 1; return; }
+    b->item = q;
+  }
+  const chol_mul_item it = { b->n_src, b->n_src, y_off, nv };
+  b->item[b->n_item++] = it;
+}
+static void mul_close_item(mul_build *b) { if (!b->fail) b->item[b->n_item - 1].src_end = b->n_src; }
+
+void chol_mul_lists_free(chol_mul_lists *w)
+{
+  for (int q = 0; q < 2; q++) { free(w->item[q]); free(w->src[q]); }
+  memset(w, 0, sizeof *w);
+}
+int chol_build_multiply(const plan_t *p, chol_mul_lists *out)
+{
+  memset(out, 0, sizeof *out);
+  const int ns = p->nsep, T = CHOL_MUL_TILE;
+  int *band = calloc((size_t)ns + 1, sizeof(int));
+  int **rfirst = NULL;
+  if (!band) { chol_set_error("out of memory"); return CHOLAMD_ERR_NOMEM; }
+  if (!getenv("CHOLAMD_SOLVE_NO_BAND")) { /* the structural zeros of the leaves, as the solve lists know them (chol_build_solve_level_part) */
+    rfirst = leaf_row_first(p);
+    unsigned char **sky = leaf_skylines(p);
+    for (int s = 1; s <= ns; s++) {
+      if (!sky[s]) continue;
+      const int n = p->sep_size[s];
+      int md = 0;
+      for (int i = 0; i * CHOL_NB < n; i++) if (i - sky[s][i] > md) md = i - sky[s][i];
+      band[s] = CHOL_NB * md + CHOL_NB - 1;
+      if (band[s] >= n) band[s] = 0;
+    }
+    free_skylines(sky, ns);
+  }
+  mul_build fw = { 0 }, bw = { 0 };
+  int *desc = NULL, cap_desc = 0; /* blocks (s, descendant) that exist, of the separator at hand */
+  for (int h = 1; h <= ns; h++) {
+    const int s = p->tree[h], n = p->sep_size[s], ld = p->panel_ld[s], x0 = p->sep_off[s];
+    if (n <= 0) continue;
+    /* FORWARD: the 16-row chunks of s gather from the diagonal block and from every descendant's panel.  The descendants whose panel stores rows of s
+     * are found once per separator (level by level downwards: the order of the sums), the chunks then walk that list */
+    int nd = 0;
+    for (int64_t lo = 2 * (int64_t)h, hi = 2 * (int64_t)h + 1; lo <= ns; lo *= 2, hi = 2 * hi + 1)
+      for (int64_t hd = lo; hd <= hi && hd <= ns; hd++) {
+        const int bi = BIDX(p, s, p->tree[hd]);
+        if (bi < 0 || p->blk[bi].rows == 0 || p->blk[bi].cols == 0) continue;
+        if (nd == cap_desc) {
+          cap_desc = cap_desc ? 2 * cap_desc : 64;
+          int *q = realloc(desc, (size_t)cap_desc * sizeof(int));
+          if (!q) { fw.fail = 1; break; }
+          desc = q;
+        }
+        desc[nd++] = bi;
+      }
+    for (int r0 = 0; r0 < n; r0 += T) {
+      const int nv = n - r0 < T ? n - r0 : T;
+      mul_open_item(&fw, x0 + r0, nv);
+      const int c0 = band[s] > 0 && r0 > band[s] ? (r0 - band[s]) & ~(T - 1) : 0;
+      mul_push_src(&fw, p->panel_off[s] + r0 + (int64_t)c0 * ld, ld, r0 + nv - c0, x0 + c0, r0 - c0);
+      for (int e = 0; e < nd; e++) {
+        const chol_block *B = &p->blk[desc[e]];
+        const int sd = B->c;
+        if (r0 >= B->rows) continue;
+        const int64_t off = chol_block_row(B, r0);
+        if (off < 0) continue;
+        int c_lo = 0;
+        if (rfirst && rfirst[sd]) {
+          const int pr = (int)((off - p->panel_off[sd]) % p->panel_ld[sd]);
+          c_lo = B->cols;
+          for (int i = 0; i < nv; i++) if (rfirst[sd][pr + i] < c_lo) c_lo = rfirst[sd][pr + i];
+          c_lo &= ~(T - 1);
+        }
+        mul_push_src(&fw, off + (int64_t)c_lo * B->ld, B->ld, B->cols - c_lo, p->sep_off[sd] + c_lo, MUL_TRI_OFF);
+      }
+      mul_close_item(&fw);
+    }
+    /* BACKWARD: the 16-column chunks of s read their own columns of panel(s): the triangle, then the stored row runs into the ancestors */
+    for (int c0 = 0; c0 < n; c0 += T) {
+      const int nv = n - c0 < T ? n - c0 : T;
+      mul_open_item(&bw, x0 + c0, nv);
+      const int r1 = band[s] > 0 && c0 + nv + band[s] < n ? c0 + nv + band[s] : n;
+      mul_push_src(&bw, p->panel_off[s] + c0 + (int64_t)c0 * ld, ld, r1 - c0, x0 + c0, 0);
+      for (int hp = h / 2; hp >= 1; hp /= 2) {
+        const int par = p->tree[hp];
+        const int bi = BIDX(p, par, s);
+        if (bi < 0) continue;
+        const chol_block *B = &p->blk[bi];
+        if (B->rows == 0 || B->cols == 0) continue;
+        blk_run *rr; const int nr = block_runs(B, 0, B->rows, &rr);
+        for (int q = 0; q < nr; q++) {
+          if (rfirst && rfirst[s]) {
+            const int pr = (int)((rr[q].off - p->panel_off[s]) % ld);
+            int f = n;
+            for (int r = 0; r < rr[q].m; r++) if (rfirst[s][pr + r] < f) f = rfirst[s][pr + r];
+            if (c0 + nv <= (f & ~(T - 1))) continue; /* the run is zero in these columns */
+          }
+          mul_push_src(&bw, rr[q].off + (int64_t)c0 * B->ld, B->ld, rr[q].m, p->sep_off[par] + rr[q].row0, -T);
+        }
+        free(rr);
+      }
+      mul_close_item(&bw);
+    }
+  }
+  if (rfirst) { for (int s = 1; s <= ns; s++) free(rfirst[s]); free(rfirst); }
+  free(band); free(desc);
+  out->item[0] = fw.item; out->n_item[0] = fw.n_item; out->src[0] = fw.src; out->n_src[0] = fw.n_src;
+  out->item[1] = bw.item; out->n_item[1] = bw.n_item; out->src[1] = bw.src; out->n_src[1] = bw.n_src;
+  if (fw.fail || bw.fail) { chol_mul_lists_free(out); chol_set_error("multiply lists: out of memory or more than 2^30 sources"); return CHOLAMD_ERR_NOMEM; }
+  /* every permuted position has exactly one owner in each direction, every source lies inside the arena */
+  for (int w = 0; w < 2; w++) {
+    int64_t owned = 0;
+    for (int i = 0; i < out->n_item[w]; i++) owned += out->item[w][i].nv;
+    if (owned != p->n) { chol_set_error("internal: the multiply items own %lld of %d positions", (long long)owned, p->n); chol_mul_lists_free(out); return CHOLAMD_ERR_INVARIANT; }
+    for (int i = 0; i < out->n_item[w]; i++)
+      for (int k = out->item[w][i].src_first; k < out->item[w][i].src_end; k++) {
+        const chol_mul_src *q = &out->src[w][k];
+        const int nv = out->item[w][i].nv;
+        const int64_t last = w == 0 ? q->a_off + (nv - 1) + (int64_t)(q->len - 1) * q->ld : q->a_off + (q->len - 1) + (int64_t)(nv - 1) * q->ld;
+        if (q->a_off < 0 || q->z_off < 0 || q->z_off + q->len > p->n || last >= p->arena) {
+          chol_set_error("internal: multiply source %d of direction %d leaves the arena or the vector", k, w); chol_mul_lists_free(out); return CHOLAMD_ERR_INVARIANT;
+        }
+      }
+  }
+  return 0;
+}
+int cholamd_plan_multiply_host(const cholamd_plan *p, const double *arena_host, int which, const double *z, double *y)
+{
+  if (!p || !arena_host || !z || !y) { chol_set_error("cholamd_plan_multiply_host: NULL %s", !p ? "plan" : !arena_host ? "arena" : !z ? "z" : "y"); return CHOLAMD_ERR_ARG; }
+  if (which != CHOLAMD_HALF_FORWARD && which != CHOLAMD_HALF_BACKWARD) { chol_set_error("cholamd_plan_multiply_host: which = %d is neither CHOLAMD_HALF_FORWARD (0) nor CHOLAMD_HALF_BACKWARD (1)", which); return CHOLAMD_ERR_ARG; }
+  chol_mul_lists w;
+  int rc = chol_build_multiply(p, &w);
+  if (rc) return rc;
+  const int n = p->n;
+  double *zp = malloc((size_t)(n > 0 ? n : 1) * sizeof(double));
+  if (!zp) { chol_mul_lists_free(&w); chol_set_error("out of memory"); return CHOLAMD_ERR_NOMEM; }
+  for (int i = 0; i < n; i++) zp[i] = z[p->perm[i]];
+  for (int i = 0; i < w.n_item[which]; i++) {
+    const chol_mul_item *it = &w.item[which][i];
+    double acc[CHOL_MUL_TILE] = { 0 };
+    for (int k = it->src_first; k < it->src_end; k++) {
+      const chol_mul_src *q = &w.src[which][k];
+      for (int e = 0; e < q->len; e++) {
+        const double ze = zp[q->z_off + e];
+        for (int l = 0; l < it->nv; l++) {
+          if (which == CHOLAMD_HALF_FORWARD ? e - l > q->tri : e < q->tri + l) continue; /* outside the lower triangle: not part of the factor */
+          acc[l] += arena_host[which == CHOLAMD_HALF_FORWARD ? q->a_off + l + (int64_t)e * q->ld : q->a_off + e + (int64_t)l * q->ld] * ze;
+        }
+      }
+    }
+    for (int l = 0; l < it->nv; l++) y[p->perm[it->y_off + l]] = acc[l];
+  }
+  free(zp);
+  chol_mul_lists_free(&w);
+  return 0;
+}
+int cholamd_plan_multiply_counts(const cholamd_plan *p, int64_t out[6])
+{
+  if (!p || !out) { chol_set_error("cholamd_plan_multiply_counts: NULL %s", !p ? "plan" : "out"); return CHOLAMD_ERR_ARG; }
+  chol_mul_lists w;
+  int rc = chol_build_multiply(p, &w);
+  if (rc) return rc;
+  for (int d = 0; d < 2; d++) {
+    int64_t entries = 0;
+    for (int i = 0; i < w.n_item[d]; i++)
+      for (int k = w.item[d][i].src_first; k < w.item[d][i].src_end; k++) {
+        const chol_mul_src *q = &w.src[d][k];
+        for (int l = 0; l < w.item[d][i].nv; l++) { /* steps of line l that are meant (chol_plan.h at chol_mul_src) */
+          const int64_t lo = d == 0 ? 0 : (q->tri + l > 0 ? q->tri + l : 0), hi = d == 0 ? ((int64_t)q->tri + l + 1 < q->len ? (int64_t)q->tri + l + 1 : q->len) : q->len;
+          if (hi > lo) entries += hi - lo;
+        }
+      }
+    out[3 * d] = w.n_item[d]; out[3 * d + 1] = w.n_src[d]; out[3 * d + 2] = entries;
+  }
+  chol_mul_lists_free(&w);
+  return 0;
+}

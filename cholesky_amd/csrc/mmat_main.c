@@ -7,6 +7,8 @@
  *        %0.8g), --precision fp64|mixed (mixed: fp32 factor + fp64 iterative refinement of the solve),
  *        --logdet (one line "logdet: %.17g" after the factorisation: log det A = 2 sum log L_ii from the factor on the device;
  *        "logdet(fp32 factor): ..." under --precision mixed),
+ *        --check (needs -b: one line "factor residual: %.3e" after the factorisation: ||A z - M M^T z|| / ||A z|| with the right-hand side as probe z and
+ *        the factor of the chosen --precision applied forwards on the device, cholamd_factor_residual),
  *        --invdiag FILE (after the factorisation: diag(A^-1) by selected inversion -- cholamd_selinv + cholamd_selinv_diag -- in the solution
  *        writer's format: n lines, original dof order, %0.8g or %.17g under --full-precision; fp64 factor only),
  *        --schur K FILE (after the factorisation: the Schur complement of A on the K kept tree levels -- cholamd_schur_factor + cholamd_schur on a second,
@@ -37,7 +39,7 @@ int main(int argc, char **argv)
 {
   const char *matrix_file = "", *separator_file = "", *clusters_file = "", *b_file = "", *solution_file = "", *factor_file = "",
              *permuted_file = "", *debug_path = "", *invdiag_file = "", *schur_file = "";
-  int debug = 0, iterations = 1, gpu = 0, full = 0, gpus = 1, want_logdet = 0, schur_k = 0;
+  int debug = 0, iterations = 1, gpu = 0, full = 0, gpus = 1, want_logdet = 0, want_check = 0, schur_k = 0;
   const char *precision = "fp64";
   for (int i = 0; i < argc; i++) {
     const char *next = i + 1 < argc ? argv[i + 1] : "";
@@ -56,6 +58,7 @@ int main(int argc, char **argv)
     else if (!strcmp(argv[i], "--precision")) precision = next;
     else if (!strcmp(argv[i], "--full-precision")) full = 1;
     else if (!strcmp(argv[i], "--logdet")) want_logdet = 1;
+    else if (!strcmp(argv[i], "--check")) want_check = 1;
     else if (!strcmp(argv[i], "--invdiag")) invdiag_file = next;
     else if (!strcmp(argv[i], "--schur")) { schur_k = atoi(next); schur_file = i + 2 < argc ? argv[i + 2] : ""; if (!*schur_file) DIE("--schur K FILE"); }
   }
@@ -89,6 +92,7 @@ int main(int argc, char **argv)
   const int mixed = !strcmp(precision, "mixed");
   if (!mixed && strcmp(precision, "fp64")) DIE("--precision %s: fp64 or mixed", precision);
   if (mixed && gpus > 1) DIE("--precision mixed is a single-GPU path");
+  if (want_check && !*b_file) DIE("--check takes the right-hand side as its probe: it needs -b");
   if (mixed && *invdiag_file) DIE("--invdiag needs the fp64 factor (--precision fp64)");
   if (*schur_file && (mixed || gpus > 1)) DIE("--schur is a single-GPU fp64 path");
   if (*schur_file && cholamd_plan_schur_size(plan, schur_k) < 0) DIE("--schur: %s", cholamd_last_error());
@@ -140,6 +144,16 @@ int main(int argc, char **argv)
     double logdet = 0.0;
     if (mixed ? cholamd_factor_logdet_f32(dev, (const float *)d_arena, &logdet, NULL) : cholamd_factor_logdet(dev, d_arena, &logdet, NULL)) DIE("logdet: %s", cholamd_last_error());
     printf(mixed ? "logdet(fp32 factor): %.17g\n" : "logdet: %.17g\n", logdet);
+  }
+  if (want_check) { /* the complete factor is on device 0; the probe is the right-hand side */
+    double *z = malloc((size_t)n * sizeof(double)), *d_z = NULL, rel = 0.0;
+    if (!z) DIE("out of memory");
+    if (cholamd_read_vector(b_file, n, z)) DIE("%s", cholamd_last_error());
+    if (cholamd_device_alloc(dev, n, &d_z) || cholamd_device_upload(dev, d_z, z, n, NULL)) DIE("%s", cholamd_last_error());
+    if (mixed ? cholamd_factor_residual_f32(dev, (const float *)d_arena, d_z, &rel, NULL) : cholamd_factor_residual(dev, d_arena, d_z, &rel, NULL)) DIE("check: %s", cholamd_last_error());
+    printf("factor residual: %.3e\n", rel);
+    cholamd_device_free(dev, d_z);
+    free(z);
   }
   if (*invdiag_file) { /* the complete factor is on device 0; the Z arena is a second arena */
     double *d_z = NULL, *d_diag = NULL, *diag = malloc((size_t)n * sizeof(double));

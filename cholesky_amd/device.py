@@ -311,6 +311,33 @@ class Device:
         check(fn(self.h, self.ptr(arena), self.ptr(out), _stream_ptr(stream)), "cholamd_factor_diag")
         return out
 
+    # -- the factor applied forwards: y = M z, M^T z, M M^T z (deterministic: one owner per element, no atomics) ---------------------------
+    def multiply_half(self, arena, z, y, which, stream=None):
+        """y = M z (which = HALF_FORWARD) or y = M^T z (HALF_BACKWARD): cholamd_multiply_half / _f32 by the arena's element type, the inverse of
+        solve_half(which); y may be z.  Asynchronous on `stream`."""
+        n = self.plan.n
+        self._f64_vec(z, "z", n)
+        self._f64_vec(y, "y", n)
+        fn = self.L.cholamd_multiply_half_f32 if self._is_f32(arena) else self.L.cholamd_multiply_half
+        check(fn(self.h, self.ptr(arena), self.ptr(z), self.ptr(y), int(which), _stream_ptr(stream)), "cholamd_multiply_half")
+
+    def multiply(self, arena, z, y, stream=None):
+        """y = M M^T z, which is A z up to the factorisation's backward error (cholamd_multiply / _f32); y may be z.  Asynchronous on `stream`."""
+        n = self.plan.n
+        self._f64_vec(z, "z", n)
+        self._f64_vec(y, "y", n)
+        fn = self.L.cholamd_multiply_f32 if self._is_f32(arena) else self.L.cholamd_multiply
+        check(fn(self.h, self.ptr(arena), self.ptr(z), self.ptr(y), _stream_ptr(stream)), "cholamd_multiply")
+
+    def factor_residual(self, arena, z, stream=None):
+        """||A z - M M^T z|| / ||A z|| for the probe z, A with the device object's CURRENT values (cholamd_factor_residual / _f32): does `arena` factor
+        them, and how well.  Synchronises `stream`; deterministic."""
+        self._f64_vec(z, "z", self.plan.n)
+        out = C.c_double(float("nan"))
+        fn = self.L.cholamd_factor_residual_f32 if self._is_f32(arena) else self.L.cholamd_factor_residual
+        check(fn(self.h, self.ptr(arena), self.ptr(z), C.byref(out), _stream_ptr(stream)), "cholamd_factor_residual")
+        return float(out.value)
+
     # -- selected inversion: the entries of A^-1 on the pattern of the factor ---------------------------------------------------------
     def _f64_vec(self, t, what, count):
         import torch

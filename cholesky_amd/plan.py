@@ -313,6 +313,24 @@ class Plan:
         check(self.L.cholamd_plan_schur_host(self.h, int(k), arena.ctypes.data, buf.ctypes.data, ld), "cholamd_plan_schur_host")
         return buf[:m, :].T if lds is not None else buf[:m, :m].T
 
+    def multiply_host(self, arena, which, z):
+        """y = M z (which = 0) or y = M^T z (1) on the CPU from a host arena (cholamd_plan_multiply_host): the owner lists of Device.multiply_half
+        walked on the host -- the lower triangles and the stored row runs only.  z and the result: n doubles in original dof order."""
+        arena = np.ascontiguousarray(arena, dtype=np.float64)
+        assert arena.size == self.arena_doubles
+        z = np.ascontiguousarray(z, dtype=np.float64)
+        assert z.shape == (self.n,)
+        y = np.full(max(self.n, 1), np.nan, dtype=np.float64)
+        check(self.L.cholamd_plan_multiply_host(self.h, arena.ctypes.data, int(which), z.ctypes.data, y.ctypes.data), "cholamd_plan_multiply_host")
+        return y[:self.n]
+
+    def multiply_counts(self):
+        """Sizes of the owner lists of the forward products (cholamd_plan_multiply_counts): a dict per direction of items, sources and the entries
+        of L one product reads."""
+        out = np.zeros(6, dtype=np.int64)
+        check(self.L.cholamd_plan_multiply_counts(self.h, out.ctypes.data), "cholamd_plan_multiply_counts")
+        return {w: dict(items=int(out[3 * i]), sources=int(out[3 * i + 1]), entries=int(out[3 * i + 2])) for i, w in enumerate(("forward", "backward"))}
+
     def arena_to_dense(self, arena):
         arena = np.ascontiguousarray(arena, dtype=np.float64)
         assert arena.size == self.arena_doubles

@@ -475,6 +475,44 @@ int cholamd_factor_logdet(cholamd_device *d, const double *d_arena, double *logd
 int cholamd_factor_logdet_f32(cholamd_device *d, const float *d_arena32, double *logdet_out, void *stream);
 int cholamd_factor_diag(cholamd_device *d, const double *d_arena, double *d_diag, void *stream);
 int cholamd_factor_diag_f32(cholamd_device *d, const float *d_arena32, double *d_diag, void *stream);
+/* ---- the factor applied FORWARDS (not in the reference): y = M z, y = M^T z and y = M M^T z with the square root M = P^T L P of the half solves above, so
+ * cholamd_multiply_half(which) is the inverse of cholamd_solve_half(which).  x = M z turns white noise z into a sample x ~ N(0, A) (A a sparse
+ * covariance; the mirror of the N(0, A^-1) sample of CHOLAMD_HALF_BACKWARD); ||M^T x||^2 = x^T A x is the energy norm; ||A z - M M^T z|| / ||A z|| says
+ * whether an arena still factors the CURRENT values of A, and how well.
+ * cholamd_multiply_half / _f32 (fp64 / fp32 factor; vectors and arithmetic fp64, an fp32 factor is converted on load): y = M z = P^T L P z
+ * (which = CHOLAMD_HALF_FORWARD) or y = M^T z = P^T L^T P z (CHOLAMD_HALF_BACKWARD), z and y n doubles on the device in original dof order, asynchronous
+ * on `stream`; d_y == d_z is allowed (z is permuted into the device object's work vector first).  Input and output of a product are distinct vectors, so
+ * there is no leaf-to-root chain: after the permute ONE launch covers the whole tree and reads every stored entry of L it needs once -- the lower triangles
+ * of the diagonal blocks (the upper triangles are not part of the factor and are never read) and the stored row runs of the panels; the structural zeros of
+ * the leaf panels that the solve skips (cholamd_plan_solve_skips) are skipped here too.
+ * cholamd_multiply / _f32: y = M M^T z, the BACKWARD product followed by the FORWARD product in permuted coordinates (the permutation applied once on the
+ * way in and once on the way out, the intermediate vector belongs to the device object): three launches.
+ * DETERMINISTIC: every element of y has ONE owner -- a 16-row chunk of a separator gathers its rows from the separator's diagonal block and from the
+ * panels of its descendants in a fixed order (FORWARD), a 16-column chunk of a separator sums over its own columns of the panel (BACKWARD) -- and a fixed
+ * summation order; no floating-point atomics anywhere: two calls on one arena and one input return the same bits (unlike the streamed solve).
+ * There is no block (nrhs) form yet: call the single-vector entry points per column.
+ * `which` other than 0 / 1, a NULL pointer, or a result that overlaps the arena: CHOLAMD_ERR_ARG, nothing written.
+ * cholamd_factor_residual / _f32: *rel_out (HOST) = ||A z - M M^T z||_2 / ||A z||_2 for the probe z (n doubles on the device, original dof order), A z from the
+ * device object's residual operator, which holds the CURRENT values (as cholamd_residual uses them after cholamd_device_set_values): two passes over L and one
+ * over A, all on the device.  Synchronises `stream`.  The two norms are reduced deterministically: one partial pair per workgroup by plain stores, summed in a
+ * fixed order by a second one-workgroup launch (the scheme of cholamd_factor_logdet), no atomics -- two calls return the same double.  A NaN or inf anywhere
+ * (z, A's values, the arena) gives CHOLAMD_ERR_ARG with *rel_out = NaN, as cholamd_solve_refine treats it.
+ * All of them need the COMPLETE factor in the arena, like the half solves: a single-GPU device object, or rank 0's after a gather; another rank of a
+ * partitioned object returns CHOLAMD_ERR_ARG.  There are no sharded variants.  ONE CALL AT A TIME per device object: the work vector, the second vector of
+ * cholamd_multiply and the lists (built and uploaded at the first call; later calls allocate nothing) belong to the object.
+ * cholamd_plan_multiply_host: the same product on the HOST over a host arena (tests and diagnostics, no device): it walks the SAME owner lists -- the same
+ * owner assignment, the lower triangles only, row compaction honoured; z and y n doubles in original dof order, y == z allowed.  It builds the lists
+ * anew at every call (a diagnostic, not a hot path).
+ * cholamd_plan_multiply_counts: the size of those lists, out = { FORWARD items, FORWARD sources, entries of L a FORWARD product reads, BACKWARD items,
+ * BACKWARD sources, entries a BACKWARD product reads } (an entry is 8 bytes of an fp64 arena, 4 of an fp32 one; a source is 24 bytes of list). */
+int cholamd_multiply_half(cholamd_device *d, const double *d_arena, const double *d_z, double *d_y, int which, void *stream);
+int cholamd_multiply_half_f32(cholamd_device *d, const float *d_arena32, const double *d_z, double *d_y, int which, void *stream);
+int cholamd_multiply(cholamd_device *d, const double *d_arena, const double *d_z, double *d_y, void *stream);
+int cholamd_multiply_f32(cholamd_device *d, const float *d_arena32, const double *d_z, double *d_y, void *stream);
+int cholamd_factor_residual(cholamd_device *d, const double *d_arena, const double *d_z, double *rel_out, void *stream);
+int cholamd_factor_residual_f32(cholamd_device *d, const float *d_arena32, const double *d_z, double *rel_out, void *stream);
+int cholamd_plan_multiply_host(const cholamd_plan *p, const double *arena_host, int which, const double *z, double *y);
+int cholamd_plan_multiply_counts(const cholamd_plan *p, int64_t out[6]);
 /* ---- selected inversion (not in the reference; the Takahashi recursion every sparse Cholesky package offers): the entries of A^-1 on the pattern of the
  * factor -- the diagonal of A^-1 (marginal variances of a Gaussian Markov random field, leverage scores), the entries on the pattern of A (the trace term
  * tr(A^-1 dA) of a likelihood gradient) -- from the factor, in a small multiple of the factorisation's flops instead of n solves.  fp64 factor only.
