@@ -49,7 +49,7 @@ $(OUT)/chol_multiply.o: $(CSRC)/chol_multiply.hip $(CSRC)/chol_plan.h $(CSRC)/ch
 	@mkdir -p $(OUT)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(OUT)/chol_api.o: $(CSRC)/chol_api.cpp $(CSRC)/chol_plan.h $(CSRC)/chol_kernels.h include/cholamd.h
+$(OUT)/chol_api.o: $(CSRC)/chol_api.cpp $(CSRC)/chol_devbuf.h $(CSRC)/chol_plan.h $(CSRC)/chol_kernels.h include/cholamd.h
 	@mkdir -p $(OUT)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
@@ -78,7 +78,7 @@ ASAN_HOST_OBJS := $(ASAN_OUT)/chol_ingest.o $(ASAN_OUT)/chol_symbolic.o $(ASAN_O
 $(ASAN_OUT)/%.o: $(CSRC)/%.c $(CSRC)/chol_plan.h include/cholamd.h
 	@mkdir -p $(ASAN_OUT)
 	$(CC) $(CFLAGS) -O1 $(SAN) -c $< -o $@
-$(ASAN_OUT)/chol_api.o: $(CSRC)/chol_api.cpp $(CSRC)/chol_plan.h $(CSRC)/chol_kernels.h include/cholamd.h
+$(ASAN_OUT)/chol_api.o: $(CSRC)/chol_api.cpp $(CSRC)/chol_devbuf.h $(CSRC)/chol_plan.h $(CSRC)/chol_kernels.h include/cholamd.h
 	@mkdir -p $(ASAN_OUT)
 	$(HIPCC) $(HIPFLAGS) -O1 $(SAN) -fno-sanitize=function -fno-gpu-sanitize -x hip -c $< -o $@
 $(ASAN_OUT)/libcholamd.so: $(ASAN_HOST_OBJS) $(ASAN_OUT)/chol_api.o $(OUT)/chol_kernels.o $(OUT)/chol_kernels_f32.o $(OUT)/chol_solve_nrhs.o $(OUT)/chol_factor_query.o $(OUT)/chol_selinv.o $(OUT)/chol_schur.o $(OUT)/chol_multiply.o
@@ -94,10 +94,16 @@ $(ASAN_OUT)/schur_host: tests/native/schur_host.c $(ASAN_OUT)/libcholamd.so
 	$(HIPCC) -x c -O1 -Iinclude $(SAN) -fno-sanitize=function -o $@ $< -L$(ASAN_OUT) -lcholamd -Wl,-rpath,$(abspath $(ASAN_OUT)) -lm
 $(ASAN_OUT)/multiply_host: tests/native/multiply_host.c $(ASAN_OUT)/libcholamd.so
 	$(HIPCC) -x c -O1 -Iinclude $(SAN) -fno-sanitize=function -o $@ $< -L$(ASAN_OUT) -lcholamd -Wl,-rpath,$(abspath $(ASAN_OUT)) -lm
+# the owning device buffers of the glue over a host allocator that can be told to fail (tests/native/devbuf_host.cpp): no library, no HIP runtime
+$(ASAN_OUT)/devbuf_host: tests/native/devbuf_host.cpp $(CSRC)/chol_devbuf.h
+	@mkdir -p $(ASAN_OUT)
+	$(HIPCC) -x c++ -O1 -I$(CSRC) $(SAN) -fno-sanitize=function -no-hip-rt -o $@ $<
 ASAN_FIXTURES := $(G)/lapl_9x9/lapl_3_2.mtx $(G)/lapl_9x9/lapl_3_2_ord_2.txt $(G)/lapl_9x9/lapl_3_2_clust_2.txt \
 	  $(G)/lapl_400x400/lapl_20_2.mtx $(G)/lapl_400x400/lapl_20_2_ord_5.txt $(G)/lapl_400x400/lapl_20_2_clust_5.txt \
 	  $(G)/lapl_3375x3375/lapl_15_3.mtx $(G)/lapl_3375x3375/lapl_15_3_ord_5.txt $(G)/lapl_3375x3375/lapl_15_3_clust_5.txt
-asan: $(ASAN_OUT)/libcholamd.so $(ASAN_OUT)/host_leak $(ASAN_OUT)/schur_host $(ASAN_OUT)/multiply_host oracle
+asan: $(ASAN_OUT)/libcholamd.so $(ASAN_OUT)/host_leak $(ASAN_OUT)/schur_host $(ASAN_OUT)/multiply_host $(ASAN_OUT)/devbuf_host oracle
+	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 LSAN_OPTIONS=suppressions=$(abspath scripts/lsan.supp):print_suppressions=0 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
+	$(ASAN_OUT)/devbuf_host
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 LSAN_OPTIONS=suppressions=$(abspath scripts/lsan.supp):print_suppressions=0 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
 	$(ASAN_OUT)/multiply_host $(ASAN_FIXTURES) $(G)/lapl_25x25/lapl_5_2.mtx $(G)/lapl_25x25/lapl_5_2_ord_3.txt $(G)/lapl_25x25/lapl_5_2_clust_3.txt
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 LSAN_OPTIONS=suppressions=$(abspath scripts/lsan.supp):print_suppressions=0 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \

@@ -148,6 +148,8 @@ def load():
     L.cholamd_factor.argtypes = [vp, vp, vp]
     L.cholamd_factor_levels.argtypes = [vp, vp, ci, ci, vp]
     L.cholamd_device_program_trace.argtypes = [vp, vp, vp, i64, vp, C.POINTER(ci)]
+    L.cholamd_debug_live_buffers.argtypes = []
+    L.cholamd_debug_live_buffers.restype = i64
     L.cholamd_factor_info.argtypes = [vp, C.POINTER(ci)]
     L.cholamd_solve.argtypes = [vp, vp, vp, vp, vp]
     L.cholamd_device_fill_f32.argtypes = [vp, vp, vp]

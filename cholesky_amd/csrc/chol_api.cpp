@@ -14,6 +14,8 @@
 #include <type_traits>
 #include <vector>
 
+#include <atomic>
+#include "chol_devbuf.h"
 #include "chol_kernels.h"
 #include "chol_plan.h"
 #include "cholamd.h"
@@ -27,31 +29,37 @@
     }                                                                                                 \
   } while (0)
 
+struct pinned_words { // pinned host memory, owned like a dev_buf: where status words are read back to
+  int64_t *p = nullptr;
+  pinned_words() = default; pinned_words(const pinned_words &) = delete; pinned_words &operator=(const pinned_words &) = delete;
+  ~pinned_words() { if (p) (void)hipHostFree(p); }
+  operator int64_t *() const { return p; }
+  int ensure(size_t n) { if (!p) HIPCHK(hipHostMalloc((void **)&p, n * sizeof(int64_t))); return 0; }
+};
+struct sum_desc;
+
 struct level_dev {
   int n_potrf = 0, n_trsm = 0, n_task = 0, n_src = 0;
   std::vector<chol_phase> phase; // launches of the level in order (big pivots are factored in column blocks)
-  chol_potrf_desc *potrf = nullptr;
-  chol_trsm_desc *trsm = nullptr;
-  chol_upd_task *task = nullptr, *task_mt = nullptr;
-  chol_upd_src *src = nullptr;
+  dev_buf<chol_potrf_desc> potrf; dev_buf<chol_trsm_desc> trsm; // (potrf: with the role tables behind the descriptors, upload_level)
+  dev_buf<chol_upd_task> task, task_mt; dev_buf<chol_upd_src> src;
   std::vector<chol_bcast> bcast;  // distributed top levels: the column blocks a phase of kind 6 broadcasts
 };
 struct solve_dev {
   int n_trsv = 0, n_grp = 0, n_fw = 0, n_bw = 0;
-  chol_trsv_desc *trsv = nullptr;
-  chol_gemv_desc *fw = nullptr, *bw = nullptr;
-  int *grp_start = nullptr, *grp_rows = nullptr, *bw_start = nullptr;
+  dev_buf<chol_trsv_desc> trsv; dev_buf<chol_gemv_desc> fw, bw;
+  dev_buf<int> grp_start, grp_rows, bw_start;
   int n_ifw = 0, n_ibw = 0, max_n = 0, max_under = 0;
   int64_t w256_off = -1; // this level's explicit span inverses in cholamd_device::w256 (levels of at most 8 separators wider than a span); -1: none
-  int *ifw = nullptr, *ibw = nullptr;
+  dev_buf<int> ifw, ibw;
 };
 struct selinv_dev { // the lists of one tree level of the selected inversion (chol_selinv_level) on the device
   std::vector<chol_selinv_sep> host; // the separator descriptors, for the launch geometry of every step
-  chol_selinv_sep *sep = nullptr; chol_selinv_tile *tile = nullptr;
-  int *chain_ld = nullptr, *chain_pos0 = nullptr; int64_t *rowoff = nullptr;
+  dev_buf<chol_selinv_sep> sep; dev_buf<chol_selinv_tile> tile;
+  dev_buf<int> chain_ld, chain_pos0; dev_buf<int64_t> rowoff;
   int max_nblk = 0;
 };
-struct schur_dev { chol_schur_desc *desc = nullptr; int64_t n = -1; }; // n < 0: not built yet
+struct schur_dev { dev_buf<chol_schur_desc> desc; int64_t n = -1; }; // n < 0: not built yet
 struct timed_launch { hipEvent_t a, b; int kind; };
 
 struct cholamd_device {
@@ -64,28 +72,28 @@ struct cholamd_device {
   std::vector<solve_dev> sv;
   bool solve_ready = false;
   int solve_rank = 0, solve_world = 1; // the partition the solve lists were built for
-  int *zr_sub = nullptr; int n_zr_sub = 0; // distributed solve: (offset, length) ranges of the permuted vector this rank starts from zero in (other ranks' subtrees; the shared top on ranks other than 0)
-  double *ws = nullptr;
-  double *ws_solve = nullptr; // 16x16 inverses of the diagonal blocks of the arena being solved with
-  int *step_flags = nullptr;  // flags of the step launches of the wide top separators' span chains (k_solve_step): one per separator of a level, 64 ints
+  dev_buf<int> zr_sub; int n_zr_sub = 0; // distributed solve: (offset, length) ranges of the permuted vector this rank starts from zero in (other ranks' subtrees; the shared top on ranks other than 0)
+  dev_buf<double> ws;
+  dev_buf<double> ws_solve; // 16x16 inverses of the diagonal blocks of the arena being solved with
+  dev_buf<int> step_flags;     // flags of the step launches of the wide top separators' span chains (k_solve_step): one per separator of a level, 64 ints
   int step_gen = 0;           // ... and the number of the last such launch (a flag equal to it: the launch's span is solved)
-  double *w256 = nullptr;     // explicit inverses of the 256-column diagonal spans of the wide top separators (k_solve_inv256, recomputed with the 16x16 inverses)
-  double *step_xt = nullptr;  // 8 x 256 doubles: a step launch's x_k before it replaces the right-hand side
+  dev_buf<double> w256;       // explicit inverses of the 256-column diagonal spans of the wide top separators (k_solve_inv256, recomputed with the 16x16 inverses)
+  dev_buf<double> step_xt;    // 8 x 256 doubles: a step launch's x_k before it replaces the right-hand side
   bool keep_inverses = false; // the correction solves of a refinement: same factor as the solve before them, its diagonal inverses (16x16, spans) are kept
-  int *info = nullptr;      // [0] first failing column, [1] separator; two slots of two ints: the program launch alternates between them (each launch clears the other
+  dev_buf<int> info;        // [0] first failing column, [1] separator; two slots of two ints: the program launch alternates between them (each launch clears the other
                             // one for the next: no memset node per factorisation), every other path uses slot 0
   int *info_last = nullptr; // the slot of the most recent factorisation (cholamd_factor_info)
   int info_parity = 0; bool info_foreign = false; // program path: slot of the next launch; slot 0 was used by another path since
-  int *progress = nullptr;  // fused launches: columns published per pivot block (epoch * 64 + columns); [nsep + 1] = TRSM workgroups finished
+  dev_buf<int> progress;    // fused launches: columns published per pivot block (epoch * 64 + columns); [nsep + 1] = TRSM workgroups finished
   int epoch = 0, done_total = 0;
-  int64_t *a_dst = nullptr; double *a_val = nullptr; int *perm = nullptr; double *ytmp = nullptr;
+  dev_buf<int64_t> a_dst; dev_buf<double> a_val; dev_buf<int> perm; dev_buf<double> ytmp;
   // distributed top levels: the entries of A in the column blocks of the shared top THIS rank owns ([0]: by the fp64 schedule's blocks, [1]: the fp32 one's)
   // top_val is gathered on the device from a_val through top_e (the entries' positions in the scatter list), so that it follows cholamd_device_set_values
-  int64_t *top_dst[2] = { nullptr, nullptr }; double *top_val[2] = { nullptr, nullptr }; int *top_e[2] = { nullptr, nullptr }; int64_t top_n[2] = { 0, 0 }; int top_gen[2] = { -1, -1 };
+  dev_buf<int64_t> top_dst[2]; dev_buf<double> top_val[2]; dev_buf<int> top_e[2]; int64_t top_n[2] = { 0, 0 }; int top_gen[2] = { -1, -1 };
   // new values of A (cholamd_device_set_values): the index lists of the gather and the entries' classes (uploaded at the first call), the status words of
   // the last call on the device ([4]), their start values ([4], device) and where they are read back to (pinned host, two slots of four)
-  int *a_src = nullptr, *csr_src = nullptr; unsigned char *e_cls = nullptr;
-  int64_t *vs_dev = nullptr, *vs_init = nullptr, *vs_host = nullptr;
+  dev_buf<int> a_src, csr_src; dev_buf<unsigned char> e_cls;
+  dev_buf<int64_t> vs_dev, vs_init; pinned_words vs_host;
   int64_t vs_last[4] = { 0, 0, 0, 0 };  // the last call's status words as read back
   bool vs_called = false, vs_last_valid = false;
   bool vs_in_force = false; // the values in force come from set_values: the fp32 range verdict comes from the status words, not from the plan's values
@@ -95,38 +103,38 @@ struct cholamd_device {
   std::vector<hipEvent_t> pool;
   // the one-launch program of the whole factorisation (single GPU, small problems: chol_build_program / k_program)
   level_dev prog;
-  chol_job *jobs = nullptr; chol_wait *pwaits = nullptr; chol_ext *exts = nullptr;
-  int *pctr = nullptr, *pctr_total = nullptr; // counters (last one: the queue head) and what one factorisation adds to each
+  dev_buf<chol_job> jobs; dev_buf<chol_wait> pwaits; dev_buf<chol_ext> exts;
+  dev_buf<int> pctr, pctr_total; // counters (last one: the queue head) and what one factorisation adds to each
   int n_job = 0, n_pctr = 0, prog_grid = 0, prog_epoch = 0, prog_epoch_limit = 0;
   bool prog_ready = false;
-  unsigned long long *trace = nullptr; // diagnostic: per-job clock stamps of the next program launches (cholamd_device_program_trace)
+  unsigned long long *trace = nullptr; // diagnostic: per-job clock stamps of the next program launches (cholamd_device_program_trace, which owns them)
   std::vector<chol_job> jobs_host;
   // mixed precision (fp32 factor + fp64 refinement): work lists of the fp32 kernels, their workspace, A as a device CSR
   std::vector<level_dev> lv32;
-  float *ws32 = nullptr;
+  dev_buf<float> ws32;
   int f32_range = -1; int64_t f32_bad = -1; // A's entries all zero or normal floats (1), or not (0: f32_bad = the first entry that is not); -1: not checked yet
-  int64_t *csr_ptr = nullptr; int *csr_col = nullptr; double *csr_val = nullptr;
-  double *rvec = nullptr, *dxvec = nullptr, *partial = nullptr;
+  dev_buf<int64_t> csr_ptr; dev_buf<int> csr_col; dev_buf<double> csr_val;
+  dev_buf<double> rvec, dxvec, partial;
   // extend-add exchange under the distributed top levels: staging of the copies received for the owned column blocks, descriptors of the sum
-  void *xstage = nullptr; size_t xstage_bytes = 0; void *xdesc = nullptr; int xdesc_gen = -1, xdesc_elem = 0, sched_gen = 0;
+  dev_buf<char> xstage; size_t xstage_bytes = 0; dev_buf<sum_desc> xdesc; int xdesc_gen = -1, xdesc_elem = 0, sched_gen = 0;
   // switches, read from the environment once at cholamd_device_create (cholamd_device_set_option changes them later)
   chol_sched_opts opt;
   bool solve_reference_shape = false; // cholamd_solve with the per-call (deterministic) kernels of the BLAS-level entry points
   // block solve (cholamd_solve_nrhs): the permuted block of one chunk (n x CHOL_NRHS_W, row-major); refinement: the chunk's right-hand sides, residual and
   // correction (n x CHOL_NRHS_W, column-major) and the per-column partial sums of the residual kernel
-  double *ynrhs = nullptr, *bnrhs = nullptr, *rnrhs = nullptr, *dxnrhs = nullptr, *pnrhs = nullptr;
+  dev_buf<double> ynrhs, bnrhs, rnrhs, dxnrhs, pnrhs;
   // factor queries (cholamd_factor_diag / _logdet): the TRSV descriptors of the whole tree in one list ordered by permuted position and the prefix of their
   // column counts (built with the solve lists of rank 0 of 1); the logdet's per-workgroup partial sums, their integer companions and the three result words
-  chol_trsv_desc *dg_desc = nullptr; int *dg_prefix = nullptr; int n_dg = 0;
-  double *ld_part = nullptr; int64_t *ld_ipart = nullptr, *ld_res = nullptr;
+  dev_buf<chol_trsv_desc> dg_desc; dev_buf<int> dg_prefix; int n_dg = 0;
+  dev_buf<double> ld_part; dev_buf<int64_t> ld_ipart, ld_res;
   // selected inversion (cholamd_selinv): the gather lists of every level and the workspace of the widest level, built at the first call
-  std::vector<selinv_dev> si; double *si_ws = nullptr; bool si_ready = false;
+  std::vector<selinv_dev> si; dev_buf<double> si_ws; bool si_ready = false;
   // Schur complement (cholamd_schur): the gather kernel's piece list per number of kept levels k (index k), uploaded at the first call with that k
   std::vector<schur_dev> sc;
   // forward products (cholamd_multiply_half / cholamd_multiply / cholamd_factor_residual): the owner lists of the whole tree per direction, uploaded at the
   // first call; the intermediate vector of cholamd_multiply (permuted coordinates); the residual's per-workgroup partial sums and result words
-  chol_mul_item *mul_item[2] = { nullptr, nullptr }; chol_mul_src *mul_src[2] = { nullptr, nullptr }; int n_mul_item[2] = { 0, 0 }; bool mul_ready = false;
-  double *mvec = nullptr, *mr_part = nullptr; int64_t *mr_ipart = nullptr, *mr_res = nullptr;
+  dev_buf<chol_mul_item> mul_item[2]; dev_buf<chol_mul_src> mul_src[2]; int n_mul_item[2] = { 0, 0 }; bool mul_ready = false;
+  dev_buf<double> mvec, mr_part; dev_buf<int64_t> mr_ipart, mr_res;
 };
 
 static int no_device_error()
@@ -140,15 +148,6 @@ extern "C" int cholamd_device_count(void)
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
   return n;
-}
-
-template <class T> static int upload_vec(T **dptr, const T *h, size_t n)
-{
-  *dptr = nullptr;
-  if (n == 0) return 0;
-  HIPCHK(hipMalloc((void **)dptr, n * sizeof(T)));
-  HIPCHK(hipMemcpy(*dptr, h, n * sizeof(T), hipMemcpyHostToDevice));
-  return 0;
 }
 
 // Every allocation of floating-point data goes through fp_malloc.  With CHOLAMD_POISON set and non-zero (read at each allocation) it takes a
@@ -170,45 +169,29 @@ static hipError_t fp_malloc(void **dptr, size_t bytes)
 {
   if (!poison_on()) return hipMalloc(dptr, bytes);
   hipError_t e = hipMalloc(dptr, bytes + CHOL_POISON_GUARD);
-  return e == hipSuccess ? poison_fill(*dptr, bytes + CHOL_POISON_GUARD) : e;
+  if (e == hipSuccess && (e = poison_fill(*dptr, bytes + CHOL_POISON_GUARD)) != hipSuccess) { (void)hipFree(*dptr); *dptr = nullptr; }
+  return e;
 }
 
-static void free_level(level_dev &l)
+// What chol_devbuf.h's owners are made of: every device buffer of the library's own comes from and goes back through these.  The release is a
+// synchronous hipFree: re-allocations rely on it waiting for the work in flight.
+static std::atomic<int64_t> g_live_buffers{ 0 };
+int chol_dev_acquire(void **p, size_t bytes, int floating_point)
 {
-  (void)hipFree(l.potrf); (void)hipFree(l.trsm); (void)hipFree(l.task); (void)hipFree(l.task_mt); (void)hipFree(l.src);
-  l = level_dev();
+  void *q = *p = nullptr;
+  HIPCHK(floating_point ? fp_malloc(&q, bytes) : hipMalloc(&q, bytes));
+  if ((*p = q)) g_live_buffers++; // (an allocation of zero bytes is no buffer)
+  return 0;
 }
-static void free_levels(cholamd_device *d)
-{
-  for (auto &l : d->lv) free_level(l);
-  d->lv.clear();
-  for (auto &l : d->lv32) free_level(l);
-  d->lv32.clear();
-  free_level(d->prog);
-  (void)hipFree(d->jobs); (void)hipFree(d->pwaits); (void)hipFree(d->exts); (void)hipFree(d->pctr); (void)hipFree(d->pctr_total);
-  d->jobs = nullptr; d->pwaits = nullptr; d->exts = nullptr; d->pctr = nullptr; d->pctr_total = nullptr;
-  d->prog_ready = false;
-}
+void chol_dev_release(void *p) { (void)hipFree(p); g_live_buffers--; }
+int chol_dev_zero(void *p, size_t bytes) { HIPCHK(hipMemset(p, 0, bytes)); return 0; }
+int chol_dev_copy_in(void *p, const void *host, size_t bytes) { HIPCHK(hipMemcpy(p, host, bytes, hipMemcpyHostToDevice)); return 0; }
+extern "C" int64_t cholamd_debug_live_buffers(void) { return g_live_buffers.load(); }
+
 static void free_solve_lists(cholamd_device *d)
 {
-  for (auto &s : d->sv) { (void)hipFree(s.trsv); (void)hipFree(s.fw); (void)hipFree(s.bw); (void)hipFree(s.grp_start); (void)hipFree(s.grp_rows); (void)hipFree(s.bw_start); (void)hipFree(s.ifw); (void)hipFree(s.ibw); }
-  d->sv.clear();
-  (void)hipFree(d->w256); d->w256 = nullptr;
-  (void)hipFree(d->dg_desc); d->dg_desc = nullptr; (void)hipFree(d->dg_prefix); d->dg_prefix = nullptr; d->n_dg = 0;
-  (void)hipFree(d->zr_sub); d->zr_sub = nullptr; d->n_zr_sub = 0;
-  d->solve_ready = false;
-}
-static void free_selinv(cholamd_device *d)
-{
-  for (auto &l : d->si) { (void)hipFree(l.sep); (void)hipFree(l.tile); (void)hipFree(l.chain_ld); (void)hipFree(l.chain_pos0); (void)hipFree(l.rowoff); }
-  d->si.clear();
-  (void)hipFree(d->si_ws); d->si_ws = nullptr;
-  d->si_ready = false;
-}
-static void free_schur(cholamd_device *d)
-{
-  for (auto &q : d->sc) (void)hipFree(q.desc);
-  d->sc.clear();
+  d->sv.clear(); d->solve_ready = false;
+  d->w256.reset(); d->dg_desc.reset(); d->dg_prefix.reset(); d->zr_sub.reset(); d->n_dg = 0; d->n_zr_sub = 0;
 }
 static int upload_level(level_dev &l, const chol_level_work &w, bool with_tables = true)
 {
@@ -229,19 +212,19 @@ static int upload_level(level_dev &l, const chol_level_work &w, bool with_tables
       }
       std::memcpy(buf.data() + (size_t)i * sizeof(chol_potrf_desc), &pd, sizeof pd);
     }
-    HIPCHK(hipMalloc((void **)&l.potrf, buf.size()));
-    HIPCHK(hipMemcpy(l.potrf, buf.data(), buf.size(), hipMemcpyHostToDevice));
-  } else rc = upload_vec(&l.potrf, w.potrf, (size_t)w.n_potrf);
-  if (!rc) rc = upload_vec(&l.trsm, w.trsm, (size_t)w.n_trsm);
-  if (!rc) rc = upload_vec(&l.task, w.task, (size_t)w.n_task);
-  if (!rc) rc = upload_vec(&l.task_mt, w.task_mt, (size_t)w.n_task_mt);
-  if (!rc) rc = upload_vec(&l.src, w.src, (size_t)w.n_src);
+    rc = l.potrf.upload_bytes(buf.data(), buf.size());
+  } else rc = l.potrf.upload(w.potrf, (size_t)w.n_potrf);
+  if (!rc) rc = l.trsm.upload(w.trsm, (size_t)w.n_trsm);
+  if (!rc) rc = l.task.upload(w.task, (size_t)w.n_task);
+  if (!rc) rc = l.task_mt.upload(w.task_mt, (size_t)w.n_task_mt);
+  if (!rc) rc = l.src.upload(w.src, (size_t)w.n_src);
   return rc;
 }
 
 static int build_levels(cholamd_device *d)
 {
-  free_levels(d);
+  d->lv.clear(); d->lv32.clear(); d->prog = level_dev(); d->prog_ready = false; // the schedule before this one
+  d->jobs.reset(); d->pwaits.reset(); d->exts.reset(); d->pctr.reset(); d->pctr_total.reset();
   d->sched_gen++;
   const int L = d->plan->levels;
   d->lv.resize(L);
@@ -278,17 +261,14 @@ static int build_levels(cholamd_device *d)
       d->prog_epoch_limit = (1 << 30) / mx;
       d->n_job = g.n_job; d->n_pctr = (int)tot.size(); d->prog_epoch = 0;
       d->jobs_host.assign(g.job, g.job + g.n_job);
-      if (!rc) rc = upload_vec(&d->jobs, g.job, (size_t)g.n_job);
+      if (!rc) rc = d->jobs.upload(g.job, (size_t)g.n_job);
       const chol_wait no_wait = { 0, 0 };
       chol_ext no_ext;
       std::memset(&no_ext, 0, sizeof no_ext);
-      if (!rc) rc = g.n_wait > 0 ? upload_vec(&d->pwaits, g.wait, (size_t)g.n_wait) : upload_vec(&d->pwaits, &no_wait, (size_t)1);
-      if (!rc) rc = g.n_ext > 0 ? upload_vec(&d->exts, g.ext, (size_t)g.n_ext) : upload_vec(&d->exts, &no_ext, (size_t)1);
-      if (!rc) rc = upload_vec(&d->pctr_total, tot.data(), tot.size());
-      if (!rc) {
-        HIPCHK(hipMalloc((void **)&d->pctr, tot.size() * sizeof(int)));
-        HIPCHK(hipMemset(d->pctr, 0, tot.size() * sizeof(int)));
-      }
+      if (!rc) rc = g.n_wait > 0 ? d->pwaits.upload(g.wait, (size_t)g.n_wait) : d->pwaits.upload(&no_wait, (size_t)1);
+      if (!rc) rc = g.n_ext > 0 ? d->exts.upload(g.ext, (size_t)g.n_ext) : d->exts.upload(&no_ext, (size_t)1);
+      if (!rc) rc = d->pctr_total.upload(tot.data(), tot.size());
+      if (!rc) rc = d->pctr.alloc_zero(tot.size());
       chol_level_work_free(&w);
       chol_program_free(&g);
       if (rc) return rc;
@@ -311,17 +291,12 @@ extern "C" int cholamd_device_create(const cholamd_plan *plan, int device_id, ch
   chol_sched_opts_from_env(&d->opt);
   { const char *e = getenv("CHOLAMD_SOLVE_REFERENCE_SHAPE"); d->solve_reference_shape = e && *e && atoi(e) != 0; }
   int rc = build_levels(d);
-  if (!rc) {
-    hipError_t e = fp_malloc((void **)&d->ws, (size_t)(plan->ws_doubles > 0 ? plan->ws_doubles : 1) * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&d->info, 4 * sizeof(int));
-    if (e == hipSuccess) e = hipMemset(d->info, 0, 4 * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&d->progress, (size_t)(plan->nsep + 2) * sizeof(int));
-    if (e == hipSuccess) e = hipMemset(d->progress, 0, (size_t)(plan->nsep + 2) * sizeof(int));
-    if (e != hipSuccess) { chol_set_error("hipMalloc: %s", hipGetErrorString(e)); rc = CHOLAMD_ERR_HIP; }
-  }
-  if (!rc) rc = upload_vec(&d->a_dst, plan->a_dst, (size_t)plan->nnz_a);
-  if (!rc) rc = upload_vec(&d->a_val, plan->a_val, (size_t)plan->nnz_a);
-  if (!rc) rc = upload_vec(&d->perm, plan->perm, (size_t)plan->n);
+  if (!rc) rc = d->ws.alloc((size_t)(plan->ws_doubles > 0 ? plan->ws_doubles : 1));
+  if (!rc) rc = d->info.alloc_zero(4);
+  if (!rc) rc = d->progress.alloc_zero((size_t)(plan->nsep + 2));
+  if (!rc) rc = d->a_dst.upload(plan->a_dst, (size_t)plan->nnz_a);
+  if (!rc) rc = d->a_val.upload(plan->a_val, (size_t)plan->nnz_a);
+  if (!rc) rc = d->perm.upload(plan->perm, (size_t)plan->n);
   if (rc) { cholamd_device_destroy(d); return rc; }
   *out = d;
   return 0;
@@ -331,28 +306,15 @@ extern "C" void cholamd_device_destroy(cholamd_device *d)
 {
   if (!d) return;
   (void)hipSetDevice(d->dev);
-  free_levels(d);
   for (auto &a : d->vmm) { // sharded arenas the caller did not free
     (void)hipDeviceSynchronize();
     (void)hipMemUnmap(a.va, a.total);
     for (auto h : a.handles) (void)hipMemRelease(h);
     (void)hipMemAddressFree(a.va, a.total);
   }
-  free_solve_lists(d);
-  free_selinv(d);
-  free_schur(d);
-  (void)hipFree(d->ws32); (void)hipFree(d->csr_ptr); (void)hipFree(d->csr_col); (void)hipFree(d->csr_val); (void)hipFree(d->rvec); (void)hipFree(d->dxvec); (void)hipFree(d->partial);
-  (void)hipFree(d->xstage); (void)hipFree(d->xdesc);
-  (void)hipFree(d->ws); (void)hipFree(d->ws_solve); (void)hipFree(d->step_flags); (void)hipFree(d->w256); (void)hipFree(d->step_xt); (void)hipFree(d->info); (void)hipFree(d->progress); (void)hipFree(d->a_dst); (void)hipFree(d->a_val); (void)hipFree(d->perm); (void)hipFree(d->ytmp);
-  (void)hipFree(d->ld_part); (void)hipFree(d->ld_ipart); (void)hipFree(d->ld_res);
-  for (int q = 0; q < 2; q++) { (void)hipFree(d->mul_item[q]); (void)hipFree(d->mul_src[q]); }
-  (void)hipFree(d->mvec); (void)hipFree(d->mr_part); (void)hipFree(d->mr_ipart); (void)hipFree(d->mr_res);
-  (void)hipFree(d->ynrhs); (void)hipFree(d->bnrhs); (void)hipFree(d->rnrhs); (void)hipFree(d->dxnrhs); (void)hipFree(d->pnrhs);
-  for (int q = 0; q < 2; q++) { (void)hipFree(d->top_dst[q]); (void)hipFree(d->top_val[q]); (void)hipFree(d->top_e[q]); }
-  (void)hipFree(d->a_src); (void)hipFree(d->csr_src); (void)hipFree(d->e_cls); (void)hipFree(d->vs_dev); (void)hipFree(d->vs_init); (void)hipHostFree(d->vs_host);
   for (auto &t : d->tl) { d->pool.push_back(t.a); d->pool.push_back(t.b); }
   for (auto e : d->pool) (void)hipEventDestroy(e);
-  delete d;
+  delete d; // with every buffer it owns
 }
 
 extern "C" int cholamd_device_set_partition(cholamd_device *d, int rank, int world)
@@ -738,17 +700,17 @@ extern "C" int cholamd_device_program_trace(cholamd_device *d, double *d_arena, 
   if (cap < (int64_t)5 * d->n_job) return 0;
   // 4 stamps per job, then CHOL_TRACE_X per job (chol_kernels.h)
   const size_t nst = (size_t)(4 + CHOL_TRACE_X) * d->n_job;
-  HIPCHK(hipMalloc((void **)&d->trace, nst * sizeof(unsigned long long)));
-  HIPCHK(hipMemset(d->trace, 0, nst * sizeof(unsigned long long)));
-  int rc = cholamd_factor(d, d_arena, stream);
   std::vector<unsigned long long> h(nst);
-  if (!rc) {
+  {
+    dev_buf<unsigned long long> stamps;
+    struct disarm { cholamd_device *d; ~disarm() { d->trace = nullptr; } } on_exit{ d }; // on every way out, before the stamps are released
+    int rc = stamps.alloc_zero(nst);
+    if (rc) return rc;
+    d->trace = stamps;
+    if ((rc = cholamd_factor(d, d_arena, stream))) return rc;
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-    HIPCHK(hipMemcpy(h.data(), d->trace, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h.data(), stamps, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   }
-  (void)hipFree(d->trace);
-  d->trace = nullptr;
-  if (rc) return rc;
   unsigned long long t0 = ~0ull;
   for (int j = 0; j < d->n_job; j++) if (h[4 * j] && h[4 * j] < t0) t0 = h[4 * j];
   for (int j = 0; j < d->n_job; j++) {
@@ -819,7 +781,7 @@ static int build_solve(cholamd_device *d, int rank = 0, int world = 1)
       }
     }
     d->n_zr_sub = (int)zr.size() / 2;
-    if (!zr.empty()) { int rc = upload_vec(&d->zr_sub, zr.data(), zr.size()); if (rc) return rc; }
+    { int rc = d->zr_sub.upload(zr.data(), zr.size()); if (rc) return rc; }
   }
   std::vector<chol_trsv_desc> diag; // the whole tree's lists only: the diagonal walk of the factor queries
   for (int lvl = 0; lvl < L; lvl++) {
@@ -829,30 +791,31 @@ static int build_solve(cholamd_device *d, int rank = 0, int world = 1)
     if (world == 1) diag.insert(diag.end(), w.trsv, w.trsv + w.n_trsv);
     solve_dev &s = d->sv[lvl];
     s.n_trsv = w.n_trsv; s.n_grp = w.n_grp; s.n_fw = w.n_fw; s.n_bw = w.n_bw;
-    rc = upload_vec(&s.trsv, w.trsv, (size_t)w.n_trsv);
-    if (!rc) rc = upload_vec(&s.fw, w.fw, (size_t)w.n_fw);
-    if (!rc) rc = upload_vec(&s.bw, w.bw, (size_t)w.n_bw);
-    if (!rc) rc = upload_vec(&s.grp_start, w.grp_start, (size_t)w.n_grp + 1);
-    if (!rc) rc = upload_vec(&s.grp_rows, w.grp_rows, (size_t)2 * w.n_grp);
-    if (!rc) rc = upload_vec(&s.bw_start, w.bw_start, (size_t)w.n_trsv + 1);
+    rc = s.trsv.upload(w.trsv, (size_t)w.n_trsv);
+    if (!rc) rc = s.fw.upload(w.fw, (size_t)w.n_fw);
+    if (!rc) rc = s.bw.upload(w.bw, (size_t)w.n_bw);
+    if (!rc) rc = s.grp_start.upload(w.grp_start, (size_t)w.n_grp + 1);
+    if (!rc) rc = s.grp_rows.upload(w.grp_rows, (size_t)2 * w.n_grp);
+    if (!rc) rc = s.bw_start.upload(w.bw_start, (size_t)w.n_trsv + 1);
     s.n_ifw = w.n_ifw; s.n_ibw = w.n_ibw; s.max_n = w.max_n; s.max_under = w.banded && w.max_rows_under_span > 0 ? -w.max_rows_under_span : w.max_rows_under_span;
-    if (!rc) rc = upload_vec(&s.ifw, w.ifw, (size_t)4 * w.n_ifw);
-    if (!rc) rc = upload_vec(&s.ibw, w.ibw, (size_t)4 * w.n_ibw);
+    if (!rc) rc = s.ifw.upload(w.ifw, (size_t)4 * w.n_ifw);
+    if (!rc) rc = s.ibw.upload(w.ibw, (size_t)4 * w.n_ibw);
     chol_solve_level_free(&w);
     if (rc) return rc;
   }
   if (!diag.empty()) {
     std::vector<int> prefix(diag.size() + 1);
     int rc = chol_diag_list(d->plan, diag.data(), (int)diag.size(), prefix.data());
-    if (!rc) rc = upload_vec(&d->dg_desc, diag.data(), diag.size());
-    if (!rc) rc = upload_vec(&d->dg_prefix, prefix.data(), prefix.size());
+    if (!rc) rc = d->dg_desc.upload(diag.data(), diag.size());
+    if (!rc) rc = d->dg_prefix.upload(prefix.data(), prefix.size());
     if (rc) return rc;
     d->n_dg = (int)diag.size();
   }
-  if (!d->ytmp) HIPCHK(fp_malloc((void **)&d->ytmp, (size_t)d->plan->n * sizeof(double)));
-  if (!d->ws_solve) HIPCHK(fp_malloc((void **)&d->ws_solve, (size_t)(d->plan->ws_doubles > 0 ? d->plan->ws_doubles : 1) * sizeof(double)));
-  if (!d->step_flags) { HIPCHK(hipMalloc((void **)&d->step_flags, CHOL_STEPW_MAX_SEPS * 16 * sizeof(int))); HIPCHK(hipMemset(d->step_flags, 0, CHOL_STEPW_MAX_SEPS * 16 * sizeof(int))); }
-  if (!d->step_xt) { HIPCHK(fp_malloc((void **)&d->step_xt, CHOL_STEPW_MAX_SEPS * 256 * sizeof(double))); HIPCHK(hipMemset(d->step_xt, 0, CHOL_STEPW_MAX_SEPS * 256 * sizeof(double))); }
+  int rc = d->ytmp.ensure((size_t)d->plan->n);
+  if (!rc) rc = d->ws_solve.ensure((size_t)(d->plan->ws_doubles > 0 ? d->plan->ws_doubles : 1));
+  if (!rc) rc = d->step_flags.ensure_zero(CHOL_STEPW_MAX_SEPS * 16);
+  if (!rc) rc = d->step_xt.ensure_zero(CHOL_STEPW_MAX_SEPS * 256);
+  if (rc) return rc;
   int64_t w256 = 0; // explicit inverses of the diagonal spans where the span chain is the solve's critical path: the levels of at most 8 separators
   if (!std::getenv("CHOLAMD_SOLVE_NO_INV256"))
     for (int lvl = 0; lvl < L; lvl++) {
@@ -861,7 +824,7 @@ static int build_solve(cholamd_device *d, int rank = 0, int world = 1)
       s.w256_off = w256;
       w256 += (int64_t)s.n_trsv * ((s.max_n + 255) / 256) * 65536;
     }
-  if (w256 > 0) HIPCHK(fp_malloc((void **)&d->w256, (size_t)w256 * sizeof(double)));
+  if (w256 > 0 && (rc = d->w256.alloc((size_t)w256))) return rc;
   d->solve_ready = true;
   return 0;
 }
@@ -989,6 +952,7 @@ static int f32_range_ok(cholamd_device *d, hipStream_t st)
 static int ensure_f32(cholamd_device *d, hipStream_t st)
 {
   { int rc = f32_range_ok(d, st); if (rc) return rc; }
+  { int rc = d->ws32.ensure((size_t)(d->plan->ws_doubles > 0 ? d->plan->ws_doubles : 1)); if (rc) return rc; }
   if (!d->lv32.empty()) return 0;
   const int L = d->plan->levels;
   chol_sched_opts o = d->opt;
@@ -999,9 +963,8 @@ static int ensure_f32(cholamd_device *d, hipStream_t st)
     int rc = chol_build_level_work(d->plan, &o, lvl, d->rank, d->world, &w);
     if (!rc) rc = upload_level(d->lv32[lvl], w, false); // the fp32 kernels have no role tables
     chol_level_work_free(&w);
-    if (rc) { for (auto &l : d->lv32) free_level(l); d->lv32.clear(); return rc; }
+    if (rc) { d->lv32.clear(); return rc; }
   }
-  if (!d->ws32) HIPCHK(fp_malloc((void **)&d->ws32, (size_t)(d->plan->ws_doubles > 0 ? d->plan->ws_doubles : 1) * sizeof(float)));
   return 0;
 }
 extern "C" int cholamd_device_fill_f32(cholamd_device *d, float *d_arena32, void *stream)
@@ -1067,18 +1030,18 @@ extern "C" int cholamd_solve_f32(cholamd_device *d, const float *d_arena32, cons
   return solve_streamed(d, d_arena32, d_b, d_x, (hipStream_t)stream);
 }
 static int ensure_refine(cholamd_device *d)
-{
-  if (d->csr_ptr) return 0;
+{ // every buffer on its own: a call after a failure completes what is missing (csr_val is not uploaded twice: it follows cholamd_device_set_values)
   const cholamd_plan *p = d->plan;
   const int n = p->n;
-  int rc = upload_vec(&d->csr_ptr, p->csr_ptr, (size_t)n + 1);
-  if (!rc) rc = upload_vec(&d->csr_col, p->csr_col, (size_t)(p->csr_ptr[n] > 0 ? p->csr_ptr[n] : 1));
-  if (!rc) rc = upload_vec(&d->csr_val, p->csr_val, (size_t)(p->csr_ptr[n] > 0 ? p->csr_ptr[n] : 1));
-  if (rc) return rc;
-  HIPCHK(fp_malloc((void **)&d->rvec, (size_t)n * sizeof(double)));
-  HIPCHK(fp_malloc((void **)&d->dxvec, (size_t)n * sizeof(double)));
-  HIPCHK(fp_malloc((void **)&d->partial, (size_t)2 * ((n + 255) / 256) * sizeof(double)));
-  return 0;
+  const size_t ncsr = (size_t)(p->csr_ptr[n] > 0 ? p->csr_ptr[n] : 1);
+  int rc = 0;
+  if (!d->csr_ptr) rc = d->csr_ptr.upload(p->csr_ptr, (size_t)n + 1);
+  if (!rc && !d->csr_col) rc = d->csr_col.upload(p->csr_col, ncsr);
+  if (!rc && !d->csr_val) rc = d->csr_val.upload(p->csr_val, ncsr);
+  if (!rc) rc = d->rvec.ensure((size_t)n);
+  if (!rc) rc = d->dxvec.ensure((size_t)n);
+  if (!rc) rc = d->partial.ensure((size_t)2 * ((n + 255) / 256));
+  return rc;
 }
 // ---------------------------------------------------------------------------------------------
 // New values of A on the same pattern (include/cholamd.h at cholamd_device_set_values).  The copies of A's values a device object holds are the
@@ -1087,20 +1050,19 @@ static int ensure_refine(cholamd_device *d)
 // ---------------------------------------------------------------------------------------------
 static int ensure_values(cholamd_device *d)
 {
-  if (d->vs_dev) return 0;
+  if (d->vs_dev) return 0; // the last one allocated
   const cholamd_plan *p = d->plan;
   int rc = ensure_refine(d); // the residual operator follows the values from now on
   if (rc) return rc;
   const size_t ncsr = (size_t)p->csr_ptr[p->n];
-  if (!d->a_src) rc = upload_vec(&d->a_src, p->a_src, (size_t)p->nnz_a);
-  if (!rc && !d->csr_src) rc = upload_vec(&d->csr_src, p->csr_src, ncsr);
-  if (!rc && !d->e_cls) rc = upload_vec(&d->e_cls, p->e_cls, (size_t)p->nz_file);
+  if (!d->a_src) rc = d->a_src.upload(p->a_src, (size_t)p->nnz_a);
+  if (!rc && !d->csr_src) rc = d->csr_src.upload(p->csr_src, ncsr);
+  if (!rc && !d->e_cls) rc = d->e_cls.upload(p->e_cls, (size_t)p->nz_file);
   const int64_t init[4] = { 0, INT64_MAX, 0, INT64_MAX };
-  if (!rc && !d->vs_init) rc = upload_vec(&d->vs_init, init, (size_t)4);
-  if (rc) return rc;
-  if (!d->vs_host) HIPCHK(hipHostMalloc((void **)&d->vs_host, 8 * sizeof(int64_t)));
-  HIPCHK(hipMalloc((void **)&d->vs_dev, 4 * sizeof(int64_t)));
-  return 0;
+  if (!rc && !d->vs_init) rc = d->vs_init.upload(init, (size_t)4);
+  if (!rc) rc = d->vs_host.ensure(8);
+  if (!rc) rc = d->vs_dev.alloc(4);
+  return rc;
 }
 static void take_f32_verdict(cholamd_device *d, const int64_t *status)
 {
@@ -1296,7 +1258,7 @@ template <class TL> static int solve_nrhs_t(cholamd_device *d, const TL *d_arena
       }
       continue;
     }
-    if (!d->ynrhs) HIPCHK(fp_malloc((void **)&d->ynrhs, (size_t)n * CHOL_NRHS_W * sizeof(double)));
+    { int rc = d->ynrhs.ensure((size_t)n * CHOL_NRHS_W); if (rc) return rc; }
     double *Y = d->ynrhs;
     HIPCHK((hipError_t)chol_nrhs_launch_permute(d_B, ldb, d->perm, Y, nullptr, 0, n, c0, cols, 0, st));
     for (int lvl = L - 1; lvl >= 0 && which != CHOLAMD_HALF_BACKWARD; lvl--) { // forward: the separators' triangles, then their panels into the ancestors
@@ -1423,9 +1385,10 @@ template <class TL> static int factor_logdet_t(cholamd_device *d, const TL *d_ar
   if (!d_arena || !logdet_out) { chol_set_error("%s: NULL %s", what, !d_arena ? "arena" : "logdet_out"); return CHOLAMD_ERR_ARG; }
   HIPCHK(hipSetDevice(d->dev));
   { int rc = build_solve(d); if (rc) return rc; }
-  if (!d->ld_part) HIPCHK(fp_malloc((void **)&d->ld_part, 2 * CHOL_LOGDET_MAX_BLOCKS * sizeof(double)));
-  if (!d->ld_ipart) HIPCHK(hipMalloc((void **)&d->ld_ipart, 2 * CHOL_LOGDET_MAX_BLOCKS * sizeof(int64_t)));
-  if (!d->ld_res) HIPCHK(hipMalloc((void **)&d->ld_res, 3 * sizeof(int64_t)));
+  int rc = d->ld_part.ensure(2 * CHOL_LOGDET_MAX_BLOCKS);
+  if (!rc) rc = d->ld_ipart.ensure(2 * CHOL_LOGDET_MAX_BLOCKS);
+  if (!rc) rc = d->ld_res.ensure(3);
+  if (rc) return rc;
   HIPCHK((hipError_t)lfactor_logdet(d_arena, d->dg_desc, d->dg_prefix, d->n_dg, d->plan->n, d->ld_part, d->ld_ipart, d->ld_res, st));
   int64_t res[3] = { 0, 0, 0 };
   HIPCHK(hipMemcpyAsync(res, d->ld_res, sizeof res, hipMemcpyDeviceToHost, st));
@@ -1453,15 +1416,14 @@ extern "C" int cholamd_factor_logdet_f32(cholamd_device *d, const float *d_arena
 static int build_selinv(cholamd_device *d)
 {
   if (d->si_ready) return 0;
-  free_selinv(d);
   const int L = d->plan->levels;
-  d->si.resize(L);
+  std::vector<selinv_dev> si(L); // handed to the device object once complete
   int64_t ws = 1;
   for (int lvl = 0; lvl < L; lvl++) {
     chol_selinv_level w;
     int rc = chol_build_selinv_level(d->plan, lvl, &w);
     if (rc) return rc;
-    selinv_dev &s = d->si[lvl];
+    selinv_dev &s = si[lvl];
     s.host.assign(w.sep, w.sep + w.n_sep);
     s.max_nblk = w.max_nblk;
     if (w.max_tiles > CHOL_SELINV_MAX_TILES) {
@@ -1470,15 +1432,16 @@ static int build_selinv(cholamd_device *d)
       return CHOLAMD_ERR_ARG;
     }
     ws = std::max(ws, w.ws_doubles);
-    rc = upload_vec(&s.sep, w.sep, (size_t)w.n_sep);
-    if (!rc) rc = upload_vec(&s.tile, w.tile, (size_t)w.n_tile);
-    if (!rc) rc = upload_vec(&s.chain_ld, w.chain_ld, (size_t)w.n_chain);
-    if (!rc) rc = upload_vec(&s.chain_pos0, w.chain_pos0, (size_t)w.n_chain);
-    if (!rc) rc = upload_vec(&s.rowoff, w.rowoff, (size_t)w.n_rowoff);
+    rc = s.sep.upload(w.sep, (size_t)w.n_sep);
+    if (!rc) rc = s.tile.upload(w.tile, (size_t)w.n_tile);
+    if (!rc) rc = s.chain_ld.upload(w.chain_ld, (size_t)w.n_chain);
+    if (!rc) rc = s.chain_pos0.upload(w.chain_pos0, (size_t)w.n_chain);
+    if (!rc) rc = s.rowoff.upload(w.rowoff, (size_t)w.n_rowoff);
     chol_selinv_level_free(&w);
     if (rc) return rc;
   }
-  HIPCHK(fp_malloc((void **)&d->si_ws, (size_t)ws * sizeof(double)));
+  { int rc = d->si_ws.alloc((size_t)ws); if (rc) return rc; }
+  d->si = std::move(si);
   d->si_ready = true;
   return 0;
 }
@@ -1523,7 +1486,7 @@ extern "C" int cholamd_selinv_entries(cholamd_device *d, const double *d_zarena,
   const cholamd_plan *p = d->plan;
   if (count != p->nz_file) { chol_set_error("cholamd_selinv_entries: room for %lld entries, the plan has %d", (long long)count, p->nz_file); return CHOLAMD_ERR_ARG; }
   HIPCHK(hipSetDevice(d->dev));
-  if (!d->a_src) { int rc = upload_vec(&d->a_src, p->a_src, (size_t)p->nnz_a); if (rc) return rc; } // the index list of cholamd_device_set_values
+  if (!d->a_src) { int rc = d->a_src.upload(p->a_src, (size_t)p->nnz_a); if (rc) return rc; } // the index list of cholamd_device_set_values
   HIPCHK((hipError_t)chol_launch_selinv_entries(d_zarena, d->a_dst, d->a_src, p->nnz_a, d_vals, count, (hipStream_t)stream));
   return 0;
 }
@@ -1541,17 +1504,16 @@ static int build_multiply(cholamd_device *d)
   chol_mul_lists w;
   int rc = chol_build_multiply(d->plan, &w);
   if (rc) return rc;
-  for (int q = 0; q < 2 && !rc; q++) {
-    (void)hipFree(d->mul_item[q]); (void)hipFree(d->mul_src[q]); d->mul_item[q] = nullptr; d->mul_src[q] = nullptr;
-    rc = upload_vec(&d->mul_item[q], w.item[q], (size_t)w.n_item[q]);
-    if (!rc) rc = upload_vec(&d->mul_src[q], w.src[q], (size_t)w.n_src[q]);
+  for (int q = 0; q < 2 && !rc; q++) { // (an upload replaces what a call that failed half-way left)
+    rc = d->mul_item[q].upload(w.item[q], (size_t)w.n_item[q]);
+    if (!rc) rc = d->mul_src[q].upload(w.src[q], (size_t)w.n_src[q]);
     d->n_mul_item[q] = w.n_item[q];
   }
   chol_mul_lists_free(&w);
-  if (rc) return rc;
   const size_t n = (size_t)(d->plan->n > 0 ? d->plan->n : 1);
-  if (!d->ytmp) HIPCHK(fp_malloc((void **)&d->ytmp, n * sizeof(double)));
-  if (!d->mvec) HIPCHK(fp_malloc((void **)&d->mvec, n * sizeof(double)));
+  if (!rc) rc = d->ytmp.ensure(n);
+  if (!rc) rc = d->mvec.ensure(n);
+  if (rc) return rc;
   d->mul_ready = true;
   return 0;
 }
@@ -1612,10 +1574,11 @@ template <class TL> static int factor_residual_t(cholamd_device *d, const TL *d_
   HIPCHK(hipSetDevice(d->dev));
   { int rc = ensure_refine(d); if (rc) return rc; } // the residual operator with the CURRENT values (cholamd_device_set_values keeps it up to date)
   const int n = d->plan->n, nb = (n + 255) / 256;
-  if (!d->mr_part) HIPCHK(fp_malloc((void **)&d->mr_part, (size_t)2 * (nb > 0 ? nb : 1) * sizeof(double)));
-  if (!d->mr_ipart) HIPCHK(hipMalloc((void **)&d->mr_ipart, (size_t)(nb > 0 ? nb : 1) * sizeof(int64_t)));
-  if (!d->mr_res) HIPCHK(hipMalloc((void **)&d->mr_res, 3 * sizeof(int64_t)));
-  { int rc = multiply_t(d, d_arena, d_z, d->rvec, CHOL_BOTH_SWEEPS, st); if (rc) return rc; } // w = M M^T z in original dof order
+  int rc = d->mr_part.ensure((size_t)2 * (nb > 0 ? nb : 1));
+  if (!rc) rc = d->mr_ipart.ensure((size_t)(nb > 0 ? nb : 1));
+  if (!rc) rc = d->mr_res.ensure(3);
+  if (rc) return rc;
+  if ((rc = multiply_t(d, d_arena, d_z, d->rvec, CHOL_BOTH_SWEEPS, st))) return rc; // w = M M^T z in original dof order
   HIPCHK((hipError_t)chol_launch_multiply_resid(d->csr_ptr, d->csr_col, d->csr_val, d_z, d->rvec, n, d->mr_part, d->mr_ipart, d->mr_res, st));
   int64_t res[3] = { 0, 0, 0 };
   HIPCHK(hipMemcpyAsync(res, d->mr_res, sizeof res, hipMemcpyDeviceToHost, st));
@@ -1668,7 +1631,7 @@ static int build_schur(cholamd_device *d, int k)
   if (cnt < 0) return (int)cnt;
   std::vector<chol_schur_desc> h((size_t)cnt);
   chol_schur_pieces(d->plan, k, 1, CHOL_SCHUR_CHUNK, cnt, h.data());
-  int rc = upload_vec(&q.desc, h.data(), (size_t)cnt);
+  int rc = q.desc.upload(h.data(), (size_t)cnt);
   if (rc) return rc;
   q.n = cnt;
   return 0;
@@ -1791,10 +1754,11 @@ extern "C" int cholamd_solve_refine_nrhs(cholamd_device *d, const float *d_arena
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int n = d->plan->n, nb = (n + 255) / 256;
-  if (!d->bnrhs) HIPCHK(fp_malloc((void **)&d->bnrhs, (size_t)n * CHOL_NRHS_W * sizeof(double)));
-  if (!d->rnrhs) HIPCHK(fp_malloc((void **)&d->rnrhs, (size_t)n * CHOL_NRHS_W * sizeof(double)));
-  if (!d->dxnrhs) HIPCHK(fp_malloc((void **)&d->dxnrhs, (size_t)n * CHOL_NRHS_W * sizeof(double)));
-  if (!d->pnrhs) HIPCHK(fp_malloc((void **)&d->pnrhs, (size_t)2 * nb * CHOL_NRHS_W * sizeof(double)));
+  if (!rc) rc = d->bnrhs.ensure((size_t)n * CHOL_NRHS_W);
+  if (!rc) rc = d->rnrhs.ensure((size_t)n * CHOL_NRHS_W);
+  if (!rc) rc = d->dxnrhs.ensure((size_t)n * CHOL_NRHS_W);
+  if (!rc) rc = d->pnrhs.ensure((size_t)2 * nb * CHOL_NRHS_W);
+  if (rc) return rc;
   if (max_iter < 0) max_iter = 0;
   // chunk by chunk: the chunk's columns of B are copied first (X may be B: in place), x0 = M^-1 b with M = L32 L32^T, then X += M^-1 (B - A X) on ALL the
   // chunk's columns until every one of them has ||b_j - A x_j|| <= tol ||b_j|| or max_iter corrections have been applied.  The inverses are formed once.
@@ -1836,22 +1800,21 @@ extern "C" int cholamd_solve_refine_nrhs(cholamd_device *d, const float *d_arena
 static inline int64_t poff(const void *p) { return (int64_t)((uintptr_t)p / sizeof(double)); }
 
 struct scratch { // per-call device scratch, freed at scope exit after the stream has been synchronised
-  std::vector<void *> ptrs;
-  ~scratch() { for (void *p : ptrs) (void)hipFree(p); }
+  std::vector<dev_buf<char>> bufs;
+  template <class T> int get(T **dptr, size_t n, int floating_point = std::is_floating_point<T>::value)
+  {
+    bufs.emplace_back();
+    int rc = bufs.back().alloc_bytes((n ? n : 1) * sizeof(T), floating_point);
+    *dptr = (T *)bufs.back().get();
+    return rc;
+  }
   template <class T> int put(T **dptr, const T *h, size_t n, hipStream_t st)
   {
     *dptr = nullptr;
     if (n == 0) return 0;
-    HIPCHK(hipMalloc((void **)dptr, n * sizeof(T)));
-    ptrs.push_back(*dptr);
+    int rc = get(dptr, n, 0); // uploads: plain memory
+    if (rc) return rc;
     HIPCHK(hipMemcpyAsync(*dptr, h, n * sizeof(T), hipMemcpyHostToDevice, st));
-    return 0;
-  }
-  template <class T> int get(T **dptr, size_t n)
-  {
-    if (std::is_floating_point<T>::value) HIPCHK(fp_malloc((void **)dptr, (n ? n : 1) * sizeof(T)));
-    else HIPCHK(hipMalloc((void **)dptr, (n ? n : 1) * sizeof(T)));
-    ptrs.push_back(*dptr);
     return 0;
   }
 };
@@ -2290,12 +2253,12 @@ extern "C" int cholamd_blas_status(void) { return g_blas_status; }
 extern "C" void cholamd_openblas_set_num_threads(int) {} // mmat.rg:1057: parallelism is the GPU's
 
 struct host_mat { // a host matrix mirrored on the device for the duration of one call
-  double *d = nullptr; double *h = nullptr; int rows = 0, cols = 0, ld = 0; bool writeback = false;
+  dev_buf<double> d; double *h = nullptr; int rows = 0, cols = 0, ld = 0; bool writeback = false;
   int up(const double *hp, int r, int c, int ldh, bool wb)
   {
     h = const_cast<double *>(hp); rows = r; cols = c; ld = ldh; writeback = wb;
     if (r == 0 || c == 0) return 0;
-    HIPCHK(fp_malloc((void **)&d, (size_t)ld * cols * sizeof(double)));
+    { int rc = d.alloc((size_t)ld * cols); if (rc) return rc; }
     HIPCHK(hipMemcpy(d, h, ((size_t)ld * (cols - 1) + rows) * sizeof(double), hipMemcpyHostToDevice));
     return 0;
   }
@@ -2304,7 +2267,6 @@ struct host_mat { // a host matrix mirrored on the device for the duration of on
     if (d && writeback) HIPCHK(hipMemcpy2D(h, (size_t)ld * sizeof(double), d, (size_t)ld * sizeof(double), (size_t)rows * sizeof(double), cols, hipMemcpyDeviceToHost));
     return 0;
   }
-  ~host_mat() { if (d) (void)hipFree(d); }
 };
 
 extern "C" int cholamd_LAPACKE_dpotrf(int layout, char uplo, int n, double *a, int lda)
@@ -2389,15 +2351,14 @@ extern "C" void cholamd_cblas_dgemv(int layout, int trans, int m, int n, double 
   const int lx = trans == CholamdNoTrans ? n : m, ly = trans == CholamdNoTrans ? m : n;
   if (m == 0 || n == 0) return;
   // x and y share one device buffer so that 32-bit relative offsets always suffice
-  double *xy = nullptr;
-  if (fp_malloc((void **)&xy, (size_t)(lx + ly) * sizeof(double)) != hipSuccess) { g_blas_status = CHOLAMD_ERR_HIP; return; }
+  dev_buf<double> xy;
+  if (xy.alloc((size_t)(lx + ly))) { g_blas_status = CHOLAMD_ERR_HIP; return; }
   host_mat A;
   rc = A.up(a, m, n, lda, false);
   if (!rc && hipMemcpy(xy, x, (size_t)lx * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = CHOLAMD_ERR_HIP;
   if (!rc && hipMemcpy(xy + lx, y, (size_t)ly * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = CHOLAMD_ERR_HIP;
   if (!rc) rc = cholamd_dgemv_dev(trans, m, n, A.d, lda, xy, xy + lx, nullptr);
   if (!rc && hipMemcpy(y, xy + lx, (size_t)ly * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = CHOLAMD_ERR_HIP;
-  (void)hipFree(xy);
   g_blas_status = rc;
 }
 
@@ -2572,8 +2533,7 @@ static int top_entries(cholamd_device *d, int f32, int64_t *below, const int64_t
   while (lo < hi) { int64_t mid = (lo + hi) / 2; if (p->a_dst[mid] < tail) lo = mid + 1; else hi = mid; }
   *below = lo;
   if (d->top_gen[f32] != d->sched_gen) { // once per schedule
-    (void)hipFree(d->top_dst[f32]); (void)hipFree(d->top_val[f32]); (void)hipFree(d->top_e[f32]);
-    d->top_dst[f32] = nullptr; d->top_val[f32] = nullptr; d->top_e[f32] = nullptr; d->top_n[f32] = 0;
+    d->top_dst[f32].reset(); d->top_val[f32].reset(); d->top_e[f32].reset(); d->top_n[f32] = 0;
     std::vector<xpiece> px;
     exchange_pieces(d, f32 ? d->lv32 : d->lv, px);
     if (px.empty()) d->top_n[f32] = d->rank == 0 ? -1 : 0; // replicated top levels: rank 0 scatters the whole tail
@@ -2588,11 +2548,11 @@ static int top_entries(cholamd_device *d, int f32, int64_t *below, const int64_t
         if (q < mine.size() && p->a_dst[e] >= mine[q].off) { td.push_back(p->a_dst[e]); te.push_back((int)e); }
       }
       if (!td.empty()) {
-        int rc = upload_vec(&d->top_dst[f32], td.data(), td.size());
-        if (!rc) rc = upload_vec(&d->top_e[f32], te.data(), te.size());
-        if (rc) return rc;
+        int rc = d->top_dst[f32].upload(td.data(), td.size());
+        if (!rc) rc = d->top_e[f32].upload(te.data(), te.size());
         // the values: the device object's CURRENT ones (the plan's, or those of the last cholamd_device_set_values)
-        HIPCHK(fp_malloc((void **)&d->top_val[f32], td.size() * sizeof(double)));
+        if (!rc) rc = d->top_val[f32].alloc(td.size());
+        if (rc) return rc;
         HIPCHK((hipError_t)chol_launch_gather(d->top_val[f32], d->a_val, d->top_e[f32], (int64_t)td.size(), st));
       }
       d->top_n[f32] = (int64_t)td.size();
@@ -2627,7 +2587,7 @@ template <class T> static int exchange_owned_sum(cholamd_device *d, T *arena, co
   if (!mine) return 0;
   HIPCHK(hipSetDevice(d->dev));
   const int64_t bx = (mx + 255) / 256;
-  hipLaunchKernelGGL(k_sum_owned<T>, dim3((unsigned)(bx < 1024 ? bx : 1024), mine), dim3(256), 0, st, arena, (const T *)d->xstage, (const sum_desc *)d->xdesc, d->world, d->rank);
+  hipLaunchKernelGGL(k_sum_owned<T>, dim3((unsigned)(bx < 1024 ? bx : 1024), mine), dim3(256), 0, st, arena, (const T *)d->xstage.get(), d->xdesc.get(), d->world, d->rank);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -2638,17 +2598,16 @@ template <class T> static int exchange_owned(cholamd_device *d, T *arena, const 
   for (const xpiece &x : px) if (x.owner == d->rank) { need += x.count * __builtin_popcount(x.contrib & ~(1u << d->rank)); mine.push_back({ x.off, x.count, x.stage, x.contrib, 0 }); }
   if ((size_t)need * sizeof(T) > d->xstage_bytes) {
     HIPCHK(hipStreamSynchronize(st));
-    (void)hipFree(d->xstage); d->xstage = nullptr; d->xstage_bytes = 0;
-    HIPCHK(fp_malloc(&d->xstage, (size_t)need * sizeof(T)));
+    d->xstage_bytes = 0;
+    { int rc = d->xstage.alloc_bytes((size_t)need * sizeof(T), 1); if (rc) return rc; }
     d->xstage_bytes = (size_t)need * sizeof(T);
   }
   if (d->xdesc_gen != d->sched_gen || d->xdesc_elem != (int)sizeof(T)) { // the descriptors of the sum kernel, once per schedule
     HIPCHK(hipStreamSynchronize(st));
-    (void)hipFree(d->xdesc); d->xdesc = nullptr;
-    if (!mine.empty()) { int rc = upload_vec((sum_desc **)&d->xdesc, mine.data(), mine.size()); if (rc) return rc; }
+    { int rc = d->xdesc.upload(mine.data(), mine.size()); if (rc) return rc; }
     d->xdesc_gen = d->sched_gen; d->xdesc_elem = (int)sizeof(T);
   }
-  T *stage = (T *)d->xstage;
+  T *stage = (T *)d->xstage.get();
   NCCLCHK(ncclGroupStart());
   for (const xpiece &x : px) {
     ncclResult_t r = ncclSuccess;

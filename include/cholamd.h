@@ -353,6 +353,8 @@ int cholamd_device_set_partition(cholamd_device *d, int rank, int world);
  * first job was drawn) when the job was drawn, when its waits were over and when it ended, and the workgroup that ran it.
  * *njobs_out = number of jobs (call with cap = 0 to size the buffer). */
 int cholamd_device_program_trace(cholamd_device *d, double *d_arena, void *stream, int64_t cap, int64_t *out, int *njobs_out);
+/* diagnostic: device buffers the library itself owns in this process right now (caller-owned allocations are not counted); no device access */
+int64_t cholamd_debug_live_buffers(void);
 /* Debug mode of the reference (mmat.rg -d <dir>): the level loop of mmat.rg:1227-1355 LITERALLY -- one fused task
  * at a time through the task-level entry points below, serialised -- printing the tasks' POTRF / TRSM / GEMM lines on stdout
  * and, after every task, dumping the whole matrix as write_blocks does (mmat.rg:174-218): <dir>/<gen_filename>.mtx
