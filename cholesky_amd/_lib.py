@@ -171,7 +171,12 @@ def load():
         getattr(L, name).argtypes = [vp, vp, vp, vp, vp]
     for name in ("cholamd_factor_residual", "cholamd_factor_residual_f32"):
         getattr(L, name).argtypes = [vp, vp, vp, C.POINTER(cd), vp]
+    for name in ("cholamd_multiply_half_nrhs", "cholamd_multiply_half_nrhs_f32"):
+        getattr(L, name).argtypes = [vp, vp, vp, i64, vp, i64, ci, ci, vp]
+    for name in ("cholamd_multiply_nrhs", "cholamd_multiply_nrhs_f32"):
+        getattr(L, name).argtypes = [vp, vp, vp, i64, vp, i64, ci, vp]
     L.cholamd_plan_multiply_host.argtypes = [vp, vp, ci, vp, vp]
+    L.cholamd_plan_multiply_host_nrhs.argtypes = [vp, vp, ci, vp, i64, vp, i64, ci]
     L.cholamd_plan_multiply_counts.argtypes = [vp, vp]
     L.cholamd_factor_logdet.argtypes = [vp, vp, C.POINTER(cd), vp]
     L.cholamd_factor_logdet_f32.argtypes = [vp, vp, C.POINTER(cd), vp]

@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cfloat>
 #include <cmath>
+#include <cctype>
 #include <cstring>
 #include <string>
 #include <type_traits>
@@ -135,6 +136,10 @@ struct cholamd_device {
   // first call; the intermediate vector of cholamd_multiply (permuted coordinates); the residual's per-workgroup partial sums and result words
   dev_buf<chol_mul_item> mul_item[2]; dev_buf<chol_mul_src> mul_src[2]; int n_mul_item[2] = { 0, 0 }; bool mul_ready = false;
   dev_buf<double> mvec, mr_part; dev_buf<int64_t> mr_ipart, mr_res;
+  // their block form (cholamd_multiply_half_nrhs / cholamd_multiply_nrhs): the two permuted blocks of one chunk (n x CHOL_NRHS_W, row-major), allocated at the
+  // first chunk that takes the block kernel; option multiply_nrhs_min: chunks of fewer columns go column by column (<= 0: the measured default)
+  dev_buf<double> mznrhs, mwnrhs;
+  int multiply_nrhs_min = 0;
 };
 
 static int no_device_error()
@@ -290,6 +295,7 @@ extern "C" int cholamd_device_create(const cholamd_plan *plan, int device_id, ch
   d->plan = plan; d->dev = device_id;
   chol_sched_opts_from_env(&d->opt);
   { const char *e = getenv("CHOLAMD_SOLVE_REFERENCE_SHAPE"); d->solve_reference_shape = e && *e && atoi(e) != 0; }
+  { const char *e = getenv("CHOLAMD_MULTIPLY_NRHS_MIN"); d->multiply_nrhs_min = e && *e ? atoi(e) : 0; }
   int rc = build_levels(d);
   if (!rc) rc = d->ws.alloc((size_t)(plan->ws_doubles > 0 ? plan->ws_doubles : 1));
   if (!rc) rc = d->info.alloc_zero(4);
@@ -361,6 +367,7 @@ extern "C" int cholamd_device_set_option(cholamd_device *d, const char *name, in
   else if (n == "stage_chunk") d->opt.stage_chunk = value < 0 ? 0 : value;
   else if (n == "dist_top") d->opt.dist_top = value;
   else if (n == "solve_reference_shape") { d->solve_reference_shape = value != 0; rebuild = false; }
+  else if (n == "multiply_nrhs_min") { d->multiply_nrhs_min = value; rebuild = false; }
   else { chol_set_error("unknown option '%s'", n.c_str()); return CHOLAMD_ERR_ARG; }
   return rebuild ? build_levels(d) : 0;
 }
@@ -1185,14 +1192,21 @@ static int lnrhs_trsv(const double *a, const chol_trsv_desc *t, int n, int mx, i
 static int lnrhs_trsv(const float *a, const chol_trsv_desc *t, int n, int mx, int mu, const double *W, const double *W256, double *Y, int bw, hipStream_t st) { return chol32_nrhs_launch_trsv(a, t, n, mx, mu, W, W256, Y, bw, st); }
 static int lnrhs_off(const double *a, const chol_gemv_desc *g, const int *it, int n, double *Y, int bw, hipStream_t st) { return chol_nrhs_launch_offdiag(a, g, it, n, Y, bw, st); }
 static int lnrhs_off(const float *a, const chol_gemv_desc *g, const int *it, int n, double *Y, int bw, hipStream_t st) { return chol32_nrhs_launch_offdiag(a, g, it, n, Y, bw, st); }
-static int nrhs_check(cholamd_device *d, const void *arena, const double *B, int64_t ldb, const double *X, int64_t ldx, int nrhs, const char *what)
+// in / out: what the entry point's header calls its two blocks (the solves: B, X; the products: Z, Y)
+static int nrhs_check(cholamd_device *d, const void *arena, const double *B, int64_t ldb, const double *X, int64_t ldx, int nrhs, const char *what, const char *in = "B", const char *out = "X")
 { // 1: nothing to do
   if (!d) { chol_set_error("%s: NULL device", what); return CHOLAMD_ERR_ARG; }
   const int n = d->plan->n;
   if (nrhs < 0) { chol_set_error("%s: nrhs = %d < 0", what, nrhs); return CHOLAMD_ERR_ARG; }
-  if (ldb < n || ldx < n) { chol_set_error("%s: leading dimensions ldb = %lld, ldx = %lld must be at least n = %d", what, (long long)ldb, (long long)ldx, n); return CHOLAMD_ERR_ARG; }
+  if (ldb < n || ldx < n) {
+    std::string li(in), lo(out); // "B" -> ldb, "Z" -> ldz
+    for (auto &c : li) c = (char)std::tolower((unsigned char)c);
+    for (auto &c : lo) c = (char)std::tolower((unsigned char)c);
+    chol_set_error("%s: leading dimensions ld%s = %lld, ld%s = %lld must be at least n = %d", what, li.c_str(), (long long)ldb, lo.c_str(), (long long)ldx, n);
+    return CHOLAMD_ERR_ARG;
+  }
   if (nrhs == 0) return 1;
-  if (!arena || !B || !X) { chol_set_error("%s: NULL %s", what, !arena ? "arena" : !B ? "B" : "X"); return CHOLAMD_ERR_ARG; }
+  if (!arena || !B || !X) { chol_set_error("%s: NULL %s", what, !arena ? "arena" : !B ? in : out); return CHOLAMD_ERR_ARG; }
   return 0;
 }
 // A chunk's sweeps cost the same for 1 and for 32 columns (the launches of the span chain and the factor's bytes, not the MFMA work, set their time), so a
@@ -1565,6 +1579,66 @@ extern "C" int cholamd_multiply(cholamd_device *d, const double *d_arena, const 
 { return multiply_half_api(d, d_arena, d_z, d_y, false, 0, (hipStream_t)stream, "cholamd_multiply"); }
 extern "C" int cholamd_multiply_f32(cholamd_device *d, const float *d_arena32, const double *d_z, double *d_y, void *stream)
 { return multiply_half_api(d, d_arena32, d_z, d_y, false, 0, (hipStream_t)stream, "cholamd_multiply_f32"); }
+// ---------------------------------------------------------------------------------------------
+// Block form of the products (include/cholamd.h at cholamd_multiply_half_nrhs; kernel in chol_multiply_nrhs.hip): the columns in chunks of CHOL_NRHS_W = 32.
+// A chunk is permuted into the object's first block, then ONE launch per direction over the items of the single-vector products; the last launch writes
+// Y in original dof order itself.  The full product puts the BACKWARD launch between them, into the second block.
+// ---------------------------------------------------------------------------------------------
+static int lmultiply_nrhs(const double *a, const chol_mul_item *it, int ni, const chol_mul_src *sr, int bw, const double *zp, double *y, const int *perm, int64_t ldy, int c0, int cols, hipStream_t st)
+{ return chol_launch_multiply_nrhs(a, it, ni, sr, bw, zp, y, perm, ldy, c0, cols, st); }
+static int lmultiply_nrhs(const float *a, const chol_mul_item *it, int ni, const chol_mul_src *sr, int bw, const double *zp, double *y, const int *perm, int64_t ldy, int c0, int cols, hipStream_t st)
+{ return chol32_launch_multiply_nrhs(a, it, ni, sr, bw, zp, y, perm, ldy, c0, cols, st); }
+// A block chunk costs nearly the same for 1 and for 32 columns (one pass over the factor), so a chunk of fewer columns than this goes column by column
+// through the single-vector products.  min = ceil(T_chunk(32 columns) / T_single) from the medians measured on one MI355X at gen:60:8, both in one process
+// (DESIGN.md section 13, table "Block form: measured times"): fp64 factor 1.035 / 0.603 ms FORWARD, 1.323 / 0.550 BACKWARD, 2.269 / 1.142 full; fp32
+// factor 0.905 / 0.971, 1.188 / 0.554, 2.002 / 1.516.
+template <class TL> static constexpr int multiply_nrhs_min_block(int which)
+{
+  return sizeof(TL) == sizeof(double) ? (which == CHOLAMD_HALF_FORWARD ? 2 : which == CHOLAMD_HALF_BACKWARD ? 3 : 2)
+                                      : (which == CHOLAMD_HALF_FORWARD ? 1 : which == CHOLAMD_HALF_BACKWARD ? 3 : 2);
+}
+template <class TL> static int multiply_nrhs_t(cholamd_device *d, const TL *d_arena, const double *d_Z, int64_t ldz, double *d_Y, int64_t ldy, int nrhs, int which, hipStream_t st)
+{
+  { int rc = build_multiply(d); if (rc) return rc; }
+  const int n = d->plan->n, F = CHOLAMD_HALF_FORWARD, B = CHOLAMD_HALF_BACKWARD;
+  const int min_block = d->multiply_nrhs_min > 0 ? d->multiply_nrhs_min : multiply_nrhs_min_block<TL>(which);
+  for (int c0 = 0; c0 < nrhs; c0 += CHOL_NRHS_W) {
+    const int cols = std::min(CHOL_NRHS_W, nrhs - c0);
+    if (cols < min_block) {
+      for (int j = c0; j < c0 + cols; j++) { int rc = multiply_t(d, d_arena, d_Z + (int64_t)j * ldz, d_Y + (int64_t)j * ldy, which, st); if (rc) return rc; }
+      continue;
+    }
+    const size_t blk = (size_t)(n > 0 ? n : 1) * CHOL_NRHS_W;
+    { int rc = d->mznrhs.ensure(blk); if (!rc) rc = d->mwnrhs.ensure(blk); if (rc) return rc; }
+    HIPCHK((hipError_t)chol_nrhs_launch_permute(d_Z, ldz, d->perm, d->mznrhs, nullptr, 0, n, c0, cols, 0, st)); // (first: Y may be Z)
+    const double *in = d->mznrhs;
+    int last = which;
+    if (which == CHOL_BOTH_SWEEPS) {
+      HIPCHK((hipError_t)lmultiply_nrhs(d_arena, d->mul_item[B], d->n_mul_item[B], d->mul_src[B], 1, in, d->mwnrhs, nullptr, 0, 0, CHOL_NRHS_W, st));
+      in = d->mwnrhs;
+      last = F;
+    }
+    HIPCHK((hipError_t)lmultiply_nrhs(d_arena, d->mul_item[last], d->n_mul_item[last], d->mul_src[last], last == B, in, d_Y, d->perm, ldy, c0, cols, st));
+  }
+  return 0;
+}
+template <class TL> static int multiply_nrhs_api(cholamd_device *d, const TL *d_arena, const double *d_Z, int64_t ldz, double *d_Y, int64_t ldy, int nrhs, bool half, int which, hipStream_t st, const char *what)
+{
+  if (d && half) { int rc = half_which_ok(which, what); if (rc) return rc; }
+  if (!half) which = CHOL_BOTH_SWEEPS;
+  { int rc = nrhs_check(d, d_arena, d_Z, ldz, d_Y, ldy, nrhs, what, "Z", "Y"); if (rc) return rc > 0 ? 0 : rc; }
+  { int rc = multiply_check(d, d_arena, d_Y, (int64_t)(nrhs - 1) * ldy + d->plan->n, what); if (rc) return rc; }
+  HIPCHK(hipSetDevice(d->dev));
+  return multiply_nrhs_t(d, d_arena, d_Z, ldz, d_Y, ldy, nrhs, which, st);
+}
+extern "C" int cholamd_multiply_half_nrhs(cholamd_device *d, const double *d_arena, const double *d_Z, int64_t ldz, double *d_Y, int64_t ldy, int nrhs, int which, void *stream)
+{ return multiply_nrhs_api(d, d_arena, d_Z, ldz, d_Y, ldy, nrhs, true, which, (hipStream_t)stream, "cholamd_multiply_half_nrhs"); }
+extern "C" int cholamd_multiply_half_nrhs_f32(cholamd_device *d, const float *d_arena32, const double *d_Z, int64_t ldz, double *d_Y, int64_t ldy, int nrhs, int which, void *stream)
+{ return multiply_nrhs_api(d, d_arena32, d_Z, ldz, d_Y, ldy, nrhs, true, which, (hipStream_t)stream, "cholamd_multiply_half_nrhs_f32"); }
+extern "C" int cholamd_multiply_nrhs(cholamd_device *d, const double *d_arena, const double *d_Z, int64_t ldz, double *d_Y, int64_t ldy, int nrhs, void *stream)
+{ return multiply_nrhs_api(d, d_arena, d_Z, ldz, d_Y, ldy, nrhs, false, 0, (hipStream_t)stream, "cholamd_multiply_nrhs"); }
+extern "C" int cholamd_multiply_nrhs_f32(cholamd_device *d, const float *d_arena32, const double *d_Z, int64_t ldz, double *d_Y, int64_t ldy, int nrhs, void *stream)
+{ return multiply_nrhs_api(d, d_arena32, d_Z, ldz, d_Y, ldy, nrhs, false, 0, (hipStream_t)stream, "cholamd_multiply_nrhs_f32"); }
 template <class TL> static int factor_residual_t(cholamd_device *d, const TL *d_arena, const double *d_z, double *rel_out, hipStream_t st, const char *what)
 {
   if (rel_out) *rel_out = std::nan("");

@@ -95,6 +95,13 @@ int chol_launch_schur_gather(const double *arena, const chol_schur_desc *descs, 
  * with one partial pair per workgroup of 256 rows (part: 2 * ceil(n / 256) doubles, ipart: ceil(n / 256) int64), summed in a fixed order */
 int chol_launch_multiply(const double *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, const double *z, double *y, const int *perm, hipStream_t st);
 int chol32_launch_multiply(const float *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, const double *z, double *y, const int *perm, hipStream_t st);
+/* block form (chol_multiply_nrhs.hip): the same items on a chunk of CHOL_NRHS_W columns, Zp the permuted row-major block of chol_nrhs_launch_permute.
+ * perm != NULL (the last stage of a call): Y[perm[pos] + (c0 + j) ldy] for the chunk's columns j < cols; perm == NULL (the first stage of the full product):
+ * Y is a second permuted block, all 32 columns written */
+int chol_launch_multiply_nrhs(const double *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, const double *Zp, double *Y, const int *perm,
+                              int64_t ldy, int c0, int cols, hipStream_t st);
+int chol32_launch_multiply_nrhs(const float *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, const double *Zp, double *Y, const int *perm,
+                                int64_t ldy, int c0, int cols, hipStream_t st);
 int chol_launch_multiply_resid(const int64_t *ptr, const int *col, const double *val, const double *z, const double *w, int n, double *part, int64_t *ipart, int64_t *res, hipStream_t st);
 /* diagnostic instance of the program launch (k_program<true>): 4 stamps per job, then CHOL_TRACE_X per job -- [0] follower: own tiles' wait over,
  * [1] its items, [2 + i] round of item i begun; [48 + k] POTRF job: column k published / TRSM job (first strip): column tile k on its channel;

@@ -466,6 +466,26 @@ typedef struct {
 int chol_build_multiply(const struct cholamd_plan *p, chol_mul_lists *out);
 void chol_mul_lists_free(chol_mul_lists *w);
 
+/* ---- block form of the products (cholamd_multiply_half_nrhs; chol_multiply_nrhs.hip): the same items and sources on a chunk of 32 columns.  The reduction
+ * range of a source is cut into CHUNKS of CHOL_MULN_KSTEP steps; chunk c of the s-th source of an item (s counted from the item's first) belongs to wave
+ * chol_muln_wave(s, c) of the item's CHOL_MULN_WAVES waves -- round robin, turned by the source's number so that an item of many short sources (one chunk
+ * each) spreads over all waves too.  A wave adds its chunks in list order into its own 16 x 32 partial tile, the CHOL_MULN_WAVES tiles are added in wave
+ * order.  chol_muln_elem is the operand of line `line` and step `k` of a source: the arena index, CLAMPED into the strip (line < nv, k < len: a tile is read
+ * whole, its reads stay inside the strip), and *meant = whether the entry takes part -- it is a line the item owns, a step the source has, and on or below
+ * the diagonal of a diagonal block (the `tri` rule of chol_mul_src).  An operand that is not meant is SELECTED to 0.0, never multiplied by zero.  The
+ * kernel and cholamd_plan_multiply_host_nrhs both use these two functions, so the host walk checks the kernel's index logic.
+ * Precondition of chol_muln_elem: nv >= 1 and q->len >= 1 (the clamp is to nv - 1 and len - 1).  chol_build_multiply makes no other item or source -- an
+ * item has 1 .. 16 positions, a source of no steps is not pushed -- and a chunk loop over [0, len) does not run for len = 0. */
+#define CHOL_MULN_KSTEP 32 /* reduction steps of one chunk: 8 MFMA steps of 4 whose loads are in flight together */
+#define CHOL_MULN_WAVES 4
+CHOL_HD int chol_muln_wave(int s, int c) { return (s + c) & (CHOL_MULN_WAVES - 1); }
+CHOL_HD int64_t chol_muln_elem(const chol_mul_src *q, int backward, int nv, int line, int k, int *meant)
+{
+  const int lc = line < nv ? line : nv - 1, kc = k < q->len ? k : q->len - 1;
+  *meant = line < nv && k < q->len && (backward ? k >= q->tri + line : k <= q->tri + line);
+  return q->a_off + (backward ? (int64_t)kc + (int64_t)lc * q->ld : (int64_t)lc + (int64_t)kc * q->ld);
+}
+
 #ifdef __cplusplus
 }
 #endif

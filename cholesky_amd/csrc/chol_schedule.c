@@ -2728,6 +2728,71 @@ int cholamd_plan_multiply_host(const cholamd_plan *p, const double *arena_host, 
   chol_mul_lists_free(&w);
   return 0;
 }
+/* One direction of the block product on the host: out (n x 32, permuted, row-major) = L zp or L^T zp with the block kernel's own partition of a source --
+ * chunks of CHOL_MULN_KSTEP steps dealt to CHOL_MULN_WAVES partial tiles by chol_muln_wave, every operand of a chunk read (clamped) and selected by
+ * chol_muln_elem as k_multiply_nrhs does, the partial tiles added in wave order */
+static void mul_host_block(const chol_mul_lists *w, int which, const double *arena, const double *zp, double *out)
+{
+  enum { T = CHOL_MUL_TILE, W = 32 };
+  double acc[CHOL_MULN_WAVES][T][W]; /* the waves' partial tiles (16 KB) */
+  for (int i = 0; i < w->n_item[which]; i++) {
+    const chol_mul_item *it = &w->item[which][i];
+    memset(acc, 0, sizeof acc);
+    for (int s = it->src_first; s < it->src_end; s++) {
+      const chol_mul_src *q = &w->src[which][s];
+      for (int c = 0; c * CHOL_MULN_KSTEP < q->len; c++) {
+        double (*a)[W] = acc[chol_muln_wave(s - it->src_first, c)];
+        for (int k = c * CHOL_MULN_KSTEP; k < (c + 1) * CHOL_MULN_KSTEP; k++)
+          for (int l = 0; l < T; l++) {
+            int meant;
+            const double v = arena[chol_muln_elem(q, which, it->nv, l, k, &meant)]; /* read whether meant or not: the clamp keeps it inside the strip */
+            if (!meant) continue;
+            const double *zr = zp + (int64_t)(q->z_off + k) * W;
+            for (int j = 0; j < W; j++) a[l][j] += v * zr[j];
+          }
+      }
+    }
+    for (int l = 0; l < it->nv; l++)
+      for (int j = 0; j < W; j++) {
+        double sum = acc[0][l][j];
+        for (int wv = 1; wv < CHOL_MULN_WAVES; wv++) sum += acc[wv][l][j];
+        out[(int64_t)(it->y_off + l) * W + j] = sum;
+      }
+  }
+}
+int cholamd_plan_multiply_host_nrhs(const cholamd_plan *p, const double *arena_host, int which, const double *Z, int64_t ldz, double *Y, int64_t ldy, int nrhs)
+{
+  const char *what = "cholamd_plan_multiply_host_nrhs";
+  if (!p) { chol_set_error("%s: NULL plan", what); return CHOLAMD_ERR_ARG; }
+  if (which != CHOLAMD_HALF_FORWARD && which != CHOLAMD_HALF_BACKWARD && which != -1) { chol_set_error("%s: which = %d is neither CHOLAMD_HALF_FORWARD (0), CHOLAMD_HALF_BACKWARD (1) nor -1 (the full product)", what, which); return CHOLAMD_ERR_ARG; }
+  const int n = p->n;
+  if (nrhs < 0) { chol_set_error("%s: nrhs = %d < 0", what, nrhs); return CHOLAMD_ERR_ARG; }
+  if (ldz < n || ldy < n) { chol_set_error("%s: leading dimensions ldz = %lld, ldy = %lld must be at least n = %d", what, (long long)ldz, (long long)ldy, n); return CHOLAMD_ERR_ARG; }
+  if (nrhs == 0) return 0;
+  if (!arena_host || !Z || !Y) { chol_set_error("%s: NULL %s", what, !arena_host ? "arena" : !Z ? "Z" : "Y"); return CHOLAMD_ERR_ARG; }
+  chol_mul_lists w;
+  int rc = chol_build_multiply(p, &w);
+  if (rc) return rc;
+  const size_t blk = (size_t)(n > 0 ? n : 1) * 32;
+  double *zp = malloc(blk * sizeof(double)), *wp = malloc(blk * sizeof(double));
+  if (!zp || !wp) { free(zp); free(wp); chol_mul_lists_free(&w); chol_set_error("out of memory"); return CHOLAMD_ERR_NOMEM; }
+  for (int c0 = 0; c0 < nrhs; c0 += 32) {
+    const int cols = nrhs - c0 < 32 ? nrhs - c0 : 32;
+    for (int i = 0; i < n; i++)
+      for (int j = 0; j < 32; j++) zp[(int64_t)i * 32 + j] = j < cols ? Z[p->perm[i] + (int64_t)(c0 + j) * ldz] : 0.0; /* (first: Y may be Z) */
+    const double *res = wp;
+    if (which == -1) {
+      mul_host_block(&w, CHOLAMD_HALF_BACKWARD, arena_host, zp, wp);
+      mul_host_block(&w, CHOLAMD_HALF_FORWARD, arena_host, wp, zp);
+      res = zp;
+    } else mul_host_block(&w, which, arena_host, zp, wp);
+    for (int i = 0; i < n; i++)
+      for (int j = 0; j < cols; j++) Y[p->perm[i] + (int64_t)(c0 + j) * ldy] = res[(int64_t)i * 32 + j];
+  }
+  free(zp); free(wp);
+  chol_mul_lists_free(&w);
+  return 0;
+}
 int cholamd_plan_multiply_counts(const cholamd_plan *p, int64_t out[6])
 {
   if (!p || !out) { chol_set_error("cholamd_plan_multiply_counts: NULL %s", !p ? "plan" : "out"); return CHOLAMD_ERR_ARG; }

@@ -329,6 +329,19 @@ class Device:
         fn = self.L.cholamd_multiply_f32 if self._is_f32(arena) else self.L.cholamd_multiply
         check(fn(self.h, self.ptr(arena), self.ptr(z), self.ptr(y), _stream_ptr(stream)), "cholamd_multiply")
 
+    def multiply_half_nrhs(self, arena, Z, Y, which, stream=None):
+        """Y = M Z (which = HALF_FORWARD) or Y = M^T Z (HALF_BACKWARD) for the k columns of Z (n x k, column-major, as solve_half_nrhs takes them) in one
+        pass over the factor per 32 columns: cholamd_multiply_half_nrhs / _f32 by the arena's element type; Y may be Z.  Asynchronous on `stream`."""
+        ldz, ldy, k = self._blocks(Z, Y)
+        fn = self.L.cholamd_multiply_half_nrhs_f32 if self._is_f32(arena) else self.L.cholamd_multiply_half_nrhs
+        check(fn(self.h, self.ptr(arena), self.ptr(Z), ldz, self.ptr(Y), ldy, k, int(which), _stream_ptr(stream)), "cholamd_multiply_half_nrhs")
+
+    def multiply_nrhs(self, arena, Z, Y, stream=None):
+        """Y = M M^T Z for the k columns of Z (cholamd_multiply_nrhs / _f32); Y may be Z.  Asynchronous on `stream`."""
+        ldz, ldy, k = self._blocks(Z, Y)
+        fn = self.L.cholamd_multiply_nrhs_f32 if self._is_f32(arena) else self.L.cholamd_multiply_nrhs
+        check(fn(self.h, self.ptr(arena), self.ptr(Z), ldz, self.ptr(Y), ldy, k, _stream_ptr(stream)), "cholamd_multiply_nrhs")
+
     def factor_residual(self, arena, z, stream=None):
         """||A z - M M^T z|| / ||A z|| for the probe z, A with the device object's CURRENT values (cholamd_factor_residual / _f32): does `arena` factor
         them, and how well.  Synchronises `stream`; deterministic."""

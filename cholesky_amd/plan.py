@@ -324,6 +324,23 @@ class Plan:
         check(self.L.cholamd_plan_multiply_host(self.h, arena.ctypes.data, int(which), z.ctypes.data, y.ctypes.data), "cholamd_plan_multiply_host")
         return y[:self.n]
 
+    def multiply_host_nrhs(self, arena, which, Z, ldz=None, ldy=None):
+        """Y = M Z (which = 0), M^T Z (1) or M M^T Z (-1) on the CPU for the columns of Z (n x k) with the block kernel's partition of every source
+        (cholamd_plan_multiply_host_nrhs).  ldz / ldy: leading dimensions of the column-major copies handed to the library (default n); the rows
+        n .. ldy - 1 of the result are checked to be untouched.  Returns n x k."""
+        arena = np.ascontiguousarray(arena, dtype=np.float64)
+        assert arena.size == self.arena_doubles
+        Z = np.asarray(Z, dtype=np.float64)
+        assert Z.ndim == 2 and Z.shape[0] == self.n
+        k = Z.shape[1]
+        ldz, ldy = int(ldz or self.n), int(ldy or self.n)
+        zb = np.full((max(k, 1), max(ldz, 1)), -3.0)     # row j of the buffer = column j of Z
+        zb[:k, :self.n] = Z.T
+        yb = np.full((max(k, 1), max(ldy, 1)), np.nan)
+        check(self.L.cholamd_plan_multiply_host_nrhs(self.h, arena.ctypes.data, int(which), zb.ctypes.data, ldz, yb.ctypes.data, ldy, k), "cholamd_plan_multiply_host_nrhs")
+        assert np.isnan(yb[:, self.n:]).all(), "rows n .. ldy - 1 of Y were written"
+        return yb[:k, :self.n].T.copy()
+
     def multiply_counts(self):
         """Sizes of the owner lists of the forward products (cholamd_plan_multiply_counts): a dict per direction of items, sources and the entries
         of L one product reads."""

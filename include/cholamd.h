@@ -492,7 +492,20 @@ int cholamd_factor_diag_f32(cholamd_device *d, const float *d_arena32, double *d
  * DETERMINISTIC: every element of y has ONE owner -- a 16-row chunk of a separator gathers its rows from the separator's diagonal block and from the
  * panels of its descendants in a fixed order (FORWARD), a 16-column chunk of a separator sums over its own columns of the panel (BACKWARD) -- and a fixed
  * summation order; no floating-point atomics anywhere: two calls on one arena and one input return the same bits (unlike the streamed solve).
- * There is no block (nrhs) form yet: call the single-vector entry points per column.
+ * cholamd_multiply_half_nrhs / cholamd_multiply_nrhs / _f32: the same products for the nrhs columns of Z, Y = M Z, M^T Z or M M^T Z.  Z and Y are column-major
+ * n x nrhs on the device in original dof order with leading dimensions ldz, ldy >= n (rows n .. ld - 1 of Y are never written), the argument rules those of
+ * cholamd_solve_half_nrhs: Y == Z with ldy == ldz is allowed (a chunk is permuted into the workspace before anything is written), nrhs == 0 returns 0 and
+ * touches nothing, nrhs < 0, a small ld or a NULL pointer with nrhs > 0 is CHOLAMD_ERR_ARG; and those of the products: a bad `which`, a Y (its
+ * (nrhs - 1) ldy + n doubles) that overlaps the arena, another rank of a partitioned object are CHOLAMD_ERR_ARG.  The columns go in chunks of 32: a chunk is
+ * permuted into a row-major block and ONE launch per direction walks the same owner lists with 16 x 32 v_mfma_f64_16x16x4_f64 tiles, so every stored entry of
+ * L is read once per chunk, not once per column; the last launch writes Y in original dof order itself.  The same determinism: one owner per element, the
+ * four partial tiles of a workgroup added in a fixed order, no floating-point atomics.  Within ONE column a NaN or inf of z reaches the whole 16-position
+ * tile of a diagonal block it belongs to (an entry above the diagonal is an operand 0.0 of the tile product, and 0 * inf is NaN); other columns never see
+ * it.  A chunk of fewer columns than a measured threshold goes column by column through the single-vector products (device option "multiply_nrhs_min",
+ * CHOLAMD_MULTIPLY_NRHS_MIN at cholamd_device_create: 1 = every chunk takes the block kernel, 33 = none does, <= 0 = the measured default).  The two n x 32
+ * blocks are allocated at the first chunk that takes the block kernel; later calls allocate nothing.  Asynchronous on `stream`.
+ * cholamd_plan_multiply_host_nrhs: the block product on the HOST (which = 0, 1, or -1: the full product) with the block kernel's own partition of a source
+ * (chol_plan.h at chol_muln_wave); the same argument rules.
  * `which` other than 0 / 1, a NULL pointer, or a result that overlaps the arena: CHOLAMD_ERR_ARG, nothing written.
  * cholamd_factor_residual / _f32: *rel_out (HOST) = ||A z - M M^T z||_2 / ||A z||_2 for the probe z (n doubles on the device, original dof order), A z from the
  * device object's residual operator, which holds the CURRENT values (as cholamd_residual uses them after cholamd_device_set_values): two passes over L and one
@@ -513,7 +526,12 @@ int cholamd_multiply(cholamd_device *d, const double *d_arena, const double *d_z
 int cholamd_multiply_f32(cholamd_device *d, const float *d_arena32, const double *d_z, double *d_y, void *stream);
 int cholamd_factor_residual(cholamd_device *d, const double *d_arena, const double *d_z, double *rel_out, void *stream);
 int cholamd_factor_residual_f32(cholamd_device *d, const float *d_arena32, const double *d_z, double *rel_out, void *stream);
+int cholamd_multiply_half_nrhs(cholamd_device *d, const double *d_arena, const double *d_Z, int64_t ldz, double *d_Y, int64_t ldy, int nrhs, int which, void *stream);
+int cholamd_multiply_half_nrhs_f32(cholamd_device *d, const float *d_arena32, const double *d_Z, int64_t ldz, double *d_Y, int64_t ldy, int nrhs, int which, void *stream);
+int cholamd_multiply_nrhs(cholamd_device *d, const double *d_arena, const double *d_Z, int64_t ldz, double *d_Y, int64_t ldy, int nrhs, void *stream);
+int cholamd_multiply_nrhs_f32(cholamd_device *d, const float *d_arena32, const double *d_Z, int64_t ldz, double *d_Y, int64_t ldy, int nrhs, void *stream);
 int cholamd_plan_multiply_host(const cholamd_plan *p, const double *arena_host, int which, const double *z, double *y);
+int cholamd_plan_multiply_host_nrhs(const cholamd_plan *p, const double *arena_host, int which, const double *Z, int64_t ldz, double *Y, int64_t ldy, int nrhs);
 int cholamd_plan_multiply_counts(const cholamd_plan *p, int64_t out[6]);
 /* ---- selected inversion (not in the reference; the Takahashi recursion every sparse Cholesky package offers): the entries of A^-1 on the pattern of the
  * factor -- the diagonal of A^-1 (marginal variances of a Gaussian Markov random field, leverage scores), the entries on the pattern of A (the trace term
