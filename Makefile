@@ -13,7 +13,7 @@ HIPFLAGS:= -O3 -fPIC --offload-arch=$(ARCH) -Iinclude -I$(CSRC) -Wall
 KERNFLAGS := -mllvm -pragma-unroll-threshold=100000
 
 HOST_OBJS := $(OUT)/chol_ingest.o $(OUT)/chol_symbolic.o $(OUT)/chol_schedule.o $(OUT)/chol_generate.o
-HIP_OBJS  := $(OUT)/chol_kernels.o $(OUT)/chol_kernels_f32.o $(OUT)/chol_solve_nrhs.o $(OUT)/chol_factor_query.o $(OUT)/chol_selinv.o $(OUT)/chol_schur.o $(OUT)/chol_multiply.o $(OUT)/chol_multiply_nrhs.o $(OUT)/chol_api.o
+HIP_OBJS  := $(OUT)/chol_kernels.o $(OUT)/chol_kernels_f32.o $(OUT)/chol_solve_nrhs.o $(OUT)/chol_factor_query.o $(OUT)/chol_selinv.o $(OUT)/chol_schur.o $(OUT)/chol_multiply.o $(OUT)/chol_multiply_nrhs.o $(OUT)/chol_solve_det.o $(OUT)/chol_api.o
 
 all: $(OUT)/libcholamd.so $(BIN)/cholamd_mmat oracle
 
@@ -53,6 +53,10 @@ $(OUT)/chol_multiply_nrhs.o: $(CSRC)/chol_multiply_nrhs.hip $(CSRC)/chol_plan.h 
 	@mkdir -p $(OUT)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+$(OUT)/chol_solve_det.o: $(CSRC)/chol_solve_det.hip $(CSRC)/chol_plan.h $(CSRC)/chol_kernels.h
+	@mkdir -p $(OUT)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
 $(OUT)/chol_api.o: $(CSRC)/chol_api.cpp $(CSRC)/chol_devbuf.h $(CSRC)/chol_plan.h $(CSRC)/chol_kernels.h include/cholamd.h
 	@mkdir -p $(OUT)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
@@ -85,7 +89,7 @@ $(ASAN_OUT)/%.o: $(CSRC)/%.c $(CSRC)/chol_plan.h include/cholamd.h
 $(ASAN_OUT)/chol_api.o: $(CSRC)/chol_api.cpp $(CSRC)/chol_devbuf.h $(CSRC)/chol_plan.h $(CSRC)/chol_kernels.h include/cholamd.h
 	@mkdir -p $(ASAN_OUT)
 	$(HIPCC) $(HIPFLAGS) -O1 $(SAN) -fno-sanitize=function -fno-gpu-sanitize -x hip -c $< -o $@
-$(ASAN_OUT)/libcholamd.so: $(ASAN_HOST_OBJS) $(ASAN_OUT)/chol_api.o $(OUT)/chol_kernels.o $(OUT)/chol_kernels_f32.o $(OUT)/chol_solve_nrhs.o $(OUT)/chol_factor_query.o $(OUT)/chol_selinv.o $(OUT)/chol_schur.o $(OUT)/chol_multiply.o $(OUT)/chol_multiply_nrhs.o
+$(ASAN_OUT)/libcholamd.so: $(ASAN_HOST_OBJS) $(ASAN_OUT)/chol_api.o $(OUT)/chol_kernels.o $(OUT)/chol_kernels_f32.o $(OUT)/chol_solve_nrhs.o $(OUT)/chol_factor_query.o $(OUT)/chol_selinv.o $(OUT)/chol_schur.o $(OUT)/chol_multiply.o $(OUT)/chol_multiply_nrhs.o $(OUT)/chol_solve_det.o
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) $(SAN) -fno-gpu-sanitize -o $@ $^ -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 # leak detection: ON, in a process of its own without an interpreter (tests/native/host_leak.c: plans, schedules of every level and
 # world size, the program builder and its self-check, the generator, error paths); the only suppression is the HIP runtime's own
@@ -100,6 +104,8 @@ $(ASAN_OUT)/multiply_host: tests/native/multiply_host.c $(ASAN_OUT)/libcholamd.s
 	$(HIPCC) -x c -O1 -Iinclude $(SAN) -fno-sanitize=function -o $@ $< -L$(ASAN_OUT) -lcholamd -Wl,-rpath,$(abspath $(ASAN_OUT)) -lm
 $(ASAN_OUT)/multiply_nrhs_host: tests/native/multiply_nrhs_host.c $(ASAN_OUT)/libcholamd.so
 	$(HIPCC) -x c -O1 -Iinclude $(SAN) -fno-sanitize=function -o $@ $< -L$(ASAN_OUT) -lcholamd -Wl,-rpath,$(abspath $(ASAN_OUT)) -lm
+$(ASAN_OUT)/solve_det_host: tests/native/solve_det_host.c $(ASAN_OUT)/libcholamd.so
+	$(HIPCC) -x c -O1 -Iinclude $(SAN) -fno-sanitize=function -o $@ $< -L$(ASAN_OUT) -lcholamd -Wl,-rpath,$(abspath $(ASAN_OUT)) -lm
 # the owning device buffers of the glue over a host allocator that can be told to fail (tests/native/devbuf_host.cpp): no library, no HIP runtime
 $(ASAN_OUT)/devbuf_host: tests/native/devbuf_host.cpp $(CSRC)/chol_devbuf.h
 	@mkdir -p $(ASAN_OUT)
@@ -107,7 +113,7 @@ $(ASAN_OUT)/devbuf_host: tests/native/devbuf_host.cpp $(CSRC)/chol_devbuf.h
 ASAN_FIXTURES := $(G)/lapl_9x9/lapl_3_2.mtx $(G)/lapl_9x9/lapl_3_2_ord_2.txt $(G)/lapl_9x9/lapl_3_2_clust_2.txt \
 	  $(G)/lapl_400x400/lapl_20_2.mtx $(G)/lapl_400x400/lapl_20_2_ord_5.txt $(G)/lapl_400x400/lapl_20_2_clust_5.txt \
 	  $(G)/lapl_3375x3375/lapl_15_3.mtx $(G)/lapl_3375x3375/lapl_15_3_ord_5.txt $(G)/lapl_3375x3375/lapl_15_3_clust_5.txt
-asan: $(ASAN_OUT)/libcholamd.so $(ASAN_OUT)/host_leak $(ASAN_OUT)/schur_host $(ASAN_OUT)/multiply_host $(ASAN_OUT)/multiply_nrhs_host $(ASAN_OUT)/devbuf_host oracle
+asan: $(ASAN_OUT)/libcholamd.so $(ASAN_OUT)/host_leak $(ASAN_OUT)/schur_host $(ASAN_OUT)/multiply_host $(ASAN_OUT)/multiply_nrhs_host $(ASAN_OUT)/solve_det_host $(ASAN_OUT)/devbuf_host oracle
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 LSAN_OPTIONS=suppressions=$(abspath scripts/lsan.supp):print_suppressions=0 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
 	$(ASAN_OUT)/devbuf_host
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 LSAN_OPTIONS=suppressions=$(abspath scripts/lsan.supp):print_suppressions=0 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
@@ -116,6 +122,8 @@ asan: $(ASAN_OUT)/libcholamd.so $(ASAN_OUT)/host_leak $(ASAN_OUT)/schur_host $(A
 	$(ASAN_OUT)/multiply_nrhs_host $(ASAN_FIXTURES) $(G)/lapl_25x25/lapl_5_2.mtx $(G)/lapl_25x25/lapl_5_2_ord_3.txt $(G)/lapl_25x25/lapl_5_2_clust_3.txt
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 LSAN_OPTIONS=suppressions=$(abspath scripts/lsan.supp):print_suppressions=0 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
 	$(ASAN_OUT)/schur_host $(ASAN_FIXTURES)
+	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 LSAN_OPTIONS=suppressions=$(abspath scripts/lsan.supp):print_suppressions=0 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
+	$(ASAN_OUT)/solve_det_host $(ASAN_FIXTURES) $(G)/lapl_25x25/lapl_5_2.mtx $(G)/lapl_25x25/lapl_5_2_ord_3.txt $(G)/lapl_25x25/lapl_5_2_clust_3.txt
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 LSAN_OPTIONS=suppressions=$(abspath scripts/lsan.supp):print_suppressions=0 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
 	$(ASAN_OUT)/host_leak $(G)/lapl_9x9/lapl_3_2.mtx $(G)/lapl_9x9/lapl_3_2_ord_2.txt $(G)/lapl_9x9/lapl_3_2_clust_2.txt \
 	  $(G)/lapl_400x400/lapl_20_2.mtx $(G)/lapl_400x400/lapl_20_2_ord_5.txt $(G)/lapl_400x400/lapl_20_2_clust_5.txt \

@@ -178,6 +178,9 @@ def load():
     L.cholamd_plan_multiply_host.argtypes = [vp, vp, ci, vp, vp]
     L.cholamd_plan_multiply_host_nrhs.argtypes = [vp, vp, ci, vp, i64, vp, i64, ci]
     L.cholamd_plan_multiply_counts.argtypes = [vp, vp]
+    L.cholamd_plan_solve_det_host.argtypes = [vp, vp, ci, vp, vp]
+    L.cholamd_plan_solve_det_counts.argtypes = [vp, vp]
+    L.cholamd_plan_solve_det_lists.argtypes = [vp, ci, vp, vp, vp]
     L.cholamd_factor_logdet.argtypes = [vp, vp, C.POINTER(cd), vp]
     L.cholamd_factor_logdet_f32.argtypes = [vp, vp, C.POINTER(cd), vp]
     L.cholamd_factor_diag.argtypes = [vp, vp, vp, vp]

@@ -121,6 +121,10 @@ struct cholamd_device {
   // switches, read from the environment once at cholamd_device_create (cholamd_device_set_option changes them later)
   chol_sched_opts opt;
   bool solve_reference_shape = false; // cholamd_solve with the per-call (deterministic) kernels of the BLAS-level entry points
+  // option solve_deterministic: the streamed sweeps with owner gathers in place of the atomic kernels (chol_solve_det.hip).  The step lists of both
+  // directions (chol_sdet_lists) are built and uploaded at the first such solve; the steps themselves stay on the host (they are the launch sequence)
+  bool solve_deterministic = false;
+  dev_buf<chol_mul_item> sdet_item[2]; dev_buf<chol_mul_src> sdet_src[2]; std::vector<chol_sdet_step> sdet_step[2]; bool sdet_ready = false;
   // block solve (cholamd_solve_nrhs): the permuted block of one chunk (n x CHOL_NRHS_W, row-major); refinement: the chunk's right-hand sides, residual and
   // correction (n x CHOL_NRHS_W, column-major) and the per-column partial sums of the residual kernel
   dev_buf<double> ynrhs, bnrhs, rnrhs, dxnrhs, pnrhs;
@@ -295,6 +299,7 @@ extern "C" int cholamd_device_create(const cholamd_plan *plan, int device_id, ch
   d->plan = plan; d->dev = device_id;
   chol_sched_opts_from_env(&d->opt);
   { const char *e = getenv("CHOLAMD_SOLVE_REFERENCE_SHAPE"); d->solve_reference_shape = e && *e && atoi(e) != 0; }
+  { const char *e = getenv("CHOLAMD_SOLVE_DETERMINISTIC"); d->solve_deterministic = e && *e && atoi(e) != 0; }
   { const char *e = getenv("CHOLAMD_MULTIPLY_NRHS_MIN"); d->multiply_nrhs_min = e && *e ? atoi(e) : 0; }
   int rc = build_levels(d);
   if (!rc) rc = d->ws.alloc((size_t)(plan->ws_doubles > 0 ? plan->ws_doubles : 1));
@@ -367,6 +372,7 @@ extern "C" int cholamd_device_set_option(cholamd_device *d, const char *name, in
   else if (n == "stage_chunk") d->opt.stage_chunk = value < 0 ? 0 : value;
   else if (n == "dist_top") d->opt.dist_top = value;
   else if (n == "solve_reference_shape") { d->solve_reference_shape = value != 0; rebuild = false; }
+  else if (n == "solve_deterministic") { d->solve_deterministic = value != 0; rebuild = false; }
   else if (n == "multiply_nrhs_min") { d->multiply_nrhs_min = value; rebuild = false; }
   else { chol_set_error("unknown option '%s'", n.c_str()); return CHOLAMD_ERR_ARG; }
   return rebuild ? build_levels(d) : 0;
@@ -895,10 +901,59 @@ template <class TL> static int solve_phase(cholamd_device *d, const TL *d_arena,
   if (phase == 2) HIPCHK((hipError_t)chol_launch_permute(y, d->perm, d_x, n, 1, st));
   return 0;
 }
+template <class TL> static int solve_det_t(cholamd_device *d, const TL *d_arena, const double *d_b, double *d_x, int which, hipStream_t st);
 template <class TL> static int solve_streamed(cholamd_device *d, const TL *d_arena, const double *d_b, double *d_x, hipStream_t st)
 {
+  if (d->solve_deterministic) return solve_det_t(d, d_arena, d_b, d_x, -1, st);
   { int rc = build_solve(d); if (rc) return rc; } // the whole tree: the arena holds the complete factor (single GPU, or gathered on this rank)
   for (int ph = 0; ph < 3; ph++) { int rc = solve_phase(d, d_arena, d_b, d_x, ph, st); if (rc) return rc; }
+  return 0;
+}
+// ---------------------------------------------------------------------------------------------
+// The deterministic streamed solve (option solve_deterministic; include/cholamd.h at "deterministic solve"): the permute, the 16x16 inverses of THIS arena
+// unless a refinement keeps them, then per step of chol_sdet_lists one gather launch (where the step has items) and one span launch (where it has a span), and the permute back.
+// which: one CHOLAMD_HALF_* sweep, or -1: FORWARD then BACKWARD.  Needs the solve lists of the whole tree (the spans' TRSV descriptors per level).
+// ---------------------------------------------------------------------------------------------
+static int build_solve_det(cholamd_device *d)
+{
+  if (d->sdet_ready) return 0;
+  chol_sdet_lists w;
+  int rc = chol_build_solve_det(d->plan, &w);
+  if (rc) return rc;
+  for (int q = 0; q < 2 && !rc; q++) { // (an upload replaces what a call that failed half-way left)
+    rc = d->sdet_item[q].upload(w.item[q], (size_t)w.n_item[q]);
+    if (!rc) rc = d->sdet_src[q].upload(w.src[q], (size_t)w.n_src[q]);
+    d->sdet_step[q].assign(w.step[q], w.step[q] + w.n_step[q]);
+  }
+  chol_sdet_lists_free(&w);
+  if (rc) return rc;
+  d->sdet_ready = true;
+  return 0;
+}
+static int lsdet_gather(const double *a, const chol_mul_item *it, int ni, const chol_mul_src *sr, int bw, double *y, hipStream_t st) { return chol_launch_solve_det_gather(a, it, ni, sr, bw, y, st); }
+static int lsdet_gather(const float *a, const chol_mul_item *it, int ni, const chol_mul_src *sr, int bw, double *y, hipStream_t st) { return chol32_launch_solve_det_gather(a, it, ni, sr, bw, y, st); }
+static int lsdet_span(const double *a, const chol_trsv_desc *t, int n, const double *W, double *y, int col0, int bw, hipStream_t st) { return chol_launch_solve_span(a, t, n, W, y, col0, bw, st); }
+static int lsdet_span(const float *a, const chol_trsv_desc *t, int n, const double *W, double *y, int col0, int bw, hipStream_t st) { return chol32_launch_solve_span(a, t, n, W, y, col0, bw, st); }
+template <class TL> static int solve_det_t(cholamd_device *d, const TL *d_arena, const double *d_b, double *d_x, int which, hipStream_t st)
+{
+  { int rc = build_solve(d); if (!rc) rc = build_solve_det(d); if (rc) return rc; }
+  const int L = d->plan->levels, n = d->plan->n;
+  double *y = d->ytmp;
+  HIPCHK((hipError_t)chol_launch_permute(d_b, d->perm, y, n, 0, st));
+  for (int lvl = 0; lvl < L && !d->keep_inverses; lvl++) {
+    const solve_dev &s = d->sv[lvl];
+    HIPCHK((hipError_t)lsolve_dinv(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, st));
+  }
+  for (int q = 0; q < 2; q++) {
+    if (which >= 0 && which != q) continue;
+    const chol_mul_item *items = d->sdet_item[q];
+    for (const chol_sdet_step &t : d->sdet_step[q]) {
+      const solve_dev &s = d->sv[t.level];
+      if (t.item_end > t.item_first) HIPCHK((hipError_t)lsdet_gather(d_arena, items + t.item_first, t.item_end - t.item_first, d->sdet_src[q], q, y, st));
+      if (t.col0 >= 0) HIPCHK((hipError_t)lsdet_span(d_arena, s.trsv, s.n_trsv, d->ws_solve, y, t.col0, q, st));
+    }
+  }
+  HIPCHK((hipError_t)chol_launch_permute(y, d->perm, d_x, n, 1, st));
   return 0;
 }
 extern "C" int cholamd_solve(cholamd_device *d, const double *d_arena, const double *d_b, double *d_x, void *stream)
@@ -1220,6 +1275,7 @@ template <class TL> static constexpr int half_nrhs_min_block() { return sizeof(T
 // launches of that sweep of solve_phase between the two permutes, the diagonal inverses of THIS arena first unless the caller keeps them.
 template <class TL> static int solve_half_streamed(cholamd_device *d, const TL *d_arena, const double *d_b, double *d_x, int which, hipStream_t st)
 {
+  if (d->solve_deterministic) return solve_det_t(d, d_arena, d_b, d_x, which, st);
   { int rc = build_solve(d); if (rc) return rc; }
   const int L = d->plan->levels, n = d->plan->n;
   double *y = d->ytmp;
@@ -1295,7 +1351,7 @@ extern "C" int cholamd_solve_nrhs(cholamd_device *d, const double *d_arena, cons
 {
   { int rc = nrhs_check(d, d_arena, d_B, ldb, d_X, ldx, nrhs, "cholamd_solve_nrhs"); if (rc) return rc > 0 ? 0 : rc; }
   HIPCHK(hipSetDevice(d->dev));
-  if (d->solve_reference_shape) { // the deterministic per-call kernels, column by column
+  if (d->solve_reference_shape || d->solve_deterministic) { // the deterministic kernels of either option, column by column
     for (int j = 0; j < nrhs; j++) { int rc = cholamd_solve(d, d_arena, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, stream); if (rc) return rc; }
     return 0;
   }
@@ -1305,7 +1361,7 @@ extern "C" int cholamd_solve_nrhs_f32(cholamd_device *d, const float *d_arena32,
 {
   { int rc = nrhs_check(d, d_arena32, d_B, ldb, d_X, ldx, nrhs, "cholamd_solve_nrhs_f32"); if (rc) return rc > 0 ? 0 : rc; }
   HIPCHK(hipSetDevice(d->dev));
-  if (d->solve_reference_shape) {
+  if (d->solve_reference_shape || d->solve_deterministic) {
     for (int j = 0; j < nrhs; j++) { int rc = cholamd_solve_f32(d, d_arena32, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, stream); if (rc) return rc; }
     return 0;
   }
@@ -1370,6 +1426,10 @@ extern "C" int cholamd_solve_half_nrhs(cholamd_device *d, const double *d_arena,
     for (int j = 0; j < nrhs; j++) { int rc = solve_half_reference(d, d_arena, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, which, (hipStream_t)stream); if (rc) return rc; }
     return 0;
   }
+  if (d->solve_deterministic) { // no deterministic block kernel: column by column
+    for (int j = 0; j < nrhs; j++) { int rc = solve_det_t(d, d_arena, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, which, (hipStream_t)stream); if (rc) return rc; }
+    return 0;
+  }
   return solve_nrhs_t(d, d_arena, d_B, ldb, d_X, ldx, nrhs, (hipStream_t)stream, which);
 }
 extern "C" int cholamd_solve_half_nrhs_f32(cholamd_device *d, const float *d_arena32, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int nrhs, int which, void *stream)
@@ -1377,6 +1437,10 @@ extern "C" int cholamd_solve_half_nrhs_f32(cholamd_device *d, const float *d_are
   if (d) { int rc = half_which_ok(which, "cholamd_solve_half_nrhs_f32"); if (rc) return rc; }
   { int rc = nrhs_check(d, d_arena32, d_B, ldb, d_X, ldx, nrhs, "cholamd_solve_half_nrhs_f32"); if (rc) return rc > 0 ? 0 : rc; }
   HIPCHK(hipSetDevice(d->dev));
+  if (d->solve_deterministic) {
+    for (int j = 0; j < nrhs; j++) { int rc = solve_det_t(d, d_arena32, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, which, (hipStream_t)stream); if (rc) return rc; }
+    return 0;
+  }
   return solve_nrhs_t(d, d_arena32, d_B, ldb, d_X, ldx, nrhs, (hipStream_t)stream, which);
 }
 static int lfactor_diag(const double *a, const chol_trsv_desc *t, const int *pre, int nd, int n, const int *perm, double *dg, hipStream_t st) { return chol_launch_factor_diag(a, t, pre, nd, n, perm, dg, st); }
@@ -1811,10 +1875,10 @@ static int residual_nrhs(cholamd_device *d, const double *d_B, int64_t ldb, cons
   }
   return 0;
 }
-// M^-1 B for `cols` columns with M = L32 L32^T: the block solve, or column by column under option solve_reference_shape
+// M^-1 B for `cols` columns with M = L32 L32^T: the block solve, or column by column under option solve_reference_shape or solve_deterministic
 static int refine_solve(cholamd_device *d, const float *d_arena32, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int cols, hipStream_t st)
 {
-  if (!d->solve_reference_shape) return solve_nrhs_t(d, d_arena32, d_B, ldb, d_X, ldx, cols, st);
+  if (!d->solve_reference_shape && !d->solve_deterministic) return solve_nrhs_t(d, d_arena32, d_B, ldb, d_X, ldx, cols, st);
   for (int j = 0; j < cols; j++) { int rc = solve_streamed(d, d_arena32, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, st); if (rc) return rc; }
   return 0;
 }

@@ -95,6 +95,14 @@ int chol_launch_schur_gather(const double *arena, const chol_schur_desc *descs, 
  * with one partial pair per workgroup of 256 rows (part: 2 * ceil(n / 256) doubles, ipart: ceil(n / 256) int64), summed in a fixed order */
 int chol_launch_multiply(const double *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, const double *z, double *y, const int *perm, hipStream_t st);
 int chol32_launch_multiply(const float *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, const double *z, double *y, const int *perm, hipStream_t st);
+/* deterministic streamed solve (chol_solve_det.hip; chol_plan.h at chol_sdet_lists): the gather launch of one step, y[item] -= sum over the item's sources,
+ * `items` = the step's first item, n_items of them, in permuted coordinates and in place (no source of a step is owned by an item of the step); one owner per
+ * position, a fixed order, no atomics.  solve_span (chol_kernels.hip): the diagonal solve of the columns [col0, col0 + 256) of the n separators `descs`
+ * (those with fewer columns do nothing) with the 16x16 inverses W of chol_launch_solve_dinv, plain stores */
+int chol_launch_solve_det_gather(const double *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, double *y, hipStream_t st);
+int chol32_launch_solve_det_gather(const float *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, double *y, hipStream_t st);
+int chol_launch_solve_span(const double *base, const chol_trsv_desc *descs, int n, const double *W, double *y, int col0, int backward, hipStream_t st);
+int chol32_launch_solve_span(const float *base, const chol_trsv_desc *descs, int n, const double *W, double *y, int col0, int backward, hipStream_t st);
 /* block form (chol_multiply_nrhs.hip): the same items on a chunk of CHOL_NRHS_W columns, Zp the permuted row-major block of chol_nrhs_launch_permute.
  * perm != NULL (the last stage of a call): Y[perm[pos] + (c0 + j) ldy] for the chunk's columns j < cols; perm == NULL (the first stage of the full product):
  * Y is a second permuted block, all 32 columns written */

@@ -2485,7 +2485,8 @@ __global__ __launch_bounds__(256) void k_bwd(const double *__restrict__ base, co
 //     the triangular solves run in 64-column block steps with the in-block work done out of LDS
 //   * off-diagonal blocks: one workgroup per row chunk of an (ancestor, separator) block, source-centric,
 //     accumulating into y with hardware fp64 atomics (the only non-deterministic summation order in the library:
-//     the solution agrees from run to run to rounding, not bit for bit)
+//     the solution agrees from run to run to rounding, not bit for bit; option solve_deterministic replaces these kernels by the
+//     owner gathers of chol_solve_det.hip and keeps only the span solvers of this file)
 // ------------------------------------------------------------------------------------------------
 #define SNB 64
 // The driver-level solve kernels are templates over the factor's element type TL (double, or float for the fp32 factor of
@@ -3602,6 +3603,19 @@ int chol_launch_solve_offdiag(const double *base, const chol_gemv_desc *blocks, 
 int chol32_launch_solve_dinv(const float *base, const chol_trsv_desc *descs, int n, int max_n, double *W, hipStream_t st) { return launch_solve_dinv_t(base, descs, n, max_n, W, st); }
 int chol32_launch_solve_trsv(const float *base, const chol_trsv_desc *descs, int n, int max_n, int max_under, const double *W, double *y, int backward, int *flags, int *gen, const double *W256, double *xt, hipStream_t st) { return launch_solve_trsv_t(base, descs, n, max_n, max_under, W, y, backward, flags, gen, W256, xt, st); }
 int chol32_launch_solve_offdiag(const float *base, const chol_gemv_desc *blocks, const int *items, int n_items, double *y, int backward, hipStream_t st) { return launch_solve_offdiag_t(base, blocks, items, n_items, y, backward, st); }
+// one 256-column diagonal span of every separator of a level on its own (plain stores; the deterministic solve puts its gathers between them)
+int chol_launch_solve_span(const double *base, const chol_trsv_desc *descs, int n, const double *W, double *y, int col0, int backward, hipStream_t st)
+{
+  if (n <= 0) return 0;
+  if (backward) launch_span<true>(base, descs, n, W, y, col0, st); else launch_span<false>(base, descs, n, W, y, col0, st);
+  return (int)hipGetLastError();
+}
+int chol32_launch_solve_span(const float *base, const chol_trsv_desc *descs, int n, const double *W, double *y, int col0, int backward, hipStream_t st)
+{
+  if (n <= 0) return 0;
+  if (backward) launch_span<true>(base, descs, n, W, y, col0, st); else launch_span<false>(base, descs, n, W, y, col0, st);
+  return (int)hipGetLastError();
+}
 int chol_launch_trsv_fwd(const double *base, const chol_trsv_desc *descs, int n, double *y, hipStream_t st)
 {
   if (n <= 0) return 0;

@@ -466,6 +466,31 @@ typedef struct {
 int chol_build_multiply(const struct cholamd_plan *p, chol_mul_lists *out);
 void chol_mul_lists_free(chol_mul_lists *w);
 
+/* ---- deterministic streamed solve (option solve_deterministic; chol_solve_det.hip): the sweeps of cholamd_solve with every off-diagonal contribution GATHERED by
+ * the owner of its target instead of scattered with atomics.  A STEP is one gather launch over its items [item_first, item_end), y[item] -= sum over the
+ * item's sources in list order, followed -- where col0 >= 0 -- by the diagonal solve of the 256-column span [col0, col0 + CHOL_SDET_SPAN) of every
+ * separator of the step's tree level wider than col0 (the span solvers of the streamed solve, plain stores).  Every level has one LEAD step (col0 = -1: no
+ * span) for what reaches it from outside its own diagonal blocks, then one step per span for what reaches the span from inside the block.  FORWARD runs the
+ * levels leaves first and span 0 first, BACKWARD root first and the last span first.  Items and sources are those of chol_mul_lists (one workgroup per
+ * item, 16 lines):
+ *   FORWARD   lead: a 16-row chunk's rows in the panel of every descendant that stores them (the FORWARD multiply sources without the diagonal block);
+ *             span: a 16-row chunk's rows in the separator's own diagonal block over the columns [first column the leaf band allows, col0)
+ *   BACKWARD  lead: the stored row runs of a 16-column chunk's columns into the ancestors (the BACKWARD multiply sources without the diagonal block);
+ *             span: the rows [col0 + CHOL_SDET_SPAN, end the leaf band allows) of a 16-column chunk's columns in the own diagonal block
+ * Every source of a step was solved by an earlier step and no item of the step owns it; a chunk without sources has no item.  Within a step every permuted
+ * position has at most one owner, and over a sweep every position is solved exactly once (chol_build_solve_det checks both).  Ordering between steps comes
+ * from kernel boundaries on the stream alone.  The lead step runs the long descendant lists of ALL chunks of a wide separator side by side; attached to
+ * the spans they would run sixteen at a time, one span after the other. */
+#define CHOL_SDET_SPAN 256
+typedef struct { int level, col0, item_first, item_end; } chol_sdet_step;
+typedef struct {
+  int n_step[2]; chol_sdet_step *step[2]; /* [CHOLAMD_HALF_FORWARD], [CHOLAMD_HALF_BACKWARD] */
+  int n_item[2]; chol_mul_item *item[2];
+  int n_src[2]; chol_mul_src *src[2];
+} chol_sdet_lists;
+int chol_build_solve_det(const struct cholamd_plan *p, chol_sdet_lists *out);
+void chol_sdet_lists_free(chol_sdet_lists *w);
+
 /* ---- block form of the products (cholamd_multiply_half_nrhs; chol_multiply_nrhs.hip): the same items and sources on a chunk of 32 columns.  The reduction
  * range of a source is cut into CHUNKS of CHOL_MULN_KSTEP steps; chunk c of the s-th source of an item (s counted from the item's first) belongs to wave
  * chol_muln_wave(s, c) of the item's CHOL_MULN_WAVES waves -- round robin, turned by the source's number so that an item of many short sources (one chunk

@@ -2814,3 +2814,251 @@ int cholamd_plan_multiply_counts(const cholamd_plan *p, int64_t out[6])
   chol_mul_lists_free(&w);
   return 0;
 }
+
+/* ---------------------------------------------------------------------------------------- */
+/* deterministic streamed solve (option solve_deterministic): the step lists of both sweeps   */
+/* (chol_plan.h at chol_sdet_lists) and their host restatement                                */
+/* ---------------------------------------------------------------------------------------- */
+void chol_sdet_lists_free(chol_sdet_lists *w)
+{
+  for (int q = 0; q < 2; q++) { free(w->step[q]); free(w->item[q]); free(w->src[q]); }
+  memset(w, 0, sizeof *w);
+}
+/* The lists are derived from the multiply lists, so leaf bands, leaf envelopes (c_lo) and row compaction are honoured exactly as chol_build_multiply honours
+ * them: the first source of a multiply item is its diagonal-block source, the others are what the solve gathers from outside the block; the part of the
+ * diagonal-block source outside the item's own span becomes the in-block source. */
+int chol_build_solve_det(const plan_t *p, chol_sdet_lists *out)
+{
+  memset(out, 0, sizeof *out);
+  const int ns = p->nsep, L = p->levels, T = CHOL_MUL_TILE, SP = CHOL_SDET_SPAN;
+  chol_mul_lists m;
+  int rc = chol_build_multiply(p, &m);
+  if (rc) return rc;
+  int *nspan = calloc((size_t)L + 1, sizeof(int)), *first_item = calloc((size_t)L + 2, sizeof(int)); /* per level: spans of the widest separator, first multiply item */
+  int *stamp = malloc((size_t)(p->n > 0 ? p->n : 1) * sizeof(int));
+  unsigned char *solved = calloc((size_t)(p->n > 0 ? p->n : 1), 1);
+  mul_build b[2] = { { 0 }, { 0 } };
+  int total = 0;
+  rc = CHOLAMD_ERR_NOMEM;
+  if (!nspan || !first_item || !stamp || !solved) { chol_set_error("out of memory"); goto done; }
+  { /* the items of both multiply lists come separator by separator in heap order, one per 16 positions */
+    int it = 0;
+    for (int h = 1; h <= ns; h++) {
+      int lvl = 0;
+      while ((h >> (lvl + 1)) > 0) lvl++;
+      const int n = p->sep_size[p->tree[h]];
+      if (lvl >= L) { chol_set_error("internal: heap index %d lies below the %d levels of the tree", h, L); rc = CHOLAMD_ERR_INVARIANT; goto done; }
+      if ((n + SP - 1) / SP > nspan[lvl]) nspan[lvl] = (n + SP - 1) / SP;
+      if (h == (1 << lvl)) first_item[lvl] = it;
+      for (int r0 = 0; r0 < n; r0 += T, it++)
+        if (it >= m.n_item[0] || it >= m.n_item[1] || m.item[0][it].y_off != p->sep_off[p->tree[h]] + r0 || m.item[1][it].y_off != m.item[0][it].y_off) {
+          chol_set_error("internal: multiply item %d is not chunk %d of separator %d", it, r0 / T, p->tree[h]); rc = CHOLAMD_ERR_INVARIANT; goto done;
+        }
+    }
+    if (it != m.n_item[0] || it != m.n_item[1]) { chol_set_error("internal: %d chunks, %d / %d multiply items", it, m.n_item[0], m.n_item[1]); rc = CHOLAMD_ERR_INVARIANT; goto done; }
+  }
+  for (int lvl = 0; lvl < L; lvl++) if (nspan[lvl] > 0) total += 1 + nspan[lvl];
+  for (int q = 0; q < 2; q++) {
+    out->step[q] = calloc((size_t)(total > 0 ? total : 1), sizeof(chol_sdet_step));
+    if (!out->step[q]) { chol_set_error("out of memory"); goto done; }
+    int t = 0;
+    for (int li = 0; li < L; li++) { /* FORWARD: leaves first, span 0 first; BACKWARD: root first, the last span first; the level's outside gather in front */
+      const int lvl = q == 0 ? L - 1 - li : li;
+      if (nspan[lvl] == 0) continue;
+      const chol_sdet_step lead = { lvl, -1, 0, 0 };
+      out->step[q][t++] = lead;
+      for (int ki = 0; ki < nspan[lvl]; ki++) {
+        const chol_sdet_step st = { lvl, (q == 0 ? ki : nspan[lvl] - 1 - ki) * SP, 0, 0 };
+        out->step[q][t++] = st;
+      }
+    }
+    out->n_step[q] = t;
+  }
+  for (int q = 0; q < 2; q++)
+    for (int t = 0; t < total; t++) {
+      chol_sdet_step *st = &out->step[q][t];
+      st->item_first = b[q].n_item;
+      int it = first_item[st->level];
+      for (int h = 1 << st->level; h < (1 << (st->level + 1)) && h <= ns; h++) {
+        const int s = p->tree[h], n = p->sep_size[s], x0 = p->sep_off[s], nch = (n + T - 1) / T;
+        const int c_lo = st->col0 < 0 ? 0 : st->col0 / T, c_hi = st->col0 < 0 ? nch : (st->col0 + SP) / T;
+        for (int c = c_lo; c < nch && c < c_hi; c++) {
+          const chol_mul_item *mi = &m.item[q][it + c];
+          if (st->col0 < 0) { /* everything but the diagonal-block source (the first one of a multiply item) */
+            if (mi->src_end - mi->src_first <= 1) continue; /* nothing to gather: no item */
+            mul_open_item(&b[q], mi->y_off, mi->nv);
+            for (int e = mi->src_first + 1; e < mi->src_end; e++) mul_push_src(&b[q], m.src[q][e].a_off, m.src[q][e].ld, m.src[q][e].len, m.src[q][e].z_off, m.src[q][e].tri);
+            mul_close_item(&b[q]);
+            continue;
+          }
+          const chol_mul_src *q0 = &m.src[q][mi->src_first]; /* the diagonal-block source */
+          const int r0 = c * T;
+          int in_len, in_z; int64_t in_off;
+          if (q == 0) { /* columns [first column of the band, col0) of the chunk's rows */
+            in_len = st->col0 - (q0->z_off - x0); in_z = q0->z_off; in_off = q0->a_off;
+          } else {      /* rows [col0 + span, end of the band) of the chunk's columns */
+            in_len = r0 + q0->len - (st->col0 + SP); in_z = x0 + st->col0 + SP; in_off = q0->a_off + (st->col0 + SP - r0);
+          }
+          if (in_len <= 0) continue;
+          mul_open_item(&b[q], mi->y_off, mi->nv);
+          mul_push_src(&b[q], in_off, q0->ld, in_len, in_z, q == 0 ? MUL_TRI_OFF : -T);
+          mul_close_item(&b[q]);
+        }
+        it += nch;
+      }
+      st->item_end = b[q].n_item;
+    }
+  for (int q = 0; q < 2; q++) {
+    out->item[q] = b[q].item; out->n_item[q] = b[q].n_item; out->src[q] = b[q].src; out->n_src[q] = b[q].n_src;
+    b[q].item = NULL; b[q].src = NULL;
+  }
+  if (b[0].fail || b[1].fail) { chol_set_error("solve lists: out of memory or more than 2^30 sources"); goto done; }
+  /* the invariants, by walking the sweeps: a source is inside the arena and solved before its step, an item owns positions of its step's level (of its
+   * step's spans) that are not solved yet and that nobody else of the step owns, the spans solve every position exactly once */
+  rc = CHOLAMD_ERR_INVARIANT;
+  for (int q = 0; q < 2; q++) {
+    memset(solved, 0, (size_t)(p->n > 0 ? p->n : 1));
+    for (int i = 0; i < p->n; i++) stamp[i] = -1;
+    for (int t = 0; t < total; t++) {
+      const chol_sdet_step *st = &out->step[q][t];
+      for (int i = st->item_first; i < st->item_end; i++) {
+        const chol_mul_item *it = &out->item[q][i];
+        if (it->nv < 1 || it->nv > T || it->y_off < 0 || it->y_off + it->nv > p->n || it->src_end <= it->src_first) { chol_set_error("internal: solve item %d of direction %d is malformed", i, q); goto done; }
+        for (int l = 0; l < it->nv; l++) {
+          const int pos = it->y_off + l, hs = p->heap_of[p->sep_of_pos[pos]];
+          if (solved[pos] || stamp[pos] == t || hs < (1 << st->level) || hs >= (1 << (st->level + 1))) {
+            chol_set_error("internal: solve item %d of direction %d owns position %d, which is solved, owned twice in the step or outside the step's level", i, q, pos); goto done;
+          }
+          stamp[pos] = t;
+        }
+        for (int k = it->src_first; k < it->src_end; k++) {
+          const chol_mul_src *s = &out->src[q][k];
+          const int64_t last = q == 0 ? s->a_off + (it->nv - 1) + (int64_t)(s->len - 1) * s->ld : s->a_off + (s->len - 1) + (int64_t)(it->nv - 1) * s->ld;
+          if (s->len < 1 || s->a_off < 0 || s->z_off < 0 || s->z_off + s->len > p->n || last >= p->arena) { chol_set_error("internal: solve source %d of direction %d leaves the arena or the vector", k, q); goto done; }
+          for (int e = 0; e < s->len; e++)
+            if (!solved[s->z_off + e]) { chol_set_error("internal: solve source %d of direction %d reads position %d before it is solved", k, q, s->z_off + e); goto done; }
+        }
+      }
+      if (st->col0 < 0) continue;
+      for (int h = 1 << st->level; h < (1 << (st->level + 1)) && h <= ns; h++) {
+        const int s = p->tree[h], n = p->sep_size[s];
+        for (int i = st->col0; i < n && i < st->col0 + SP; i++) {
+          if (solved[p->sep_off[s] + i]) { chol_set_error("internal: position %d is solved twice", p->sep_off[s] + i); goto done; }
+          solved[p->sep_off[s] + i] = 1;
+        }
+      }
+      for (int i = st->item_first; i < st->item_end; i++)
+        for (int l = 0; l < out->item[q][i].nv; l++)
+          if (!solved[out->item[q][i].y_off + l]) { chol_set_error("internal: solve item %d of direction %d lies outside its step's spans", i, q); goto done; }
+    }
+    for (int i = 0; i < p->n; i++) if (!solved[i]) { chol_set_error("internal: position %d is never solved", i); goto done; }
+  }
+  rc = 0;
+done:
+  free(nspan); free(first_item); free(stamp); free(solved);
+  for (int q = 0; q < 2; q++) { free(b[q].item); free(b[q].src); }
+  chol_mul_lists_free(&m);
+  if (rc) chol_sdet_lists_free(out);
+  return rc;
+}
+/* one sweep over a host arena in permuted coordinates: per step the gathers, item by item and source by source in list order, then the span of every
+ * separator of the level by substitution inside the span's own triangle (rows / columns of the span only; the lower triangle only) */
+static void sdet_host_sweep(const plan_t *p, const chol_sdet_lists *w, int which, const double *arena, double *y)
+{
+  for (int t = 0; t < w->n_step[which]; t++) {
+    const chol_sdet_step *st = &w->step[which][t];
+    for (int i = st->item_first; i < st->item_end; i++) {
+      const chol_mul_item *it = &w->item[which][i];
+      double acc[CHOL_MUL_TILE] = { 0 };
+      for (int k = it->src_first; k < it->src_end; k++) {
+        const chol_mul_src *q = &w->src[which][k];
+        for (int e = 0; e < q->len; e++) {
+          const double ze = y[q->z_off + e];
+          for (int l = 0; l < it->nv; l++)
+            acc[l] += arena[which == CHOLAMD_HALF_FORWARD ? q->a_off + l + (int64_t)e * q->ld : q->a_off + e + (int64_t)l * q->ld] * ze;
+        }
+      }
+      for (int l = 0; l < it->nv; l++) y[it->y_off + l] -= acc[l];
+    }
+    if (st->col0 < 0) continue; /* the level's outside gather: no span */
+    for (int h = 1 << st->level; h < (1 << (st->level + 1)) && h <= p->nsep; h++) {
+      const int s = p->tree[h], n = p->sep_size[s], ld = p->panel_ld[s];
+      if (n <= st->col0) continue;
+      const int n1 = n < st->col0 + CHOL_SDET_SPAN ? n : st->col0 + CHOL_SDET_SPAN;
+      const double *Lm = arena + p->panel_off[s];
+      double *x = y + p->sep_off[s];
+      if (which == CHOLAMD_HALF_FORWARD)
+        for (int i = st->col0; i < n1; i++) {
+          double v = x[i];
+          for (int j = st->col0; j < i; j++) v -= Lm[i + (int64_t)j * ld] * x[j];
+          x[i] = v / Lm[i + (int64_t)i * ld];
+        }
+      else
+        for (int i = n1 - 1; i >= st->col0; i--) {
+          double v = x[i];
+          for (int j = i + 1; j < n1; j++) v -= Lm[j + (int64_t)i * ld] * x[j];
+          x[i] = v / Lm[i + (int64_t)i * ld];
+        }
+    }
+  }
+}
+int cholamd_plan_solve_det_host(const cholamd_plan *p, const double *arena_host, int which, const double *b, double *x)
+{
+  if (!p || !arena_host || !b || !x) { chol_set_error("cholamd_plan_solve_det_host: NULL %s", !p ? "plan" : !arena_host ? "arena" : !b ? "b" : "x"); return CHOLAMD_ERR_ARG; }
+  if (which != CHOLAMD_HALF_FORWARD && which != CHOLAMD_HALF_BACKWARD && which != -1) { chol_set_error("cholamd_plan_solve_det_host: which = %d is neither CHOLAMD_HALF_FORWARD (0), CHOLAMD_HALF_BACKWARD (1) nor -1 (the whole solve)", which); return CHOLAMD_ERR_ARG; }
+  chol_sdet_lists w;
+  int rc = chol_build_solve_det(p, &w);
+  if (rc) return rc;
+  const int n = p->n;
+  double *y = malloc((size_t)(n > 0 ? n : 1) * sizeof(double));
+  if (!y) { chol_sdet_lists_free(&w); chol_set_error("out of memory"); return CHOLAMD_ERR_NOMEM; }
+  for (int i = 0; i < n; i++) y[i] = b[p->perm[i]]; /* (first: x may be b) */
+  if (which != CHOLAMD_HALF_BACKWARD) sdet_host_sweep(p, &w, CHOLAMD_HALF_FORWARD, arena_host, y);
+  if (which != CHOLAMD_HALF_FORWARD) sdet_host_sweep(p, &w, CHOLAMD_HALF_BACKWARD, arena_host, y);
+  for (int i = 0; i < n; i++) x[p->perm[i]] = y[i];
+  free(y);
+  chol_sdet_lists_free(&w);
+  return 0;
+}
+int cholamd_plan_solve_det_counts(const cholamd_plan *p, int64_t out[8])
+{
+  if (!p || !out) { chol_set_error("cholamd_plan_solve_det_counts: NULL %s", !p ? "plan" : "out"); return CHOLAMD_ERR_ARG; }
+  chol_sdet_lists w;
+  int rc = chol_build_solve_det(p, &w);
+  if (rc) return rc;
+  for (int d = 0; d < 2; d++) {
+    int64_t entries = 0;
+    for (int i = 0; i < w.n_item[d]; i++)
+      for (int k = w.item[d][i].src_first; k < w.item[d][i].src_end; k++) entries += (int64_t)w.item[d][i].nv * w.src[d][k].len;
+    for (int s = 1; s <= p->nsep; s++) /* the spans' own lower triangles */
+      for (int c0 = 0; c0 < p->sep_size[s]; c0 += CHOL_SDET_SPAN) {
+        const int64_t m = p->sep_size[s] - c0 < CHOL_SDET_SPAN ? p->sep_size[s] - c0 : CHOL_SDET_SPAN;
+        entries += m * (m + 1) / 2;
+      }
+    out[4 * d] = w.n_step[d]; out[4 * d + 1] = w.n_item[d]; out[4 * d + 2] = w.n_src[d]; out[4 * d + 3] = entries;
+  }
+  chol_sdet_lists_free(&w);
+  return 0;
+}
+int cholamd_plan_solve_det_lists(const cholamd_plan *p, int which, int64_t *steps, int64_t *items, int64_t *srcs)
+{
+  if (!p || !steps || !items || !srcs) { chol_set_error("cholamd_plan_solve_det_lists: NULL %s", !p ? "plan" : "output"); return CHOLAMD_ERR_ARG; }
+  if (which != CHOLAMD_HALF_FORWARD && which != CHOLAMD_HALF_BACKWARD) { chol_set_error("cholamd_plan_solve_det_lists: which = %d is neither CHOLAMD_HALF_FORWARD (0) nor CHOLAMD_HALF_BACKWARD (1)", which); return CHOLAMD_ERR_ARG; }
+  chol_sdet_lists w;
+  int rc = chol_build_solve_det(p, &w);
+  if (rc) return rc;
+  for (int t = 0; t < w.n_step[which]; t++) {
+    const chol_sdet_step *s = &w.step[which][t];
+    steps[4 * t] = s->level; steps[4 * t + 1] = s->col0; steps[4 * t + 2] = s->item_first; steps[4 * t + 3] = s->item_end;
+  }
+  for (int i = 0; i < w.n_item[which]; i++) {
+    const chol_mul_item *it = &w.item[which][i];
+    items[4 * i] = it->y_off; items[4 * i + 1] = it->nv; items[4 * i + 2] = it->src_first; items[4 * i + 3] = it->src_end;
+  }
+  for (int k = 0; k < w.n_src[which]; k++) {
+    const chol_mul_src *q = &w.src[which][k];
+    srcs[5 * k] = q->a_off; srcs[5 * k + 1] = q->ld; srcs[5 * k + 2] = q->len; srcs[5 * k + 3] = q->z_off; srcs[5 * k + 4] = q->tri;
+  }
+  chol_sdet_lists_free(&w);
+  return 0;
+}

@@ -39,7 +39,7 @@ int main(int argc, char **argv)
 {
   const char *matrix_file = "", *separator_file = "", *clusters_file = "", *b_file = "", *solution_file = "", *factor_file = "",
              *permuted_file = "", *debug_path = "", *invdiag_file = "", *schur_file = "";
-  int debug = 0, iterations = 1, gpu = 0, full = 0, gpus = 1, want_logdet = 0, want_check = 0, schur_k = 0;
+  int debug = 0, iterations = 1, gpu = 0, full = 0, gpus = 1, want_logdet = 0, want_check = 0, schur_k = 0, det_solve = 0;
   const char *precision = "fp64";
   for (int i = 0; i < argc; i++) {
     const char *next = i + 1 < argc ? argv[i + 1] : "";
@@ -59,6 +59,7 @@ int main(int argc, char **argv)
     else if (!strcmp(argv[i], "--full-precision")) full = 1;
     else if (!strcmp(argv[i], "--logdet")) want_logdet = 1;
     else if (!strcmp(argv[i], "--check")) want_check = 1;
+    else if (!strcmp(argv[i], "--deterministic-solve")) det_solve = 1; /* device option solve_deterministic for the solve of -b: the same bits in every run */
     else if (!strcmp(argv[i], "--invdiag")) invdiag_file = next;
     else if (!strcmp(argv[i], "--schur")) { schur_k = atoi(next); schur_file = i + 2 < argc ? argv[i + 2] : ""; if (!*schur_file) DIE("--schur K FILE"); }
   }
@@ -110,6 +111,7 @@ int main(int argc, char **argv)
   if (gpus > 1 && cholamd_comm_create_all(devs, gpus, comms)) DIE("rccl: %s", cholamd_last_error());
   cholamd_device *dev = devs[0];
   double *d_arena = arenas[0];
+  if (det_solve && cholamd_device_set_option(dev, "solve_deterministic", 1)) DIE("--deterministic-solve: %s", cholamd_last_error());
   printf("Done fill.\n");
   double t_factor = 0;
   for (int it = 0; it < iterations; it++) { /* mmat.rg:1212-1358 */

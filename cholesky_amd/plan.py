@@ -348,6 +348,37 @@ class Plan:
         check(self.L.cholamd_plan_multiply_counts(self.h, out.ctypes.data), "cholamd_plan_multiply_counts")
         return {w: dict(items=int(out[3 * i]), sources=int(out[3 * i + 1]), entries=int(out[3 * i + 2])) for i, w in enumerate(("forward", "backward"))}
 
+    def solve_det_host(self, arena, which, b):
+        """x = M^-1 b (which = 0), M^-T b (1) or A^-1 b (-1: FORWARD then BACKWARD) on the CPU from a host arena (cholamd_plan_solve_det_host): the step
+        lists of the deterministic streamed solve (Device option solve_deterministic) walked on the host.  b and the result: n doubles in original
+        dof order."""
+        arena = np.ascontiguousarray(arena, dtype=np.float64)
+        assert arena.size == self.arena_doubles
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        assert b.shape == (self.n,)
+        x = np.full(max(self.n, 1), np.nan, dtype=np.float64)
+        check(self.L.cholamd_plan_solve_det_host(self.h, arena.ctypes.data, int(which), b.ctypes.data, x.ctypes.data), "cholamd_plan_solve_det_host")
+        return x[:self.n]
+
+    def solve_det_counts(self):
+        """Sizes of the step lists of the deterministic streamed solve (cholamd_plan_solve_det_counts): a dict per direction of steps (one span launch
+        each, preceded by a gather launch where the step has items), items, sources and the entries of L one sweep reads."""
+        out = np.zeros(8, dtype=np.int64)
+        check(self.L.cholamd_plan_solve_det_counts(self.h, out.ctypes.data), "cholamd_plan_solve_det_counts")
+        return {w: dict(steps=int(out[4 * i]), items=int(out[4 * i + 1]), sources=int(out[4 * i + 2]), entries=int(out[4 * i + 3]))
+                for i, w in enumerate(("forward", "backward"))}
+
+    def solve_det_lists(self, which):
+        """The lists of one direction (cholamd_plan_solve_det_lists) as int64 arrays: steps [n, 4] = level, first column of the span, first item, end
+        item; items [n, 4] = first permuted position, positions, first source, end source; sources [n, 5] = arena offset, leading dimension,
+        reduction steps, first permuted position read, triangle rule."""
+        c = self.solve_det_counts()["forward" if which == 0 else "backward"]
+        steps = np.zeros((max(c["steps"], 1), 4), dtype=np.int64)
+        items = np.zeros((max(c["items"], 1), 4), dtype=np.int64)
+        srcs = np.zeros((max(c["sources"], 1), 5), dtype=np.int64)
+        check(self.L.cholamd_plan_solve_det_lists(self.h, int(which), steps.ctypes.data, items.ctypes.data, srcs.ctypes.data), "cholamd_plan_solve_det_lists")
+        return steps[:c["steps"]], items[:c["items"]], srcs[:c["sources"]]
+
     def arena_to_dense(self, arena):
         arena = np.ascontiguousarray(arena, dtype=np.float64)
         assert arena.size == self.arena_doubles

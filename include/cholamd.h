@@ -369,8 +369,9 @@ int cholamd_factor_debug(cholamd_device *d, double *d_arena, const char *dir, in
 int cholamd_factor_info(cholamd_device *d, int *sep_out);
 /* Schedule / kernel-selection switches of this device object.  They default to the values the environment gave when
  * the object was created (CHOLAMD_SPLIT_MIN, CHOLAMD_SPLIT_NB, CHOLAMD_NO_FUSE, CHOLAMD_FUSE_UPDATE_MAX,
- * CHOLAMD_MT_MIN_TILES, CHOLAMD_NO_CELLS, CHOLAMD_SOLVE_REFERENCE_SHAPE: read once, there); names: "split_min",
- * "split_nb", "fuse", "fuse_update_max", "mt_min_tiles", "cells", "solve_reference_shape", "program" (the whole factorisation
+ * CHOLAMD_MT_MIN_TILES, CHOLAMD_NO_CELLS, CHOLAMD_SOLVE_REFERENCE_SHAPE, CHOLAMD_SOLVE_DETERMINISTIC: read once, there); names: "split_min",
+ * "split_nb", "fuse", "fuse_update_max", "mt_min_tiles", "cells", "solve_reference_shape", "solve_deterministic" (the bit-reproducible
+ * streamed solve, see "deterministic solve" below; neither of the two solve options rebuilds the work lists), "program" (the whole factorisation
  * of a small problem as one launch; CHOLAMD_NO_PROGRAM), "follow" (its pivot blocks follow their children's TRSM strips;
  * CHOLAMD_NO_FOLLOW), "follow_tail" (followers of more than four tile columns take the last follow_tail column tiles of each source
  * themselves, update jobs bring the rest; 0 = they take everything; CHOLAMD_FOLLOW_TAIL; "follow_tail_split": the same for the next
@@ -394,8 +395,9 @@ int cholamd_device_set_option(cholamd_device *d, const char *name, int value);
 int cholamd_device_bcast_phases(const cholamd_device *d);
 /* Solve phase, mmat.rg:1364-1495: b and x in ORIGINAL dof order (device pointers, n doubles).
  * The off-diagonal blocks accumulate into the vector with hardware fp64 atomics, so x agrees from run to run to
- * rounding (~1e-16 relative), NOT bit for bit; option "solve_reference_shape" selects the deterministic per-call
- * kernels of the BLAS-level entry points instead (slow beyond ~10^5 unknowns).
+ * rounding (~1e-16 relative), NOT bit for bit -- unless option "solve_deterministic" is set (below: the streamed sweeps with every contribution
+ * gathered by its owner, fp64 and fp32 factor), or option "solve_reference_shape", which selects the deterministic per-call
+ * kernels of the BLAS-level entry points instead (fp64 factor only, slow beyond ~10^5 unknowns).
  * What the streamed solve does NOT read: the structural zeros of the leaf panels (cholamd_plan_solve_skips; CHOLAMD_SOLVE_NO_BAND=1 in the environment
  * when the device object builds its solve lists reads everything).  The levels of at most 128 separators wider than 256 columns are solved with EXPLICIT
  * inverses of their 256-column diagonal spans (formed from the factor at the start of a solve -- of a refinement: its corrections reuse them -- in
@@ -403,6 +405,40 @@ int cholamd_device_bcast_phases(const cholamd_device *d);
  * between workgroups INSIDE a launch behind flags; the waits are bounded like the program launch's, and one that gives up poisons its part of the
  * vector with NaN (a residual or refinement then reports it) instead of hanging the device. */
 int cholamd_solve(cholamd_device *d, const double *d_arena, const double *d_b, double *d_x, void *stream);
+/* ---- deterministic solve: device option "solve_deterministic" (cholamd_device_set_option, or CHOLAMD_SOLVE_DETERMINISTIC non-zero in the environment at
+ * cholamd_device_create; default off -- with it off nothing changes, not even which kernels run).  THE CONTRACT: with the option on, cholamd_solve,
+ * cholamd_solve_f32, cholamd_solve_half, cholamd_solve_half_f32 and every solve inside cholamd_solve_refine return the SAME BITS for the same arena and the
+ * same right-hand side -- from call to call, from one device object of a plan to another, in place or out of place, and BACKWARD(FORWARD(b)) equals the solve
+ * bit for bit.  Hence cholamd_solve_refine takes the same number of corrections and returns the same x and relres every time.
+ * How: the sweeps run level by level in STEPS.  A level's lead step is one gather launch that subtracts what reaches the level from outside its own
+ * diagonal blocks -- FORWARD: a 16-row chunk's rows in the panels of its descendants; BACKWARD: a 16-column chunk's stored row runs into the ancestors.
+ * Then, per 256-column span of the level's separators, one gather launch subtracts what reaches the span from inside the block (FORWARD: the chunk's
+ * rows left of the span; BACKWARD: its rows below the span) and one launch solves the span.  One owner per position, sources summed in a fixed
+ * list order, NO floating-point atomics; the span itself is solved out of LDS by the streamed solve's span kernels with plain stores.  Steps are ordered by
+ * kernel boundaries on the stream alone: no workgroup waits for another inside a launch, there are no flags.  The 16x16 inverses are formed per call (kept
+ * across the corrections of a refinement); the 256-column explicit inverses and the step launches are not used.  Structural zeros of the leaves, row
+ * compaction and the upper triangles (never read) are treated as by cholamd_multiply_half, whose owner lists these are derived from.  The lists are built and
+ * uploaded at the first such solve on a device object (setting the option builds nothing).
+ * Precedence: where "solve_reference_shape" is also set and applies (the fp64 factor), it wins.
+ * The _nrhs entry points (cholamd_solve_nrhs, cholamd_solve_half_nrhs, their _f32 forms, cholamd_solve_refine_nrhs) go COLUMN BY COLUMN through the
+ * deterministic single-vector solve under the option, as they do under "solve_reference_shape": column j has the bits of the single solve of column j; there
+ * is no deterministic block kernel.
+ * NOT COVERED (they keep the atomic path whatever the option says): the sharded and multi-GPU solves (cholamd_solve_sharded, cholamd_solve_multi, the
+ * sharded refinement) on more than one rank, and the Schur condense / expand.
+ * Needs the COMPLETE factor in the arena, like cholamd_solve: a single-GPU device object, or rank 0's after a gather.
+ * cholamd_plan_solve_det_host: the same walk on the HOST over a host arena with the same lists (which = CHOLAMD_HALF_FORWARD, CHOLAMD_HALF_BACKWARD, or -1:
+ * the whole solve = FORWARD then BACKWARD; b and x n doubles in original dof order, x == b allowed); a span is solved by substitution inside its own lower
+ * triangle.  Deterministic, but not the device's bits (the span kernels order their sums differently).  Builds the lists anew at every call.
+ * cholamd_plan_solve_det_counts: out = { FORWARD steps, items, sources, entries of L read, BACKWARD steps, items, sources, entries of L read }; a step is one
+ * gather launch where it has items, followed by one span launch unless it is a level's lead step; the entries are those of the gather sources plus the
+ * spans' own lower triangles.
+ * cholamd_plan_solve_det_lists: the lists of one direction as int64 rows, sized by the counts: steps (level, first column of the span or -1: the level's
+ * lead step, first item, end item),
+ * items (first permuted position, positions, first source, end source), sources (arena offset, leading dimension, reduction steps, first permuted position
+ * read, triangle rule of chol_mul_src). */
+int cholamd_plan_solve_det_host(const cholamd_plan *p, const double *arena_host, int which, const double *b, double *x);
+int cholamd_plan_solve_det_counts(const cholamd_plan *p, int64_t out[8]);
+int cholamd_plan_solve_det_lists(const cholamd_plan *p, int which, int64_t *steps, int64_t *items, int64_t *srcs);
 /* ---- mixed precision (BASELINE config 5; not in the reference, whose arithmetic is fp64 CBLAS throughout): fp32 factor +
  * fp64 iterative refinement.  The fp32 arena has the fp64 arena's element layout: cholamd_plan_arena_doubles() FLOATS.
  * The fp32 schedule factors pivots in blocks of at most 128 columns out of LDS (v_mfma_f32 kernels, one launch per phase);
@@ -429,7 +465,8 @@ int cholamd_residual(cholamd_device *d, const double *d_b, const double *d_x, do
  * the off-diagonal blocks accumulate by fp64 atomics, so X agrees with cholamd_solve per column to rounding, not bit for bit); the 16x16 and span inverses are
  * formed once per call.  A chunk costs about the same for any number of columns up to 32: ~3 single solves with an fp64 factor, ~5 with an fp32 one, so
  * a chunk of fewer than 4 (fp64) / 6 (fp32) columns -- nrhs == 1 among them -- is solved column by column with the single-vector path instead.  Option
- * "solve_reference_shape" solves every column through cholamd_solve / cholamd_solve_f32.
+ * "solve_reference_shape" solves every column through cholamd_solve / cholamd_solve_f32, and so does option "solve_deterministic" (here and in
+ * cholamd_solve_refine_nrhs: every column then has the bits of its single deterministic solve).
  * nrhs == 0 returns 0 and touches nothing; nrhs < 0, ldb < n, ldx < n or a NULL pointer with nrhs > 0: CHOLAMD_ERR_ARG.
  * cholamd_solve_nrhs / _f32 (fp64 / fp32 factor; vectors and arithmetic fp64) are asynchronous on `stream`.  cholamd_solve_refine_nrhs is
  * cholamd_solve_refine for every column (fp32 factor, residual in fp64 against the matrix file's A) and synchronises: chunk by chunk (the chunk's columns
@@ -448,9 +485,10 @@ int cholamd_solve_refine_nrhs(cholamd_device *d, const float *d_arena32, const d
  * cholamd_solve_half / _f32 (fp64 / fp32 factor; vectors and arithmetic fp64): x = M^-1 b (which = CHOLAMD_HALF_FORWARD) or x = M^-T b
  * (CHOLAMD_HALF_BACKWARD), b and x n doubles on the device in original dof order, asynchronous on `stream`; d_x == d_b is allowed (as in cholamd_solve, b is
  * permuted into the work vector first).  Each is the permute, that sweep's launches of cholamd_solve, and the permute back: BACKWARD(FORWARD(b)) is the
- * solve and agrees with cholamd_solve to rounding (atomics in the off-diagonal blocks: not bit for bit).  The 16x16 and 256-column span inverses are formed
+ * solve and agrees with cholamd_solve to rounding (atomics in the off-diagonal blocks: not bit for bit; bit for bit under option "solve_deterministic").  The 16x16 and 256-column span inverses are formed
  * from d_arena at the start of EVERY half call (as at the start of a solve): a BACKWARD call does not rely on a preceding FORWARD call, whose arena may have
- * been another.  Option "solve_reference_shape" selects the deterministic per-call kernels for the halves of an fp64 factor as it does for cholamd_solve.
+ * been another.  Option "solve_reference_shape" selects the deterministic per-call kernels for the halves of an fp64 factor as it does for cholamd_solve;
+ * option "solve_deterministic" selects the deterministic streamed sweeps for the halves of either factor (the _nrhs forms then go column by column).
  * cholamd_solve_half_nrhs / _f32: the same for nrhs columns, with the argument rules of cholamd_solve_nrhs verbatim (column-major n x nrhs, ldb, ldx >= n,
  * rows n .. ld - 1 of X never written, in place with X == B and ldx == ldb; nrhs == 0 returns 0 and touches nothing; nrhs < 0, ldb < n, ldx < n or a NULL
  * pointer with nrhs > 0: CHOLAMD_ERR_ARG), the 32-column chunks and kernels of cholamd_solve_nrhs with one sweep instead of two, the inverses once per
@@ -491,7 +529,7 @@ int cholamd_factor_diag_f32(cholamd_device *d, const float *d_arena32, double *d
  * way in and once on the way out, the intermediate vector belongs to the device object): three launches.
  * DETERMINISTIC: every element of y has ONE owner -- a 16-row chunk of a separator gathers its rows from the separator's diagonal block and from the
  * panels of its descendants in a fixed order (FORWARD), a 16-column chunk of a separator sums over its own columns of the panel (BACKWARD) -- and a fixed
- * summation order; no floating-point atomics anywhere: two calls on one arena and one input return the same bits (unlike the streamed solve).
+ * summation order; no floating-point atomics anywhere: two calls on one arena and one input return the same bits (unlike the streamed solve without option "solve_deterministic").
  * cholamd_multiply_half_nrhs / cholamd_multiply_nrhs / _f32: the same products for the nrhs columns of Z, Y = M Z, M^T Z or M M^T Z.  Z and Y are column-major
  * n x nrhs on the device in original dof order with leading dimensions ldz, ldy >= n (rows n .. ld - 1 of Y are never written), the argument rules those of
  * cholamd_solve_half_nrhs: Y == Z with ldy == ldz is allowed (a chunk is permuted into the workspace before anything is written), nrhs == 0 returns 0 and
