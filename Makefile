@@ -10,7 +10,7 @@ CFLAGS  := -O2 -fPIC -Wall -Wextra -std=gnu11 -Iinclude -I$(CSRC)
 HIPFLAGS:= -O3 -fPIC --offload-arch=$(ARCH) -Iinclude -I$(CSRC) -Wall
 # the TRSM strips' step loop (trsm_rr_body, up to 20 column tiles) must unroll completely: its register tiles are indexed by the step; beyond
 # LLVM's default pragma-unroll budget the loop stays rolled and the tiles go to scratch (160 B per lane)
-KERNFLAGS := -mllvm -pragma-unroll-threshold=100000
+$(OUT)/chol_kernels.o: KERNFLAGS := -mllvm -pragma-unroll-threshold=100000
 
 HOST_OBJS := $(OUT)/chol_ingest.o $(OUT)/chol_symbolic.o $(OUT)/chol_schedule.o $(OUT)/chol_generate.o
 HIP_OBJS  := $(OUT)/chol_kernels.o $(OUT)/chol_kernels_f32.o $(OUT)/chol_solve_nrhs.o $(OUT)/chol_factor_query.o $(OUT)/chol_selinv.o $(OUT)/chol_schur.o $(OUT)/chol_multiply.o $(OUT)/chol_multiply_nrhs.o $(OUT)/chol_solve_det.o $(OUT)/chol_api.o
@@ -21,41 +21,9 @@ $(OUT)/%.o: $(CSRC)/%.c $(CSRC)/chol_plan.h include/cholamd.h
 	@mkdir -p $(OUT)
 	$(CC) $(CFLAGS) -c $< -o $@
 
-$(OUT)/chol_kernels.o: $(CSRC)/chol_kernels.hip $(CSRC)/chol_plan.h $(CSRC)/chol_kernels.h
+$(OUT)/%.o: $(CSRC)/%.hip $(CSRC)/chol_plan.h $(CSRC)/chol_kernels.h
 	@mkdir -p $(OUT)
 	$(HIPCC) $(HIPFLAGS) $(KERNFLAGS) -c $< -o $@
-
-$(OUT)/chol_kernels_f32.o: $(CSRC)/chol_kernels_f32.hip $(CSRC)/chol_plan.h $(CSRC)/chol_kernels.h
-	@mkdir -p $(OUT)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(OUT)/chol_solve_nrhs.o: $(CSRC)/chol_solve_nrhs.hip $(CSRC)/chol_plan.h $(CSRC)/chol_kernels.h
-	@mkdir -p $(OUT)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(OUT)/chol_factor_query.o: $(CSRC)/chol_factor_query.hip $(CSRC)/chol_plan.h $(CSRC)/chol_kernels.h
-	@mkdir -p $(OUT)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(OUT)/chol_selinv.o: $(CSRC)/chol_selinv.hip $(CSRC)/chol_plan.h $(CSRC)/chol_kernels.h
-	@mkdir -p $(OUT)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(OUT)/chol_schur.o: $(CSRC)/chol_schur.hip $(CSRC)/chol_plan.h $(CSRC)/chol_kernels.h
-	@mkdir -p $(OUT)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(OUT)/chol_multiply.o: $(CSRC)/chol_multiply.hip $(CSRC)/chol_plan.h $(CSRC)/chol_kernels.h
-	@mkdir -p $(OUT)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(OUT)/chol_multiply_nrhs.o: $(CSRC)/chol_multiply_nrhs.hip $(CSRC)/chol_plan.h $(CSRC)/chol_kernels.h
-	@mkdir -p $(OUT)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(OUT)/chol_solve_det.o: $(CSRC)/chol_solve_det.hip $(CSRC)/chol_plan.h $(CSRC)/chol_kernels.h
-	@mkdir -p $(OUT)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(OUT)/chol_api.o: $(CSRC)/chol_api.cpp $(CSRC)/chol_devbuf.h $(CSRC)/chol_plan.h $(CSRC)/chol_kernels.h include/cholamd.h
 	@mkdir -p $(OUT)

@@ -543,26 +543,6 @@ extern "C" int cholamd_device_free_arena(cholamd_device *d, void *dptr)
   return 0;
 }
 
-// Multi-GPU: which entries of A a rank's fill scatters.  Everything under the cut on every rank (the panels of the other ranks' subtrees are
-// never read).  The shared top of the tree (the tail of the arena) must start from A on exactly ONE rank per element, so that the sum over
-// the ranks after the local levels is A_top - all contributions: with replicated top levels (one all-reduce of the tail) that is rank 0; with
-// the top levels distributed by column blocks it is the block's OWNER -- the extend-add exchange then carries a block only from the ranks whose
-// subtrees reach it (chol_top_contributors), and rank 0 sends no more than any other rank.  `*below` = leading entries of (a_dst, a_val) to
-// scatter; (*tdst, *tval, *ntop) = further entries (device arrays).  f32: the fp32 schedule's column blocks.
-static void exchange_pieces(const cholamd_device *d, const std::vector<level_dev> &lv, std::vector<struct xpiece> &out);
-static int top_entries(cholamd_device *d, int f32, int64_t *below, const int64_t **tdst, const double **tval, int64_t *ntop, hipStream_t st);
-extern "C" int cholamd_device_fill(cholamd_device *d, double *d_arena, void *stream)
-{
-  HIPCHK(hipSetDevice(d->dev));
-  hipStream_t st = (hipStream_t)stream;
-  { int rc = clear_owned(d, d_arena, sizeof(double), st); if (rc) return rc; }
-  int64_t below = 0, ntop = 0; const int64_t *tdst = nullptr; const double *tval = nullptr;
-  { int rc = top_entries(d, 0, &below, &tdst, &tval, &ntop, st); if (rc) return rc; }
-  HIPCHK((hipError_t)chol_launch_scatter(d_arena, d->a_dst, d->a_val, below, st));
-  if (ntop > 0) HIPCHK((hipError_t)chol_launch_scatter(d_arena, tdst, tval, ntop, st));
-  return 0;
-}
-
 // ---- timing helpers -------------------------------------------------------------------------
 static hipEvent_t get_event(cholamd_device *d)
 {
@@ -634,56 +614,7 @@ extern "C" int cholamd_device_event_overhead(cholamd_device *d, void *stream, fl
   return 0;
 }
 
-// ---- the hot path ---------------------------------------------------------------------------
-static int launch_phase(cholamd_device *d, const level_dev &l, const chol_phase &ph, double *d_arena, hipStream_t st)
-{
-  if (ph.kind == 5) {
-    // the progress words (epoch * 64 + columns) and the count of finished TRSM workgroups are monotonic across launches:
-    // both start over, in stream order, long before either can wrap
-    if (d->epoch >= (1 << 24) || d->done_total >= (1 << 30)) { HIPCHK(hipMemsetAsync(d->progress, 0, (size_t)(d->plan->nsep + 2) * sizeof(int), st)); d->epoch = 0; d->done_total = 0; }
-    d->epoch++;
-    if (ph.n3 > 0) d->done_total += (ph.n2 + 2) / 3; // TRSM workgroups of this launch count themselves out only when update tasks ride along
-    HIPCHK((hipError_t)chol_launch_potrf_trsm(d_arena, d->ws, l.potrf + ph.first, ph.n, l.trsm + ph.first2, ph.n2, l.task + ph.first3, l.src, ph.n3,
-                                              d->info, d->progress, d->epoch * 64, d->progress + d->plan->nsep + 1, d->done_total, st));
-  } else if (ph.kind == 0) HIPCHK((hipError_t)chol_launch_potrf(d_arena, d->ws, l.potrf + ph.first, ph.n, d->info, st));
-  else if (ph.kind == 1) HIPCHK((hipError_t)chol_launch_trsm(d_arena, d->ws, l.trsm + ph.first, ph.n, st));
-  else if (ph.kind == 4) HIPCHK((hipError_t)chol_launch_trsm_w(d_arena, d->ws, l.trsm + ph.first, ph.n, st));
-  else if (ph.kind == 7) HIPCHK((hipError_t)chol_launch_trsm_wt(d_arena, d->ws, l.trsm + ph.first, ph.n, st));
-  else if (ph.kind == 2) HIPCHK((hipError_t)chol_launch_update(d_arena, l.task + ph.first, l.src, ph.n, st));
-  else if (ph.kind == 3) HIPCHK((hipError_t)chol_launch_update_mt(d_arena, l.task_mt + ph.first, l.src, ph.n, (int64_t)d->plan->arena, st));
-  return 0;
-}
-struct cholamd_comm;
-static int bcast_rank(cholamd_device *d, const level_dev &l, const chol_phase &ph, double *d_arena, cholamd_comm *c, hipStream_t st);
-// levels [level_lo, level_hi] of one rank; a broadcast phase (kind 6: distributed top levels) goes through `c`
-static int factor_levels_comm(cholamd_device *d, double *d_arena, int level_hi, int level_lo, cholamd_comm *c, hipStream_t st)
-{
-  HIPCHK(hipSetDevice(d->dev));
-  const int L = d->plan->levels;
-  if (level_hi >= L) level_hi = L - 1;
-  if (level_lo < 0) level_lo = 0;
-  if (level_hi == L - 1) HIPCHK(hipMemsetAsync(d->info, 0, 2 * sizeof(int), st));
-  d->info_last = d->info; d->info_foreign = true; // slot 0: the level-by-level paths
-  for (int lvl = level_hi; lvl >= level_lo; lvl--) { // mmat.rg:1227
-    const level_dev &l = d->lv[lvl];
-    for (const chol_phase &ph : l.phase) {
-      if (ph.kind == 6) {
-        scoped_timer t(d, st, CHOL_TK_BCAST, ph.n > 0);
-        int rc = bcast_rank(d, l, ph, d_arena, c, st);
-        if (rc) return rc;
-        continue;
-      }
-      scoped_timer t(d, st, ph.kind == 3 ? 2 : (ph.kind == 4 || ph.kind == 7) ? 1 : ph.kind == 5 ? 0 : ph.kind, ph.n > 0);
-      int rc = launch_phase(d, l, ph, d_arena, st);
-      if (rc) return rc;
-    }
-  }
-  return 0;
-}
-extern "C" int cholamd_factor_levels(cholamd_device *d, double *d_arena, int level_hi, int level_lo, void *stream)
-{
-  return factor_levels_comm(d, d_arena, level_hi, level_lo, nullptr, (hipStream_t)stream);
-}
+// ---- the hot path (the program launch; the fill and the level-by-level driver of both precisions: at factor_levels_comm below) ----
 extern "C" int cholamd_factor(cholamd_device *d, double *d_arena, void *stream)
 {
   if (!d->prog_ready) return cholamd_factor_levels(d, d_arena, d->plan->levels - 1, 0, stream);
@@ -850,14 +781,8 @@ struct keep_inverses_scope { // set on the devices of a refinement after its fir
   keep_inverses_scope(cholamd_device *const *devs_, int n_) : devs(devs_), n(n_) { for (int g = 0; g < n; g++) devs[g]->keep_inverses = true; }
   ~keep_inverses_scope() { for (int g = 0; g < n; g++) devs[g]->keep_inverses = false; }
 };
-static int lsolve_dinv(const double *a, const chol_trsv_desc *t, int n, int mx, double *W, hipStream_t st) { return chol_launch_solve_dinv(a, t, n, mx, W, st); }
-static int lsolve_dinv(const float *a, const chol_trsv_desc *t, int n, int mx, double *W, hipStream_t st) { return chol32_launch_solve_dinv(a, t, n, mx, W, st); }
-static int lsolve_trsv(cholamd_device *d, const double *a, const chol_trsv_desc *t, int n, int mx, int mu, const double *W, double *y, int bw, const double *W256, hipStream_t st) { return chol_launch_solve_trsv(a, t, n, mx, mu, W, y, bw, d->step_flags, &d->step_gen, W256, d->step_xt, st); }
-static int lsolve_trsv(cholamd_device *d, const float *a, const chol_trsv_desc *t, int n, int mx, int mu, const double *W, double *y, int bw, const double *W256, hipStream_t st) { return chol32_launch_solve_trsv(a, t, n, mx, mu, W, y, bw, d->step_flags, &d->step_gen, W256, d->step_xt, st); }
-static int lsolve_inv256(const double *a, const chol_trsv_desc *t, int n, int mx, const double *W16, double *W256, hipStream_t st) { return chol_launch_solve_inv256(a, t, n, mx, W16, W256, st); }
-static int lsolve_inv256(const float *a, const chol_trsv_desc *t, int n, int mx, const double *W16, double *W256, hipStream_t st) { return chol32_launch_solve_inv256(a, t, n, mx, W16, W256, st); }
-static int lsolve_off(const double *a, const chol_gemv_desc *g, const int *it, int n, double *y, int bw, hipStream_t st) { return chol_launch_solve_offdiag(a, g, it, n, y, bw, st); }
-static int lsolve_off(const float *a, const chol_gemv_desc *g, const int *it, int n, double *y, int bw, hipStream_t st) { return chol32_launch_solve_offdiag(a, g, it, n, y, bw, st); }
+template <class TL> static int lsolve_trsv(cholamd_device *d, const TL *a, const chol_trsv_desc *t, int n, int mx, int mu, const double *W, double *y, int bw, const double *W256, hipStream_t st)
+{ return chol_launch_solve_trsv(a, t, n, mx, mu, W, y, bw, d->step_flags, &d->step_gen, W256, d->step_xt, st); } // (the step launches' flags, counter and scratch are the device object's)
 // The streamed solve in three phases, so that a partitioned device can put the two vector reductions of the distributed solve between them:
 //   phase 0: y = P b (a rank of a partition: zero outside what it owns), the 16x16 inverses, forward sweep of the levels under the cut
 //            -> [sum of the shared top's part of y over the ranks]
@@ -875,8 +800,8 @@ template <class TL> static int solve_phase(cholamd_device *d, const TL *d_arena,
     // the 16x16 inverses of this arena's diagonal blocks (the factorisation's workspace belongs to the last arena factored)
     for (int lvl = 0; lvl < L && !d->keep_inverses; lvl++) {
       const solve_dev &s = d->sv[lvl];
-      HIPCHK((hipError_t)lsolve_dinv(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, st));
-      if (s.w256_off >= 0 && d->w256) HIPCHK((hipError_t)lsolve_inv256(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, d->w256 + s.w256_off, st));
+      HIPCHK((hipError_t)chol_launch_solve_dinv(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, st));
+      if (s.w256_off >= 0 && d->w256) HIPCHK((hipError_t)chol_launch_solve_inv256(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, d->w256 + s.w256_off, st));
     }
   }
   if (phase <= 1) {
@@ -884,13 +809,13 @@ template <class TL> static int solve_phase(cholamd_device *d, const TL *d_arena,
     for (int lvl = hi; lvl >= lo; lvl--) { // forward, mmat.rg:1395-1435: TRSV per separator, then its panel into the ancestors
       const solve_dev &s = d->sv[lvl];
       HIPCHK((hipError_t)lsolve_trsv(d, d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, y, 0, s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr, st));
-      HIPCHK((hipError_t)lsolve_off(d_arena, s.bw, s.ifw, s.n_ifw, y, 0, st));
+      HIPCHK((hipError_t)chol_launch_solve_offdiag(d_arena, s.bw, s.ifw, s.n_ifw, y, 0, st));
     }
   }
   if (phase == 1) {
     for (int lvl = 0; lvl < L; lvl++) { // backward, mmat.rg:1438-1479: gather from the ancestors, then TRSV^T
       const solve_dev &s = d->sv[lvl];
-      HIPCHK((hipError_t)lsolve_off(d_arena, s.bw, s.ibw, s.n_ibw, y, 1, st));
+      HIPCHK((hipError_t)chol_launch_solve_offdiag(d_arena, s.bw, s.ibw, s.n_ibw, y, 1, st));
       HIPCHK((hipError_t)lsolve_trsv(d, d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, y, 1, s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr, st));
     }
     if (d->solve_world > 1 && d->solve_rank != 0) { // the top's part of the solution is counted once in the sum that follows: rank 0's
@@ -930,10 +855,6 @@ static int build_solve_det(cholamd_device *d)
   d->sdet_ready = true;
   return 0;
 }
-static int lsdet_gather(const double *a, const chol_mul_item *it, int ni, const chol_mul_src *sr, int bw, double *y, hipStream_t st) { return chol_launch_solve_det_gather(a, it, ni, sr, bw, y, st); }
-static int lsdet_gather(const float *a, const chol_mul_item *it, int ni, const chol_mul_src *sr, int bw, double *y, hipStream_t st) { return chol32_launch_solve_det_gather(a, it, ni, sr, bw, y, st); }
-static int lsdet_span(const double *a, const chol_trsv_desc *t, int n, const double *W, double *y, int col0, int bw, hipStream_t st) { return chol_launch_solve_span(a, t, n, W, y, col0, bw, st); }
-static int lsdet_span(const float *a, const chol_trsv_desc *t, int n, const double *W, double *y, int col0, int bw, hipStream_t st) { return chol32_launch_solve_span(a, t, n, W, y, col0, bw, st); }
 template <class TL> static int solve_det_t(cholamd_device *d, const TL *d_arena, const double *d_b, double *d_x, int which, hipStream_t st)
 {
   { int rc = build_solve(d); if (!rc) rc = build_solve_det(d); if (rc) return rc; }
@@ -942,15 +863,15 @@ template <class TL> static int solve_det_t(cholamd_device *d, const TL *d_arena,
   HIPCHK((hipError_t)chol_launch_permute(d_b, d->perm, y, n, 0, st));
   for (int lvl = 0; lvl < L && !d->keep_inverses; lvl++) {
     const solve_dev &s = d->sv[lvl];
-    HIPCHK((hipError_t)lsolve_dinv(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, st));
+    HIPCHK((hipError_t)chol_launch_solve_dinv(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, st));
   }
   for (int q = 0; q < 2; q++) {
     if (which >= 0 && which != q) continue;
     const chol_mul_item *items = d->sdet_item[q];
     for (const chol_sdet_step &t : d->sdet_step[q]) {
       const solve_dev &s = d->sv[t.level];
-      if (t.item_end > t.item_first) HIPCHK((hipError_t)lsdet_gather(d_arena, items + t.item_first, t.item_end - t.item_first, d->sdet_src[q], q, y, st));
-      if (t.col0 >= 0) HIPCHK((hipError_t)lsdet_span(d_arena, s.trsv, s.n_trsv, d->ws_solve, y, t.col0, q, st));
+      if (t.item_end > t.item_first) HIPCHK((hipError_t)chol_launch_solve_det_gather(d_arena, items + t.item_first, t.item_end - t.item_first, d->sdet_src[q], q, y, st));
+      if (t.col0 >= 0) HIPCHK((hipError_t)chol_launch_solve_span(d_arena, s.trsv, s.n_trsv, d->ws_solve, y, t.col0, q, st));
     }
   }
   HIPCHK((hipError_t)chol_launch_permute(y, d->perm, d_x, n, 1, st));
@@ -1028,62 +949,6 @@ static int ensure_f32(cholamd_device *d, hipStream_t st)
     if (rc) { d->lv32.clear(); return rc; }
   }
   return 0;
-}
-extern "C" int cholamd_device_fill_f32(cholamd_device *d, float *d_arena32, void *stream)
-{
-  HIPCHK(hipSetDevice(d->dev));
-  hipStream_t st = (hipStream_t)stream;
-  { int rc = ensure_f32(d, st); if (rc) return rc; } // the fp32 schedule's column blocks decide which entries of the shared top are this rank's
-  { int rc = clear_owned(d, d_arena32, sizeof(float), st); if (rc) return rc; }
-  int64_t below = 0, ntop = 0; const int64_t *tdst = nullptr; const double *tval = nullptr;
-  { int rc = top_entries(d, 1, &below, &tdst, &tval, &ntop, st); if (rc) return rc; }
-  HIPCHK((hipError_t)chol32_launch_scatter(d_arena32, d->a_dst, d->a_val, below, st));
-  if (ntop > 0) HIPCHK((hipError_t)chol32_launch_scatter(d_arena32, tdst, tval, ntop, st));
-  return 0;
-}
-static int launch_phase_f32(cholamd_device *d, const level_dev &l, const chol_phase &ph, float *d_arena32, hipStream_t st)
-{
-  if (ph.kind == 0) HIPCHK((hipError_t)chol32_launch_potrf(d_arena32, d->ws32, l.potrf + ph.first, ph.n, d->info, st));
-  else if (ph.kind == 7) HIPCHK((hipError_t)chol32_launch_trsm_wt(d_arena32, d->ws32, l.trsm + ph.first, ph.n, st));
-  else if (ph.kind == 1 || ph.kind == 4) HIPCHK((hipError_t)chol32_launch_trsm(d_arena32, d->ws32, l.trsm + ph.first, ph.n, st));
-  else if (ph.kind == 2) HIPCHK((hipError_t)chol32_launch_update(d_arena32, l.task + ph.first, l.src, ph.n, st));
-  else if (ph.kind == 3) HIPCHK((hipError_t)chol32_launch_update_mt(d_arena32, l.task_mt + ph.first, l.src, ph.n, (int64_t)d->plan->arena, st));
-  else { chol_set_error("internal: phase kind %d in the fp32 schedule", ph.kind); return CHOLAMD_ERR_ARG; }
-  return 0;
-}
-template <class T> static int bcast_rank_t(cholamd_device *d, const level_dev &l, const chol_phase &ph, T *d_arena, cholamd_comm *c, hipStream_t st);
-static int factor_levels_f32_comm(cholamd_device *d, float *d_arena32, int level_hi, int level_lo, cholamd_comm *c, hipStream_t st);
-extern "C" int cholamd_factor_levels_f32(cholamd_device *d, float *d_arena32, int level_hi, int level_lo, void *stream)
-{
-  return factor_levels_f32_comm(d, d_arena32, level_hi, level_lo, nullptr, (hipStream_t)stream);
-}
-static int factor_levels_f32_comm(cholamd_device *d, float *d_arena32, int level_hi, int level_lo, cholamd_comm *c, hipStream_t st)
-{
-  HIPCHK(hipSetDevice(d->dev));
-  int rc = ensure_f32(d, st);
-  if (rc) return rc;
-  const int L = d->plan->levels;
-  if (level_hi >= L) level_hi = L - 1;
-  if (level_lo < 0) level_lo = 0;
-  if (level_hi == L - 1) HIPCHK(hipMemsetAsync(d->info, 0, 2 * sizeof(int), st));
-  d->info_last = d->info; d->info_foreign = true; // slot 0: the level-by-level paths
-  for (int lvl = level_hi; lvl >= level_lo; lvl--) {
-    const level_dev &l = d->lv32[lvl];
-    for (const chol_phase &ph : l.phase) {
-      if (ph.kind == 6) { // distributed top levels: the step's column blocks travel from their owners to every rank
-        scoped_timer t(d, st, CHOL_TK_BCAST, ph.n > 0);
-        if ((rc = bcast_rank_t<float>(d, l, ph, d_arena32, c, st))) return rc;
-        continue;
-      }
-      scoped_timer t(d, st, ph.kind == 3 ? 2 : (ph.kind == 4 || ph.kind == 7) ? 1 : ph.kind, ph.n > 0);
-      if ((rc = launch_phase_f32(d, l, ph, d_arena32, st))) return rc;
-    }
-  }
-  return 0;
-}
-extern "C" int cholamd_factor_f32(cholamd_device *d, float *d_arena32, void *stream)
-{
-  return cholamd_factor_levels_f32(d, d_arena32, d->plan->levels - 1, 0, stream);
 }
 extern "C" int cholamd_solve_f32(cholamd_device *d, const float *d_arena32, const double *d_b, double *d_x, void *stream)
 {
@@ -1243,10 +1108,6 @@ extern "C" int cholamd_solve_refine(cholamd_device *d, const float *d_arena32, c
 // Block solve (not in the reference, whose mmat.rg -b solves one vector): nrhs right-hand sides in chunks of CHOL_NRHS_W columns, each chunk one forward
 // and one backward sweep over the solve lists of the whole tree (chol_solve_nrhs.hip), so the factor is read once per sweep per chunk.
 // ---------------------------------------------------------------------------------------------
-static int lnrhs_trsv(const double *a, const chol_trsv_desc *t, int n, int mx, int mu, const double *W, const double *W256, double *Y, int bw, hipStream_t st) { return chol_nrhs_launch_trsv(a, t, n, mx, mu, W, W256, Y, bw, st); }
-static int lnrhs_trsv(const float *a, const chol_trsv_desc *t, int n, int mx, int mu, const double *W, const double *W256, double *Y, int bw, hipStream_t st) { return chol32_nrhs_launch_trsv(a, t, n, mx, mu, W, W256, Y, bw, st); }
-static int lnrhs_off(const double *a, const chol_gemv_desc *g, const int *it, int n, double *Y, int bw, hipStream_t st) { return chol_nrhs_launch_offdiag(a, g, it, n, Y, bw, st); }
-static int lnrhs_off(const float *a, const chol_gemv_desc *g, const int *it, int n, double *Y, int bw, hipStream_t st) { return chol32_nrhs_launch_offdiag(a, g, it, n, Y, bw, st); }
 // in / out: what the entry point's header calls its two blocks (the solves: B, X; the products: Z, Y)
 static int nrhs_check(cholamd_device *d, const void *arena, const double *B, int64_t ldb, const double *X, int64_t ldx, int nrhs, const char *what, const char *in = "B", const char *out = "X")
 { // 1: nothing to do
@@ -1282,19 +1143,19 @@ template <class TL> static int solve_half_streamed(cholamd_device *d, const TL *
   HIPCHK((hipError_t)chol_launch_permute(d_b, d->perm, y, n, 0, st));
   for (int lvl = 0; lvl < L && !d->keep_inverses; lvl++) {
     const solve_dev &s = d->sv[lvl];
-    HIPCHK((hipError_t)lsolve_dinv(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, st));
-    if (s.w256_off >= 0 && d->w256) HIPCHK((hipError_t)lsolve_inv256(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, d->w256 + s.w256_off, st));
+    HIPCHK((hipError_t)chol_launch_solve_dinv(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, st));
+    if (s.w256_off >= 0 && d->w256) HIPCHK((hipError_t)chol_launch_solve_inv256(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, d->w256 + s.w256_off, st));
   }
   if (which == CHOLAMD_HALF_FORWARD)
     for (int lvl = L - 1; lvl >= 0; lvl--) {
       const solve_dev &s = d->sv[lvl];
       HIPCHK((hipError_t)lsolve_trsv(d, d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, y, 0, s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr, st));
-      HIPCHK((hipError_t)lsolve_off(d_arena, s.bw, s.ifw, s.n_ifw, y, 0, st));
+      HIPCHK((hipError_t)chol_launch_solve_offdiag(d_arena, s.bw, s.ifw, s.n_ifw, y, 0, st));
     }
   else
     for (int lvl = 0; lvl < L; lvl++) {
       const solve_dev &s = d->sv[lvl];
-      HIPCHK((hipError_t)lsolve_off(d_arena, s.bw, s.ibw, s.n_ibw, y, 1, st));
+      HIPCHK((hipError_t)chol_launch_solve_offdiag(d_arena, s.bw, s.ibw, s.n_ibw, y, 1, st));
       HIPCHK((hipError_t)lsolve_trsv(d, d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, y, 1, s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr, st));
     }
   HIPCHK((hipError_t)chol_launch_permute(y, d->perm, d_x, n, 1, st));
@@ -1313,8 +1174,8 @@ template <class TL> static int solve_nrhs_t(cholamd_device *d, const TL *d_arena
   const int L = d->plan->levels, n = d->plan->n;
   for (int lvl = 0; lvl < L && !d->keep_inverses; lvl++) { // the diagonal inverses once per call, as solve_phase
     const solve_dev &s = d->sv[lvl];
-    HIPCHK((hipError_t)lsolve_dinv(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, st));
-    if (s.w256_off >= 0 && d->w256) HIPCHK((hipError_t)lsolve_inv256(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, d->w256 + s.w256_off, st));
+    HIPCHK((hipError_t)chol_launch_solve_dinv(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, st));
+    if (s.w256_off >= 0 && d->w256) HIPCHK((hipError_t)chol_launch_solve_inv256(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, d->w256 + s.w256_off, st));
   }
   keep_restore kr(d);
   d->keep_inverses = true; // (the column-by-column chunks: solve_streamed reuses them)
@@ -1334,14 +1195,14 @@ template <class TL> static int solve_nrhs_t(cholamd_device *d, const TL *d_arena
     for (int lvl = L - 1; lvl >= 0 && which != CHOLAMD_HALF_BACKWARD; lvl--) { // forward: the separators' triangles, then their panels into the ancestors
       const solve_dev &s = d->sv[lvl];
       const double *W256 = s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr;
-      HIPCHK((hipError_t)lnrhs_trsv(d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, W256, Y, 0, st));
-      HIPCHK((hipError_t)lnrhs_off(d_arena, s.bw, s.ifw, s.n_ifw, Y, 0, st));
+      HIPCHK((hipError_t)chol_nrhs_launch_trsv(d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, W256, Y, 0, st));
+      HIPCHK((hipError_t)chol_nrhs_launch_offdiag(d_arena, s.bw, s.ifw, s.n_ifw, Y, 0, st));
     }
     for (int lvl = 0; lvl < L && which != CHOLAMD_HALF_FORWARD; lvl++) { // backward: gather from the ancestors, then the transposed triangles
       const solve_dev &s = d->sv[lvl];
       const double *W256 = s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr;
-      HIPCHK((hipError_t)lnrhs_off(d_arena, s.bw, s.ibw, s.n_ibw, Y, 1, st));
-      HIPCHK((hipError_t)lnrhs_trsv(d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, W256, Y, 1, st));
+      HIPCHK((hipError_t)chol_nrhs_launch_offdiag(d_arena, s.bw, s.ibw, s.n_ibw, Y, 1, st));
+      HIPCHK((hipError_t)chol_nrhs_launch_trsv(d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, W256, Y, 1, st));
     }
     HIPCHK((hipError_t)chol_nrhs_launch_permute(nullptr, 0, d->perm, Y, d_X, ldx, n, c0, cols, 1, st));
   }
@@ -1443,17 +1304,13 @@ extern "C" int cholamd_solve_half_nrhs_f32(cholamd_device *d, const float *d_are
   }
   return solve_nrhs_t(d, d_arena32, d_B, ldb, d_X, ldx, nrhs, (hipStream_t)stream, which);
 }
-static int lfactor_diag(const double *a, const chol_trsv_desc *t, const int *pre, int nd, int n, const int *perm, double *dg, hipStream_t st) { return chol_launch_factor_diag(a, t, pre, nd, n, perm, dg, st); }
-static int lfactor_diag(const float *a, const chol_trsv_desc *t, const int *pre, int nd, int n, const int *perm, double *dg, hipStream_t st) { return chol32_launch_factor_diag(a, t, pre, nd, n, perm, dg, st); }
-static int lfactor_logdet(const double *a, const chol_trsv_desc *t, const int *pre, int nd, int n, double *part, int64_t *ipart, int64_t *res, hipStream_t st) { return chol_launch_factor_logdet(a, t, pre, nd, n, part, ipart, res, st); }
-static int lfactor_logdet(const float *a, const chol_trsv_desc *t, const int *pre, int nd, int n, double *part, int64_t *ipart, int64_t *res, hipStream_t st) { return chol32_launch_factor_logdet(a, t, pre, nd, n, part, ipart, res, st); }
 template <class TL> static int factor_diag_t(cholamd_device *d, const TL *d_arena, double *d_diag, hipStream_t st, const char *what)
 {
   if (!d) { chol_set_error("%s: NULL device", what); return CHOLAMD_ERR_ARG; }
   if (!d_arena || !d_diag) { chol_set_error("%s: NULL %s", what, !d_arena ? "arena" : "d_diag"); return CHOLAMD_ERR_ARG; }
   HIPCHK(hipSetDevice(d->dev));
   { int rc = build_solve(d); if (rc) return rc; }
-  HIPCHK((hipError_t)lfactor_diag(d_arena, d->dg_desc, d->dg_prefix, d->n_dg, d->plan->n, d->perm, d_diag, st));
+  HIPCHK((hipError_t)chol_launch_factor_diag(d_arena, d->dg_desc, d->dg_prefix, d->n_dg, d->plan->n, d->perm, d_diag, st));
   return 0;
 }
 template <class TL> static int factor_logdet_t(cholamd_device *d, const TL *d_arena, double *logdet_out, hipStream_t st, const char *what)
@@ -1467,7 +1324,7 @@ template <class TL> static int factor_logdet_t(cholamd_device *d, const TL *d_ar
   if (!rc) rc = d->ld_ipart.ensure(2 * CHOL_LOGDET_MAX_BLOCKS);
   if (!rc) rc = d->ld_res.ensure(3);
   if (rc) return rc;
-  HIPCHK((hipError_t)lfactor_logdet(d_arena, d->dg_desc, d->dg_prefix, d->n_dg, d->plan->n, d->ld_part, d->ld_ipart, d->ld_res, st));
+  HIPCHK((hipError_t)chol_launch_factor_logdet(d_arena, d->dg_desc, d->dg_prefix, d->n_dg, d->plan->n, d->ld_part, d->ld_ipart, d->ld_res, st));
   int64_t res[3] = { 0, 0, 0 };
   HIPCHK(hipMemcpyAsync(res, d->ld_res, sizeof res, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -1595,8 +1452,6 @@ static int build_multiply(cholamd_device *d)
   d->mul_ready = true;
   return 0;
 }
-static int lmultiply(const double *a, const chol_mul_item *it, int ni, const chol_mul_src *sr, int bw, const double *z, double *y, const int *perm, hipStream_t st) { return chol_launch_multiply(a, it, ni, sr, bw, z, y, perm, st); }
-static int lmultiply(const float *a, const chol_mul_item *it, int ni, const chol_mul_src *sr, int bw, const double *z, double *y, const int *perm, hipStream_t st) { return chol32_launch_multiply(a, it, ni, sr, bw, z, y, perm, st); }
 // the checks every product shares, after the NULL / which / nrhs rules of the half solves: the complete factor, y outside the arena
 template <class TL> static int multiply_check(cholamd_device *d, const TL *d_arena, const double *d_y, int64_t y_doubles, const char *what)
 {
@@ -1618,11 +1473,11 @@ template <class TL> static int multiply_t(cholamd_device *d, const TL *d_arena, 
   HIPCHK((hipError_t)chol_launch_permute(d_z, d->perm, d->ytmp, n, 0, st)); // (first: d_y may be d_z)
   const double *in = d->ytmp;
   if (which == CHOL_BOTH_SWEEPS) {
-    HIPCHK((hipError_t)lmultiply(d_arena, d->mul_item[B], d->n_mul_item[B], d->mul_src[B], 1, in, d->mvec, nullptr, st));
+    HIPCHK((hipError_t)chol_launch_multiply(d_arena, d->mul_item[B], d->n_mul_item[B], d->mul_src[B], 1, in, d->mvec, nullptr, st));
     in = d->mvec;
     which = F;
   }
-  HIPCHK((hipError_t)lmultiply(d_arena, d->mul_item[which], d->n_mul_item[which], d->mul_src[which], which == B, in, d_y, d->perm, st));
+  HIPCHK((hipError_t)chol_launch_multiply(d_arena, d->mul_item[which], d->n_mul_item[which], d->mul_src[which], which == B, in, d_y, d->perm, st));
   return 0;
 }
 template <class TL> static int multiply_half_api(cholamd_device *d, const TL *d_arena, const double *d_z, double *d_y, bool half, int which, hipStream_t st, const char *what)
@@ -1648,10 +1503,6 @@ extern "C" int cholamd_multiply_f32(cholamd_device *d, const float *d_arena32, c
 // A chunk is permuted into the object's first block, then ONE launch per direction over the items of the single-vector products; the last launch writes
 // Y in original dof order itself.  The full product puts the BACKWARD launch between them, into the second block.
 // ---------------------------------------------------------------------------------------------
-static int lmultiply_nrhs(const double *a, const chol_mul_item *it, int ni, const chol_mul_src *sr, int bw, const double *zp, double *y, const int *perm, int64_t ldy, int c0, int cols, hipStream_t st)
-{ return chol_launch_multiply_nrhs(a, it, ni, sr, bw, zp, y, perm, ldy, c0, cols, st); }
-static int lmultiply_nrhs(const float *a, const chol_mul_item *it, int ni, const chol_mul_src *sr, int bw, const double *zp, double *y, const int *perm, int64_t ldy, int c0, int cols, hipStream_t st)
-{ return chol32_launch_multiply_nrhs(a, it, ni, sr, bw, zp, y, perm, ldy, c0, cols, st); }
 // A block chunk costs nearly the same for 1 and for 32 columns (one pass over the factor), so a chunk of fewer columns than this goes column by column
 // through the single-vector products.  min = ceil(T_chunk(32 columns) / T_single) from the medians measured on one MI355X at gen:60:8, both in one process
 // (DESIGN.md section 13, table "Block form: measured times"): fp64 factor 1.035 / 0.603 ms FORWARD, 1.323 / 0.550 BACKWARD, 2.269 / 1.142 full; fp32
@@ -1678,11 +1529,11 @@ template <class TL> static int multiply_nrhs_t(cholamd_device *d, const TL *d_ar
     const double *in = d->mznrhs;
     int last = which;
     if (which == CHOL_BOTH_SWEEPS) {
-      HIPCHK((hipError_t)lmultiply_nrhs(d_arena, d->mul_item[B], d->n_mul_item[B], d->mul_src[B], 1, in, d->mwnrhs, nullptr, 0, 0, CHOL_NRHS_W, st));
+      HIPCHK((hipError_t)chol_launch_multiply_nrhs(d_arena, d->mul_item[B], d->n_mul_item[B], d->mul_src[B], 1, in, d->mwnrhs, nullptr, 0, 0, CHOL_NRHS_W, st));
       in = d->mwnrhs;
       last = F;
     }
-    HIPCHK((hipError_t)lmultiply_nrhs(d_arena, d->mul_item[last], d->n_mul_item[last], d->mul_src[last], last == B, in, d_Y, d->perm, ldy, c0, cols, st));
+    HIPCHK((hipError_t)chol_launch_multiply_nrhs(d_arena, d->mul_item[last], d->n_mul_item[last], d->mul_src[last], last == B, in, d_Y, d->perm, ldy, c0, cols, st));
   }
   return 0;
 }
@@ -1758,7 +1609,7 @@ extern "C" int cholamd_schur_factor(cholamd_device *d, double *d_arena, int k, v
   const int m = schur_args(d, k, "cholamd_schur_factor", nullptr);
   if (m < 0) return m;
   if (!d_arena) { chol_set_error("cholamd_schur_factor: NULL arena"); return CHOLAMD_ERR_ARG; }
-  return factor_levels_comm(d, d_arena, d->plan->levels - 1, k, nullptr, (hipStream_t)stream); // the per-level launches, never the program
+  return cholamd_factor_levels(d, d_arena, d->plan->levels - 1, k, stream); // the per-level launches, never the program
 }
 static int build_schur(cholamd_device *d, int k)
 {
@@ -1795,8 +1646,8 @@ template <class TL> static int schur_inverses(cholamd_device *d, const TL *d_are
 {
   for (int lvl = k; lvl < d->plan->levels; lvl++) {
     const solve_dev &s = d->sv[lvl];
-    HIPCHK((hipError_t)lsolve_dinv(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, st));
-    if (s.w256_off >= 0 && d->w256) HIPCHK((hipError_t)lsolve_inv256(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, d->w256 + s.w256_off, st));
+    HIPCHK((hipError_t)chol_launch_solve_dinv(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, st));
+    if (s.w256_off >= 0 && d->w256) HIPCHK((hipError_t)chol_launch_solve_inv256(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, d->w256 + s.w256_off, st));
   }
   return 0;
 }
@@ -1820,7 +1671,7 @@ template <class TL> static int schur_condense_t(cholamd_device *d, const TL *d_a
   for (int lvl = L - 1; lvl >= k; lvl--) { // forward sweep under the cut: TRSV per separator, then its panel into the ancestors (the kept ones included)
     const solve_dev &s = d->sv[lvl];
     HIPCHK((hipError_t)lsolve_trsv(d, d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, d_w, 0, s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr, st));
-    HIPCHK((hipError_t)lsolve_off(d_arena, s.bw, s.ifw, s.n_ifw, d_w, 0, st));
+    HIPCHK((hipError_t)chol_launch_solve_offdiag(d_arena, s.bw, s.ifw, s.n_ifw, d_w, 0, st));
   }
   if (m > 0) HIPCHK(hipMemcpyAsync(d_g, d_w + t0, mb, hipMemcpyDeviceToDevice, st)); // the tail of the permuted vector is g, in Schur order
   return 0;
@@ -1845,7 +1696,7 @@ template <class TL> static int schur_expand_t(cholamd_device *d, const TL *d_are
   { int rc = schur_inverses(d, d_arena, k, st); if (rc) return rc; } // as at the start of every half solve: the arena of the call before may have been another
   for (int lvl = k; lvl < L; lvl++) { // backward sweep under the cut: gather from the ancestors, then TRSV^T
     const solve_dev &s = d->sv[lvl];
-    HIPCHK((hipError_t)lsolve_off(d_arena, s.bw, s.ibw, s.n_ibw, y, 1, st));
+    HIPCHK((hipError_t)chol_launch_solve_offdiag(d_arena, s.bw, s.ibw, s.n_ibw, y, 1, st));
     HIPCHK((hipError_t)lsolve_trsv(d, d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, y, 1, s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr, st));
   }
   HIPCHK((hipError_t)chol_launch_permute(y, d->perm, d_x, n, 1, st));
@@ -1995,7 +1846,7 @@ static int run_updates(std::vector<chol_upd_task> &tasks, std::vector<chol_upd_s
   int rc = sc.put(&dt, tasks.data(), tasks.size(), st);
   if (!rc) rc = sc.put(&ds, srcs.data(), srcs.size(), st);
   if (rc) return rc;
-  HIPCHK((hipError_t)chol_launch_update(nullptr, dt, ds, (int)tasks.size(), st));
+  HIPCHK((hipError_t)chol_launch_update((double *)nullptr, dt, ds, (int)tasks.size(), st));
   HIPCHK(hipStreamSynchronize(st));
   return 0;
 }
@@ -2021,7 +1872,7 @@ static int run_trsm(const double *Lp, int n, int ldl, const std::vector<chol_trs
   rc = sc.put(&dd, v.data(), v.size(), st);
   if (rc) return rc;
   if (n <= CHOL_TRSM_W_MAXN) HIPCHK((hipError_t)chol_launch_trsm_w(nullptr, nullptr, dd, (int)v.size(), st));
-  else if (n <= CHOL_RR_MAXN) HIPCHK((hipError_t)chol_launch_trsm(nullptr, nullptr, dd, (int)v.size(), st));
+  else if (n <= CHOL_RR_MAXN) HIPCHK((hipError_t)chol_launch_trsm((double *)nullptr, nullptr, dd, (int)v.size(), st));
   else HIPCHK((hipError_t)chol_launch_trsm_big(nullptr, nullptr, dd, (int)v.size(), st));
   HIPCHK(hipStreamSynchronize(st));
   return 0;
@@ -2661,6 +2512,12 @@ static void exchange_pieces(const cholamd_device *d, const std::vector<level_dev
   int64_t st = 0; // staging slots of the pieces this rank owns: one copy per contributing rank other than itself, senders in rank order
   for (xpiece &x : out) if (x.owner == d->rank) { x.stage = st; st += x.count * __builtin_popcount(x.contrib & ~(1u << d->rank)); }
 }
+// Multi-GPU: which entries of A a rank's fill scatters.  Everything under the cut on every rank (the panels of the other ranks' subtrees are
+// never read).  The shared top of the tree (the tail of the arena) must start from A on exactly ONE rank per element, so that the sum over
+// the ranks after the local levels is A_top - all contributions: with replicated top levels (one all-reduce of the tail) that is rank 0; with
+// the top levels distributed by column blocks it is the block's OWNER -- the extend-add exchange then carries a block only from the ranks whose
+// subtrees reach it (chol_top_contributors), and rank 0 sends no more than any other rank.  `*below` = leading entries of (a_dst, a_val) to
+// scatter; (*tdst, *tval, *ntop) = further entries (device arrays).  f32: the fp32 schedule's column blocks.
 static int top_entries(cholamd_device *d, int f32, int64_t *below, const int64_t **tdst, const double **tval, int64_t *ntop, hipStream_t st)
 {
   const cholamd_plan *p = d->plan;
@@ -2814,38 +2671,96 @@ template <class T> static int bcast_rank_t(cholamd_device *d, const level_dev &l
   NCCLCHK(ncclGroupEnd());
   return 0;
 }
-static int bcast_rank(cholamd_device *d, const level_dev &l, const chol_phase &ph, double *d_arena, cholamd_comm *c, hipStream_t st)
+// ---- the level-by-level factor, written once for both element types of the arena ----
+// T = double: the fp64 schedule (lv) and workspace; T = float: the fp32 ones, which ensure_f32 builds at the first call that needs them
+template <class T> static const std::vector<level_dev> &levels_of(const cholamd_device *d) { if constexpr (sizeof(T) == 4) return d->lv32; else return d->lv; }
+template <class T> static T *ws_of(const cholamd_device *d) { if constexpr (sizeof(T) == 4) return d->ws32; else return d->ws; }
+template <class T> static int device_fill(cholamd_device *d, T *d_arena, hipStream_t st)
 {
-  return bcast_rank_t<double>(d, l, ph, d_arena, c, st);
+  constexpr bool F32 = sizeof(T) == 4;
+  HIPCHK(hipSetDevice(d->dev));
+  if constexpr (F32) { int rc = ensure_f32(d, st); if (rc) return rc; } // the fp32 schedule's column blocks decide which entries of the shared top are this rank's
+  { int rc = clear_owned(d, d_arena, sizeof(T), st); if (rc) return rc; }
+  int64_t below = 0, ntop = 0; const int64_t *tdst = nullptr; const double *tval = nullptr;
+  { int rc = top_entries(d, F32, &below, &tdst, &tval, &ntop, st); if (rc) return rc; }
+  HIPCHK((hipError_t)chol_launch_scatter(d_arena, d->a_dst, d->a_val, below, st));
+  if (ntop > 0) HIPCHK((hipError_t)chol_launch_scatter(d_arena, tdst, tval, ntop, st));
+  return 0;
 }
-static int factor_levels_f32_comm(cholamd_device *d, float *d_arena32, int level_hi, int level_lo, cholamd_comm *c, hipStream_t st);
-extern "C" int cholamd_factor_sharded(cholamd_device *d, double *d_arena, cholamd_comm *c, void *stream)
+extern "C" int cholamd_device_fill(cholamd_device *d, double *d_arena, void *stream) { return device_fill(d, d_arena, (hipStream_t)stream); }
+extern "C" int cholamd_device_fill_f32(cholamd_device *d, float *d_arena32, void *stream) { return device_fill(d, d_arena32, (hipStream_t)stream); }
+template <class T> static int launch_phase(cholamd_device *d, const level_dev &l, const chol_phase &ph, T *d_arena, hipStream_t st)
+{
+  constexpr bool F32 = sizeof(T) == 4;
+  T *const ws = ws_of<T>(d);
+  const int kind = F32 && ph.kind == 4 ? 1 : ph.kind; // the one-wave strips of kind 4 are an fp64 kernel: the fp32 factor takes them like kind 1
+  if (kind == 0) HIPCHK((hipError_t)chol_launch_potrf(d_arena, ws, l.potrf + ph.first, ph.n, d->info, st));
+  else if (kind == 1) HIPCHK((hipError_t)chol_launch_trsm(d_arena, ws, l.trsm + ph.first, ph.n, st));
+  else if (kind == 7) HIPCHK((hipError_t)chol_launch_trsm_wt(d_arena, ws, l.trsm + ph.first, ph.n, st));
+  else if (kind == 2) HIPCHK((hipError_t)chol_launch_update(d_arena, l.task + ph.first, l.src, ph.n, st));
+  else if (kind == 3) HIPCHK((hipError_t)chol_launch_update_mt(d_arena, l.task_mt + ph.first, l.src, ph.n, (int64_t)d->plan->arena, st));
+  else if constexpr (F32) { chol_set_error("internal: phase kind %d in the fp32 schedule", ph.kind); return CHOLAMD_ERR_ARG; }
+  else if (kind == 4) HIPCHK((hipError_t)chol_launch_trsm_w(d_arena, ws, l.trsm + ph.first, ph.n, st));
+  else if (kind == 5) { // the fused launch (fp64 only)
+    // the progress words (epoch * 64 + columns) and the count of finished TRSM workgroups are monotonic across launches:
+    // both start over, in stream order, long before either can wrap
+    if (d->epoch >= (1 << 24) || d->done_total >= (1 << 30)) { HIPCHK(hipMemsetAsync(d->progress, 0, (size_t)(d->plan->nsep + 2) * sizeof(int), st)); d->epoch = 0; d->done_total = 0; }
+    d->epoch++;
+    if (ph.n3 > 0) d->done_total += (ph.n2 + 2) / 3; // TRSM workgroups of this launch count themselves out only when update tasks ride along
+    HIPCHK((hipError_t)chol_launch_potrf_trsm(d_arena, ws, l.potrf + ph.first, ph.n, l.trsm + ph.first2, ph.n2, l.task + ph.first3, l.src, ph.n3,
+                                              d->info, d->progress, d->epoch * 64, d->progress + d->plan->nsep + 1, d->done_total, st));
+  }
+  return 0;
+}
+// levels [level_lo, level_hi] of one rank; a broadcast phase (kind 6: distributed top levels: the step's column blocks travel from their owners to every
+// rank) goes through `c`
+template <class T> static int factor_levels_comm(cholamd_device *d, T *d_arena, int level_hi, int level_lo, cholamd_comm *c, hipStream_t st)
+{
+  HIPCHK(hipSetDevice(d->dev));
+  if constexpr (sizeof(T) == 4) { int rc = ensure_f32(d, st); if (rc) return rc; }
+  const int L = d->plan->levels;
+  if (level_hi >= L) level_hi = L - 1;
+  if (level_lo < 0) level_lo = 0;
+  if (level_hi == L - 1) HIPCHK(hipMemsetAsync(d->info, 0, 2 * sizeof(int), st));
+  d->info_last = d->info; d->info_foreign = true; // slot 0: the level-by-level paths
+  for (int lvl = level_hi; lvl >= level_lo; lvl--) { // mmat.rg:1227
+    const level_dev &l = levels_of<T>(d)[lvl];
+    for (const chol_phase &ph : l.phase) {
+      if (ph.kind == 6) {
+        scoped_timer t(d, st, CHOL_TK_BCAST, ph.n > 0);
+        int rc = bcast_rank_t<T>(d, l, ph, d_arena, c, st);
+        if (rc) return rc;
+        continue;
+      }
+      scoped_timer t(d, st, ph.kind == 3 ? 2 : (ph.kind == 4 || ph.kind == 7) ? 1 : ph.kind == 5 ? 0 : ph.kind, ph.n > 0);
+      int rc = launch_phase<T>(d, l, ph, d_arena, st);
+      if (rc) return rc;
+    }
+  }
+  return 0;
+}
+extern "C" int cholamd_factor_levels(cholamd_device *d, double *d_arena, int level_hi, int level_lo, void *stream)
+{ return factor_levels_comm(d, d_arena, level_hi, level_lo, nullptr, (hipStream_t)stream); }
+extern "C" int cholamd_factor_levels_f32(cholamd_device *d, float *d_arena32, int level_hi, int level_lo, void *stream)
+{ return factor_levels_comm(d, d_arena32, level_hi, level_lo, nullptr, (hipStream_t)stream); }
+extern "C" int cholamd_factor_f32(cholamd_device *d, float *d_arena32, void *stream) { return cholamd_factor_levels_f32(d, d_arena32, d->plan->levels - 1, 0, stream); }
+// one rank of a sharded factorisation: its subtrees' levels, the extend-add exchange of the shared top, the top levels.  The fp32 factor (BASELINE config 5:
+// mixed precision x multi-GPU): an fp32 arena of the fp64 arena's element layout, the fp32 schedule partitioned like the fp64 one, the exchange and the
+// broadcasts on floats
+template <class T> static int factor_sharded(cholamd_device *d, T *d_arena, cholamd_comm *c, hipStream_t st)
 {
   const int L = d->plan->levels, split = chol_split_level(d->world);
-  if (d->world == 1) return cholamd_factor(d, d_arena, stream);
-  int rc = cholamd_factor_levels(d, d_arena, L - 1, split, stream);
+  if (d->world == 1) { if constexpr (sizeof(T) == 4) return cholamd_factor_f32(d, d_arena, st); else return cholamd_factor(d, d_arena, st); } // (fp64: the program launch)
+  int rc = factor_levels_comm(d, d_arena, L - 1, split, nullptr, st);
   if (!rc) {
-    scoped_timer t(d, (hipStream_t)stream, CHOL_TK_EXCHANGE, true);
-    rc = cholamd_exchange_tail(d, d_arena, c, stream);
+    scoped_timer t(d, st, CHOL_TK_EXCHANGE, true);
+    rc = exchange_tail_t<T>(d, d_arena, levels_of<T>(d), c, st);
   }
-  if (!rc) rc = factor_levels_comm(d, d_arena, split - 1, 0, c, (hipStream_t)stream);
+  if (!rc) rc = factor_levels_comm(d, d_arena, split - 1, 0, c, st);
   return rc;
 }
-// the same with the fp32 factor (BASELINE config 5: mixed precision x multi-GPU): fp32 arena of the fp64 arena's element layout, the
-// fp32 schedule partitioned like the fp64 one, the exchange and the broadcasts on floats
-extern "C" int cholamd_factor_sharded_f32(cholamd_device *d, float *d_arena32, cholamd_comm *c, void *stream)
-{
-  const int L = d->plan->levels, split = chol_split_level(d->world);
-  if (d->world == 1) return cholamd_factor_f32(d, d_arena32, stream);
-  int rc = ensure_f32(d, (hipStream_t)stream);
-  if (!rc) rc = factor_levels_f32_comm(d, d_arena32, L - 1, split, nullptr, (hipStream_t)stream);
-  if (!rc) {
-    scoped_timer t(d, (hipStream_t)stream, CHOL_TK_EXCHANGE, true);
-    rc = exchange_tail_t<float>(d, d_arena32, d->lv32, c, (hipStream_t)stream);
-  }
-  if (!rc) rc = factor_levels_f32_comm(d, d_arena32, split - 1, 0, c, (hipStream_t)stream);
-  return rc;
-}
+extern "C" int cholamd_factor_sharded(cholamd_device *d, double *d_arena, cholamd_comm *c, void *stream) { return factor_sharded(d, d_arena, c, (hipStream_t)stream); }
+extern "C" int cholamd_factor_sharded_f32(cholamd_device *d, float *d_arena32, cholamd_comm *c, void *stream) { return factor_sharded(d, d_arena32, c, (hipStream_t)stream); }
 
 // ---- one process driving n ranks ----
 struct ptr_pack { void *p[CHOL_LOCAL_MAX]; };
@@ -2927,7 +2842,6 @@ template <class T> static int local_bcast(cholamd_device *const *devs, T *const 
   }
   return 0;
 }
-static int launch_phase_f32(cholamd_device *d, const level_dev &l, const chol_phase &ph, float *d_arena32, hipStream_t st);
 // T = double: the fp64 schedule (devs[g]->lv); T = float: the fp32 one (lv32)
 template <class T> static int factor_multi_t(cholamd_device *const *devs, T *const *arenas, cholamd_comm *const *comms, int n, void *const *streams)
 { // one process, n ranks: everything is asynchronous on each rank's stream
@@ -2939,22 +2853,19 @@ template <class T> static int factor_multi_t(cholamd_device *const *devs, T *con
     if (devs[g]->world != n || devs[g]->rank != g) { chol_set_error("device %d is not partitioned as rank %d of %d", g, g, n); return CHOLAMD_ERR_ARG; }
     if (comm_matches(devs[g], comms[g])) return CHOLAMD_ERR_ARG;
     if (comms[g]->local != G || (!G && !comms[g]->comm)) { chol_set_error("the %d communicators are not of one kind", n); return CHOLAMD_ERR_ARG; }
-    int rc;
-    if (F32) { rc = ensure_f32(devs[g], stream_of(streams, g)); if (!rc) rc = factor_levels_f32_comm(devs[g], (float *)arenas[g], L - 1, split, nullptr, stream_of(streams, g)); }
-    else rc = cholamd_factor_levels(devs[g], (double *)arenas[g], L - 1, split, stream_of(streams, g));
+    int rc = factor_levels_comm(devs[g], arenas[g], L - 1, split, nullptr, stream_of(streams, g));
     if (rc) return rc;
   }
-  auto levels_of = [&](int g) -> const std::vector<level_dev> & { return F32 ? devs[g]->lv32 : devs[g]->lv; };
-  if (G) { int rc = local_exchange<T>(devs, arenas, levels_of(0), G, n, streams); if (rc) return rc; }
+  if (G) { int rc = local_exchange<T>(devs, arenas, levels_of<T>(devs[0]), G, n, streams); if (rc) return rc; }
   else {
     NCCLCHK(ncclGroupStart());
     for (int g = 0; g < n; g++) {
-      int rc = exchange_tail_t<T>(devs[g], arenas[g], levels_of(g), comms[g], stream_of(streams, g), true);
+      int rc = exchange_tail_t<T>(devs[g], arenas[g], levels_of<T>(devs[g]), comms[g], stream_of(streams, g), true);
       if (rc) { (void)ncclGroupEnd(); return rc; }
     }
     NCCLCHK(ncclGroupEnd());
     // the owners' sums go behind the sends and receives, which entered the streams only now (the end of the outermost group)
-    for (int g = 0; g < n; g++) { int rc = exchange_sum_t<T>(devs[g], arenas[g], levels_of(g), stream_of(streams, g)); if (rc) return rc; }
+    for (int g = 0; g < n; g++) { int rc = exchange_sum_t<T>(devs[g], arenas[g], levels_of<T>(devs[g]), stream_of(streams, g)); if (rc) return rc; }
   }
   // top levels: every rank runs its phases up to its next broadcast phase; the broadcasts of all ranks form one group
   for (int lvl = split - 1; lvl >= 0; lvl--) {
@@ -2962,10 +2873,10 @@ template <class T> static int factor_multi_t(cholamd_device *const *devs, T *con
     for (;;) {
       int at_bcast = 0;
       for (int g = 0; g < n; g++) {
-        const level_dev &l = levels_of(g)[lvl];
+        const level_dev &l = levels_of<T>(devs[g])[lvl];
         HIPCHK(hipSetDevice(devs[g]->dev));
         while (cur[g] < l.phase.size() && l.phase[cur[g]].kind != 6) {
-          int rc = F32 ? launch_phase_f32(devs[g], l, l.phase[cur[g]], (float *)arenas[g], stream_of(streams, g)) : launch_phase(devs[g], l, l.phase[cur[g]], (double *)arenas[g], stream_of(streams, g));
+          int rc = launch_phase(devs[g], l, l.phase[cur[g]], arenas[g], stream_of(streams, g));
           if (rc) return rc;
           cur[g]++;
         }
@@ -2973,11 +2884,11 @@ template <class T> static int factor_multi_t(cholamd_device *const *devs, T *con
       }
       if (at_bcast == 0) break;
       if (at_bcast != n) { chol_set_error("internal: the ranks disagree on the broadcast sequence of level %d", lvl); return CHOLAMD_ERR_ARG; }
-      if (G) { int rc = local_bcast<T>(devs, arenas, G, n, streams, levels_of(0)[lvl], levels_of(0)[lvl].phase[cur[0]]); if (rc) return rc; }
+      if (G) { int rc = local_bcast<T>(devs, arenas, G, n, streams, levels_of<T>(devs[0])[lvl], levels_of<T>(devs[0])[lvl].phase[cur[0]]); if (rc) return rc; }
       else {
         NCCLCHK(ncclGroupStart());
         for (int g = 0; g < n; g++) {
-          const level_dev &l = levels_of(g)[lvl];
+          const level_dev &l = levels_of<T>(devs[g])[lvl];
           const chol_phase &ph = l.phase[cur[g]];
           for (int i = ph.first; i < ph.first + ph.n; i++) {
             const chol_bcast &b = l.bcast[i];

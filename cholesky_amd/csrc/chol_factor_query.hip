@@ -114,14 +114,14 @@ __global__ __launch_bounds__(FQ_THREADS) void k_factor_logdet_sum(const double *
 }
 
 template <class TL>
-static int launch_factor_diag_t(const TL *base, const chol_trsv_desc *descs, const int *prefix, int nd, int n, const int *perm, double *diag, hipStream_t st)
+int chol_launch_factor_diag(const TL *base, const chol_trsv_desc *descs, const int *prefix, int nd, int n, const int *perm, double *diag, hipStream_t st)
 {
   if (n <= 0 || nd <= 0) return 0;
   hipLaunchKernelGGL(k_factor_diag<TL>, dim3((n + FQ_THREADS - 1) / FQ_THREADS), dim3(FQ_THREADS), 0, st, base, descs, prefix, nd, n, perm, diag);
   return (int)hipGetLastError();
 }
 template <class TL>
-static int launch_factor_logdet_t(const TL *base, const chol_trsv_desc *descs, const int *prefix, int nd, int n, double *part, int64_t *ipart, int64_t *res, hipStream_t st)
+int chol_launch_factor_logdet(const TL *base, const chol_trsv_desc *descs, const int *prefix, int nd, int n, double *part, int64_t *ipart, int64_t *res, hipStream_t st)
 {
   int nblk = (n + FQ_THREADS - 1) / FQ_THREADS;
   if (nblk > CHOL_LOGDET_MAX_BLOCKS) nblk = CHOL_LOGDET_MAX_BLOCKS;
@@ -135,13 +135,7 @@ static int launch_factor_logdet_t(const TL *base, const chol_trsv_desc *descs, c
   return (int)hipGetLastError();
 }
 
-extern "C" {
-int chol_launch_factor_diag(const double *base, const chol_trsv_desc *descs, const int *prefix, int nd, int n, const int *perm, double *diag, hipStream_t st)
-{ return launch_factor_diag_t(base, descs, prefix, nd, n, perm, diag, st); }
-int chol32_launch_factor_diag(const float *base, const chol_trsv_desc *descs, const int *prefix, int nd, int n, const int *perm, double *diag, hipStream_t st)
-{ return launch_factor_diag_t(base, descs, prefix, nd, n, perm, diag, st); }
-int chol_launch_factor_logdet(const double *base, const chol_trsv_desc *descs, const int *prefix, int nd, int n, double *part, int64_t *ipart, int64_t *res, hipStream_t st)
-{ return launch_factor_logdet_t(base, descs, prefix, nd, n, part, ipart, res, st); }
-int chol32_launch_factor_logdet(const float *base, const chol_trsv_desc *descs, const int *prefix, int nd, int n, double *part, int64_t *ipart, int64_t *res, hipStream_t st)
-{ return launch_factor_logdet_t(base, descs, prefix, nd, n, part, ipart, res, st); }
-}
+template int chol_launch_factor_diag(const double *, const chol_trsv_desc *, const int *, int, int, const int *, double *, hipStream_t);
+template int chol_launch_factor_diag(const float *, const chol_trsv_desc *, const int *, int, int, const int *, double *, hipStream_t);
+template int chol_launch_factor_logdet(const double *, const chol_trsv_desc *, const int *, int, int, double *, int64_t *, int64_t *, hipStream_t);
+template int chol_launch_factor_logdet(const float *, const chol_trsv_desc *, const int *, int, int, double *, int64_t *, int64_t *, hipStream_t);

@@ -1,12 +1,12 @@
-/* Launchers of the HIP kernels in chol_kernels.hip (internal). */
+/* Launchers of the HIP kernels (internal, C++).  A launcher that works on the factor takes either precision under one name and resolves on the pointer type of
+ * the factor: `template <class TL>` where one kernel template serves both (TL = double or float, explicitly instantiated for the two in the defining .hip:
+ * the streamed, block and deterministic solves, the factor queries, the products), a pair of overloads where fp64 and fp32 are different kernels
+ * (chol_kernels.hip / chol_kernels_f32.hip: scatter, potrf, trsm, trsm_wt, update, update_mt).  Everything else exists for the fp64 factor only. */
 #ifndef CHOL_KERNELS_H
 #define CHOL_KERNELS_H
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 #include "chol_plan.h"
-#ifdef __cplusplus
-extern "C" {
-#endif
 int chol_launch_scatter(double *arena, const int64_t *dst, const double *val, int64_t nnz, hipStream_t st);
 /* new values of A (cholamd_device_set_values): `parts` = CHOL_VALUES_STATUS (the four status words of the value array, which start at
  * { 0, INT64_MAX, 0, INT64_MAX }) | CHOL_VALUES_GATHER (a_val[e] = vals[a_src[e]], csr_val[k] = vals[csr_src[k]]) in one launch */
@@ -31,40 +31,34 @@ int chol_launch_trsm(double *base, const double *ws, const chol_trsm_desc *descs
 int chol_launch_update(double *base, const chol_upd_task *tasks, const chol_upd_src *srcs, int ntask, hipStream_t st);
 int chol_launch_update_mt(double *base, const chol_upd_task *tasks, const chol_upd_src *srcs, int ntask, int64_t arena_elems, hipStream_t st);
 int chol_launch_permute(const double *in, const int *perm, double *out, int n, int inverse, hipStream_t st);
-int chol_launch_solve_dinv(const double *base, const chol_trsv_desc *descs, int n, int max_n, double *W, hipStream_t st);
-int chol_launch_solve_trsv(const double *base, const chol_trsv_desc *descs, int n, int max_n, int max_under, const double *W, double *y, int backward, int *flags, int *gen, const double *W256, double *xt, hipStream_t st);
+template <class TL> int chol_launch_solve_dinv(const TL *base, const chol_trsv_desc *descs, int n, int max_n, double *W, hipStream_t st);
+/* flags / gen: STEP flags of the device object (one int per separator of a top level, zero at allocation) and its launch counter (host) -- the step launches
+ * of the wide top separators (k_solve_step); NULL: launch by launch */
+template <class TL> int chol_launch_solve_trsv(const TL *base, const chol_trsv_desc *descs, int n, int max_n, int max_under, const double *W, double *y, int backward, int *flags, int *gen, const double *W256, double *xt, hipStream_t st);
 /* explicit inverses of the 256-column diagonal spans of a level's separators (levels of at most 8 separators wider than a span): W256[(separator * spans + span) * 65536
  * + column * 256 + row], from the 16x16 inverses W16 of chol_launch_solve_dinv; passed to chol_launch_solve_trsv (with xt: 8 x 256 doubles of scratch) they turn
  * the span solve of the step launches into a matrix-vector product over sixteen workgroups (k_solve_stepw); NULL: k_solve_step */
 #define CHOL_STEPW_MAX_SEPS 128 /* most separators of a level that takes the step launches with explicit span inverses: flags = 16 ints, xt = 256 doubles per separator */
-int chol_launch_solve_inv256(const double *base, const chol_trsv_desc *descs, int n, int max_n, const double *W16, double *W256, hipStream_t st);
-int chol32_launch_solve_inv256(const float *base, const chol_trsv_desc *descs, int n, int max_n, const double *W16, double *W256, hipStream_t st);
-int chol_launch_solve_offdiag(const double *base, const chol_gemv_desc *blocks, const int *items, int n_items, double *y, int backward, hipStream_t st);
+template <class TL> int chol_launch_solve_inv256(const TL *base, const chol_trsv_desc *descs, int n, int max_n, const double *W16, double *W256, hipStream_t st);
+template <class TL> int chol_launch_solve_offdiag(const TL *base, const chol_gemv_desc *blocks, const int *items, int n_items, double *y, int backward, hipStream_t st);
 int chol_launch_trsv_fwd(const double *base, const chol_trsv_desc *descs, int n, double *y, hipStream_t st);
 int chol_launch_gemv_fwd(const double *base, const chol_gemv_desc *descs, const int *grp_start, const int *grp_rows, int ngroups, double *y, hipStream_t st);
 int chol_launch_bwd(const double *base, const chol_trsv_desc *descs, const chol_gemv_desc *gd, const int *gstart, int n, double *y, hipStream_t st);
 /* fp32 factor (chol_kernels_f32.hip) and the fp64 refinement helpers */
-int chol32_launch_scatter(float *arena, const int64_t *dst, const double *val, int64_t nnz, hipStream_t st);
-int chol32_launch_potrf(float *base, float *ws, const chol_potrf_desc *descs, int n, int *info, hipStream_t st);
-int chol32_launch_trsm(float *base, const float *ws, const chol_trsm_desc *descs, int n, hipStream_t st);
-int chol32_launch_trsm_wt(float *base, const float *ws, const chol_trsm_desc *descs, int n, hipStream_t st);
-int chol32_launch_update(float *base, const chol_upd_task *tasks, const chol_upd_src *srcs, int ntask, hipStream_t st);
-int chol32_launch_update_mt(float *base, const chol_upd_task *tasks, const chol_upd_src *srcs, int ntask, int64_t arena_elems, hipStream_t st);
-int chol32_launch_solve_dinv(const float *base, const chol_trsv_desc *descs, int n, int max_n, double *W, hipStream_t st);
-/* flags / gen: STEP flags of the device object (one int per separator of a top level, zero at allocation) and its launch counter (host) -- the step launches
- * of the wide top separators (k_solve_step); NULL: launch by launch */
-int chol32_launch_solve_trsv(const float *base, const chol_trsv_desc *descs, int n, int max_n, int max_under, const double *W, double *y, int backward, int *flags, int *gen, const double *W256, double *xt, hipStream_t st);
-int chol32_launch_solve_offdiag(const float *base, const chol_gemv_desc *blocks, const int *items, int n_items, double *y, int backward, hipStream_t st);
+int chol_launch_scatter(float *arena, const int64_t *dst, const double *val, int64_t nnz, hipStream_t st);
+int chol_launch_potrf(float *base, float *ws, const chol_potrf_desc *descs, int n, int *info, hipStream_t st);
+int chol_launch_trsm(float *base, const float *ws, const chol_trsm_desc *descs, int n, hipStream_t st); /* (the fp32 schedule's kinds 1 and 4) */
+int chol_launch_trsm_wt(float *base, const float *ws, const chol_trsm_desc *descs, int n, hipStream_t st);
+int chol_launch_update(float *base, const chol_upd_task *tasks, const chol_upd_src *srcs, int ntask, hipStream_t st);
+int chol_launch_update_mt(float *base, const chol_upd_task *tasks, const chol_upd_src *srcs, int ntask, int64_t arena_elems, hipStream_t st);
 int chol_launch_residual(const int64_t *ptr, const int *col, const double *val, const double *b, const double *x, double *r, int n, double *partial, hipStream_t st);
 int chol_launch_axpy1(double *x, const double *dx, int n, hipStream_t st);
 /* block solve (chol_solve_nrhs.hip): right-hand sides in chunks of CHOL_NRHS_W columns in a permuted block Y (n x CHOL_NRHS_W, row-major); W16 / W256 as for
  * chol_launch_solve_trsv (W256 NULL: the substitution chain of the 16x16 inverses) */
 #define CHOL_NRHS_W 32
 int chol_nrhs_launch_permute(const double *B, int64_t ldb, const int *perm, double *Y, double *X, int64_t ldx, int n, int c0, int cols, int inverse, hipStream_t st);
-int chol_nrhs_launch_trsv(const double *base, const chol_trsv_desc *descs, int n, int max_n, int max_under, const double *W16, const double *W256, double *Y, int backward, hipStream_t st);
-int chol32_nrhs_launch_trsv(const float *base, const chol_trsv_desc *descs, int n, int max_n, int max_under, const double *W16, const double *W256, double *Y, int backward, hipStream_t st);
-int chol_nrhs_launch_offdiag(const double *base, const chol_gemv_desc *blocks, const int *items, int n_items, double *Y, int backward, hipStream_t st);
-int chol32_nrhs_launch_offdiag(const float *base, const chol_gemv_desc *blocks, const int *items, int n_items, double *Y, int backward, hipStream_t st);
+template <class TL> int chol_nrhs_launch_trsv(const TL *base, const chol_trsv_desc *descs, int n, int max_n, int max_under, const double *W16, const double *W256, double *Y, int backward, hipStream_t st);
+template <class TL> int chol_nrhs_launch_offdiag(const TL *base, const chol_gemv_desc *blocks, const int *items, int n_items, double *Y, int backward, hipStream_t st);
 /* R(:, j) = B(:, j) - A X(:, j), j < cols; partial[2 (j * nb + blk) + {0, 1}] = the row block's sum of r^2 / b^2, nb = (n + 255) / 256 */
 int chol_nrhs_launch_residual(const int64_t *ptr, const int *col, const double *val, const double *B, int64_t ldb, const double *X, int64_t ldx, double *R, int64_t ldr,
                               int n, int cols, double *partial, hipStream_t st);
@@ -75,10 +69,8 @@ int chol_nrhs_launch_axpy(double *X, int64_t ldx, const double *D, int64_t ldd, 
  * partials in a fixed order, as pairs) writes res[0] = the bits of the fp64 sum, res[1] = bad entries, res[2] = the first one's position.  No atomics.
  * part: 2 * CHOL_LOGDET_MAX_BLOCKS doubles, ipart: 2 * CHOL_LOGDET_MAX_BLOCKS int64, res: 3 int64. */
 #define CHOL_LOGDET_MAX_BLOCKS 1024
-int chol_launch_factor_diag(const double *base, const chol_trsv_desc *descs, const int *prefix, int nd, int n, const int *perm, double *diag, hipStream_t st);
-int chol32_launch_factor_diag(const float *base, const chol_trsv_desc *descs, const int *prefix, int nd, int n, const int *perm, double *diag, hipStream_t st);
-int chol_launch_factor_logdet(const double *base, const chol_trsv_desc *descs, const int *prefix, int nd, int n, double *part, int64_t *ipart, int64_t *res, hipStream_t st);
-int chol32_launch_factor_logdet(const float *base, const chol_trsv_desc *descs, const int *prefix, int nd, int n, double *part, int64_t *ipart, int64_t *res, hipStream_t st);
+template <class TL> int chol_launch_factor_diag(const TL *base, const chol_trsv_desc *descs, const int *prefix, int nd, int n, const int *perm, double *diag, hipStream_t st);
+template <class TL> int chol_launch_factor_logdet(const TL *base, const chol_trsv_desc *descs, const int *prefix, int nd, int n, double *part, int64_t *ipart, int64_t *res, hipStream_t st);
 /* selected inversion (chol_selinv.hip): one column-block step of one tree level -- block nblk - 1 - step of the first n_act separators of the level's list
  * (chol_selinv_level, uploaded as it is): L_JJ^-1, Y, the gather-product Z[below, J] and the diagonal block Z[J, J], four launches, no atomics.
  * max_below_tiles: the most 16-row tiles any of them has below the block.  ws: the level's workspace (chol_selinv_level.ws_doubles).
@@ -93,29 +85,21 @@ int chol_launch_schur_gather(const double *arena, const chol_schur_desc *descs, 
  * permuted coordinates, z and y distinct; perm != NULL: the result goes to y[perm[pos]] (original dof order).  One owner per element, no atomics.
  * resid: res[0], res[1] = the bits of ||A z - w||^2 and ||A z||^2 (A as CSR in original dof order), res[2] = rows where either is not finite; two stages
  * with one partial pair per workgroup of 256 rows (part: 2 * ceil(n / 256) doubles, ipart: ceil(n / 256) int64), summed in a fixed order */
-int chol_launch_multiply(const double *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, const double *z, double *y, const int *perm, hipStream_t st);
-int chol32_launch_multiply(const float *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, const double *z, double *y, const int *perm, hipStream_t st);
+template <class TL> int chol_launch_multiply(const TL *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, const double *z, double *y, const int *perm, hipStream_t st);
 /* deterministic streamed solve (chol_solve_det.hip; chol_plan.h at chol_sdet_lists): the gather launch of one step, y[item] -= sum over the item's sources,
  * `items` = the step's first item, n_items of them, in permuted coordinates and in place (no source of a step is owned by an item of the step); one owner per
  * position, a fixed order, no atomics.  solve_span (chol_kernels.hip): the diagonal solve of the columns [col0, col0 + 256) of the n separators `descs`
  * (those with fewer columns do nothing) with the 16x16 inverses W of chol_launch_solve_dinv, plain stores */
-int chol_launch_solve_det_gather(const double *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, double *y, hipStream_t st);
-int chol32_launch_solve_det_gather(const float *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, double *y, hipStream_t st);
-int chol_launch_solve_span(const double *base, const chol_trsv_desc *descs, int n, const double *W, double *y, int col0, int backward, hipStream_t st);
-int chol32_launch_solve_span(const float *base, const chol_trsv_desc *descs, int n, const double *W, double *y, int col0, int backward, hipStream_t st);
+template <class TL> int chol_launch_solve_det_gather(const TL *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, double *y, hipStream_t st);
+template <class TL> int chol_launch_solve_span(const TL *base, const chol_trsv_desc *descs, int n, const double *W, double *y, int col0, int backward, hipStream_t st);
 /* block form (chol_multiply_nrhs.hip): the same items on a chunk of CHOL_NRHS_W columns, Zp the permuted row-major block of chol_nrhs_launch_permute.
  * perm != NULL (the last stage of a call): Y[perm[pos] + (c0 + j) ldy] for the chunk's columns j < cols; perm == NULL (the first stage of the full product):
  * Y is a second permuted block, all 32 columns written */
-int chol_launch_multiply_nrhs(const double *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, const double *Zp, double *Y, const int *perm,
-                              int64_t ldy, int c0, int cols, hipStream_t st);
-int chol32_launch_multiply_nrhs(const float *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, const double *Zp, double *Y, const int *perm,
-                                int64_t ldy, int c0, int cols, hipStream_t st);
+template <class TL> int chol_launch_multiply_nrhs(const TL *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, const double *Zp, double *Y, const int *perm,
+                                                  int64_t ldy, int c0, int cols, hipStream_t st);
 int chol_launch_multiply_resid(const int64_t *ptr, const int *col, const double *val, const double *z, const double *w, int n, double *part, int64_t *ipart, int64_t *res, hipStream_t st);
 /* diagnostic instance of the program launch (k_program<true>): 4 stamps per job, then CHOL_TRACE_X per job -- [0] follower: own tiles' wait over,
  * [1] its items, [2 + i] round of item i begun; [48 + k] POTRF job: column k published / TRSM job (first strip): column tile k on its channel;
  * [72 + k] POTRF job: the factor wave starts column k / TRSM job: the POTRF's column k seen */
 #define CHOL_TRACE_X 96
-#ifdef __cplusplus
-}
-#endif
 #endif

@@ -3377,7 +3377,7 @@ __global__ __launch_bounds__(256) void k_solve_gather_bwd(const TL *__restrict__
   if ((lane & 15) < 4 && c < ncol) unsafeAtomicAdd(&y[blocks[q0].y_off + cw + c], -sum);
 }
 
-template <class TL> static int launch_solve_dinv_t(const TL *base, const chol_trsv_desc *descs, int n, int max_n, double *W, hipStream_t st)
+template <class TL> int chol_launch_solve_dinv(const TL *base, const chol_trsv_desc *descs, int n, int max_n, double *W, hipStream_t st)
 {
   if (n <= 0 || max_n <= 0) return 0;
   hipLaunchKernelGGL(k_solve_dinv<TL>, dim3(n, (max_n + TS - 1) / TS), dim3(64), 0, st, base, descs, W);
@@ -3386,15 +3386,10 @@ template <class TL> static int launch_solve_dinv_t(const TL *base, const chol_tr
 #ifndef SOLVE_SPAN32
 #define SOLVE_SPAN32 1 /* 0: the fp32 factor's spans through k_solve_trsv<., float> like the fp64 factor's (A/B) */
 #endif
-template <bool BWD> static void launch_span(const double *base, const chol_trsv_desc *descs, int n, const double *W, double *y, int col0, hipStream_t st)
-{
-  hipLaunchKernelGGL((k_solve_trsv<BWD, double>), dim3(n), dim3(256), 0, st, base, descs, W, y, col0);
-}
-template <bool BWD> static void launch_span(const float *base, const chol_trsv_desc *descs, int n, const double *W, double *y, int col0, hipStream_t st)
-{
-  if (SOLVE_SPAN32) hipLaunchKernelGGL((k_solve_span32<BWD>), dim3(n), dim3(256), 0, st, base, descs, W, y, col0);
-  else hipLaunchKernelGGL((k_solve_trsv<BWD, float>), dim3(n), dim3(256), 0, st, base, descs, W, y, col0);
-}
+// one diagonal span of n separators: different kernels for the fp64 and the fp32 factor (defined with chol_launch_solve_span below, behind the explicit
+// instantiations: kernels are emitted in the order of their first use, and these keep their place at the end of the code object)
+static void launch_span(const double *base, const chol_trsv_desc *descs, int n, const double *W, double *y, int col0, bool bwd, hipStream_t st);
+static void launch_span(const float *base, const chol_trsv_desc *descs, int n, const double *W, double *y, int col0, bool bwd, hipStream_t st);
 #ifndef SOLVE_STEP32
 #define SOLVE_STEP32 1 /* 0: span and panel launch by launch at every level (A/B) */
 #endif
@@ -3441,8 +3436,8 @@ template <class TL> static bool launch_leaves(const TL *base, const chol_trsv_de
   return true;
 }
 template <class TL>
-static int launch_solve_trsv_t(const TL *base, const chol_trsv_desc *descs, int n, int max_n, int max_under, const double *W, double *y, int backward, int *flags, int *gen,
-                               const double *W256, double *xt, hipStream_t st)
+int chol_launch_solve_trsv(const TL *base, const chol_trsv_desc *descs, int n, int max_n, int max_under, const double *W, double *y, int backward, int *flags, int *gen,
+                           const double *W256, double *xt, hipStream_t st)
 { // all separators of a level; wide ones in spans of SSPAN columns: diagonal span by one workgroup each, the rows below by all CUs (max_under: the most
   // rows any separator of the level has to read under a span -- its band if it is a leaf; negative: every separator of the level is banded within one span)
   if (n <= 0) return 0;
@@ -3457,22 +3452,22 @@ static int launch_solve_trsv_t(const TL *base, const chol_trsv_desc *descs, int 
     const int below = min(max_n - (col0 + SSPAN), max_under); // rows under the span in the widest separator
     if (backward) {
       if (below > 0) hipLaunchKernelGGL((k_solve_panel<true, TL>), dim3(n, (below + SPANEL_BW_ROWS - 1) / SPANEL_BW_ROWS), dim3(256), 0, st, base, descs, y, col0);
-      launch_span<true>(base, descs, n, W, y, col0, st);
+      launch_span(base, descs, n, W, y, col0, true, st);
     } else {
-      launch_span<false>(base, descs, n, W, y, col0, st);
+      launch_span(base, descs, n, W, y, col0, false, st);
       if (below > 0) hipLaunchKernelGGL((k_solve_panel<false, TL>), dim3(n, (below + 255) / 256), dim3(256), 0, st, base, descs, y, col0);
     }
   }
   return (int)hipGetLastError();
 }
-template <class TL> static int launch_solve_inv256_t(const TL *base, const chol_trsv_desc *descs, int n, int max_n, const double *W16, double *W256, hipStream_t st)
+template <class TL> int chol_launch_solve_inv256(const TL *base, const chol_trsv_desc *descs, int n, int max_n, const double *W16, double *W256, hipStream_t st)
 {
   if (n <= 0 || max_n <= SSPAN) return 0;
   const int nspan = (max_n + SSPAN - 1) / SSPAN;
   hipLaunchKernelGGL(k_solve_inv256<TL>, dim3(n, nspan, SSPAN / TS), dim3(64), 0, st, base, descs, W16, W256, nspan);
   return (int)hipGetLastError();
 }
-template <class TL> static int launch_solve_offdiag_t(const TL *base, const chol_gemv_desc *blocks, const int *items, int n_items, double *y, int backward, hipStream_t st)
+template <class TL> int chol_launch_solve_offdiag(const TL *base, const chol_gemv_desc *blocks, const int *items, int n_items, double *y, int backward, hipStream_t st)
 {
   if (n_items <= 0) return 0;
   if (backward) hipLaunchKernelGGL(k_solve_gather_bwd<TL>, dim3(n_items), dim3(256), 0, st, base, blocks, items, y);
@@ -3481,10 +3476,8 @@ template <class TL> static int launch_solve_offdiag_t(const TL *base, const chol
 }
 
 // ------------------------------------------------------------------------------------------------
-// launchers (extern "C", called from chol_api.cpp)
+// launchers (chol_kernels.h, called from chol_api.cpp)
 // ------------------------------------------------------------------------------------------------
-extern "C" {
-
 int chol_launch_scatter(double *arena, const int64_t *dst, const double *val, int64_t nnz, hipStream_t st)
 {
   if (nnz <= 0) return 0;
@@ -3595,27 +3588,37 @@ int chol_launch_permute(const double *in, const int *perm, double *out, int n, i
   else hipLaunchKernelGGL(k_permute_in, dim3((n + 255) / 256), dim3(256), 0, st, in, perm, out, n);
   return (int)hipGetLastError();
 }
-int chol_launch_solve_dinv(const double *base, const chol_trsv_desc *descs, int n, int max_n, double *W, hipStream_t st) { return launch_solve_dinv_t(base, descs, n, max_n, W, st); }
-int chol_launch_solve_trsv(const double *base, const chol_trsv_desc *descs, int n, int max_n, int max_under, const double *W, double *y, int backward, int *flags, int *gen, const double *W256, double *xt, hipStream_t st) { return launch_solve_trsv_t(base, descs, n, max_n, max_under, W, y, backward, flags, gen, W256, xt, st); }
-int chol_launch_solve_inv256(const double *base, const chol_trsv_desc *descs, int n, int max_n, const double *W16, double *W256, hipStream_t st) { return launch_solve_inv256_t(base, descs, n, max_n, W16, W256, st); }
-int chol32_launch_solve_inv256(const float *base, const chol_trsv_desc *descs, int n, int max_n, const double *W16, double *W256, hipStream_t st) { return launch_solve_inv256_t(base, descs, n, max_n, W16, W256, st); }
-int chol_launch_solve_offdiag(const double *base, const chol_gemv_desc *blocks, const int *items, int n_items, double *y, int backward, hipStream_t st) { return launch_solve_offdiag_t(base, blocks, items, n_items, y, backward, st); }
-int chol32_launch_solve_dinv(const float *base, const chol_trsv_desc *descs, int n, int max_n, double *W, hipStream_t st) { return launch_solve_dinv_t(base, descs, n, max_n, W, st); }
-int chol32_launch_solve_trsv(const float *base, const chol_trsv_desc *descs, int n, int max_n, int max_under, const double *W, double *y, int backward, int *flags, int *gen, const double *W256, double *xt, hipStream_t st) { return launch_solve_trsv_t(base, descs, n, max_n, max_under, W, y, backward, flags, gen, W256, xt, st); }
-int chol32_launch_solve_offdiag(const float *base, const chol_gemv_desc *blocks, const int *items, int n_items, double *y, int backward, hipStream_t st) { return launch_solve_offdiag_t(base, blocks, items, n_items, y, backward, st); }
+template int chol_launch_solve_dinv(const double *, const chol_trsv_desc *, int, int, double *, hipStream_t);
+template int chol_launch_solve_trsv(const double *, const chol_trsv_desc *, int, int, int, const double *, double *, int, int *, int *, const double *, double *, hipStream_t);
+template int chol_launch_solve_inv256(const double *, const chol_trsv_desc *, int, int, const double *, double *, hipStream_t);
+template int chol_launch_solve_inv256(const float *, const chol_trsv_desc *, int, int, const double *, double *, hipStream_t);
+template int chol_launch_solve_offdiag(const double *, const chol_gemv_desc *, const int *, int, double *, int, hipStream_t);
+template int chol_launch_solve_dinv(const float *, const chol_trsv_desc *, int, int, double *, hipStream_t);
+template int chol_launch_solve_trsv(const float *, const chol_trsv_desc *, int, int, int, const double *, double *, int, int *, int *, const double *, double *, hipStream_t);
+template int chol_launch_solve_offdiag(const float *, const chol_gemv_desc *, const int *, int, double *, int, hipStream_t);
+static void launch_span(const double *base, const chol_trsv_desc *descs, int n, const double *W, double *y, int col0, bool bwd, hipStream_t st)
+{
+  if (bwd) hipLaunchKernelGGL((k_solve_trsv<true, double>), dim3(n), dim3(256), 0, st, base, descs, W, y, col0);
+  else hipLaunchKernelGGL((k_solve_trsv<false, double>), dim3(n), dim3(256), 0, st, base, descs, W, y, col0);
+}
+template <bool BWD> static void launch_span32(const float *base, const chol_trsv_desc *descs, int n, const double *W, double *y, int col0, hipStream_t st)
+{
+  if (SOLVE_SPAN32) hipLaunchKernelGGL((k_solve_span32<BWD>), dim3(n), dim3(256), 0, st, base, descs, W, y, col0);
+  else hipLaunchKernelGGL((k_solve_trsv<BWD, float>), dim3(n), dim3(256), 0, st, base, descs, W, y, col0);
+}
+static void launch_span(const float *base, const chol_trsv_desc *descs, int n, const double *W, double *y, int col0, bool bwd, hipStream_t st)
+{
+  if (bwd) launch_span32<true>(base, descs, n, W, y, col0, st); else launch_span32<false>(base, descs, n, W, y, col0, st);
+}
 // one 256-column diagonal span of every separator of a level on its own (plain stores; the deterministic solve puts its gathers between them)
-int chol_launch_solve_span(const double *base, const chol_trsv_desc *descs, int n, const double *W, double *y, int col0, int backward, hipStream_t st)
+template <class TL> int chol_launch_solve_span(const TL *base, const chol_trsv_desc *descs, int n, const double *W, double *y, int col0, int backward, hipStream_t st)
 {
   if (n <= 0) return 0;
-  if (backward) launch_span<true>(base, descs, n, W, y, col0, st); else launch_span<false>(base, descs, n, W, y, col0, st);
+  launch_span(base, descs, n, W, y, col0, backward != 0, st);
   return (int)hipGetLastError();
 }
-int chol32_launch_solve_span(const float *base, const chol_trsv_desc *descs, int n, const double *W, double *y, int col0, int backward, hipStream_t st)
-{
-  if (n <= 0) return 0;
-  if (backward) launch_span<true>(base, descs, n, W, y, col0, st); else launch_span<false>(base, descs, n, W, y, col0, st);
-  return (int)hipGetLastError();
-}
+template int chol_launch_solve_span(const double *, const chol_trsv_desc *, int, const double *, double *, int, int, hipStream_t);
+template int chol_launch_solve_span(const float *, const chol_trsv_desc *, int, const double *, double *, int, int, hipStream_t);
 int chol_launch_trsv_fwd(const double *base, const chol_trsv_desc *descs, int n, double *y, hipStream_t st)
 {
   if (n <= 0) return 0;
@@ -3634,5 +3637,3 @@ int chol_launch_bwd(const double *base, const chol_trsv_desc *descs, const chol_
   hipLaunchKernelGGL(k_bwd, dim3(n), dim3(256), 0, st, base, descs, gd, gstart, y);
   return (int)hipGetLastError();
 }
-
-} // extern "C"

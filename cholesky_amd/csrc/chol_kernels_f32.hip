@@ -659,8 +659,7 @@ __global__ void k_axpy1(double *__restrict__ x, const double *__restrict__ dx, i
   if (i < n) x[i] += dx[i];
 }
 
-extern "C" {
-int chol32_launch_scatter(float *arena, const int64_t *dst, const double *val, int64_t nnz, hipStream_t st)
+int chol_launch_scatter(float *arena, const int64_t *dst, const double *val, int64_t nnz, hipStream_t st)
 {
   if (nnz <= 0) return 0;
   int blocks = (int)((nnz + 255) / 256);
@@ -668,7 +667,7 @@ int chol32_launch_scatter(float *arena, const int64_t *dst, const double *val, i
   hipLaunchKernelGGL(k32_scatter, dim3(blocks), dim3(256), 0, st, arena, dst, val, nnz);
   return (int)hipGetLastError();
 }
-int chol32_launch_potrf(float *base, float *ws, const chol_potrf_desc *descs, int n, int *info, hipStream_t st)
+int chol_launch_potrf(float *base, float *ws, const chol_potrf_desc *descs, int n, int *info, hipStream_t st)
 {
   if (n <= 0) return 0;
   static bool attr = false;
@@ -677,26 +676,26 @@ int chol32_launch_potrf(float *base, float *ws, const chol_potrf_desc *descs, in
   hipLaunchKernelGGL(k32_potrf, dim3(n), dim3(256), lds, st, base, ws, descs, info);
   return (int)hipGetLastError();
 }
-int chol32_launch_trsm(float *base, const float *ws, const chol_trsm_desc *descs, int n, hipStream_t st)
+int chol_launch_trsm(float *base, const float *ws, const chol_trsm_desc *descs, int n, hipStream_t st)
 {
   if (n <= 0) return 0;
   hipLaunchKernelGGL(k32_trsm, dim3((n + 3) / 4), dim3(256), 0, st, base, ws, descs, n);
   return (int)hipGetLastError();
 }
-int chol32_launch_trsm_wt(float *base, const float *ws, const chol_trsm_desc *descs, int n, hipStream_t st)
+int chol_launch_trsm_wt(float *base, const float *ws, const chol_trsm_desc *descs, int n, hipStream_t st)
 { // every aligned group of CHOL32_TRSM_GROUP descriptors shares one pivot block (m = 0: placeholder)
   if (n <= 0) return 0;
   hipLaunchKernelGGL(k32_trsm_wt, dim3((n + T32_WAVES - 1) / T32_WAVES), dim3(64 * T32_WAVES), 0, st, base, ws, descs, n);
   return (int)hipGetLastError();
 }
-int chol32_launch_update(float *base, const chol_upd_task *tasks, const chol_upd_src *srcs, int ntask, hipStream_t st)
+int chol_launch_update(float *base, const chol_upd_task *tasks, const chol_upd_src *srcs, int ntask, hipStream_t st)
 {
   if (ntask <= 0) return 0;
   const int per_xcd = (ntask + 7) / 8;
   hipLaunchKernelGGL(k32_update, dim3(per_xcd * 8), dim3(256), 0, st, base, tasks, srcs, ntask, per_xcd);
   return (int)hipGetLastError();
 }
-int chol32_launch_update_mt(float *base, const chol_upd_task *tasks, const chol_upd_src *srcs, int ntask, int64_t arena_elems, hipStream_t st)
+int chol_launch_update_mt(float *base, const chol_upd_task *tasks, const chol_upd_src *srcs, int ntask, int64_t arena_elems, hipStream_t st)
 { // arena_elems: floats in the arena behind `base` (0: unknown -- edge tiles then stage their operands through registers)
   if (ntask <= 0) return 0;
   const int per_xcd = (ntask + 7) / 8;
@@ -715,4 +714,3 @@ int chol_launch_axpy1(double *x, const double *dx, int n, hipStream_t st)
   hipLaunchKernelGGL(k_axpy1, dim3((n + 255) / 256), dim3(256), 0, st, x, dx, n);
   return (int)hipGetLastError();
 }
-} // extern "C"

@@ -113,7 +113,7 @@ __global__ __launch_bounds__(MUL_THREADS) void k_multiply_resid_sum(const double
 }
 
 template <class TL>
-static int launch_multiply_t(const TL *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, const double *z, double *y, const int *perm, hipStream_t st)
+int chol_launch_multiply(const TL *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, const double *z, double *y, const int *perm, hipStream_t st)
 {
   if (n_items <= 0) return 0;
   if (backward) hipLaunchKernelGGL((k_multiply<TL, 1>), dim3(n_items), dim3(MUL_THREADS), 0, st, base, items, srcs, z, y, perm);
@@ -121,11 +121,8 @@ static int launch_multiply_t(const TL *base, const chol_mul_item *items, int n_i
   return (int)hipGetLastError();
 }
 
-extern "C" {
-int chol_launch_multiply(const double *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, const double *z, double *y, const int *perm, hipStream_t st)
-{ return launch_multiply_t(base, items, n_items, srcs, backward, z, y, perm, st); }
-int chol32_launch_multiply(const float *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, const double *z, double *y, const int *perm, hipStream_t st)
-{ return launch_multiply_t(base, items, n_items, srcs, backward, z, y, perm, st); }
+template int chol_launch_multiply(const double *, const chol_mul_item *, int, const chol_mul_src *, int, const double *, double *, const int *, hipStream_t);
+template int chol_launch_multiply(const float *, const chol_mul_item *, int, const chol_mul_src *, int, const double *, double *, const int *, hipStream_t);
 int chol_launch_multiply_resid(const int64_t *ptr, const int *col, const double *val, const double *z, const double *w, int n, double *part, int64_t *ipart, int64_t *res, hipStream_t st)
 {
   const int nblk = n > 0 ? (n + MUL_THREADS - 1) / MUL_THREADS : 0;
@@ -136,5 +133,4 @@ int chol_launch_multiply_resid(const int64_t *ptr, const int *col, const double 
   }
   hipLaunchKernelGGL(k_multiply_resid_sum, dim3(1), dim3(MUL_THREADS), 0, st, part, (const long long *)ipart, nblk, (long long *)res);
   return (int)hipGetLastError();
-}
 }

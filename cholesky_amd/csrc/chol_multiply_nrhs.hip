@@ -88,8 +88,8 @@ __global__ __launch_bounds__(MULN_THREADS) void k_multiply_nrhs(const TL *__rest
 }
 
 template <class TL>
-static int launch_multiply_nrhs_t(const TL *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, const double *Zp, double *Y, const int *perm,
-                                  int64_t ldy, int c0, int cols, hipStream_t st)
+int chol_launch_multiply_nrhs(const TL *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, const double *Zp, double *Y, const int *perm,
+                              int64_t ldy, int c0, int cols, hipStream_t st)
 {
   if (n_items <= 0) return 0;
   if (backward) hipLaunchKernelGGL((k_multiply_nrhs<TL, 1>), dim3(n_items), dim3(MULN_THREADS), 0, st, base, items, srcs, Zp, Y, perm, ldy, c0, cols);
@@ -97,11 +97,5 @@ static int launch_multiply_nrhs_t(const TL *base, const chol_mul_item *items, in
   return (int)hipGetLastError();
 }
 
-extern "C" {
-int chol_launch_multiply_nrhs(const double *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, const double *Zp, double *Y, const int *perm,
-                              int64_t ldy, int c0, int cols, hipStream_t st)
-{ return launch_multiply_nrhs_t(base, items, n_items, srcs, backward, Zp, Y, perm, ldy, c0, cols, st); }
-int chol32_launch_multiply_nrhs(const float *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, const double *Zp, double *Y, const int *perm,
-                                int64_t ldy, int c0, int cols, hipStream_t st)
-{ return launch_multiply_nrhs_t(base, items, n_items, srcs, backward, Zp, Y, perm, ldy, c0, cols, st); }
-}
+template int chol_launch_multiply_nrhs(const double *, const chol_mul_item *, int, const chol_mul_src *, int, const double *, double *, const int *, int64_t, int, int, hipStream_t);
+template int chol_launch_multiply_nrhs(const float *, const chol_mul_item *, int, const chol_mul_src *, int, const double *, double *, const int *, int64_t, int, int, hipStream_t);

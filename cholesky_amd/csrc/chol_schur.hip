@@ -47,7 +47,7 @@ __global__ __launch_bounds__(256) void k_schur_gather(const double *__restrict__
   }
 }
 
-extern "C" int chol_launch_schur_gather(const double *arena, const chol_schur_desc *descs, int64_t ndesc, double *S, int64_t lds, hipStream_t st)
+int chol_launch_schur_gather(const double *arena, const chol_schur_desc *descs, int64_t ndesc, double *S, int64_t lds, hipStream_t st)
 {
   if (ndesc <= 0) return (int)hipSuccess;
   if (ndesc > 0x7fffffff) return (int)hipErrorInvalidValue;

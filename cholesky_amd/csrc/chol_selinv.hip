@@ -196,7 +196,6 @@ __global__ void k_selinv_entries(const double *__restrict__ Z, const int64_t *__
   if (e < nnz) vals[a_src[e]] = Z[a_dst[e]];
 }
 
-extern "C" {
 // the separators of a step lie on grid.x (a deep tree level has more of them than grid.y takes), the tiles below on grid.y (CHOL_SELINV_MAX_TILES)
 int chol_launch_selinv_step(const double *L, double *Z, double *ws, const chol_selinv_sep *seps, int n_act, const chol_selinv_tile *tiles, const int *chain_ld,
                             const int *chain_pos0, const int64_t *rowoff, int step, int max_below_tiles, hipStream_t st)
@@ -224,5 +223,4 @@ int chol_launch_selinv_entries(const double *Z, const int64_t *a_dst, const int 
   }
   if (nnz > 0) hipLaunchKernelGGL(k_selinv_entries, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, st, Z, a_dst, a_src, nnz, vals);
   return (int)hipGetLastError();
-}
 }

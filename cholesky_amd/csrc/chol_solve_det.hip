@@ -67,7 +67,7 @@ __global__ __launch_bounds__(SDET_THREADS) void k_solve_det_gather(const TL *__r
 }
 
 template <class TL>
-static int launch_solve_det_gather_t(const TL *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, double *y, hipStream_t st)
+int chol_launch_solve_det_gather(const TL *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, double *y, hipStream_t st)
 {
   if (n_items <= 0) return 0;
   if (backward) hipLaunchKernelGGL((k_solve_det_gather<TL, 1>), dim3(n_items), dim3(SDET_THREADS), 0, st, base, items, srcs, y);
@@ -75,9 +75,5 @@ static int launch_solve_det_gather_t(const TL *base, const chol_mul_item *items,
   return (int)hipGetLastError();
 }
 
-extern "C" {
-int chol_launch_solve_det_gather(const double *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, double *y, hipStream_t st)
-{ return launch_solve_det_gather_t(base, items, n_items, srcs, backward, y, st); }
-int chol32_launch_solve_det_gather(const float *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, double *y, hipStream_t st)
-{ return launch_solve_det_gather_t(base, items, n_items, srcs, backward, y, st); }
-}
+template int chol_launch_solve_det_gather(const double *, const chol_mul_item *, int, const chol_mul_src *, int, double *, hipStream_t);
+template int chol_launch_solve_det_gather(const float *, const chol_mul_item *, int, const chol_mul_src *, int, double *, hipStream_t);

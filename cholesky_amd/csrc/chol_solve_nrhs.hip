@@ -271,7 +271,7 @@ __global__ __launch_bounds__(256) void k_nrhs_axpy(double *__restrict__ X, int64
 }
 
 template <class TL>
-static int launch_trsv_t(const TL *base, const chol_trsv_desc *descs, int n, int max_n, int max_under, const double *W16, const double *W256, double *Y, int backward, hipStream_t st)
+int chol_nrhs_launch_trsv(const TL *base, const chol_trsv_desc *descs, int n, int max_n, int max_under, const double *W16, const double *W256, double *Y, int backward, hipStream_t st)
 {
   if (n <= 0 || max_n <= 0) return 0;
   const int nspan = (max_n + NSPAN - 1) / NSPAN, mu = max_under < 0 ? -max_under : max_under;
@@ -289,7 +289,7 @@ static int launch_trsv_t(const TL *base, const chol_trsv_desc *descs, int n, int
   }
   return (int)hipGetLastError();
 }
-template <class TL> static int launch_offdiag_t(const TL *base, const chol_gemv_desc *blocks, const int *items, int n_items, double *Y, int backward, hipStream_t st)
+template <class TL> int chol_nrhs_launch_offdiag(const TL *base, const chol_gemv_desc *blocks, const int *items, int n_items, double *Y, int backward, hipStream_t st)
 {
   if (n_items <= 0) return 0;
   if (backward) hipLaunchKernelGGL((k_nrhs_offdiag<true, TL>), dim3(n_items), dim3(256), 0, st, base, blocks, items, Y);
@@ -297,7 +297,6 @@ template <class TL> static int launch_offdiag_t(const TL *base, const chol_gemv_
   return (int)hipGetLastError();
 }
 
-extern "C" {
 int chol_nrhs_launch_permute(const double *B, int64_t ldb, const int *perm, double *Y, double *X, int64_t ldx, int n, int c0, int cols, int inverse, hipStream_t st)
 {
   if (n <= 0) return 0;
@@ -306,14 +305,10 @@ int chol_nrhs_launch_permute(const double *B, int64_t ldb, const int *perm, doub
   else hipLaunchKernelGGL(k_nrhs_permute_in, dim3(blocks), dim3(256), 0, st, B, ldb, perm, Y, n, c0, cols);
   return (int)hipGetLastError();
 }
-int chol_nrhs_launch_trsv(const double *base, const chol_trsv_desc *descs, int n, int max_n, int max_under, const double *W16, const double *W256, double *Y, int backward, hipStream_t st)
-{ return launch_trsv_t(base, descs, n, max_n, max_under, W16, W256, Y, backward, st); }
-int chol32_nrhs_launch_trsv(const float *base, const chol_trsv_desc *descs, int n, int max_n, int max_under, const double *W16, const double *W256, double *Y, int backward, hipStream_t st)
-{ return launch_trsv_t(base, descs, n, max_n, max_under, W16, W256, Y, backward, st); }
-int chol_nrhs_launch_offdiag(const double *base, const chol_gemv_desc *blocks, const int *items, int n_items, double *Y, int backward, hipStream_t st)
-{ return launch_offdiag_t(base, blocks, items, n_items, Y, backward, st); }
-int chol32_nrhs_launch_offdiag(const float *base, const chol_gemv_desc *blocks, const int *items, int n_items, double *Y, int backward, hipStream_t st)
-{ return launch_offdiag_t(base, blocks, items, n_items, Y, backward, st); }
+template int chol_nrhs_launch_trsv(const double *, const chol_trsv_desc *, int, int, int, const double *, const double *, double *, int, hipStream_t);
+template int chol_nrhs_launch_trsv(const float *, const chol_trsv_desc *, int, int, int, const double *, const double *, double *, int, hipStream_t);
+template int chol_nrhs_launch_offdiag(const double *, const chol_gemv_desc *, const int *, int, double *, int, hipStream_t);
+template int chol_nrhs_launch_offdiag(const float *, const chol_gemv_desc *, const int *, int, double *, int, hipStream_t);
 int chol_nrhs_launch_residual(const int64_t *ptr, const int *col, const double *val, const double *B, int64_t ldb, const double *X, int64_t ldx, double *R, int64_t ldr,
                               int n, int cols, double *partial, hipStream_t st)
 {
@@ -327,4 +322,3 @@ int chol_nrhs_launch_axpy(double *X, int64_t ldx, const double *D, int64_t ldd, 
   hipLaunchKernelGGL(k_nrhs_axpy, dim3((n + 255) / 256, cols), dim3(256), 0, st, X, ldx, D, ldd, n);
   return (int)hipGetLastError();
 }
-} // extern "C"

@@ -36,7 +36,7 @@ int main(int argc, char **argv)
   float best = 1e9f;
   for (int rep = 0; rep < 5; rep++) {
     hipEventRecord(e0);
-    chol32_launch_update_mt(nullptr, dt, ds, (int)tasks.size(), LLONG_MAX, 0);
+    chol_launch_update_mt((float *)nullptr, dt, ds, (int)tasks.size(), LLONG_MAX, 0);
     hipEventRecord(e1);
     hipDeviceSynchronize();
     float ms; hipEventElapsedTime(&ms, e0, e1);

@@ -555,8 +555,6 @@ def test_only_the_ranks_under_a_top_separator_touch_its_blocks(case, world, mixe
 
     one = ca.Device(plan, 0)
     one.set_option("dist_top", 1)
-    if mixed and not hasattr(one, "factor_levels_f32"):
-        pytest.skip("no level-range entry point for the fp32 factor in the Python mirror")
     ref = run(one)
     parts = []
     for r in range(world):
