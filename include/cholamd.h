@@ -365,7 +365,10 @@ int cholamd_factor_debug(cholamd_device *d, double *d_arena, const char *dir, in
 /* LAPACK-style info after the stream has been synchronised: 0 ok; k > 0 = leading minor k of the
  * pivot of separator *sep_out is not positive definite (the reference ignores this, blas.rg:71);
  * < 0 = the factorisation itself failed (CHOLAMD_ERR_STALL, or a HIP error code of this call) and
- * cholamd_last_error() says why -- callers must not use the factor in either non-zero case. */
+ * cholamd_last_error() says why -- callers must not use the factor in either non-zero case.
+ * info belongs to the device object: in a multi-rank factorisation a rank reports the pivots it factored itself (its subtrees; of the shared top all
+ * of them, or under "dist_top" its own column blocks) and otherwise 0 or a later pivot that NaN reached.  A caller must read EVERY rank's info: the
+ * factor is good only if all are 0, and the first failing pivot is the smallest permuted position reported (sep_offsets[*sep_out - 1] + info - 1). */
 int cholamd_factor_info(cholamd_device *d, int *sep_out);
 /* Schedule / kernel-selection switches of this device object.  They default to the values the environment gave when
  * the object was created (CHOLAMD_SPLIT_MIN, CHOLAMD_SPLIT_NB, CHOLAMD_NO_FUSE, CHOLAMD_FUSE_UPDATE_MAX,

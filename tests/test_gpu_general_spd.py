@@ -8,6 +8,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 import spd_inputs as si  # noqa: E402
+from sharded import assemble as _assemble  # noqa: E402
 from spd_inputs import U32  # noqa: E402
 from test_gpu_factor import LAUNCH_PATHS  # noqa: E402
 
@@ -343,24 +344,6 @@ def test_nan_in_a_leaf_entry_is_a_failed_pivot(spd):
 # ------------------------------------------------------------------------------------------------
 # f. sharded
 # ------------------------------------------------------------------------------------------------
-def _assemble(plan, parts, world):
-    """Panel of separator s from its owner's arena, the top from rank 0 (as test_distributed does)."""
-    d = world.bit_length() - 1
-    tree = plan.tree
-    owner = {}
-    for h in range(1, plan.nsep + 1):
-        lvl = h.bit_length() - 1
-        owner[int(tree[h - 1])] = 0 if lvl < d else (h >> (lvl - d)) - (1 << d)
-    diag = {int(b[1]): int(b[7]) for b in plan.blocks if b[0] == b[1]}
-    order = sorted(diag)
-    out = np.zeros_like(parts[0])
-    for i, s in enumerate(order):
-        lo = diag[s]
-        hi = diag[order[i + 1]] if i + 1 < len(order) else plan.arena_doubles
-        out[lo:hi] = parts[owner[s]][lo:hi]
-    return out
-
-
 @pytest.mark.parametrize("world", [2, 4])
 @pytest.mark.parametrize("f32", [False, True])
 @pytest.mark.parametrize("name", ["g16_subset", "tree_skew"])

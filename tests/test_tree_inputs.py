@@ -7,7 +7,7 @@ import pytest
 import spd_inputs as si
 import tree_inputs as ti
 
-ALL = ti.NAMED + ti.SINGLE
+ALL = ti.NAMED + ti.SINGLE + ti.TOP
 
 
 @pytest.fixture(scope="module")
@@ -16,7 +16,7 @@ def spd(tmp_path_factory):
 
 
 def test_named_trees_are_the_suites_inputs():
-    assert si.NAMES[-len(ti.NAMED):] == ti.NAMED and not set(ti.SINGLE) & set(si.NAMES)
+    assert si.NAMES[-len(ti.NAMED):] == ti.NAMED and not set(ti.SINGLE + ti.TOP) & set(si.NAMES)
     assert si.NAMES.index("g7_ragged") == 9             # the inputs before the trees keep their places, and so their seeds
 
 
@@ -128,7 +128,7 @@ def test_sparse_arena_reader_equals_the_dense_one(name, spd):
     assert np.array_equal(Ls.toarray(), np.tril(S.PAP))
 
 
-@pytest.mark.parametrize("name", ti.WITH_TILES)
+@pytest.mark.parametrize("name", ti.WITH_TILES + ti.TOP)
 def test_tiles_couplings_are_row_compacted(name, spd):
     S = spd(name)
     assert S.tree.untouched_tiles > 0 and "tiles" in S.tree.kinds.values()
@@ -139,6 +139,28 @@ def test_tiles_couplings_are_row_compacted(name, spd):
         if r != c:
             gone += int((S.plan.block_tile_map(r, c) < 0).sum())
     assert gone > 0
+
+
+def test_tree_top_has_top_separators_of_three_and_four_column_blocks(spd):
+    """What tree_top is for, read from the library's own piece list of the distributed top: the root is cut in 112 + 112 + 112 + 97 columns and
+    heap index 2 in 112 + 112 + 65; at world 4 the cyclic owner rule wraps (ranks 1, 2, 3, 0 and 2, 3, 0) and the one-column separator is rank
+    3's; at world 2 each rank owns two blocks of the root that are not neighbours."""
+    S = spd("tree_top")
+    P = S.plan
+    assert S.n == 967 and S.tree.untouched_tiles > 0
+    ld = {int(b[1]): int(b[6]) for b in P.blocks if b[0] == b[1]}
+
+    def cut(world, heap):
+        rows = P.exchange_pieces(world, 1)
+        rows = rows[rows[:, 3] == heap]
+        rows = rows[np.argsort(rows[:, 0])]
+        assert (rows[:, 1] % ld[int(P.tree[heap - 1])] == 0).all()
+        return (rows[:, 1] // ld[int(P.tree[heap - 1])]).tolist(), rows[:, 2].tolist()
+
+    assert cut(4, 1) == ([112, 112, 112, 97], [1, 2, 3, 0])
+    assert cut(4, 2) == ([112, 112, 65], [2, 3, 0])
+    assert cut(4, 3) == ([1], [3])
+    assert cut(2, 1) == ([112, 112, 112, 97], [1, 0, 1, 0])
 
 
 def test_a_dropped_tile_contribution_fails_the_measures(spd):

@@ -28,7 +28,7 @@ import numpy as np
 SWEEP_SIZES = [1, 15, 16, 17, 63, 64, 65, 127, 128, 129, 143, 144, 145, 159, 160, 161, 175, 176, 177, 191, 192, 193, 255, 256, 257, 271, 272, 273,
                287, 288, 289, 511, 512, 513]
 
-# the named trees: the first four join spd_inputs.INPUTS, the last two are single-purpose
+# the named trees: the first four join spd_inputs.INPUTS, the others are single-purpose
 TREES = {
     "tree_over": dict(levels=3, sizes=[193, 177, 145, 257, 273, 17, 1], tile=32, leaf=[("band", 17), "dense", ("random", 0.3), "dense"],
                       inner=["dense", ("random", 0.5)], coupling=["dense", "tiles", "tiles"], seed=11),
@@ -42,9 +42,16 @@ TREES = {
                       coupling=["dense", ("random", 0.4), "none", "tiles"], seed=14),
     "tree_single": dict(levels=1, sizes=[300], tile=32, leaf=[("random", 0.2)], inner=["dense"], coupling=["dense"], seed=15),
     "tree_two": dict(levels=2, sizes=[129, 65, 127], tile=32, leaf=[("band", 17), "arrow"], inner=["dense"], coupling=[("random", 0.3)], seed=16),
+    # top separators of more than two column blocks (433 = 112 + 112 + 112 + 97, 289 = 112 + 112 + 65) next to one of a single column: under the
+    # distributed top the cyclic owner rule (block + heap index) mod world wraps, a super-block of three column blocks ends inside the root and
+    # at world 2 a rank owns two blocks of one separator that are not neighbours
+    "tree_top": dict(levels=3, sizes=[433, 289, 1, 65, 17, 33, 129], tile="random",
+                     leaf=["dense", ("band", 17), "arrow", ("random", 0.3)], inner=["dense", ("random", 0.5)],
+                     coupling=["tiles", "dense", ("random", 0.3)], seed=17),
 }
 NAMED = ["tree_over", "tree_at", "tree_skew", "tree_tiny"]
 SINGLE = ["tree_single", "tree_two"]
+TOP = ["tree_top"]                                       # the multi-rank tests' own input (tests/test_gpu_sharded_general.py)
 WITH_TILES = ["tree_over", "tree_at", "tree_skew"]       # "tiles" couplings above the parent with more than one 16-row tile to choose from
 
 
