@@ -74,6 +74,8 @@ $(ASAN_OUT)/multiply_nrhs_host: tests/native/multiply_nrhs_host.c $(ASAN_OUT)/li
 	$(HIPCC) -x c -O1 -Iinclude $(SAN) -fno-sanitize=function -o $@ $< -L$(ASAN_OUT) -lcholamd -Wl,-rpath,$(abspath $(ASAN_OUT)) -lm
 $(ASAN_OUT)/solve_det_host: tests/native/solve_det_host.c $(ASAN_OUT)/libcholamd.so
 	$(HIPCC) -x c -O1 -Iinclude $(SAN) -fno-sanitize=function -o $@ $< -L$(ASAN_OUT) -lcholamd -Wl,-rpath,$(abspath $(ASAN_OUT)) -lm
+$(ASAN_OUT)/solve_det_nrhs_host: tests/native/solve_det_nrhs_host.c $(ASAN_OUT)/libcholamd.so
+	$(HIPCC) -x c -O1 -Iinclude $(SAN) -fno-sanitize=function -o $@ $< -L$(ASAN_OUT) -lcholamd -Wl,-rpath,$(abspath $(ASAN_OUT)) -lm
 # the owning device buffers of the glue over a host allocator that can be told to fail (tests/native/devbuf_host.cpp): no library, no HIP runtime
 $(ASAN_OUT)/devbuf_host: tests/native/devbuf_host.cpp $(CSRC)/chol_devbuf.h
 	@mkdir -p $(ASAN_OUT)
@@ -81,7 +83,7 @@ $(ASAN_OUT)/devbuf_host: tests/native/devbuf_host.cpp $(CSRC)/chol_devbuf.h
 ASAN_FIXTURES := $(G)/lapl_9x9/lapl_3_2.mtx $(G)/lapl_9x9/lapl_3_2_ord_2.txt $(G)/lapl_9x9/lapl_3_2_clust_2.txt \
 	  $(G)/lapl_400x400/lapl_20_2.mtx $(G)/lapl_400x400/lapl_20_2_ord_5.txt $(G)/lapl_400x400/lapl_20_2_clust_5.txt \
 	  $(G)/lapl_3375x3375/lapl_15_3.mtx $(G)/lapl_3375x3375/lapl_15_3_ord_5.txt $(G)/lapl_3375x3375/lapl_15_3_clust_5.txt
-asan: $(ASAN_OUT)/libcholamd.so $(ASAN_OUT)/host_leak $(ASAN_OUT)/schur_host $(ASAN_OUT)/multiply_host $(ASAN_OUT)/multiply_nrhs_host $(ASAN_OUT)/solve_det_host $(ASAN_OUT)/devbuf_host oracle
+asan: $(ASAN_OUT)/libcholamd.so $(ASAN_OUT)/host_leak $(ASAN_OUT)/schur_host $(ASAN_OUT)/multiply_host $(ASAN_OUT)/multiply_nrhs_host $(ASAN_OUT)/solve_det_host $(ASAN_OUT)/solve_det_nrhs_host $(ASAN_OUT)/devbuf_host oracle
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 LSAN_OPTIONS=suppressions=$(abspath scripts/lsan.supp):print_suppressions=0 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
 	$(ASAN_OUT)/devbuf_host
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 LSAN_OPTIONS=suppressions=$(abspath scripts/lsan.supp):print_suppressions=0 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
@@ -92,6 +94,8 @@ asan: $(ASAN_OUT)/libcholamd.so $(ASAN_OUT)/host_leak $(ASAN_OUT)/schur_host $(A
 	$(ASAN_OUT)/schur_host $(ASAN_FIXTURES)
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 LSAN_OPTIONS=suppressions=$(abspath scripts/lsan.supp):print_suppressions=0 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
 	$(ASAN_OUT)/solve_det_host $(ASAN_FIXTURES) $(G)/lapl_25x25/lapl_5_2.mtx $(G)/lapl_25x25/lapl_5_2_ord_3.txt $(G)/lapl_25x25/lapl_5_2_clust_3.txt
+	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 LSAN_OPTIONS=suppressions=$(abspath scripts/lsan.supp):print_suppressions=0 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
+	$(ASAN_OUT)/solve_det_nrhs_host $(ASAN_FIXTURES) $(G)/lapl_25x25/lapl_5_2.mtx $(G)/lapl_25x25/lapl_5_2_ord_3.txt $(G)/lapl_25x25/lapl_5_2_clust_3.txt
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 LSAN_OPTIONS=suppressions=$(abspath scripts/lsan.supp):print_suppressions=0 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
 	$(ASAN_OUT)/host_leak $(G)/lapl_9x9/lapl_3_2.mtx $(G)/lapl_9x9/lapl_3_2_ord_2.txt $(G)/lapl_9x9/lapl_3_2_clust_2.txt \
 	  $(G)/lapl_400x400/lapl_20_2.mtx $(G)/lapl_400x400/lapl_20_2_ord_5.txt $(G)/lapl_400x400/lapl_20_2_clust_5.txt \

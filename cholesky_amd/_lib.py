@@ -179,6 +179,7 @@ def load():
     L.cholamd_plan_multiply_host_nrhs.argtypes = [vp, vp, ci, vp, i64, vp, i64, ci]
     L.cholamd_plan_multiply_counts.argtypes = [vp, vp]
     L.cholamd_plan_solve_det_host.argtypes = [vp, vp, ci, vp, vp]
+    L.cholamd_plan_solve_det_host_nrhs.argtypes = [vp, vp, ci, vp, i64, vp, i64, ci]
     L.cholamd_plan_solve_det_counts.argtypes = [vp, vp]
     L.cholamd_plan_solve_det_lists.argtypes = [vp, ci, vp, vp, vp]
     L.cholamd_factor_logdet.argtypes = [vp, vp, C.POINTER(cd), vp]

@@ -124,6 +124,9 @@ struct cholamd_device {
   // option solve_deterministic: the streamed sweeps with owner gathers in place of the atomic kernels (chol_solve_det.hip).  The step lists of both
   // directions (chol_sdet_lists) are built and uploaded at the first such solve; the steps themselves stay on the host (they are the launch sequence)
   bool solve_deterministic = false;
+  // option solve_deterministic_block: under solve_deterministic (and without solve_reference_shape) the _nrhs entry points take the deterministic BLOCK path
+  // (solve_det_nrhs_t: the same step lists on chunks of 32 columns) instead of going column by column; no effect otherwise
+  bool solve_deterministic_block = false;
   dev_buf<chol_mul_item> sdet_item[2]; dev_buf<chol_mul_src> sdet_src[2]; std::vector<chol_sdet_step> sdet_step[2]; bool sdet_ready = false;
   // block solve (cholamd_solve_nrhs): the permuted block of one chunk (n x CHOL_NRHS_W, row-major); refinement: the chunk's right-hand sides, residual and
   // correction (n x CHOL_NRHS_W, column-major) and the per-column partial sums of the residual kernel
@@ -300,6 +303,7 @@ extern "C" int cholamd_device_create(const cholamd_plan *plan, int device_id, ch
   chol_sched_opts_from_env(&d->opt);
   { const char *e = getenv("CHOLAMD_SOLVE_REFERENCE_SHAPE"); d->solve_reference_shape = e && *e && atoi(e) != 0; }
   { const char *e = getenv("CHOLAMD_SOLVE_DETERMINISTIC"); d->solve_deterministic = e && *e && atoi(e) != 0; }
+  { const char *e = getenv("CHOLAMD_SOLVE_DETERMINISTIC_BLOCK"); d->solve_deterministic_block = e && *e && atoi(e) != 0; }
   { const char *e = getenv("CHOLAMD_MULTIPLY_NRHS_MIN"); d->multiply_nrhs_min = e && *e ? atoi(e) : 0; }
   int rc = build_levels(d);
   if (!rc) rc = d->ws.alloc((size_t)(plan->ws_doubles > 0 ? plan->ws_doubles : 1));
@@ -373,6 +377,7 @@ extern "C" int cholamd_device_set_option(cholamd_device *d, const char *name, in
   else if (n == "dist_top") d->opt.dist_top = value;
   else if (n == "solve_reference_shape") { d->solve_reference_shape = value != 0; rebuild = false; }
   else if (n == "solve_deterministic") { d->solve_deterministic = value != 0; rebuild = false; }
+  else if (n == "solve_deterministic_block") { d->solve_deterministic_block = value != 0; rebuild = false; }
   else if (n == "multiply_nrhs_min") { d->multiply_nrhs_min = value; rebuild = false; }
   else { chol_set_error("unknown option '%s'", n.c_str()); return CHOLAMD_ERR_ARG; }
   return rebuild ? build_levels(d) : 0;
@@ -877,6 +882,36 @@ template <class TL> static int solve_det_t(cholamd_device *d, const TL *d_arena,
   HIPCHK((hipError_t)chol_launch_permute(y, d->perm, d_x, n, 1, st));
   return 0;
 }
+// The deterministic BLOCK solve (option solve_deterministic_block; include/cholamd.h at "deterministic solve"): the steps of solve_det_t on chunks of
+// CHOL_NRHS_W = 32 columns in the permuted row-major block of the block solve.  Per step one block gather (k_solve_det_gather_nrhs) where the step has items
+// and one k_nrhs_span launch in its substitution form where it has a span; the atomic kernels of the block solve (k_nrhs_panel, k_nrhs_offdiag) are never
+// launched.  EVERY chunk takes these kernels, whatever its column count: a column's bits must not depend on how many columns travel with it.
+static bool det_block(const cholamd_device *d) { return d->solve_deterministic && d->solve_deterministic_block && !d->solve_reference_shape; }
+template <class TL> static int solve_det_nrhs_t(cholamd_device *d, const TL *d_arena, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int nrhs, int which, hipStream_t st)
+{
+  { int rc = build_solve(d); if (!rc) rc = build_solve_det(d); if (!rc) rc = d->ynrhs.ensure((size_t)d->plan->n * CHOL_NRHS_W); if (rc) return rc; }
+  const int L = d->plan->levels, n = d->plan->n;
+  double *Y = d->ynrhs;
+  for (int lvl = 0; lvl < L && !d->keep_inverses; lvl++) { // the 16x16 inverses of this arena once per call (a refinement keeps them)
+    const solve_dev &s = d->sv[lvl];
+    HIPCHK((hipError_t)chol_launch_solve_dinv(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, st));
+  }
+  for (int c0 = 0; c0 < nrhs; c0 += CHOL_NRHS_W) {
+    const int cols = std::min(CHOL_NRHS_W, nrhs - c0);
+    HIPCHK((hipError_t)chol_nrhs_launch_permute(d_B, ldb, d->perm, Y, nullptr, 0, n, c0, cols, 0, st));
+    for (int q = 0; q < 2; q++) {
+      if (which >= 0 && which != q) continue;
+      const chol_mul_item *items = d->sdet_item[q];
+      for (const chol_sdet_step &t : d->sdet_step[q]) {
+        const solve_dev &s = d->sv[t.level];
+        if (t.item_end > t.item_first) HIPCHK((hipError_t)chol_launch_solve_det_gather_nrhs(d_arena, items + t.item_first, t.item_end - t.item_first, d->sdet_src[q], q, Y, st));
+        if (t.col0 >= 0) HIPCHK((hipError_t)chol_nrhs_launch_span(d_arena, s.trsv, s.n_trsv, d->ws_solve, Y, t.col0, q, st));
+      }
+    }
+    HIPCHK((hipError_t)chol_nrhs_launch_permute(nullptr, 0, d->perm, Y, d_X, ldx, n, c0, cols, 1, st));
+  }
+  return 0;
+}
 extern "C" int cholamd_solve(cholamd_device *d, const double *d_arena, const double *d_b, double *d_x, void *stream)
 {
   HIPCHK(hipSetDevice(d->dev));
@@ -1212,6 +1247,7 @@ extern "C" int cholamd_solve_nrhs(cholamd_device *d, const double *d_arena, cons
 {
   { int rc = nrhs_check(d, d_arena, d_B, ldb, d_X, ldx, nrhs, "cholamd_solve_nrhs"); if (rc) return rc > 0 ? 0 : rc; }
   HIPCHK(hipSetDevice(d->dev));
+  if (det_block(d)) return solve_det_nrhs_t(d, d_arena, d_B, ldb, d_X, ldx, nrhs, CHOL_BOTH_SWEEPS, (hipStream_t)stream);
   if (d->solve_reference_shape || d->solve_deterministic) { // the deterministic kernels of either option, column by column
     for (int j = 0; j < nrhs; j++) { int rc = cholamd_solve(d, d_arena, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, stream); if (rc) return rc; }
     return 0;
@@ -1222,6 +1258,7 @@ extern "C" int cholamd_solve_nrhs_f32(cholamd_device *d, const float *d_arena32,
 {
   { int rc = nrhs_check(d, d_arena32, d_B, ldb, d_X, ldx, nrhs, "cholamd_solve_nrhs_f32"); if (rc) return rc > 0 ? 0 : rc; }
   HIPCHK(hipSetDevice(d->dev));
+  if (det_block(d)) return solve_det_nrhs_t(d, d_arena32, d_B, ldb, d_X, ldx, nrhs, CHOL_BOTH_SWEEPS, (hipStream_t)stream);
   if (d->solve_reference_shape || d->solve_deterministic) {
     for (int j = 0; j < nrhs; j++) { int rc = cholamd_solve_f32(d, d_arena32, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, stream); if (rc) return rc; }
     return 0;
@@ -1287,7 +1324,8 @@ extern "C" int cholamd_solve_half_nrhs(cholamd_device *d, const double *d_arena,
     for (int j = 0; j < nrhs; j++) { int rc = solve_half_reference(d, d_arena, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, which, (hipStream_t)stream); if (rc) return rc; }
     return 0;
   }
-  if (d->solve_deterministic) { // no deterministic block kernel: column by column
+  if (det_block(d)) return solve_det_nrhs_t(d, d_arena, d_B, ldb, d_X, ldx, nrhs, which, (hipStream_t)stream);
+  if (d->solve_deterministic) { // without option solve_deterministic_block: column by column, every column the single deterministic solve
     for (int j = 0; j < nrhs; j++) { int rc = solve_det_t(d, d_arena, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, which, (hipStream_t)stream); if (rc) return rc; }
     return 0;
   }
@@ -1298,6 +1336,7 @@ extern "C" int cholamd_solve_half_nrhs_f32(cholamd_device *d, const float *d_are
   if (d) { int rc = half_which_ok(which, "cholamd_solve_half_nrhs_f32"); if (rc) return rc; }
   { int rc = nrhs_check(d, d_arena32, d_B, ldb, d_X, ldx, nrhs, "cholamd_solve_half_nrhs_f32"); if (rc) return rc > 0 ? 0 : rc; }
   HIPCHK(hipSetDevice(d->dev));
+  if (det_block(d)) return solve_det_nrhs_t(d, d_arena32, d_B, ldb, d_X, ldx, nrhs, which, (hipStream_t)stream);
   if (d->solve_deterministic) {
     for (int j = 0; j < nrhs; j++) { int rc = solve_det_t(d, d_arena32, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, which, (hipStream_t)stream); if (rc) return rc; }
     return 0;
@@ -1726,9 +1765,11 @@ static int residual_nrhs(cholamd_device *d, const double *d_B, int64_t ldb, cons
   }
   return 0;
 }
-// M^-1 B for `cols` columns with M = L32 L32^T: the block solve, or column by column under option solve_reference_shape or solve_deterministic
+// M^-1 B for `cols` columns with M = L32 L32^T: the block solve, the deterministic block solve (option solve_deterministic_block), or column by column under
+// option solve_reference_shape or solve_deterministic
 static int refine_solve(cholamd_device *d, const float *d_arena32, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int cols, hipStream_t st)
 {
+  if (det_block(d)) return solve_det_nrhs_t(d, d_arena32, d_B, ldb, d_X, ldx, cols, CHOL_BOTH_SWEEPS, st);
   if (!d->solve_reference_shape && !d->solve_deterministic) return solve_nrhs_t(d, d_arena32, d_B, ldb, d_X, ldx, cols, st);
   for (int j = 0; j < cols; j++) { int rc = solve_streamed(d, d_arena32, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, st); if (rc) return rc; }
   return 0;

@@ -92,6 +92,13 @@ template <class TL> int chol_launch_multiply(const TL *base, const chol_mul_item
  * (those with fewer columns do nothing) with the 16x16 inverses W of chol_launch_solve_dinv, plain stores */
 template <class TL> int chol_launch_solve_det_gather(const TL *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, double *y, hipStream_t st);
 template <class TL> int chol_launch_solve_span(const TL *base, const chol_trsv_desc *descs, int n, const double *W, double *y, int col0, int backward, hipStream_t st);
+/* block form of the deterministic solve (option solve_deterministic_block): the gather of one step on a chunk of CHOL_NRHS_W columns,
+ * Yp[(item) 32 + j] -= sum over the item's sources, Yp the permuted row-major block of chol_nrhs_launch_permute, in place; the partition of
+ * chol_launch_multiply_nrhs (chol_muln_wave / chol_muln_elem), no atomics.  chol_nrhs_launch_span (chol_solve_nrhs.hip): the diagonal solve of the columns
+ * [col0, col0 + 256) of the n_descs separators `descs` on the block's 32 columns by the substitution chain of the 16x16 inverses W16 -- that one kernel
+ * alone, plain stores */
+template <class TL> int chol_launch_solve_det_gather_nrhs(const TL *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, double *Yp, hipStream_t st);
+template <class TL> int chol_nrhs_launch_span(const TL *base, const chol_trsv_desc *descs, int n_descs, const double *W16, double *Y, int col0, int backward, hipStream_t st);
 /* block form (chol_multiply_nrhs.hip): the same items on a chunk of CHOL_NRHS_W columns, Zp the permuted row-major block of chol_nrhs_launch_permute.
  * perm != NULL (the last stage of a call): Y[perm[pos] + (c0 + j) ldy] for the chunk's columns j < cols; perm == NULL (the first stage of the full product):
  * Y is a second permuted block, all 32 columns written */

@@ -498,7 +498,9 @@ void chol_sdet_lists_free(chol_sdet_lists *w);
  * order.  chol_muln_elem is the operand of line `line` and step `k` of a source: the arena index, CLAMPED into the strip (line < nv, k < len: a tile is read
  * whole, its reads stay inside the strip), and *meant = whether the entry takes part -- it is a line the item owns, a step the source has, and on or below
  * the diagonal of a diagonal block (the `tri` rule of chol_mul_src).  An operand that is not meant is SELECTED to 0.0, never multiplied by zero.  The
- * kernel and cholamd_plan_multiply_host_nrhs both use these two functions, so the host walk checks the kernel's index logic.
+ * kernel and cholamd_plan_multiply_host_nrhs both use these two functions, so the host walk checks the kernel's index logic.  So do the block gather of the
+ * deterministic solve (k_solve_det_gather_nrhs, option solve_deterministic_block) and its host walk cholamd_plan_solve_det_host_nrhs, on the items and
+ * sources of chol_sdet_lists.
  * Precondition of chol_muln_elem: nv >= 1 and q->len >= 1 (the clamp is to nv - 1 and len - 1).  chol_build_multiply makes no other item or source -- an
  * item has 1 .. 16 positions, a source of no steps is not pushed -- and a chunk loop over [0, len) does not run for len = 0. */
 #define CHOL_MULN_KSTEP 32 /* reduction steps of one chunk: 8 MFMA steps of 4 whose loads are in flight together */

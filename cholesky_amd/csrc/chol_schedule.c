@@ -3020,6 +3020,93 @@ int cholamd_plan_solve_det_host(const cholamd_plan *p, const double *arena_host,
   chol_sdet_lists_free(&w);
   return 0;
 }
+/* The block form (option solve_deterministic_block of the device; chol_solve_det.hip at k_solve_det_gather_nrhs): one sweep over a host arena on the
+ * permuted ROW-major block yp (n x 32).  A gather has the kernel's own partition -- chol_muln_wave deals a source's chunks of CHOL_MULN_KSTEP steps to four
+ * partial tiles, chol_muln_elem gives the operand (read clamped, skipped where it is not meant), the four partial sums of an element are added in wave
+ * order and subtracted from the owner's value.  A span is solved by substitution inside its own lower triangle, column by column of the block, as
+ * sdet_host_sweep does (the device's span kernel sums in another order: the host walk does not return the device's bits).  Every column of the block
+ * goes through its own scalar operations: no column's result depends on another's. */
+static void sdet_host_block_sweep(const plan_t *p, const chol_sdet_lists *w, int which, const double *arena, double *yp)
+{
+  enum { T = CHOL_MUL_TILE, W = 32 };
+  double acc[CHOL_MULN_WAVES][T][W];
+  for (int t = 0; t < w->n_step[which]; t++) {
+    const chol_sdet_step *st = &w->step[which][t];
+    for (int i = st->item_first; i < st->item_end; i++) {
+      const chol_mul_item *it = &w->item[which][i];
+      memset(acc, 0, sizeof acc);
+      for (int s = it->src_first; s < it->src_end; s++) {
+        const chol_mul_src *q = &w->src[which][s];
+        for (int c = 0; c * CHOL_MULN_KSTEP < q->len; c++) {
+          double (*a)[W] = acc[chol_muln_wave(s - it->src_first, c)];
+          for (int k = c * CHOL_MULN_KSTEP; k < (c + 1) * CHOL_MULN_KSTEP; k++)
+            for (int l = 0; l < T; l++) {
+              int meant;
+              const double v = arena[chol_muln_elem(q, which, it->nv, l, k, &meant)]; /* read whether meant or not: the clamp keeps it inside the strip */
+              if (!meant) continue;
+              const double *zr = yp + (int64_t)(q->z_off + k) * W;
+              for (int j = 0; j < W; j++) a[l][j] += v * zr[j];
+            }
+        }
+      }
+      for (int l = 0; l < it->nv; l++)
+        for (int j = 0; j < W; j++) {
+          double sum = acc[0][l][j];
+          for (int wv = 1; wv < CHOL_MULN_WAVES; wv++) sum += acc[wv][l][j];
+          yp[(int64_t)(it->y_off + l) * W + j] -= sum;
+        }
+    }
+    if (st->col0 < 0) continue; /* the level's outside gather: no span */
+    for (int h = 1 << st->level; h < (1 << (st->level + 1)) && h <= p->nsep; h++) {
+      const int s = p->tree[h], n = p->sep_size[s], ld = p->panel_ld[s];
+      if (n <= st->col0) continue;
+      const int n1 = n < st->col0 + CHOL_SDET_SPAN ? n : st->col0 + CHOL_SDET_SPAN;
+      const double *Lm = arena + p->panel_off[s];
+      double *x = yp + (int64_t)p->sep_off[s] * W;
+      for (int c = 0; c < W; c++)
+        if (which == CHOLAMD_HALF_FORWARD)
+          for (int i = st->col0; i < n1; i++) {
+            double v = x[(int64_t)i * W + c];
+            for (int j = st->col0; j < i; j++) v -= Lm[i + (int64_t)j * ld] * x[(int64_t)j * W + c];
+            x[(int64_t)i * W + c] = v / Lm[i + (int64_t)i * ld];
+          }
+        else
+          for (int i = n1 - 1; i >= st->col0; i--) {
+            double v = x[(int64_t)i * W + c];
+            for (int j = i + 1; j < n1; j++) v -= Lm[j + (int64_t)i * ld] * x[(int64_t)j * W + c];
+            x[(int64_t)i * W + c] = v / Lm[i + (int64_t)i * ld];
+          }
+    }
+  }
+}
+int cholamd_plan_solve_det_host_nrhs(const cholamd_plan *p, const double *arena_host, int which, const double *B, int64_t ldb, double *X, int64_t ldx, int nrhs)
+{
+  const char *what = "cholamd_plan_solve_det_host_nrhs";
+  if (!p) { chol_set_error("%s: NULL plan", what); return CHOLAMD_ERR_ARG; }
+  if (which != CHOLAMD_HALF_FORWARD && which != CHOLAMD_HALF_BACKWARD && which != -1) { chol_set_error("%s: which = %d is neither CHOLAMD_HALF_FORWARD (0), CHOLAMD_HALF_BACKWARD (1) nor -1 (the whole solve)", what, which); return CHOLAMD_ERR_ARG; }
+  const int n = p->n;
+  if (nrhs < 0) { chol_set_error("%s: nrhs = %d < 0", what, nrhs); return CHOLAMD_ERR_ARG; }
+  if (ldb < n || ldx < n) { chol_set_error("%s: leading dimensions ldb = %lld, ldx = %lld must be at least n = %d", what, (long long)ldb, (long long)ldx, n); return CHOLAMD_ERR_ARG; }
+  if (nrhs == 0) return 0;
+  if (!arena_host || !B || !X) { chol_set_error("%s: NULL %s", what, !arena_host ? "arena" : !B ? "B" : "X"); return CHOLAMD_ERR_ARG; }
+  chol_sdet_lists w;
+  int rc = chol_build_solve_det(p, &w);
+  if (rc) return rc;
+  double *yp = malloc((size_t)(n > 0 ? n : 1) * 32 * sizeof(double));
+  if (!yp) { chol_sdet_lists_free(&w); chol_set_error("out of memory"); return CHOLAMD_ERR_NOMEM; }
+  for (int c0 = 0; c0 < nrhs; c0 += 32) {
+    const int cols = nrhs - c0 < 32 ? nrhs - c0 : 32;
+    for (int i = 0; i < n; i++)
+      for (int j = 0; j < 32; j++) yp[(int64_t)i * 32 + j] = j < cols ? B[p->perm[i] + (int64_t)(c0 + j) * ldb] : 0.0; /* (first: X may be B) */
+    if (which != CHOLAMD_HALF_BACKWARD) sdet_host_block_sweep(p, &w, CHOLAMD_HALF_FORWARD, arena_host, yp);
+    if (which != CHOLAMD_HALF_FORWARD) sdet_host_block_sweep(p, &w, CHOLAMD_HALF_BACKWARD, arena_host, yp);
+    for (int i = 0; i < n; i++)
+      for (int j = 0; j < cols; j++) X[p->perm[i] + (int64_t)(c0 + j) * ldx] = yp[(int64_t)i * 32 + j];
+  }
+  free(yp);
+  chol_sdet_lists_free(&w);
+  return 0;
+}
 int cholamd_plan_solve_det_counts(const cholamd_plan *p, int64_t out[8])
 {
   if (!p || !out) { chol_set_error("cholamd_plan_solve_det_counts: NULL %s", !p ? "plan" : "out"); return CHOLAMD_ERR_ARG; }

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include "chol_kernels.h"
+#include "chol_plan.h"
 
 #define SDET_THREADS 256
 #define SDET_STEPS (SDET_THREADS / CHOL_MUL_TILE) // reduction steps a lane takes per staged block of the vector
@@ -77,3 +78,90 @@ int chol_launch_solve_det_gather(const TL *base, const chol_mul_item *items, int
 
 template int chol_launch_solve_det_gather(const double *, const chol_mul_item *, int, const chol_mul_src *, int, double *, hipStream_t);
 template int chol_launch_solve_det_gather(const float *, const chol_mul_item *, int, const chol_mul_src *, int, double *, hipStream_t);
+
+// Block form (option solve_deterministic_block): the gather of a step on a chunk of CHOL_NRHS_W = 32 columns, Yp[(y_off + line) 32 + j] -= sum over the
+// item's sources of L(line, k) Yp[(z_off + k) 32 + j].  Yp is the permuted ROW-major block of the block solve (k_nrhs_permute_in, padding columns zero).
+// It is k_multiply_nrhs (chol_multiply_nrhs.hip) turned into a subtracting gather: one workgroup of CHOL_MULN_WAVES = 4 waves per item, every source's
+// reduction range cut into chunks of CHOL_MULN_KSTEP steps dealt to the waves by chol_muln_wave, operands and their clamping from chol_muln_elem (an operand
+// that is not meant is SELECTED to 0.0, never multiplied; the lists' `tri` values make every source whole), one 16 x 32 partial tile per wave in two
+// v_mfma_f64_16x16x4_f64 accumulators, the four tiles added in wave order out of LDS by the element's owner.  One owner per element, a fixed order, no
+// floating-point atomics, no waiting: two calls leave the same bits, and a column's bits depend on that column alone (an MFMA result column reads one column
+// of B; padding columns and other columns never mix in).
+//
+// IN PLACE: the B operand and the result are the same buffer, so Yp carries no __restrict__.  That is safe because the rows a step READS (z_off + k) were
+// solved by earlier launches on the stream and are owned by no item of the step (chol_build_solve_det checks both), and the rows an item WRITES are its own
+// alone, read (for the subtraction) by their owner only: no workgroup of a launch reads what another one writes.
+//
+// Reduction tiles in LDS: pitch 32 doubles, not padded.  The stores are ds_write_b64 (lane groups of 16 contiguous lanes, bank = dword mod 32): a group
+// is one lane group g of the MFMA result, 16 consecutive doubles of one row = 32 distinct banks at any pitch.  The reads are ds_read_b64 (two groups of 32
+// lanes, bank = dword mod 64): 32 consecutive lanes read the 32 consecutive doubles of one row = 64 distinct banks.  (k_multiply_nrhs pads to 33 for its
+// other read order, along the lines of one column; this kernel has the row order only.)
+#define SDN_THREADS (64 * CHOL_MULN_WAVES)
+#define SDN_U (CHOL_MULN_KSTEP / 4) // MFMA steps per chunk
+#define SDN_NW CHOL_NRHS_W
+#define SDN_TILE (CHOL_MUL_TILE * SDN_NW)
+static_assert(SDN_NW == 32 && CHOL_MUL_TILE == 16 && CHOL_MULN_WAVES == 4, "a tile is 16 lines x two 16-column halves, four waves per item");
+
+typedef double sdn_d4 __attribute__((ext_vector_type(4)));
+
+template <class TL, int BW>
+__global__ __launch_bounds__(SDN_THREADS) void k_solve_det_gather_nrhs(const TL *__restrict__ base, const chol_mul_item *__restrict__ items, const chol_mul_src *__restrict__ srcs, double *Yp)
+{
+  __shared__ double red[CHOL_MULN_WAVES * SDN_TILE];
+  const chol_mul_item it = items[blockIdx.x];
+  const int t = threadIdx.x, wave = t >> 6, lane = t & 63, i16 = lane & 15, g = lane >> 4;
+  sdn_d4 acc0 = { 0.0, 0.0, 0.0, 0.0 }, acc1 = { 0.0, 0.0, 0.0, 0.0 };
+  for (int s = it.src_first; s < it.src_end; s++) {
+    const chol_mul_src q = srcs[s];
+    const double *B = Yp + (int64_t)q.z_off * SDN_NW;
+    // this wave's chunks of the source: c = first, first + 4, ... with chol_muln_wave(s - src_first, c) == wave
+    const int first = (wave - (s - it.src_first)) & (CHOL_MULN_WAVES - 1);
+    for (int k0 = first * CHOL_MULN_KSTEP; k0 < q.len; k0 += CHOL_MULN_WAVES * CHOL_MULN_KSTEP) {
+      double a[SDN_U], b0[SDN_U], b1[SDN_U];
+#pragma unroll
+      for (int u = 0; u < SDN_U; ++u) {
+        const int k = k0 + 4 * u + g, kk = min(k, q.len - 1);
+        int meant;
+        const int64_t e = chol_muln_elem(&q, BW, it.nv, i16, k, &meant);
+        const double v = (double)base[e];
+        a[u] = meant ? v : 0.0;
+        const double z0 = B[(int64_t)kk * SDN_NW + i16], z1 = B[(int64_t)kk * SDN_NW + 16 + i16];
+        b0[u] = k < q.len ? z0 : 0.0;
+        b1[u] = k < q.len ? z1 : 0.0;
+      }
+#pragma unroll
+      for (int u = 0; u < SDN_U; ++u) {
+        acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], b0[u], acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], b1[u], acc1, 0, 0, 0);
+      }
+    }
+  }
+  double *mine = red + wave * SDN_TILE;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    mine[(g + 4 * r) * SDN_NW + i16] = acc0[r];
+    mine[(g + 4 * r) * SDN_NW + 16 + i16] = acc1[r];
+  }
+  __syncthreads();
+  // 512 elements, two per lane along the 32 columns of a row of the block, the waves' partial tiles in wave order
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int e = t + h * SDN_THREADS, line = e / SDN_NW;
+    double sum = red[e];
+#pragma unroll
+    for (int w = 1; w < CHOL_MULN_WAVES; ++w) sum += red[w * SDN_TILE + e];
+    if (line < it.nv) Yp[(int64_t)it.y_off * SDN_NW + e] -= sum;
+  }
+}
+
+template <class TL>
+int chol_launch_solve_det_gather_nrhs(const TL *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, double *Yp, hipStream_t st)
+{
+  if (n_items <= 0) return 0;
+  if (backward) hipLaunchKernelGGL((k_solve_det_gather_nrhs<TL, 1>), dim3(n_items), dim3(SDN_THREADS), 0, st, base, items, srcs, Yp);
+  else hipLaunchKernelGGL((k_solve_det_gather_nrhs<TL, 0>), dim3(n_items), dim3(SDN_THREADS), 0, st, base, items, srcs, Yp);
+  return (int)hipGetLastError();
+}
+
+template int chol_launch_solve_det_gather_nrhs(const double *, const chol_mul_item *, int, const chol_mul_src *, int, double *, hipStream_t);
+template int chol_launch_solve_det_gather_nrhs(const float *, const chol_mul_item *, int, const chol_mul_src *, int, double *, hipStream_t);

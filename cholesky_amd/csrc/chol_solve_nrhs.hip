@@ -289,6 +289,15 @@ int chol_nrhs_launch_trsv(const TL *base, const chol_trsv_desc *descs, int n, in
   }
   return (int)hipGetLastError();
 }
+// The span [col0, col0 + 256) of every separator of `descs` by the substitution chain of the 16x16 inverses (W256 = NULL), and nothing else: the span
+// step of the deterministic block solve (option solve_deterministic_block), whose rows outside the span are the business of its gather launches.
+template <class TL> int chol_nrhs_launch_span(const TL *base, const chol_trsv_desc *descs, int n_descs, const double *W16, double *Y, int col0, int backward, hipStream_t st)
+{
+  if (n_descs <= 0) return 0;
+  if (backward) hipLaunchKernelGGL((k_nrhs_span<true, TL>), dim3(n_descs), dim3(256), 0, st, base, descs, W16, (const double *)nullptr, 0, Y, col0);
+  else hipLaunchKernelGGL((k_nrhs_span<false, TL>), dim3(n_descs), dim3(256), 0, st, base, descs, W16, (const double *)nullptr, 0, Y, col0);
+  return (int)hipGetLastError();
+}
 template <class TL> int chol_nrhs_launch_offdiag(const TL *base, const chol_gemv_desc *blocks, const int *items, int n_items, double *Y, int backward, hipStream_t st)
 {
   if (n_items <= 0) return 0;
@@ -307,6 +316,8 @@ int chol_nrhs_launch_permute(const double *B, int64_t ldb, const int *perm, doub
 }
 template int chol_nrhs_launch_trsv(const double *, const chol_trsv_desc *, int, int, int, const double *, const double *, double *, int, hipStream_t);
 template int chol_nrhs_launch_trsv(const float *, const chol_trsv_desc *, int, int, int, const double *, const double *, double *, int, hipStream_t);
+template int chol_nrhs_launch_span(const double *, const chol_trsv_desc *, int, const double *, double *, int, int, hipStream_t);
+template int chol_nrhs_launch_span(const float *, const chol_trsv_desc *, int, const double *, double *, int, int, hipStream_t);
 template int chol_nrhs_launch_offdiag(const double *, const chol_gemv_desc *, const int *, int, double *, int, hipStream_t);
 template int chol_nrhs_launch_offdiag(const float *, const chol_gemv_desc *, const int *, int, double *, int, hipStream_t);
 int chol_nrhs_launch_residual(const int64_t *ptr, const int *col, const double *val, const double *B, int64_t ldb, const double *X, int64_t ldx, double *R, int64_t ldr,

@@ -159,7 +159,10 @@ class Device:
         return self.L.cholamd_device_bcast_phases(self.h) > 0
 
     def set_option(self, name, value):
-        """Schedule / kernel-selection switch of this device object (cholamd_device_set_option)."""
+        """Schedule / kernel-selection switch of this device object (cholamd_device_set_option).  Among them "solve_deterministic" (the same bits from
+        every single-vector solve) and, on top of it, "solve_deterministic_block": the _nrhs solves then take the deterministic block path -- one
+        pass over the factor per 32 columns, the same bits every time, every column's bits independent of the other columns (include/cholamd.h at
+        "deterministic solve")."""
         check(self.L.cholamd_device_set_option(self.h, name.encode(), int(value)), "cholamd_device_set_option")
 
     def program_trace(self, arena, stream=None):
@@ -267,7 +270,8 @@ class Device:
 
     def solve_nrhs(self, arena, B, X, stream=None):
         """X = A^-1 B for the k columns of B (n x k, column-major: stride(0) == 1) in one pass over the factor per 32 columns
-        (cholamd_solve_nrhs / _f32 by the arena's element type); asynchronous on `stream`."""
+        (cholamd_solve_nrhs / _f32 by the arena's element type); asynchronous on `stream`.  Under option solve_deterministic: column by column, or, with
+        solve_deterministic_block set too, the deterministic block path (bit-reproducible, columns independent of each other)."""
         import torch
         ldb, ldx, k = self._blocks(B, X)
         f32 = arena.elem_bytes == 4 if isinstance(arena, RankArena) else arena.dtype == torch.float32
@@ -286,7 +290,8 @@ class Device:
         check(fn(self.h, self.ptr(arena), self.ptr(b), self.ptr(x), int(which), _stream_ptr(stream)), "cholamd_solve_half")
 
     def solve_half_nrhs(self, arena, B, X, which, stream=None):
-        """The same for the k columns of B (n x k, column-major, as solve_nrhs takes them): cholamd_solve_half_nrhs / _f32."""
+        """The same for the k columns of B (n x k, column-major, as solve_nrhs takes them): cholamd_solve_half_nrhs / _f32.  With the options
+        solve_deterministic and solve_deterministic_block BACKWARD of FORWARD of B equals solve_nrhs(B) bit for bit."""
         ldb, ldx, k = self._blocks(B, X)
         fn = self.L.cholamd_solve_half_nrhs_f32 if self._is_f32(arena) else self.L.cholamd_solve_half_nrhs
         check(fn(self.h, self.ptr(arena), self.ptr(B), ldb, self.ptr(X), ldx, k, int(which), _stream_ptr(stream)), "cholamd_solve_half_nrhs")
@@ -438,7 +443,9 @@ class Device:
         return x
 
     def solve_refine_nrhs(self, arena32, B, X, max_iter=20, tol=1e-12, stream=None):
-        """cholamd_solve_refine_nrhs: every column of X = A^-1 B by iterative refinement on the fp32 factor; returns (corrections applied, relres per column)."""
+        """cholamd_solve_refine_nrhs: every column of X = A^-1 B by iterative refinement on the fp32 factor; returns (corrections applied, relres per column).
+        With the options solve_deterministic and solve_deterministic_block every solve inside is the deterministic block solve: two calls return the
+        same corrections, relres and bits (the columns of a chunk of 32 share the number of corrections, so they are not independent of each other)."""
         ldb, ldx, k = self._blocks(B, X)
         it = C.c_int(0)
         rel = np.zeros(max(k, 1), dtype=np.float64)

@@ -360,6 +360,24 @@ class Plan:
         check(self.L.cholamd_plan_solve_det_host(self.h, arena.ctypes.data, int(which), b.ctypes.data, x.ctypes.data), "cholamd_plan_solve_det_host")
         return x[:self.n]
 
+    def solve_det_host_nrhs(self, arena, which, B, ldb=None, ldx=None):
+        """X = M^-1 B (which = 0), M^-T B (1) or A^-1 B (-1) on the CPU for the columns of B (n x k) with the step lists and the block gather's own
+        partition of every source (cholamd_plan_solve_det_host_nrhs; Device option solve_deterministic_block).  ldb / ldx: leading dimensions of the
+        column-major copies handed to the library (default n); the rows n .. ldx - 1 of the result are checked to be untouched.  Returns n x k.
+        Deterministic and column by column independent, but not the device's bits."""
+        arena = np.ascontiguousarray(arena, dtype=np.float64)
+        assert arena.size == self.arena_doubles
+        B = np.asarray(B, dtype=np.float64)
+        assert B.ndim == 2 and B.shape[0] == self.n
+        k = B.shape[1]
+        ldb, ldx = int(ldb or self.n), int(ldx or self.n)
+        bb = np.full((max(k, 1), max(ldb, 1)), -3.0)     # row j of the buffer = column j of B
+        bb[:k, :self.n] = B.T
+        xb = np.full((max(k, 1), max(ldx, 1)), np.nan)
+        check(self.L.cholamd_plan_solve_det_host_nrhs(self.h, arena.ctypes.data, int(which), bb.ctypes.data, ldb, xb.ctypes.data, ldx, k), "cholamd_plan_solve_det_host_nrhs")
+        assert np.isnan(xb[:, self.n:]).all(), "rows n .. ldx - 1 of X were written"
+        return xb[:k, :self.n].T.copy()
+
     def solve_det_counts(self):
         """Sizes of the step lists of the deterministic streamed solve (cholamd_plan_solve_det_counts): a dict per direction of steps (one span launch
         each, preceded by a gather launch where the step has items), items, sources and the entries of L one sweep reads."""

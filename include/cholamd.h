@@ -424,14 +424,37 @@ int cholamd_solve(cholamd_device *d, const double *d_arena, const double *d_b, d
  * uploaded at the first such solve on a device object (setting the option builds nothing).
  * Precedence: where "solve_reference_shape" is also set and applies (the fp64 factor), it wins.
  * The _nrhs entry points (cholamd_solve_nrhs, cholamd_solve_half_nrhs, their _f32 forms, cholamd_solve_refine_nrhs) go COLUMN BY COLUMN through the
- * deterministic single-vector solve under the option, as they do under "solve_reference_shape": column j has the bits of the single solve of column j; there
- * is no deterministic block kernel.
+ * deterministic single-vector solve under the option, as they do under "solve_reference_shape": column j has the bits of the single solve of column j --
+ * unless option "solve_deterministic_block" is set too (next paragraph).
+ * BLOCK FORM: device option "solve_deterministic_block" (cholamd_device_set_option, or CHOLAMD_SOLVE_DETERMINISTIC_BLOCK non-zero in the environment at
+ * cholamd_device_create; default off; setting it rebuilds nothing).  It has an effect only where "solve_deterministic" is on, "solve_deterministic_block" is
+ * on and "solve_reference_shape" is off; in every other combination every entry point does exactly what it does without it, down to which kernels run.
+ * Where the three hold, cholamd_solve_nrhs, cholamd_solve_half_nrhs, their _f32 forms and every solve inside cholamd_solve_refine_nrhs walk the same step
+ * lists on chunks of 32 columns: per step one block gather (16 x 32 tiles on v_mfma_f64_16x16x4_f64, four waves per item, their partial tiles added in wave
+ * order by the element's owner) and one launch of the block solve's span kernel in its substitution form, plain stores.  One pass over L and one launch
+ * chain per 32 columns instead of one per column; no floating-point atomic, no flag, no wait inside a launch.  EVERY chunk takes the block kernels, whatever
+ * its column count (nrhs = 1 included: a caller with one column has cholamd_solve).  THE CONTRACT of the block form:
+ *  (a) the same bits for the same arena and the same B -- from call to call, from one device object of a plan to another, on a device object created under
+ *      CHOLAMD_POISON=1, in place (X == B, ldx == ldb) and with ldb, ldx > n;
+ *  (b) COLUMN INDEPENDENCE: the bits of column j of X depend on the arena and on column j of B only -- not on nrhs, not on the column's position (its chunk,
+ *      its half of the 32-column tile), not on the other columns' contents: a NaN in another column never reaches it;
+ *  (c) cholamd_solve_half_nrhs(BACKWARD) of cholamd_solve_half_nrhs(FORWARD) of B equals cholamd_solve_nrhs(B) bit for bit;
+ *  (d) cholamd_solve_refine_nrhs called twice returns the same iters, the same relres per column and the same bits of X.  Column independence does NOT
+ *      hold for the refinement: the columns of a chunk share the number of corrections;
+ *  (e) rows n .. ld - 1 of X and columns >= nrhs are never written.
+ * NOT PROMISED: the bits of the single-vector deterministic solve (the sums are partitioned differently); the two agree to rounding.
+ * NOT COVERED by the block form either: the sharded and multi-GPU solves, the Schur condense / expand, and anything under "solve_reference_shape".
  * NOT COVERED (they keep the atomic path whatever the option says): the sharded and multi-GPU solves (cholamd_solve_sharded, cholamd_solve_multi, the
  * sharded refinement) on more than one rank, and the Schur condense / expand.
  * Needs the COMPLETE factor in the arena, like cholamd_solve: a single-GPU device object, or rank 0's after a gather.
  * cholamd_plan_solve_det_host: the same walk on the HOST over a host arena with the same lists (which = CHOLAMD_HALF_FORWARD, CHOLAMD_HALF_BACKWARD, or -1:
  * the whole solve = FORWARD then BACKWARD; b and x n doubles in original dof order, x == b allowed); a span is solved by substitution inside its own lower
  * triangle.  Deterministic, but not the device's bits (the span kernels order their sums differently).  Builds the lists anew at every call.
+ * cholamd_plan_solve_det_host_nrhs: the BLOCK form on the host (which as above; B, X: n x nrhs column-major in original dof order with leading dimensions
+ * ldb, ldx >= n, X == B allowed with ldx == ldb; nrhs = 0 returns 0 and touches nothing; the argument rules of cholamd_plan_multiply_host_nrhs).  A gather
+ * uses the block kernel's own partition (chol_muln_wave, chol_muln_elem of chol_plan.h: four partial sums per element, added in wave order), so the host
+ * walk checks the kernel's index logic; a span is solved by substitution inside its own lower triangle.  Deterministic, every column independent of the
+ * others (contract (b) and (c) hold on the host too), but NOT the device's bits: the device's span kernel sums in another order.
  * cholamd_plan_solve_det_counts: out = { FORWARD steps, items, sources, entries of L read, BACKWARD steps, items, sources, entries of L read }; a step is one
  * gather launch where it has items, followed by one span launch unless it is a level's lead step; the entries are those of the gather sources plus the
  * spans' own lower triangles.
@@ -440,6 +463,7 @@ int cholamd_solve(cholamd_device *d, const double *d_arena, const double *d_b, d
  * items (first permuted position, positions, first source, end source), sources (arena offset, leading dimension, reduction steps, first permuted position
  * read, triangle rule of chol_mul_src). */
 int cholamd_plan_solve_det_host(const cholamd_plan *p, const double *arena_host, int which, const double *b, double *x);
+int cholamd_plan_solve_det_host_nrhs(const cholamd_plan *p, const double *arena_host, int which, const double *B, int64_t ldb, double *X, int64_t ldx, int nrhs);
 int cholamd_plan_solve_det_counts(const cholamd_plan *p, int64_t out[8]);
 int cholamd_plan_solve_det_lists(const cholamd_plan *p, int which, int64_t *steps, int64_t *items, int64_t *srcs);
 /* ---- mixed precision (BASELINE config 5; not in the reference, whose arithmetic is fp64 CBLAS throughout): fp32 factor +

@@ -10,7 +10,14 @@ halves.  Reported besides: launches per sweep (one span launch per step that has
 inverses come on top for every path), the entries of L a sweep reads (Plan.solve_det_counts) and those bytes over the time as a fraction of the HBM peak.
 
 THE CONDITION (fp64): the deterministic solve is faster than solve_reference_shape by more than the two spreads -- its slowest repeat below the other's
-fastest.  The last line says whether it holds."""
+fastest.  The last line says whether it holds.
+
+  python scripts/solve_det_bench.py CASE PRECISION NRHS   the BLOCK form on NRHS right-hand sides (DESIGN.md section 14 at "Block form")
+
+With NRHS the call is solve_nrhs on an n x NRHS block and three paths alternate in the same way: the deterministic block solve (options solve_deterministic
+and solve_deterministic_block), the deterministic column-wise solve (solve_deterministic alone: one single-vector solve per column) and the atomic block
+solve (both off).  Bytes: the entries of L once per chunk of 32 columns.  ITS CONDITION: the block solve's slowest repeat below the column-wise solve's
+fastest."""
 import os
 import statistics
 import sys
@@ -41,6 +48,7 @@ def main():
     dev.sync()
     assert dev.info() == (0, 0)
     n = plan.n
+    nrhs = int(sys.argv[3]) if len(sys.argv) > 3 else 0
     b = torch.randn(n, dtype=torch.float64, device="cuda")
     x = torch.empty_like(b)
     t0 = time.perf_counter()
@@ -55,6 +63,9 @@ def main():
     if not f32:
         paths.append(("reference_shape", {"solve_deterministic": 0, "solve_reference_shape": 1}))
     solve = dev.solve_f32 if f32 else dev.solve
+    if nrhs > 0:
+        block_bench(dev, a, plan, cnt, case, prec, nrhs, reps)
+        return
     calls = [("solve", lambda: solve(a, b, x)), ("half FORWARD", lambda: dev.solve_half(a, b, x, 0)), ("half BACKWARD", lambda: dev.solve_half(a, b, x, 1))]
 
     def use(opts):
@@ -96,6 +107,46 @@ def main():
         d, r = results["solve", "deterministic"], results["solve", "reference_shape"]
         ok = d[2] < r[1]
         print(f"condition (the deterministic solve's slowest repeat {d[2]:.3f} ms below solve_reference_shape's fastest {r[1]:.3f} ms): {'HOLDS' if ok else 'FAILS'}")
+
+
+def block_bench(dev, a, plan, cnt, case, prec, nrhs, reps):
+    import torch
+    n, esz = plan.n, 4 if prec == "fp32" else 8
+    B = torch.randn(nrhs, n, dtype=torch.float64, device="cuda").T      # column-major n x nrhs
+    X = torch.empty(nrhs, n, dtype=torch.float64, device="cuda").T
+    paths = [("det block", {"solve_deterministic": 1, "solve_deterministic_block": 1}), ("det column-wise", {"solve_deterministic": 1, "solve_deterministic_block": 0}),
+             ("atomic block", {"solve_deterministic": 0, "solve_deterministic_block": 0})]
+    dev.set_option("solve_reference_shape", 0)
+    chunks = (nrhs + 31) // 32
+    nbytes = esz * chunks * (cnt["forward"]["entries"] + cnt["backward"]["entries"])
+    print(f"{case} {prec}: n = {n}, solve_nrhs of {nrhs} columns ({chunks} chunks of 32), {reps} repeats")
+    ts = {p: [] for p, _ in paths}
+    for p, opts in paths:                           # warm-up: lists built and uploaded, kernels loaded
+        for k, v in opts.items():
+            dev.set_option(k, v)
+        for _ in range(2):
+            dev.solve_nrhs(a, B, X)
+    torch.cuda.synchronize()
+    for _ in range(reps):
+        for p, opts in paths:
+            for k, v in opts.items():
+                dev.set_option(k, v)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            dev.solve_nrhs(a, B, X)
+            e1.record()
+            e1.synchronize()
+            ts[p].append(e0.elapsed_time(e1))
+    res = {}
+    for p, _ in paths:
+        t = res[p] = (statistics.median(ts[p]), min(ts[p]), max(ts[p]))
+        print(f"solve_nrhs({nrhs:3d}) {p:16s} {t[0]:10.3f} ms [{t[1]:.3f}, {t[2]:.3f}]   {t[0] / nrhs:8.4f} ms per column   "
+              f"{nbytes / (t[0] * 1e-3) / 1e12:.3f} TB/s = {nbytes / (t[0] * 1e-3) / HBM_PEAK:.1%} of peak (the bytes of L per chunk)")
+    for k in ("solve_deterministic", "solve_deterministic_block"):
+        dev.set_option(k, 0)
+    d, c, at = res["det block"], res["det column-wise"], res["atomic block"]
+    print(f"det block / atomic block = {d[0] / at[0]:.2f}, det column-wise / det block = {c[0] / d[0]:.2f}")
+    print(f"condition (the block solve's slowest repeat {d[2]:.3f} ms below the column-wise solve's fastest {c[1]:.3f} ms): {'HOLDS' if d[2] < c[1] else 'FAILS'}")
 
 
 if __name__ == "__main__":
