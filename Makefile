@@ -103,3 +103,11 @@ asan: $(ASAN_OUT)/libcholamd.so $(ASAN_OUT)/host_leak $(ASAN_OUT)/schur_host $(A
 	CHOLAMD_LIB=$(abspath $(ASAN_OUT)/libcholamd.so) LD_PRELOAD=$$($(CC) -print-file-name=libasan.so):$$($(CC) -print-file-name=libubsan.so) \
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 python3 -m pytest tests/test_host.py -x -q -p no:cacheprovider
 .PHONY: asan
+# the host restatement of the block Schur condense / expand under the sanitizers, in a process of its own (tests/native/schur_solve_host.c: it generates
+# its input): `make schur_solve_host` builds and runs this program alone
+$(ASAN_OUT)/schur_solve_host: tests/native/schur_solve_host.c $(ASAN_OUT)/libcholamd.so
+	$(HIPCC) -x c -O1 -Iinclude $(SAN) -fno-sanitize=function -o $@ $< -L$(ASAN_OUT) -lcholamd -Wl,-rpath,$(abspath $(ASAN_OUT)) -lm
+schur_solve_host: $(ASAN_OUT)/schur_solve_host
+	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 LSAN_OPTIONS=suppressions=$(abspath scripts/lsan.supp):print_suppressions=0 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
+	$(ASAN_OUT)/schur_solve_host
+.PHONY: schur_solve_host

@@ -200,6 +200,13 @@ def load():
     L.cholamd_schur.argtypes = [vp, vp, ci, vp, i64, vp]
     for f in (L.cholamd_schur_condense, L.cholamd_schur_condense_f32, L.cholamd_schur_expand, L.cholamd_schur_expand_f32):
         f.argtypes = [vp, vp, ci, vp, vp, vp, vp]
+    for f in (L.cholamd_schur_condense_nrhs, L.cholamd_schur_condense_nrhs_f32, L.cholamd_schur_expand_nrhs, L.cholamd_schur_expand_nrhs_f32):
+        f.argtypes = [vp, vp, ci, vp, i64, vp, i64, vp, i64, ci, vp]
+    L.cholamd_device_schur_launches.argtypes = [vp, vp]
+    L.cholamd_plan_schur_condense_host_nrhs.argtypes = [vp, ci, vp, vp, i64, vp, i64, vp, i64, ci]
+    L.cholamd_plan_schur_expand_host_nrhs.argtypes = [vp, ci, vp, vp, i64, vp, i64, vp, i64, ci]
+    L.cholamd_plan_schur_det_counts.argtypes = [vp, ci, vp]
+    L.cholamd_plan_schur_det_lists.argtypes = [vp, ci, ci, vp, vp, vp]
     L.cholamd_device_alloc_arena.argtypes = [vp, ci, C.POINTER(vp), C.POINTER(C.c_int64)]
     L.cholamd_device_free_arena.argtypes = [vp, vp]
     L.cholamd_device_set_timing.argtypes = [vp, ci]

@@ -61,6 +61,8 @@ struct selinv_dev { // the lists of one tree level of the selected inversion (ch
   int max_nblk = 0;
 };
 struct schur_dev { dev_buf<chol_schur_desc> desc; int64_t n = -1; }; // n < 0: not built yet
+// the deterministic step lists of condense / expand cut at k kept levels (chol_build_schur_det), on the device; the steps stay on the host
+struct schur_det_dev { dev_buf<chol_mul_item> item[2]; dev_buf<chol_mul_src> src[2]; std::vector<chol_sdet_step> step[2]; bool ready = false; };
 struct timed_launch { hipEvent_t a, b; int kind; };
 
 struct cholamd_device {
@@ -139,6 +141,11 @@ struct cholamd_device {
   std::vector<selinv_dev> si; dev_buf<double> si_ws; bool si_ready = false;
   // Schur complement (cholamd_schur): the gather kernel's piece list per number of kept levels k (index k), uploaded at the first call with that k
   std::vector<schur_dev> sc;
+  // option schur_deterministic: condense / expand (single vector and _nrhs) walk the step lists cut at k (index k), built and uploaded at the first such
+  // call with that k.  schur_launches: { atomic sweep, deterministic gather, deterministic span, pack / unpack } launches of the Schur sweeps so far
+  bool schur_deterministic = false;
+  std::vector<schur_det_dev> scd;
+  int64_t schur_launches[4] = { 0, 0, 0, 0 };
   // forward products (cholamd_multiply_half / cholamd_multiply / cholamd_factor_residual): the owner lists of the whole tree per direction, uploaded at the
   // first call; the intermediate vector of cholamd_multiply (permuted coordinates); the residual's per-workgroup partial sums and result words
   dev_buf<chol_mul_item> mul_item[2]; dev_buf<chol_mul_src> mul_src[2]; int n_mul_item[2] = { 0, 0 }; bool mul_ready = false;
@@ -304,6 +311,7 @@ extern "C" int cholamd_device_create(const cholamd_plan *plan, int device_id, ch
   { const char *e = getenv("CHOLAMD_SOLVE_REFERENCE_SHAPE"); d->solve_reference_shape = e && *e && atoi(e) != 0; }
   { const char *e = getenv("CHOLAMD_SOLVE_DETERMINISTIC"); d->solve_deterministic = e && *e && atoi(e) != 0; }
   { const char *e = getenv("CHOLAMD_SOLVE_DETERMINISTIC_BLOCK"); d->solve_deterministic_block = e && *e && atoi(e) != 0; }
+  { const char *e = getenv("CHOLAMD_SCHUR_DETERMINISTIC"); d->schur_deterministic = e && *e && atoi(e) != 0; }
   { const char *e = getenv("CHOLAMD_MULTIPLY_NRHS_MIN"); d->multiply_nrhs_min = e && *e ? atoi(e) : 0; }
   int rc = build_levels(d);
   if (!rc) rc = d->ws.alloc((size_t)(plan->ws_doubles > 0 ? plan->ws_doubles : 1));
@@ -378,6 +386,7 @@ extern "C" int cholamd_device_set_option(cholamd_device *d, const char *name, in
   else if (n == "solve_reference_shape") { d->solve_reference_shape = value != 0; rebuild = false; }
   else if (n == "solve_deterministic") { d->solve_deterministic = value != 0; rebuild = false; }
   else if (n == "solve_deterministic_block") { d->solve_deterministic_block = value != 0; rebuild = false; }
+  else if (n == "schur_deterministic") { d->schur_deterministic = value != 0; rebuild = false; }
   else if (n == "multiply_nrhs_min") { d->multiply_nrhs_min = value; rebuild = false; }
   else { chol_set_error("unknown option '%s'", n.c_str()); return CHOLAMD_ERR_ARG; }
   return rebuild ? build_levels(d) : 0;
@@ -1690,6 +1699,70 @@ template <class TL> static int schur_inverses(cholamd_device *d, const TL *d_are
   }
   return 0;
 }
+// ---- option schur_deterministic: the step lists cut at k (chol_build_schur_det), per (device object, k), built at the first such call and kept
+static int build_schur_det(cholamd_device *d, int k)
+{
+  if (d->scd.empty()) d->scd.resize(d->plan->levels);
+  schur_det_dev &q = d->scd[k];
+  if (q.ready) return 0;
+  chol_sdet_lists w;
+  int rc = chol_build_schur_det(d->plan, k, &w);
+  if (rc) return rc;
+  for (int c = 0; c < 2 && !rc; c++) { // (an upload replaces what a call that failed half-way left)
+    rc = q.item[c].upload(w.item[c], (size_t)w.n_item[c]);
+    if (!rc) rc = q.src[c].upload(w.src[c], (size_t)w.n_src[c]);
+    q.step[c].assign(w.step[c], w.step[c] + w.n_step[c]);
+  }
+  chol_sdet_lists_free(&w);
+  if (rc) return rc;
+  q.ready = true;
+  return 0;
+}
+// the 16x16 inverses of the levels under the cut alone: the deterministic sweeps use no span inverses
+template <class TL> static int schur_dinv(cholamd_device *d, const TL *d_arena, int k, hipStream_t st)
+{
+  for (int lvl = k; lvl < d->plan->levels; lvl++) {
+    const solve_dev &s = d->sv[lvl];
+    HIPCHK((hipError_t)chol_launch_solve_dinv(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, st));
+  }
+  return 0;
+}
+// one sweep of the cut lists on the permuted vector y, as solve_det_t walks the whole-tree lists; the kept lead step (level -1) is a gather alone
+template <class TL> static int schur_det_sweep(cholamd_device *d, const TL *d_arena, int k, int q, double *y, hipStream_t st)
+{
+  const schur_det_dev &c = d->scd[k];
+  const chol_mul_item *items = c.item[q];
+  for (const chol_sdet_step &t : c.step[q]) {
+    if (t.item_end > t.item_first) {
+      HIPCHK((hipError_t)chol_launch_solve_det_gather(d_arena, items + t.item_first, t.item_end - t.item_first, c.src[q], q, y, st));
+      d->schur_launches[1]++;
+    }
+    if (t.col0 >= 0) {
+      const solve_dev &s = d->sv[t.level];
+      HIPCHK((hipError_t)chol_launch_solve_span(d_arena, s.trsv, s.n_trsv, d->ws_solve, y, t.col0, q, st));
+      d->schur_launches[2]++;
+    }
+  }
+  return 0;
+}
+// the same on the permuted row-major block Y of one chunk, as solve_det_nrhs_t
+template <class TL> static int schur_det_sweep_nrhs(cholamd_device *d, const TL *d_arena, int k, int q, double *Y, hipStream_t st)
+{
+  const schur_det_dev &c = d->scd[k];
+  const chol_mul_item *items = c.item[q];
+  for (const chol_sdet_step &t : c.step[q]) {
+    if (t.item_end > t.item_first) {
+      HIPCHK((hipError_t)chol_launch_solve_det_gather_nrhs(d_arena, items + t.item_first, t.item_end - t.item_first, c.src[q], q, Y, st));
+      d->schur_launches[1]++;
+    }
+    if (t.col0 >= 0) {
+      const solve_dev &s = d->sv[t.level];
+      HIPCHK((hipError_t)chol_nrhs_launch_span(d_arena, s.trsv, s.n_trsv, d->ws_solve, Y, t.col0, q, st));
+      d->schur_launches[2]++;
+    }
+  }
+  return 0;
+}
 template <class TL> static int schur_condense_t(cholamd_device *d, const TL *d_arena, int k, const double *d_b, double *d_w, double *d_g, hipStream_t st, const char *what)
 {
   int t0 = 0;
@@ -1706,9 +1779,15 @@ template <class TL> static int schur_condense_t(cholamd_device *d, const TL *d_a
   { int rc = build_solve(d); if (rc) return rc; }
   const int L = d->plan->levels, n = d->plan->n;
   HIPCHK((hipError_t)chol_launch_permute(d_b, d->perm, d_w, n, 0, st));
-  { int rc = schur_inverses(d, d_arena, k, st); if (rc) return rc; }
+  if (d->schur_deterministic) {
+    { int rc = build_schur_det(d, k); if (!rc && !d->keep_inverses) rc = schur_dinv(d, d_arena, k, st); if (!rc) rc = schur_det_sweep(d, d_arena, k, CHOLAMD_HALF_FORWARD, d_w, st); if (rc) return rc; }
+    if (m > 0) HIPCHK(hipMemcpyAsync(d_g, d_w + t0, mb, hipMemcpyDeviceToDevice, st));
+    return 0;
+  }
+  if (!d->keep_inverses) { int rc = schur_inverses(d, d_arena, k, st); if (rc) return rc; } // (kept: the column-by-column chunks of the block form)
   for (int lvl = L - 1; lvl >= k; lvl--) { // forward sweep under the cut: TRSV per separator, then its panel into the ancestors (the kept ones included)
     const solve_dev &s = d->sv[lvl];
+    d->schur_launches[0] += 2;
     HIPCHK((hipError_t)lsolve_trsv(d, d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, d_w, 0, s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr, st));
     HIPCHK((hipError_t)chol_launch_solve_offdiag(d_arena, s.bw, s.ifw, s.n_ifw, d_w, 0, st));
   }
@@ -1732,9 +1811,15 @@ template <class TL> static int schur_expand_t(cholamd_device *d, const TL *d_are
   double *y = d->ytmp; // w stays as it is: the sweep runs in the device object's work vector
   if (t0 > 0) HIPCHK(hipMemcpyAsync(y, d_w, (size_t)t0 * sizeof(double), hipMemcpyDeviceToDevice, st));
   if (m > 0) HIPCHK(hipMemcpyAsync(y + t0, d_xt, mb, hipMemcpyDeviceToDevice, st));
-  { int rc = schur_inverses(d, d_arena, k, st); if (rc) return rc; } // as at the start of every half solve: the arena of the call before may have been another
+  if (d->schur_deterministic) {
+    { int rc = build_schur_det(d, k); if (!rc && !d->keep_inverses) rc = schur_dinv(d, d_arena, k, st); if (!rc) rc = schur_det_sweep(d, d_arena, k, CHOLAMD_HALF_BACKWARD, y, st); if (rc) return rc; }
+    HIPCHK((hipError_t)chol_launch_permute(y, d->perm, d_x, n, 1, st));
+    return 0;
+  }
+  if (!d->keep_inverses) { int rc = schur_inverses(d, d_arena, k, st); if (rc) return rc; } // as at the start of every half solve: the arena of the call before may have been another
   for (int lvl = k; lvl < L; lvl++) { // backward sweep under the cut: gather from the ancestors, then TRSV^T
     const solve_dev &s = d->sv[lvl];
+    d->schur_launches[0] += 2;
     HIPCHK((hipError_t)chol_launch_solve_offdiag(d_arena, s.bw, s.ibw, s.n_ibw, y, 1, st));
     HIPCHK((hipError_t)lsolve_trsv(d, d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, y, 1, s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr, st));
   }
@@ -1749,6 +1834,133 @@ extern "C" int cholamd_schur_expand(cholamd_device *d, const double *d_arena, in
 { return schur_expand_t(d, d_arena, k, d_w, d_xt, d_x, (hipStream_t)stream, "cholamd_schur_expand"); }
 extern "C" int cholamd_schur_expand_f32(cholamd_device *d, const float *d_arena32, int k, const double *d_w, const double *d_xt, double *d_x, void *stream)
 { return schur_expand_t(d, d_arena32, k, d_w, d_xt, d_x, (hipStream_t)stream, "cholamd_schur_expand_f32"); }
+
+// ---- block forms (include/cholamd.h at cholamd_schur_condense_nrhs): chunks of CHOL_NRHS_W columns through the permuted row-major block ynrhs; the pack /
+// unpack kernels of chol_schur.hip stand where the block solve has its permutes.  a, b, c: the call's three blocks with their rows and names
+struct schur_blk { const double *p; int64_t ld; int rows; const char *name; };
+static size_t blk_bytes(const schur_blk &x, int nrhs) { return ((size_t)(nrhs - 1) * (size_t)x.ld + (size_t)x.rows) * sizeof(double); }
+static int schur_nrhs_args(const cholamd_device *d, const void *arena, int k, const schur_blk (&x)[3], int nrhs, const char *what, int *t0)
+{ // m, or the error; *t0 < 0: nothing to do
+  const int m = schur_args(d, k, what, t0);
+  if (m < 0) return m;
+  if (nrhs < 0) { chol_set_error("%s: nrhs = %d < 0", what, nrhs); return CHOLAMD_ERR_ARG; }
+  for (const schur_blk &b : x)
+    if (b.ld < (b.rows == 0 ? m : b.rows)) { chol_set_error("%s: leading dimension of %s = %lld is less than its %d rows", what, b.name, (long long)b.ld, b.rows == 0 ? m : b.rows); return CHOLAMD_ERR_ARG; }
+  if (nrhs == 0) { *t0 = -1; return m; }
+  if (!arena) { chol_set_error("%s: NULL arena", what); return CHOLAMD_ERR_ARG; }
+  for (const schur_blk &b : x) if (!b.p) { chol_set_error("%s: NULL %s", what, b.name); return CHOLAMD_ERR_ARG; }
+  return m;
+}
+template <class TL> static int schur_condense_nrhs_t(cholamd_device *d, const TL *d_arena, int k, const double *d_B, int64_t ldb, double *d_W, int64_t ldw, double *d_G, int64_t ldg,
+                                                     int nrhs, hipStream_t st, const char *what)
+{
+  if (!d) { chol_set_error("%s: NULL device", what); return CHOLAMD_ERR_ARG; }
+  const int n = d->plan->n;
+  int t0 = 0;
+  schur_blk x[3] = { { d_B, ldb, n, "B" }, { d_W, ldw, n, "W" }, { d_G, ldg, 0, "G" } };
+  const int m = schur_nrhs_args(d, d_arena, k, x, nrhs, what, &t0);
+  if (m < 0) return m;
+  if (t0 < 0) return 0;
+  x[2].rows = m;
+  const size_t ab = (size_t)d->plan->arena * sizeof(TL);
+  for (int i = 0; i < 3; i++) {
+    if (x[i].rows == 0) continue; // (m = 0: G has no element)
+    bool bad = ranges_overlap(x[i].p, blk_bytes(x[i], nrhs), d_arena, ab);
+    for (int j = i + 1; j < 3 && !bad; j++) bad = x[j].rows > 0 && ranges_overlap(x[i].p, blk_bytes(x[i], nrhs), x[j].p, blk_bytes(x[j], nrhs));
+    if (bad) { chol_set_error("%s: B, W, G and the arena must not overlap each other", what); return CHOLAMD_ERR_ARG; }
+  }
+  HIPCHK(hipSetDevice(d->dev));
+  { int rc = build_solve(d); if (!rc && d->schur_deterministic) rc = build_schur_det(d, k); if (!rc) rc = d->ynrhs.ensure((size_t)n * CHOL_NRHS_W); if (rc) return rc; }
+  const int L = d->plan->levels;
+  { int rc = d->schur_deterministic ? schur_dinv(d, d_arena, k, st) : schur_inverses(d, d_arena, k, st); if (rc) return rc; } // once per call
+  keep_restore kr(d);
+  d->keep_inverses = true; // (the column-by-column chunks reuse them)
+  double *Y = d->ynrhs;
+  for (int c0 = 0; c0 < nrhs; c0 += CHOL_NRHS_W) {
+    const int cols = std::min(CHOL_NRHS_W, nrhs - c0);
+    if (!d->schur_deterministic && cols < half_nrhs_min_block<TL>()) {
+      for (int j = c0; j < c0 + cols; j++) {
+        int rc = schur_condense_t(d, d_arena, k, d_B + (int64_t)j * ldb, d_W + (int64_t)j * ldw, d_G + (int64_t)j * ldg, st, what);
+        if (rc) return rc;
+      }
+      continue;
+    }
+    HIPCHK((hipError_t)chol_nrhs_launch_permute(d_B, ldb, d->perm, Y, nullptr, 0, n, c0, cols, 0, st));
+    if (d->schur_deterministic) { int rc = schur_det_sweep_nrhs(d, d_arena, k, CHOLAMD_HALF_FORWARD, Y, st); if (rc) return rc; }
+    else
+      for (int lvl = L - 1; lvl >= k; lvl--) { // forward under the cut: the separators' triangles, then their panels into the ancestors (the kept ones included)
+        const solve_dev &s = d->sv[lvl];
+        const double *W256 = s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr;
+        HIPCHK((hipError_t)chol_nrhs_launch_trsv(d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, W256, Y, 0, st));
+        HIPCHK((hipError_t)chol_nrhs_launch_offdiag(d_arena, s.bw, s.ifw, s.n_ifw, Y, 0, st));
+        d->schur_launches[0] += 2;
+      }
+    HIPCHK((hipError_t)chol_launch_schur_unpack(Y, n, t0, c0, cols, d_W, ldw, d_G, ldg, st));
+    d->schur_launches[3]++;
+  }
+  return 0;
+}
+template <class TL> static int schur_expand_nrhs_t(cholamd_device *d, const TL *d_arena, int k, const double *d_W, int64_t ldw, const double *d_XT, int64_t ldxt, double *d_X, int64_t ldx,
+                                                   int nrhs, hipStream_t st, const char *what)
+{
+  if (!d) { chol_set_error("%s: NULL device", what); return CHOLAMD_ERR_ARG; }
+  const int n = d->plan->n;
+  int t0 = 0;
+  schur_blk x[3] = { { d_W, ldw, n, "W" }, { d_XT, ldxt, 0, "XT" }, { d_X, ldx, n, "X" } };
+  const int m = schur_nrhs_args(d, d_arena, k, x, nrhs, what, &t0);
+  if (m < 0) return m;
+  if (t0 < 0) return 0;
+  x[1].rows = m;
+  const size_t ab = (size_t)d->plan->arena * sizeof(TL), xb = blk_bytes(x[2], nrhs);
+  if (ranges_overlap(d_X, xb, d_W, blk_bytes(x[0], nrhs)) || (m > 0 && ranges_overlap(d_X, xb, d_XT, blk_bytes(x[1], nrhs))) || ranges_overlap(d_X, xb, d_arena, ab)) {
+    chol_set_error("%s: X must not overlap W, XT or the arena", what);
+    return CHOLAMD_ERR_ARG;
+  }
+  HIPCHK(hipSetDevice(d->dev));
+  { int rc = build_solve(d); if (!rc && d->schur_deterministic) rc = build_schur_det(d, k); if (!rc) rc = d->ynrhs.ensure((size_t)n * CHOL_NRHS_W); if (rc) return rc; }
+  const int L = d->plan->levels;
+  { int rc = d->schur_deterministic ? schur_dinv(d, d_arena, k, st) : schur_inverses(d, d_arena, k, st); if (rc) return rc; }
+  keep_restore kr(d);
+  d->keep_inverses = true;
+  double *Y = d->ynrhs;
+  for (int c0 = 0; c0 < nrhs; c0 += CHOL_NRHS_W) {
+    const int cols = std::min(CHOL_NRHS_W, nrhs - c0);
+    if (!d->schur_deterministic && cols < half_nrhs_min_block<TL>()) {
+      for (int j = c0; j < c0 + cols; j++) {
+        int rc = schur_expand_t(d, d_arena, k, d_W + (int64_t)j * ldw, d_XT + (int64_t)j * ldxt, d_X + (int64_t)j * ldx, st, what);
+        if (rc) return rc;
+      }
+      continue;
+    }
+    HIPCHK((hipError_t)chol_launch_schur_pack(d_W, ldw, d_XT, ldxt, n, t0, c0, cols, Y, st));
+    d->schur_launches[3]++;
+    if (d->schur_deterministic) { int rc = schur_det_sweep_nrhs(d, d_arena, k, CHOLAMD_HALF_BACKWARD, Y, st); if (rc) return rc; }
+    else
+      for (int lvl = k; lvl < L; lvl++) { // backward under the cut: gather from the ancestors, then the transposed triangles
+        const solve_dev &s = d->sv[lvl];
+        const double *W256 = s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr;
+        HIPCHK((hipError_t)chol_nrhs_launch_offdiag(d_arena, s.bw, s.ibw, s.n_ibw, Y, 1, st));
+        HIPCHK((hipError_t)chol_nrhs_launch_trsv(d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, W256, Y, 1, st));
+        d->schur_launches[0] += 2;
+      }
+    HIPCHK((hipError_t)chol_nrhs_launch_permute(nullptr, 0, d->perm, Y, d_X, ldx, n, c0, cols, 1, st));
+  }
+  return 0;
+}
+extern "C" int cholamd_schur_condense_nrhs(cholamd_device *d, const double *d_arena, int k, const double *d_B, int64_t ldb, double *d_W, int64_t ldw, double *d_G, int64_t ldg, int nrhs, void *stream)
+{ return schur_condense_nrhs_t(d, d_arena, k, d_B, ldb, d_W, ldw, d_G, ldg, nrhs, (hipStream_t)stream, "cholamd_schur_condense_nrhs"); }
+extern "C" int cholamd_schur_condense_nrhs_f32(cholamd_device *d, const float *d_arena32, int k, const double *d_B, int64_t ldb, double *d_W, int64_t ldw, double *d_G, int64_t ldg, int nrhs, void *stream)
+{ return schur_condense_nrhs_t(d, d_arena32, k, d_B, ldb, d_W, ldw, d_G, ldg, nrhs, (hipStream_t)stream, "cholamd_schur_condense_nrhs_f32"); }
+extern "C" int cholamd_schur_expand_nrhs(cholamd_device *d, const double *d_arena, int k, const double *d_W, int64_t ldw, const double *d_XT, int64_t ldxt, double *d_X, int64_t ldx, int nrhs, void *stream)
+{ return schur_expand_nrhs_t(d, d_arena, k, d_W, ldw, d_XT, ldxt, d_X, ldx, nrhs, (hipStream_t)stream, "cholamd_schur_expand_nrhs"); }
+extern "C" int cholamd_schur_expand_nrhs_f32(cholamd_device *d, const float *d_arena32, int k, const double *d_W, int64_t ldw, const double *d_XT, int64_t ldxt, double *d_X, int64_t ldx, int nrhs, void *stream)
+{ return schur_expand_nrhs_t(d, d_arena32, k, d_W, ldw, d_XT, ldxt, d_X, ldx, nrhs, (hipStream_t)stream, "cholamd_schur_expand_nrhs_f32"); }
+extern "C" int cholamd_device_schur_launches(const cholamd_device *d, int64_t out[4])
+{
+  if (!d || !out) { chol_set_error("cholamd_device_schur_launches: NULL %s", !d ? "device" : "out"); return CHOLAMD_ERR_ARG; }
+  for (int i = 0; i < 4; i++) out[i] = d->schur_launches[i];
+  return 0;
+}
 
 // one chunk's residuals: R = B - A X (column-major, ld n), rel[j] = ||r_j|| / ||b_j||
 static int residual_nrhs(cholamd_device *d, const double *d_B, int64_t ldb, const double *d_X, int64_t ldx, int cols, double *rel, hipStream_t st)

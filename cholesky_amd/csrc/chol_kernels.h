@@ -81,6 +81,10 @@ int chol_launch_selinv_entries(const double *Z, const int64_t *a_dst, const int 
 /* Schur complement (chol_schur.hip): S (m x m, column-major, leading dimension lds) from the pieces of chol_schur_pieces(p, k, 1, CHOL_SCHUR_CHUNK): both
  * triangles, the zeros of the pieces without storage included; one owner per element, no atomics */
 int chol_launch_schur_gather(const double *arena, const chol_schur_desc *descs, int64_t ndesc, double *S, int64_t lds, hipStream_t st);
+/* block forms of condense / expand: the transposing copies between the permuted row-major block Y of one chunk (chol_nrhs_launch_permute) and the caller's
+ * column-major W (n rows, permuted order), G / XT (m = n - t0 rows, Schur order), columns c0 .. c0 + cols - 1 */
+int chol_launch_schur_unpack(const double *Y, int n, int t0, int c0, int cols, double *W, int64_t ldw, double *G, int64_t ldg, hipStream_t st);
+int chol_launch_schur_pack(const double *W, int64_t ldw, const double *XT, int64_t ldxt, int n, int t0, int c0, int cols, double *Y, hipStream_t st);
 /* forward products with the factor (chol_multiply.hip): one launch over the items of one direction of chol_mul_lists, y = L z (backward = 0) or L^T z (1) in
  * permuted coordinates, z and y distinct; perm != NULL: the result goes to y[perm[pos]] (original dof order).  One owner per element, no atomics.
  * resid: res[0], res[1] = the bits of ||A z - w||^2 and ||A z||^2 (A as CSR in original dof order), res[2] = rows where either is not finite; two stages

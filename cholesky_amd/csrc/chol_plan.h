@@ -490,6 +490,10 @@ typedef struct {
 } chol_sdet_lists;
 int chol_build_solve_det(const struct cholamd_plan *p, chol_sdet_lists *out);
 void chol_sdet_lists_free(chol_sdet_lists *w);
+/* The same lists CUT at level k for the Schur condense / expand (device option schur_deterministic; include/cholamd.h at cholamd_schur_condense_nrhs): FORWARD
+ * the steps of the levels levels - 1 .. k and one KEPT LEAD step (level = -1, col0 = -1: the lead-step sources of the kept chunks that read positions under
+ * the cut), BACKWARD the steps of the levels k .. levels - 1.  Checks its own invariants as chol_build_solve_det does. */
+int chol_build_schur_det(const struct cholamd_plan *p, int k, chol_sdet_lists *out);
 
 /* ---- block form of the products (cholamd_multiply_half_nrhs; chol_multiply_nrhs.hip): the same items and sources on a chunk of 32 columns.  The reduction
  * range of a source is cut into CHUNKS of CHOL_MULN_KSTEP steps; chunk c of the s-th source of an item (s counted from the item's first) belongs to wave

@@ -3149,3 +3149,243 @@ int cholamd_plan_solve_det_lists(const cholamd_plan *p, int which, int64_t *step
   chol_sdet_lists_free(&w);
   return 0;
 }
+
+/* ---------------------------------------------------------------------------------------- */
+/* Schur condense / expand on the deterministic step lists (device option schur_deterministic): */
+/* the lists of chol_build_solve_det CUT at level k (chol_plan.h at chol_build_schur_det), and  */
+/* their host restatement on chunks of 32 columns                                               */
+/* ---------------------------------------------------------------------------------------- */
+static void schur_det_copy_items(mul_build *b, const chol_sdet_lists *w, int q, const chol_sdet_step *st, int t0, int only_under)
+{
+  for (int i = st->item_first; i < st->item_end; i++) {
+    const chol_mul_item *it = &w->item[q][i];
+    int n = 0;
+    for (int e = it->src_first; e < it->src_end; e++) n += !only_under || w->src[q][e].z_off < t0;
+    if (!n) continue; /* nothing to gather: no item */
+    mul_open_item(b, it->y_off, it->nv);
+    for (int e = it->src_first; e < it->src_end; e++) {
+      const chol_mul_src *s = &w->src[q][e];
+      if (only_under && s->z_off >= t0) continue; /* a panel of a kept separator: it holds S, not L */
+      mul_push_src(b, s->a_off, s->ld, s->len, s->z_off, s->tri);
+    }
+    mul_close_item(b);
+  }
+}
+int chol_build_schur_det(const plan_t *p, int k, chol_sdet_lists *out)
+{
+  memset(out, 0, sizeof *out);
+  int t0 = 0;
+  const int m = chol_schur_range(p, k, &t0);
+  if (m < 0) return m;
+  chol_sdet_lists w;
+  int rc = chol_build_solve_det(p, &w);
+  if (rc) return rc;
+  const int n = p->n;
+  mul_build b[2] = { { 0 }, { 0 } };
+  unsigned char *solved = calloc((size_t)(n > 0 ? n : 1), 1), *owned = calloc((size_t)(n > 0 ? n : 1), 1);
+  rc = CHOLAMD_ERR_NOMEM;
+  if (!solved || !owned) { chol_set_error("out of memory"); goto done; }
+  for (int q = 0; q < 2; q++) {
+    out->step[q] = calloc((size_t)w.n_step[q] + 1, sizeof(chol_sdet_step));
+    if (!out->step[q]) { chol_set_error("out of memory"); goto done; }
+    int t = 0;
+    for (int i = 0; i < w.n_step[q]; i++) { /* the steps of the levels under the cut, unchanged and in their order */
+      const chol_sdet_step *st = &w.step[q][i];
+      if (st->level < k) continue;
+      chol_sdet_step *o = &out->step[q][t++];
+      o->level = st->level; o->col0 = st->col0; o->item_first = b[q].n_item;
+      schur_det_copy_items(&b[q], &w, q, st, t0, 0);
+      o->item_end = b[q].n_item;
+    }
+    if (q == 0) { /* the kept lead step: what the eliminated panels add to the kept positions, one launch */
+      chol_sdet_step *o = &out->step[q][t++];
+      o->level = -1; o->col0 = -1; o->item_first = b[q].n_item;
+      for (int i = 0; i < w.n_step[q]; i++)
+        if (w.step[q][i].level < k && w.step[q][i].col0 < 0) schur_det_copy_items(&b[q], &w, q, &w.step[q][i], t0, 1);
+      o->item_end = b[q].n_item;
+    }
+    out->n_step[q] = t;
+  }
+  for (int q = 0; q < 2; q++) {
+    out->item[q] = b[q].item; out->n_item[q] = b[q].n_item; out->src[q] = b[q].src; out->n_src[q] = b[q].n_src;
+    b[q].item = NULL; b[q].src = NULL;
+  }
+  if (b[0].fail || b[1].fail) { chol_set_error("Schur solve lists: out of memory or more than 2^30 sources"); goto done; }
+  /* no source may lie in a block of two kept separators.  A source is a strip of ONE panel: FORWARD the panel of the separator its factors z come from,
+   * BACKWARD the panel of the separator the item's columns belong to; the panel of a kept separator holds nothing but such blocks */
+  rc = CHOLAMD_ERR_INVARIANT;
+  for (int q = 0; q < 2; q++)
+    for (int i = 0; i < out->n_item[q]; i++) {
+      const chol_mul_item *it = &out->item[q][i];
+      if (it->nv < 1 || it->nv > CHOL_MUL_TILE || it->y_off < 0 || it->y_off + it->nv > n || it->src_end <= it->src_first) { chol_set_error("internal: Schur solve item %d of direction %d is malformed", i, q); goto done; }
+      for (int e = it->src_first; e < it->src_end; e++) {
+        const chol_mul_src *s = &out->src[q][e];
+        if (s->len < 1 || s->z_off < 0 || s->z_off + s->len > n) { chol_set_error("internal: Schur solve item %d of direction %d: source %d leaves the vector", i, q, e); goto done; }
+        const int64_t last = q == 0 ? s->a_off + (it->nv - 1) + (int64_t)(s->len - 1) * s->ld : s->a_off + (s->len - 1) + (int64_t)(it->nv - 1) * s->ld;
+        if (s->a_off < 0 || last >= p->arena) { chol_set_error("internal: Schur solve item %d of direction %d: source %d leaves the arena", i, q, e); goto done; }
+        if (p->heap_of[p->sep_of_pos[q == 0 ? s->z_off : it->y_off]] < (1 << k)) { chol_set_error("internal: Schur solve item %d of direction %d: source %d lies in a block of two kept separators", i, q, e); goto done; }
+      }
+    }
+  /* the sweeps walked: under the cut every position is solved exactly once and read only after that; the kept positions are read by the expand (they are
+   * its input) and owned at most once by the kept lead step, whose sources all lie under the cut */
+  for (int q = 0; q < 2; q++) {
+    memset(solved, 0, (size_t)(n > 0 ? n : 1));
+    memset(owned, 0, (size_t)(n > 0 ? n : 1));
+    for (int i = t0; i < n && q == 1; i++) solved[i] = 1; /* xt */
+    for (int t = 0; t < out->n_step[q]; t++) {
+      const chol_sdet_step *st = &out->step[q][t];
+      for (int i = st->item_first; i < st->item_end; i++) {
+        const chol_mul_item *it = &out->item[q][i];
+        for (int l = 0; l < it->nv; l++) {
+          const int pos = it->y_off + l;
+          if (st->level < 0) {
+            if (pos < t0 || owned[pos]) { chol_set_error("internal: kept lead item %d owns position %d, which lies under the cut or has an owner already", i, pos); goto done; }
+            owned[pos] = 1;
+          } else if (pos >= t0 || solved[pos]) { chol_set_error("internal: Schur solve item %d of direction %d owns position %d, which is kept or solved already", i, q, pos); goto done; }
+        }
+        for (int e = it->src_first; e < it->src_end; e++) {
+          const chol_mul_src *s = &out->src[q][e];
+          if (st->level < 0 && s->z_off + s->len > t0) { chol_set_error("internal: kept lead item %d: source %d reads position %d at or above the cut", i, e, s->z_off + s->len - 1); goto done; }
+          for (int c = 0; c < s->len; c++)
+            if (!solved[s->z_off + c]) { chol_set_error("internal: Schur solve item %d of direction %d: source %d reads position %d before it is solved", i, q, e, s->z_off + c); goto done; }
+        }
+      }
+      if (st->col0 < 0) continue;
+      for (int h = 1 << st->level; h < (1 << (st->level + 1)) && h <= p->nsep; h++) {
+        const int s = p->tree[h];
+        for (int i = st->col0; i < p->sep_size[s] && i < st->col0 + CHOL_SDET_SPAN; i++) {
+          const int pos = p->sep_off[s] + i;
+          if (pos >= t0 || solved[pos]) { chol_set_error("internal: Schur sweep %d solves position %d twice or above the cut", q, pos); goto done; }
+          solved[pos] = 1;
+        }
+      }
+    }
+    for (int i = 0; i < t0; i++) if (!solved[i]) { chol_set_error("internal: Schur sweep %d never solves position %d", q, i); goto done; }
+  }
+  rc = 0;
+done:
+  free(solved); free(owned);
+  for (int q = 0; q < 2; q++) { free(b[q].item); free(b[q].src); }
+  chol_sdet_lists_free(&w);
+  if (rc) chol_sdet_lists_free(out);
+  return rc;
+}
+/* one sweep of the cut lists on the permuted row-major block: sdet_host_block_sweep's arithmetic (the kernel's partition of a gather, substitution inside a
+ * span's own triangle); a kept lead step (level -1) has no span */
+static void schur_det_host_block_sweep(const plan_t *p, const chol_sdet_lists *w, int which, const double *arena, double *yp)
+{
+  chol_sdet_lists one = *w; /* a step at a time through the walk of the whole-tree lists; the kept lead step has col0 < 0, so its level is never looked at */
+  for (int t = 0; t < w->n_step[which]; t++) {
+    one.n_step[which] = 1; one.step[which] = (chol_sdet_step *)&w->step[which][t];
+    sdet_host_block_sweep(p, &one, which, arena, yp);
+  }
+}
+static int schur_nrhs_host_args(const plan_t *p, int k, const char *what, const void *arena, const void *a, const void *b, const void *c, const char *na, const char *nb, const char *nc,
+                                int64_t lda, int64_t ldb, int64_t ldc, int rows_a, int rows_b, int rows_c, int nrhs)
+{ /* 1: nothing to do */
+  if (nrhs < 0) { chol_set_error("%s: nrhs = %d < 0", what, nrhs); return CHOLAMD_ERR_ARG; }
+  if (lda < rows_a || ldb < rows_b || ldc < rows_c) {
+    chol_set_error("%s: leading dimensions of %s, %s, %s = %lld, %lld, %lld must be at least %d, %d, %d", what, na, nb, nc, (long long)lda, (long long)ldb, (long long)ldc, rows_a, rows_b, rows_c);
+    return CHOLAMD_ERR_ARG;
+  }
+  if (nrhs == 0) return 1;
+  if (!arena || !a || !b || !c) { chol_set_error("%s: NULL %s", what, !arena ? "arena" : !a ? na : !b ? nb : nc); return CHOLAMD_ERR_ARG; }
+  (void)p; (void)k;
+  return 0;
+}
+int cholamd_plan_schur_condense_host_nrhs(const cholamd_plan *p, int k, const double *arena_host, const double *B, int64_t ldb, double *W, int64_t ldw, double *G, int64_t ldg, int nrhs)
+{
+  const char *what = "cholamd_plan_schur_condense_host_nrhs";
+  if (!p) { chol_set_error("%s: NULL plan", what); return CHOLAMD_ERR_ARG; }
+  int t0 = 0;
+  const int m = chol_schur_range(p, k, &t0), n = p->n;
+  if (m < 0) return m;
+  { int rc = schur_nrhs_host_args(p, k, what, arena_host, B, W, G, "B", "W", "G", ldb, ldw, ldg, n, n, m, nrhs); if (rc) return rc > 0 ? 0 : rc; }
+  chol_sdet_lists w;
+  int rc = chol_build_schur_det(p, k, &w);
+  if (rc) return rc;
+  double *yp = malloc((size_t)(n > 0 ? n : 1) * 32 * sizeof(double));
+  if (!yp) { chol_sdet_lists_free(&w); chol_set_error("out of memory"); return CHOLAMD_ERR_NOMEM; }
+  for (int c0 = 0; c0 < nrhs; c0 += 32) {
+    const int cols = nrhs - c0 < 32 ? nrhs - c0 : 32;
+    for (int i = 0; i < n; i++)
+      for (int j = 0; j < 32; j++) yp[(int64_t)i * 32 + j] = j < cols ? B[p->perm[i] + (int64_t)(c0 + j) * ldb] : 0.0;
+    schur_det_host_block_sweep(p, &w, CHOLAMD_HALF_FORWARD, arena_host, yp);
+    for (int i = 0; i < n; i++)
+      for (int j = 0; j < cols; j++) {
+        W[i + (int64_t)(c0 + j) * ldw] = yp[(int64_t)i * 32 + j];
+        if (i >= t0) G[(i - t0) + (int64_t)(c0 + j) * ldg] = yp[(int64_t)i * 32 + j];
+      }
+  }
+  free(yp);
+  chol_sdet_lists_free(&w);
+  return 0;
+}
+int cholamd_plan_schur_expand_host_nrhs(const cholamd_plan *p, int k, const double *arena_host, const double *W, int64_t ldw, const double *XT, int64_t ldxt, double *X, int64_t ldx, int nrhs)
+{
+  const char *what = "cholamd_plan_schur_expand_host_nrhs";
+  if (!p) { chol_set_error("%s: NULL plan", what); return CHOLAMD_ERR_ARG; }
+  int t0 = 0;
+  const int m = chol_schur_range(p, k, &t0), n = p->n;
+  if (m < 0) return m;
+  { int rc = schur_nrhs_host_args(p, k, what, arena_host, W, XT, X, "W", "XT", "X", ldw, ldxt, ldx, n, m, n, nrhs); if (rc) return rc > 0 ? 0 : rc; }
+  chol_sdet_lists w;
+  int rc = chol_build_schur_det(p, k, &w);
+  if (rc) return rc;
+  double *yp = malloc((size_t)(n > 0 ? n : 1) * 32 * sizeof(double));
+  if (!yp) { chol_sdet_lists_free(&w); chol_set_error("out of memory"); return CHOLAMD_ERR_NOMEM; }
+  for (int c0 = 0; c0 < nrhs; c0 += 32) {
+    const int cols = nrhs - c0 < 32 ? nrhs - c0 : 32;
+    for (int i = 0; i < n; i++)
+      for (int j = 0; j < 32; j++)
+        yp[(int64_t)i * 32 + j] = j >= cols ? 0.0 : i < t0 ? W[i + (int64_t)(c0 + j) * ldw] : XT[(i - t0) + (int64_t)(c0 + j) * ldxt];
+    schur_det_host_block_sweep(p, &w, CHOLAMD_HALF_BACKWARD, arena_host, yp);
+    for (int i = 0; i < n; i++)
+      for (int j = 0; j < cols; j++) X[p->perm[i] + (int64_t)(c0 + j) * ldx] = yp[(int64_t)i * 32 + j];
+  }
+  free(yp);
+  chol_sdet_lists_free(&w);
+  return 0;
+}
+int cholamd_plan_schur_det_counts(const cholamd_plan *p, int k, int64_t out[8])
+{
+  if (!p || !out) { chol_set_error("cholamd_plan_schur_det_counts: NULL %s", !p ? "plan" : "out"); return CHOLAMD_ERR_ARG; }
+  chol_sdet_lists w;
+  int rc = chol_build_schur_det(p, k, &w);
+  if (rc) return rc;
+  for (int d = 0; d < 2; d++) {
+    int64_t entries = 0;
+    for (int i = 0; i < w.n_item[d]; i++)
+      for (int e = w.item[d][i].src_first; e < w.item[d][i].src_end; e++) entries += (int64_t)w.item[d][i].nv * w.src[d][e].len;
+    for (int h = 1 << k; h <= p->nsep; h++) /* the spans' own lower triangles, under the cut */
+      for (int c0 = 0; c0 < p->sep_size[p->tree[h]]; c0 += CHOL_SDET_SPAN) {
+        const int64_t mm = p->sep_size[p->tree[h]] - c0 < CHOL_SDET_SPAN ? p->sep_size[p->tree[h]] - c0 : CHOL_SDET_SPAN;
+        entries += mm * (mm + 1) / 2;
+      }
+    out[4 * d] = w.n_step[d]; out[4 * d + 1] = w.n_item[d]; out[4 * d + 2] = w.n_src[d]; out[4 * d + 3] = entries;
+  }
+  chol_sdet_lists_free(&w);
+  return 0;
+}
+int cholamd_plan_schur_det_lists(const cholamd_plan *p, int k, int which, int64_t *steps, int64_t *items, int64_t *srcs)
+{
+  if (!p || !steps || !items || !srcs) { chol_set_error("cholamd_plan_schur_det_lists: NULL %s", !p ? "plan" : "output"); return CHOLAMD_ERR_ARG; }
+  if (which != CHOLAMD_HALF_FORWARD && which != CHOLAMD_HALF_BACKWARD) { chol_set_error("cholamd_plan_schur_det_lists: which = %d is neither CHOLAMD_HALF_FORWARD (0) nor CHOLAMD_HALF_BACKWARD (1)", which); return CHOLAMD_ERR_ARG; }
+  chol_sdet_lists w;
+  int rc = chol_build_schur_det(p, k, &w);
+  if (rc) return rc;
+  for (int t = 0; t < w.n_step[which]; t++) {
+    const chol_sdet_step *s = &w.step[which][t];
+    steps[4 * t] = s->level; steps[4 * t + 1] = s->col0; steps[4 * t + 2] = s->item_first; steps[4 * t + 3] = s->item_end;
+  }
+  for (int i = 0; i < w.n_item[which]; i++) {
+    const chol_mul_item *it = &w.item[which][i];
+    items[4 * i] = it->y_off; items[4 * i + 1] = it->nv; items[4 * i + 2] = it->src_first; items[4 * i + 3] = it->src_end;
+  }
+  for (int e = 0; e < w.n_src[which]; e++) {
+    const chol_mul_src *q = &w.src[which][e];
+    srcs[5 * e] = q->a_off; srcs[5 * e + 1] = q->ld; srcs[5 * e + 2] = q->len; srcs[5 * e + 3] = q->z_off; srcs[5 * e + 4] = q->tri;
+  }
+  chol_sdet_lists_free(&w);
+  return 0;
+}

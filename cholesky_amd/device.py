@@ -162,7 +162,8 @@ class Device:
         """Schedule / kernel-selection switch of this device object (cholamd_device_set_option).  Among them "solve_deterministic" (the same bits from
         every single-vector solve) and, on top of it, "solve_deterministic_block": the _nrhs solves then take the deterministic block path -- one
         pass over the factor per 32 columns, the same bits every time, every column's bits independent of the other columns (include/cholamd.h at
-        "deterministic solve")."""
+        "deterministic solve"), and "schur_deterministic": schur_condense / schur_expand and their _nrhs forms walk deterministic step lists cut at
+        the kept levels -- the same bits every time, columns independent, S never read (include/cholamd.h at cholamd_schur_condense_nrhs)."""
         check(self.L.cholamd_device_set_option(self.h, name.encode(), int(value)), "cholamd_device_set_option")
 
     def program_trace(self, arena, stream=None):
@@ -441,6 +442,51 @@ class Device:
         fn = self.L.cholamd_schur_expand_f32 if self._is_f32(arena) else self.L.cholamd_schur_expand
         check(fn(self.h, self.ptr(arena), int(k), self.ptr(w), self.ptr(xt), self.ptr(x), _stream_ptr(stream)), "cholamd_schur_expand")
         return x
+
+    def _schur_block(self, t, what, rows, cols=None):
+        """_block for an array of `rows` rows; with `cols`: allocate-free check that it has that many columns.  Returns ld."""
+        ld, k = self._block(t, what, rows)
+        if cols is not None and k != cols:
+            raise ValueError(f"{what} has {k} columns, expected {cols}")
+        return ld
+
+    def schur_condense_nrhs(self, arena, k, B, W=None, G=None, stream=None):
+        """The block form of schur_condense for the columns of B (n x nrhs, column-major, original dof order): W (n x nrhs; column j = the state w of
+        column j) and G (m x nrhs, Schur order), allocated when None; returns (W, G).  cholamd_schur_condense_nrhs / _f32 by the arena's element
+        type: one pass over the eliminated part of the factor per 32 columns.  Asynchronous on `stream`."""
+        import torch
+        n, m = self.plan.n, self.plan.schur_size(k)
+        ldb, c = self._block(B, "B", n)
+        dev = f"cuda:{self.device_id}"
+        if W is None:
+            W = torch.empty((c, n), dtype=torch.float64, device=dev).T
+        if G is None:
+            G = torch.empty((c, m), dtype=torch.float64, device=dev).T
+        ldw, ldg = self._schur_block(W, "W", n, c), self._schur_block(G, "G", m, c)
+        fn = self.L.cholamd_schur_condense_nrhs_f32 if self._is_f32(arena) else self.L.cholamd_schur_condense_nrhs
+        check(fn(self.h, self.ptr(arena), int(k), self.ptr(B), ldb, self.ptr(W), ldw, self.ptr(G), ldg, c, _stream_ptr(stream)), "cholamd_schur_condense_nrhs")
+        return W, G
+
+    def schur_expand_nrhs(self, arena, k, W, XT, X=None, stream=None):
+        """The block form of schur_expand: X (n x nrhs, original dof order; allocated when None, returned) from W of schur_condense_nrhs and the
+        caller's XT (m x nrhs, Schur order).  W is not modified.  cholamd_schur_expand_nrhs / _f32 by the arena's element type."""
+        import torch
+        n, m = self.plan.n, self.plan.schur_size(k)
+        ldw, c = self._block(W, "W", n)
+        ldxt = self._schur_block(XT, "XT", m, c)
+        if X is None:
+            X = torch.empty((c, n), dtype=torch.float64, device=f"cuda:{self.device_id}").T
+        ldx = self._schur_block(X, "X", n, c)
+        fn = self.L.cholamd_schur_expand_nrhs_f32 if self._is_f32(arena) else self.L.cholamd_schur_expand_nrhs
+        check(fn(self.h, self.ptr(arena), int(k), self.ptr(W), ldw, self.ptr(XT), ldxt, self.ptr(X), ldx, c, _stream_ptr(stream)), "cholamd_schur_expand_nrhs")
+        return X
+
+    def schur_launches(self):
+        """Launches of the Schur condense / expand sweeps on this device object so far (cholamd_device_schur_launches): a dict of atomic (the sweep
+        kernels that accumulate by atomics), gather and span (the deterministic step lists), copy (the pack / unpack kernels of the block forms)."""
+        out = np.zeros(4, dtype=np.int64)
+        check(self.L.cholamd_device_schur_launches(self.h, out.ctypes.data), "cholamd_device_schur_launches")
+        return dict(zip(("atomic", "gather", "span", "copy"), (int(v) for v in out)))
 
     def solve_refine_nrhs(self, arena32, B, X, max_iter=20, tol=1e-12, stream=None):
         """cholamd_solve_refine_nrhs: every column of X = A^-1 B by iterative refinement on the fp32 factor; returns (corrections applied, relres per column).

@@ -313,6 +313,69 @@ class Plan:
         check(self.L.cholamd_plan_schur_host(self.h, int(k), arena.ctypes.data, buf.ctypes.data, ld), "cholamd_plan_schur_host")
         return buf[:m, :].T if lds is not None else buf[:m, :m].T
 
+    @staticmethod
+    def _colmajor(M, rows, ld, fill):
+        """A (columns, ld) buffer whose row j holds column j of M (rows x k) and `fill` behind it: the column-major copy handed to the library."""
+        k = M.shape[1]
+        buf = np.full((max(k, 1), max(ld, 1)), fill, dtype=np.float64)
+        buf[:k, :rows] = M.T
+        return buf
+
+    def schur_condense_host_nrhs(self, k, arena, B, ldb=None, ldw=None, ldg=None):
+        """(W, G) = the block condense on the CPU over a host arena whose levels under the cut are factored (cholamd_plan_schur_condense_host_nrhs): the
+        cut step lists of Device option schur_deterministic with the block gather's partition.  B: n x nrhs in original dof order; W: n x nrhs (column
+        j = the state w of column j), G: m x nrhs in Schur order.  ld*: leading dimensions of the column-major copies handed to the library (defaults:
+        the row counts); the rows behind the arrays are checked to be untouched.  Deterministic, columns independent; not the device's bits."""
+        arena = np.ascontiguousarray(arena, dtype=np.float64)
+        assert arena.size == self.arena_doubles
+        B = np.asarray(B, dtype=np.float64)
+        assert B.ndim == 2 and B.shape[0] == self.n
+        n, m, c = self.n, self.schur_size(k), B.shape[1]
+        ldb, ldw, ldg = int(ldb or n), int(ldw or n), int(ldg or m)
+        bb = self._colmajor(B, n, ldb, -3.0)
+        wb, gb = np.full((max(c, 1), max(ldw, 1)), np.nan), np.full((max(c, 1), max(ldg, 1)), np.nan)
+        check(self.L.cholamd_plan_schur_condense_host_nrhs(self.h, int(k), arena.ctypes.data, bb.ctypes.data, ldb, wb.ctypes.data, ldw, gb.ctypes.data, ldg, c),
+              "cholamd_plan_schur_condense_host_nrhs")
+        assert np.isnan(wb[:, n:]).all() and np.isnan(gb[:, m:]).all(), "rows behind W or G were written"
+        return wb[:c, :n].T.copy(), gb[:c, :m].T.copy()
+
+    def schur_expand_host_nrhs(self, k, arena, W, XT, ldw=None, ldxt=None, ldx=None):
+        """X (n x nrhs, original dof order) = the block expand on the CPU from W of schur_condense_host_nrhs and the caller's XT (m x nrhs, Schur order):
+        cholamd_plan_schur_expand_host_nrhs.  W is not modified (checked)."""
+        arena = np.ascontiguousarray(arena, dtype=np.float64)
+        assert arena.size == self.arena_doubles
+        W, XT = np.asarray(W, dtype=np.float64), np.asarray(XT, dtype=np.float64)
+        n, m = self.n, self.schur_size(k)
+        assert W.ndim == 2 and W.shape[0] == n and XT.ndim == 2 and XT.shape == (m, W.shape[1])
+        c = W.shape[1]
+        ldw, ldxt, ldx = int(ldw or n), int(ldxt or m), int(ldx or n)
+        wb, tb = self._colmajor(W, n, ldw, -3.0), self._colmajor(XT, m, ldxt, -3.0)
+        w0 = wb.copy()
+        xb = np.full((max(c, 1), max(ldx, 1)), np.nan)
+        check(self.L.cholamd_plan_schur_expand_host_nrhs(self.h, int(k), arena.ctypes.data, wb.ctypes.data, ldw, tb.ctypes.data, ldxt, xb.ctypes.data, ldx, c),
+              "cholamd_plan_schur_expand_host_nrhs")
+        assert np.isnan(xb[:, n:]).all(), "rows n .. ldx - 1 of X were written"
+        assert wb.tobytes() == w0.tobytes(), "the expand wrote W"
+        return xb[:c, :n].T.copy()
+
+    def schur_det_counts(self, k):
+        """Sizes of the step lists of condense (forward) and expand (backward) cut at k kept levels (cholamd_plan_schur_det_counts): steps, items,
+        sources and the entries of L one sweep reads."""
+        out = np.zeros(8, dtype=np.int64)
+        check(self.L.cholamd_plan_schur_det_counts(self.h, int(k), out.ctypes.data), "cholamd_plan_schur_det_counts")
+        return {w: dict(steps=int(out[4 * i]), items=int(out[4 * i + 1]), sources=int(out[4 * i + 2]), entries=int(out[4 * i + 3]))
+                for i, w in enumerate(("forward", "backward"))}
+
+    def schur_det_lists(self, k, which):
+        """The cut lists of one direction (cholamd_plan_schur_det_lists) in the formats of solve_det_lists; the kept lead step of the forward list has
+        level = -1 (and no span: first column -1)."""
+        c = self.schur_det_counts(k)["forward" if which == 0 else "backward"]
+        steps = np.zeros((max(c["steps"], 1), 4), dtype=np.int64)
+        items = np.zeros((max(c["items"], 1), 4), dtype=np.int64)
+        srcs = np.zeros((max(c["sources"], 1), 5), dtype=np.int64)
+        check(self.L.cholamd_plan_schur_det_lists(self.h, int(k), int(which), steps.ctypes.data, items.ctypes.data, srcs.ctypes.data), "cholamd_plan_schur_det_lists")
+        return steps[:c["steps"]], items[:c["items"]], srcs[:c["sources"]]
+
     def multiply_host(self, arena, which, z):
         """y = M z (which = 0) or y = M^T z (1) on the CPU from a host arena (cholamd_plan_multiply_host): the owner lists of Device.multiply_half
         walked on the host -- the lower triangles and the stored row runs only.  z and the result: n doubles in original dof order."""

@@ -374,7 +374,8 @@ int cholamd_factor_info(cholamd_device *d, int *sep_out);
  * the object was created (CHOLAMD_SPLIT_MIN, CHOLAMD_SPLIT_NB, CHOLAMD_NO_FUSE, CHOLAMD_FUSE_UPDATE_MAX,
  * CHOLAMD_MT_MIN_TILES, CHOLAMD_NO_CELLS, CHOLAMD_SOLVE_REFERENCE_SHAPE, CHOLAMD_SOLVE_DETERMINISTIC: read once, there); names: "split_min",
  * "split_nb", "fuse", "fuse_update_max", "mt_min_tiles", "cells", "solve_reference_shape", "solve_deterministic" (the bit-reproducible
- * streamed solve, see "deterministic solve" below; neither of the two solve options rebuilds the work lists), "program" (the whole factorisation
+ * streamed solve, see "deterministic solve" below; neither of the two solve options rebuilds the work lists), "schur_deterministic" (the Schur condense / expand on
+ * deterministic step lists, see cholamd_schur_condense_nrhs; CHOLAMD_SCHUR_DETERMINISTIC; rebuilds nothing), "program" (the whole factorisation
  * of a small problem as one launch; CHOLAMD_NO_PROGRAM), "follow" (its pivot blocks follow their children's TRSM strips;
  * CHOLAMD_NO_FOLLOW), "follow_tail" (followers of more than four tile columns take the last follow_tail column tiles of each source
  * themselves, update jobs bring the rest; 0 = they take everything; CHOLAMD_FOLLOW_TAIL; "follow_tail_split": the same for the next
@@ -443,9 +444,10 @@ int cholamd_solve(cholamd_device *d, const double *d_arena, const double *d_b, d
  *      hold for the refinement: the columns of a chunk share the number of corrections;
  *  (e) rows n .. ld - 1 of X and columns >= nrhs are never written.
  * NOT PROMISED: the bits of the single-vector deterministic solve (the sums are partitioned differently); the two agree to rounding.
- * NOT COVERED by the block form either: the sharded and multi-GPU solves, the Schur condense / expand, and anything under "solve_reference_shape".
+ * NOT COVERED by the block form either: the sharded and multi-GPU solves, and anything under "solve_reference_shape".
  * NOT COVERED (they keep the atomic path whatever the option says): the sharded and multi-GPU solves (cholamd_solve_sharded, cholamd_solve_multi, the
- * sharded refinement) on more than one rank, and the Schur condense / expand.
+ * sharded refinement) on more than one rank.  The Schur condense / expand have an option of their own, "schur_deterministic" (at cholamd_schur_condense_nrhs
+ * below); the two solve options do not reach them.
  * Needs the COMPLETE factor in the arena, like cholamd_solve: a single-GPU device object, or rank 0's after a gather.
  * cholamd_plan_solve_det_host: the same walk on the HOST over a host arena with the same lists (which = CHOLAMD_HALF_FORWARD, CHOLAMD_HALF_BACKWARD, or -1:
  * the whole solve = FORWARD then BACKWARD; b and x n doubles in original dof order, x == b allowed); a span is solved by substitution inside its own lower
@@ -662,7 +664,7 @@ int cholamd_plan_selinv_front(const cholamd_plan *p, int sep, int block, int cap
  *   m .. lds - 1 untouched.  NULL pointer or lds < m: CHOLAMD_ERR_ARG, nothing written.
  *
  * Device side.  Common rules -- CHOLAMD_ERR_ARG with NOTHING written for: k out of range, a NULL pointer, a partitioned device object (world > 1).  There are
- * NO sharded variants and NO _nrhs variants of these calls.
+ * NO sharded variants of these calls.  Condense and expand have block forms for many right-hand sides (cholamd_schur_condense_nrhs, below).
  * cholamd_schur_factor: eliminates the levels levels - 1 .. k of a filled arena by the per-level launches -- the launches of cholamd_factor_levels(d, a,
  *   levels - 1, k); it never uses the one-launch program, whatever the problem's size.  Asynchronous on `stream`; cholamd_factor_info reports pivots as usual.
  *   cholamd_factor_levels(d, a, k - 1, 0) afterwards COMPLETES the factor: the arena is then bit-identical to one factored by cholamd_factor_levels(d, a,
@@ -675,7 +677,7 @@ int cholamd_plan_selinv_front(const cholamd_plan *p, int sep, int block, int cap
  * cholamd_schur_condense: d_b n doubles in ORIGINAL dof order; d_g m doubles in Schur order = b_T - A_TI A_II^-1 b_I; d_w n doubles of opaque state for the
  *   expand (the permuted, forward-swept vector).  The call permutes, forms the 16x16 and span inverses of the levels >= k ONLY -- the levels < k hold S, not a
  *   factor, and are never read as one -- and runs the forward sweep of the levels levels - 1 .. k with the kernels of cholamd_solve.  The off-diagonal blocks
- *   accumulate by fp64 atomics: g agrees from run to run to rounding, not bit for bit.  Asynchronous.  b, w, g and the arena must not overlap each other:
+ *   accumulate by fp64 atomics: g agrees from run to run to rounding, not bit for bit (unless option "schur_deterministic" is set, below).  Asynchronous.  b, w, g and the arena must not overlap each other:
  *   CHOLAMD_ERR_ARG.
  * cholamd_schur_expand: d_xt = the caller's solution of S x_T = g (m doubles, Schur order); d_x = the full solution, n doubles, original order.  Backward sweep
  *   of the levels k .. levels - 1 and the inverse permutation.  d_w is NOT modified (the sweep runs in the device object's work vector, and the inverses are
@@ -694,6 +696,64 @@ int cholamd_schur_condense(cholamd_device *d, const double *d_arena, int k, cons
 int cholamd_schur_expand(cholamd_device *d, const double *d_arena, int k, const double *d_w, const double *d_xt, double *d_x, void *stream);
 int cholamd_schur_condense_f32(cholamd_device *d, const float *d_arena32, int k, const double *d_b, double *d_w, double *d_g, void *stream);
 int cholamd_schur_expand_f32(cholamd_device *d, const float *d_arena32, int k, const double *d_w, const double *d_xt, double *d_x, void *stream);
+/* ---- Schur condense / expand for many right-hand sides, and the bit-reproducible form of all of them.
+ * cholamd_schur_condense_nrhs / cholamd_schur_expand_nrhs (and _f32: an fp32 arena eliminated with cholamd_factor_levels_f32(d, a32, levels - 1, k)):
+ *   B, X   n x nrhs column-major in ORIGINAL dof order, ldb, ldx >= n
+ *   W      n x nrhs column-major, ldw >= n: column j is what cholamd_schur_condense writes as w for column j of B (the permuted, forward-swept vector, whose
+ *          tail is g).  A column of W is a valid w for cholamd_schur_expand, and a w is a valid column of W.
+ *   G, XT  m x nrhs column-major in Schur order, ldg, ldxt >= m
+ * NEVER WRITTEN: rows past n (m) up to the leading dimension, columns >= nrhs, and W by the expand (one condense serves any number of expands).
+ * nrhs == 0 returns 0 and touches nothing; nrhs < 0, a leading dimension that is too small, or a NULL pointer with nrhs > 0: CHOLAMD_ERR_ARG, nothing written;
+ * so for k out of range and a partitioned device object.  Condense: B, W, G and the arena must be pairwise disjoint over their full (nrhs - 1) ld + rows
+ * extents; expand: X must be disjoint from W, XT and the arena; there is no in-place form.  Asynchronous on `stream`; ONE CALL AT A TIME per device object.
+ * The columns go in chunks of 32 through the device object's permuted row-major block: the 16x16 and span inverses of the levels >= k ONLY are formed once per
+ * call, the condense runs the forward loop of the block solve over the levels levels - 1 .. k and unpacks the block into W and G, the expand packs W's rows
+ * < t0 and XT into the block and runs the backward loop over k .. levels - 1.  A chunk of fewer than 4 (fp64 arena) / 6 (fp32 arena) columns goes column
+ * by column through the single-vector calls.  The off-diagonal blocks accumulate by fp64 atomics: results agree from run to run to rounding.
+ *
+ * DEVICE OPTION "schur_deterministic" (cholamd_device_set_option, or CHOLAMD_SCHUR_DETERMINISTIC non-zero in the environment at cholamd_device_create;
+ * default off; setting it rebuilds nothing).  With it off every entry point does exactly what it does without it, down to which kernels run -- the Schur
+ * sweeps under "solve_deterministic" included.  It does not depend on the solve_* options and does not change them.  With it on, cholamd_schur_condense /
+ * _expand / _f32 walk deterministic step lists CUT at level k with the gather and span kernels of the deterministic solve, and the four _nrhs calls walk the
+ * same lists on 32-column chunks with the block gather and the block span kernel in its substitution form; EVERY chunk takes the block kernels, whatever
+ * its column count, nrhs = 1 included.  No floating-point atomic, no flag, no wait inside a launch.  The lists are built per (device object, k) at the
+ * first such call and kept; later calls allocate nothing:
+ *   FORWARD (condense)  the FORWARD steps of the deterministic solve of the levels levels - 1 .. k, unchanged, then ONE kept lead step: for every 16-row
+ *                       chunk of every kept separator the sources of its ordinary lead-step item that read permuted positions < t0 (the panels of its
+ *                       eliminated descendants).  Sources in panels of kept separators are dropped: those hold S, not L.  One launch, no span step.
+ *   BACKWARD (expand)   the BACKWARD steps of the levels k .. levels - 1, unchanged: their sources into kept ancestors are rows L[T, s] of eliminated panels.
+ * The builder refuses (CHOLAMD_ERR_INVARIANT, naming the item) a list in which a kept-lead source reads a position >= t0, a source lies in a block of two
+ * kept separators, a position under the cut is not solved exactly once, or a kept position has more than one owner.  The 16x16 inverses are formed for the
+ * levels >= k only.  THE CONTRACT with the option on:
+ *  (a) the same bits of W, G and X for the same arena and inputs -- from call to call, between device objects of one plan, and on a device object created
+ *      under CHOLAMD_POISON=1;
+ *  (b) in the _nrhs forms column j depends on the arena and on column j of the inputs only -- not on nrhs, not on its chunk or its half of the 32-column
+ *      tile, not on the other columns: a NaN elsewhere never reaches it;
+ *  (c) nothing stored in a block of two kept separators influences any output: condense and expand never read S;
+ *  (d) NOT PROMISED: the bits of the atomic path, or equality of the single-vector and the block bits.  They agree to rounding.
+ * cholamd_device_schur_launches (tests and diagnostics): launches of the Schur condense / expand sweeps on this device object since its creation, out =
+ *   { launches of the atomic sweep kernels, deterministic gather launches, deterministic span launches, pack / unpack launches }.
+ *
+ * Host side (no device): cholamd_plan_schur_condense_host_nrhs / cholamd_plan_schur_expand_host_nrhs walk the SAME cut lists over a host arena whose
+ *   eliminated part is factored: the gather has the block kernel's partition (chol_muln_wave / chol_muln_elem), a span is solved by substitution inside its
+ *   own lower triangle.  Layout and argument rules as on the device (no overlap checks).  Deterministic, columns independent; not the device's bits.
+ * cholamd_plan_schur_det_counts: out = { FORWARD steps, items, sources, entries of L read, BACKWARD steps, items, sources, entries of L read }.
+ * cholamd_plan_schur_det_lists: the lists of one direction in the row formats of cholamd_plan_solve_det_lists; the kept lead step has level = -1. */
+int cholamd_schur_condense_nrhs(cholamd_device *d, const double *d_arena, int k, const double *d_B, int64_t ldb, double *d_W, int64_t ldw,
+                                double *d_G, int64_t ldg, int nrhs, void *stream);
+int cholamd_schur_expand_nrhs(cholamd_device *d, const double *d_arena, int k, const double *d_W, int64_t ldw, const double *d_XT, int64_t ldxt,
+                              double *d_X, int64_t ldx, int nrhs, void *stream);
+int cholamd_schur_condense_nrhs_f32(cholamd_device *d, const float *d_arena32, int k, const double *d_B, int64_t ldb, double *d_W, int64_t ldw,
+                                    double *d_G, int64_t ldg, int nrhs, void *stream);
+int cholamd_schur_expand_nrhs_f32(cholamd_device *d, const float *d_arena32, int k, const double *d_W, int64_t ldw, const double *d_XT, int64_t ldxt,
+                                  double *d_X, int64_t ldx, int nrhs, void *stream);
+int cholamd_device_schur_launches(const cholamd_device *d, int64_t out[4]);
+int cholamd_plan_schur_condense_host_nrhs(const cholamd_plan *p, int k, const double *arena_host, const double *B, int64_t ldb, double *W, int64_t ldw,
+                                          double *G, int64_t ldg, int nrhs);
+int cholamd_plan_schur_expand_host_nrhs(const cholamd_plan *p, int k, const double *arena_host, const double *W, int64_t ldw, const double *XT, int64_t ldxt,
+                                        double *X, int64_t ldx, int nrhs);
+int cholamd_plan_schur_det_counts(const cholamd_plan *p, int k, int64_t out[8]);
+int cholamd_plan_schur_det_lists(const cholamd_plan *p, int k, int which, int64_t *steps, int64_t *items, int64_t *srcs);
 /* average device time (ms) of the three kernel families of the last cholamd_factor call measured
  * with HIP events on its stream; valid after cholamd_device_sync.  Enable with set_timing(1). */
 int cholamd_device_set_timing(cholamd_device *d, int on);
