@@ -683,7 +683,8 @@ extern "C" int cholamd_device_program_trace(cholamd_device *d, double *d_arena, 
         const int kind = d->jobs_host[j].kind;
         bool any = false;
         for (int i = 0; i < CHOL_TRACE_X; i++) any = any || x[i] != 0;
-        if (kind == 2 || !any) continue;
+        if (!any) continue;
+        if (kind == 2) { fprintf(fp, "job %d kind 2 last-stage-held %.1f\n", j, (double)(x[0] - t0) * 0.01); continue; } // update job: wave 0 saw its last staged wait hold
         fprintf(fp, "job %d kind %d", j, kind);
         if (kind == 0 && x[1]) {
           fprintf(fp, " items %llu own-tiles-wait-over %.1f rounds:", x[1], x[0] ? (double)(x[0] - t0) * 0.01 : -1.0);

@@ -109,7 +109,7 @@ template <class TL> int chol_nrhs_launch_span(const TL *base, const chol_trsv_de
 template <class TL> int chol_launch_multiply_nrhs(const TL *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, const double *Zp, double *Y, const int *perm,
                                                   int64_t ldy, int c0, int cols, hipStream_t st);
 int chol_launch_multiply_resid(const int64_t *ptr, const int *col, const double *val, const double *z, const double *w, int n, double *part, int64_t *ipart, int64_t *res, hipStream_t st);
-/* diagnostic instance of the program launch (k_program<true>): 4 stamps per job, then CHOL_TRACE_X per job -- [0] follower: own tiles' wait over,
+/* diagnostic instance of the program launch (k_program<true>): 4 stamps per job, then CHOL_TRACE_X per job -- [0] follower: own tiles' wait over / update job: wave 0 saw the job's last staged wait hold,
  * [1] its items, [2 + i] round of item i begun; [48 + k] POTRF job: column k published / TRSM job (first strip): column tile k on its channel;
  * [72 + k] POTRF job: the factor wave starts column k / TRSM job: the POTRF's column k seen */
 #define CHOL_TRACE_X 96

@@ -78,52 +78,27 @@ __device__ __forceinline__ int wait_progress(const int *progress, int target, in
 // ------------------------------------------------------------------------------------------------
 // acc(r, c) += sum_{k < K} X[r + k ldx] * Y[c + k ldy],  r0 <= r < mv, c0 <= c < nv (rows outside are read as 0)
 // ------------------------------------------------------------------------------------------------
-template <bool PUB = false>
 __device__ __forceinline__ d4 rank_k_16x16(d4 acc, const double *__restrict__ X, int ldx, int mv,
                                            const double *__restrict__ Y, int ldy, int nv, int K, int lane, int r0 = 0, int c0 = 0)
-{ // rows [r0, mv) of X and [c0, nv) of Y take part
+{ // rows [r0, mv) of X and [c0, nv) of Y take part.  Operands of launches that ended (the hand-off form inside a launch: upd_stream below)
   const int r = lane & 15, kq = lane >> 4;
   const bool vx = r >= r0 && r < mv, vy = r >= c0 && r < nv;
   const double *px = X + r + (int64_t)kq * ldx;
   const double *py = Y + r + (int64_t)kq * ldy;
   int k0 = 0;
-  if (PUB) {
-    // in-launch hand-offs are read past the L2 of the producer's XCD: a memory round trip per batch.  Two batches of sixteen
-    // loads are kept in flight (the next trip's loads are issued ahead of this trip's MFMAs)
-    double x[8], y[8];
-    if (K >= 32) {
-#pragma unroll
-      for (int u = 0; u < 8; ++u) { x[u] = vx ? gload<PUB>(&px[(int64_t)(4 * u) * ldx]) : 0.0; y[u] = vy ? gload<PUB>(&py[(int64_t)(4 * u) * ldy]) : 0.0; }
-    }
-    for (; k0 + 32 <= K; k0 += 32) {
-      double xn[8], yn[8];
-      px += 32 * (int64_t)ldx; py += 32 * (int64_t)ldy;
-      const bool more = k0 + 64 <= K;
-      if (more) {
-#pragma unroll
-        for (int u = 0; u < 8; ++u) { xn[u] = vx ? gload<PUB>(&px[(int64_t)(4 * u) * ldx]) : 0.0; yn[u] = vy ? gload<PUB>(&py[(int64_t)(4 * u) * ldy]) : 0.0; }
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(y[u], x[u], acc, 0, 0, 0);
-      if (more) {
-#pragma unroll
-        for (int u = 0; u < 8; ++u) { x[u] = xn[u]; y[u] = yn[u]; }
-      }
-    }
-  } else
   for (; k0 + 32 <= K; k0 += 32) { // eight MFMAs per trip, sixteen loads in flight
     double x[8], y[8];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) { x[u] = vx ? gload<PUB>(&px[(int64_t)(4 * u) * ldx]) : 0.0; y[u] = vy ? gload<PUB>(&py[(int64_t)(4 * u) * ldy]) : 0.0; }
+    for (int u = 0; u < 8; ++u) { x[u] = vx ? px[(int64_t)(4 * u) * ldx] : 0.0; y[u] = vy ? py[(int64_t)(4 * u) * ldy] : 0.0; }
 #pragma unroll
     for (int u = 0; u < 8; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(y[u], x[u], acc, 0, 0, 0);
     px += 32 * (int64_t)ldx; py += 32 * (int64_t)ldy;
   }
   for (; k0 + 16 <= K; k0 += 16) { // four MFMAs per trip, eight loads in flight
-    double x0 = vx ? gload<PUB>(&px[0]) : 0.0, y0 = vy ? gload<PUB>(&py[0]) : 0.0;
-    double x1 = vx ? gload<PUB>(&px[4 * (int64_t)ldx]) : 0.0, y1 = vy ? gload<PUB>(&py[4 * (int64_t)ldy]) : 0.0;
-    double x2 = vx ? gload<PUB>(&px[8 * (int64_t)ldx]) : 0.0, y2 = vy ? gload<PUB>(&py[8 * (int64_t)ldy]) : 0.0;
-    double x3 = vx ? gload<PUB>(&px[12 * (int64_t)ldx]) : 0.0, y3 = vy ? gload<PUB>(&py[12 * (int64_t)ldy]) : 0.0;
+    double x0 = vx ? px[0] : 0.0, y0 = vy ? py[0] : 0.0;
+    double x1 = vx ? px[4 * (int64_t)ldx] : 0.0, y1 = vy ? py[4 * (int64_t)ldy] : 0.0;
+    double x2 = vx ? px[8 * (int64_t)ldx] : 0.0, y2 = vy ? py[8 * (int64_t)ldy] : 0.0;
+    double x3 = vx ? px[12 * (int64_t)ldx] : 0.0, y3 = vy ? py[12 * (int64_t)ldy] : 0.0;
     acc = __builtin_amdgcn_mfma_f64_16x16x4f64(y0, x0, acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f64_16x16x4f64(y1, x1, acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f64_16x16x4f64(y2, x2, acc, 0, 0, 0);
@@ -132,7 +107,7 @@ __device__ __forceinline__ d4 rank_k_16x16(d4 acc, const double *__restrict__ X,
   }
   for (; k0 < K; k0 += 4) {
     const bool vk = k0 + kq < K;
-    double x = (vx && vk) ? gload<PUB>(&px[0]) : 0.0, y = (vy && vk) ? gload<PUB>(&py[0]) : 0.0;
+    double x = (vx && vk) ? px[0] : 0.0, y = (vy && vk) ? py[0] : 0.0;
     acc = __builtin_amdgcn_mfma_f64_16x16x4f64(y, x, acc, 0, 0, 0);
     px += 4 * (int64_t)ldx; py += 4 * (int64_t)ldy;
   }
@@ -227,6 +202,108 @@ __device__ __forceinline__ int wait_stage(const stage_waits &sw, int need, int l
   return have;
 }
 // ------------------------------------------------------------------------------------------------
+// Hand-off form of an update task's walk (operands written by other workgroups of the SAME launch: agent-scope loads that go past the
+// L2 of the reader's XCD, a memory round trip of 1.5-2 us each time the wave waits).  A wave's work is a list of pieces (source, K range)
+// in program order; it is cut into batches of up to 32 columns (8 k-steps of v_mfma_f64_16x16x4), only a piece's last batch is partial,
+// and the batches go through two register slots as ONE stream: both slots are requested, then both are multiplied, so that a round trip
+// carries two batches whatever they are -- 32 + 7 columns of one source, the last 3 columns of a source and the first 32 of the next,
+// two whole sources of 13 and 22 columns.  (The loop that came before pipelined full batches only; a 16-column batch and then every
+// remaining 4 columns were a trip of their own, issued after the MFMAs before them, and every source began with an empty pipeline.)
+// A partial batch skips its missing k-steps by scalar branches -- K is wave-uniform -- so no load addresses a column >= K; the lanes of
+// the last k-step beyond K are selected to 0.0 (never multiplied by zero: what lies there may be anything).  The count of loads in
+// flight is then not a constant, and the compiler's s_waitcnt in front of the first slot's MFMAs covers the second slot too: that is
+// why the slots are filled and drained in pairs instead of in rotation (a rotating slot would wait for the request issued just before).
+// Accumulation order: sources in program order, K ascending, four columns per MFMA -- as in rank_k_16x16, the same bits.
+// In front of a source whose staged wait has not been seen to hold the stream drains, waits (wait_stage) and starts again: nothing is
+// requested from a source before that.
+// ------------------------------------------------------------------------------------------------
+struct upd_piece { const double *px, *py; int ldx, ldy; bool vx, vy; int krem; }; // the open piece: lane pointers at its next column, columns left
+// opens the wave's next piece that is not empty: sources s, s + step, ... < s_end, of each the whole K (quarter < 0) or the K range of the
+// wave `quarter` of four.  1: p holds it; 0: the list is through; -stage: the next source's stage does not hold yet (s stays in front of it)
+__device__ __forceinline__ int upd_piece_open(upd_piece &p, int &s, int s_end, int step, int quarter, const double *__restrict__ base, const chol_upd_task &t,
+                                              const chol_upd_src *__restrict__ srcs, int st_done, int lane)
+{
+  while (s < s_end) {
+    const chol_upd_src sd = srcs[s];
+    if (sd.stage > st_done) return -sd.stage;
+    s += step;
+    int k_lo = 0, kn = sd.k;
+    if (quarter >= 0) {
+      const int kc = ((((sd.k + 3) >> 2) + 3) >> 2) << 2; // K per wave, a multiple of 4
+      k_lo = quarter * kc; kn = min(kc, sd.k - k_lo);
+    }
+    if (kn <= 0) continue;
+    const int r = lane & 15, kq = lane >> 4;
+    const int r0 = sd.range & 255, r1 = sd.range ? (sd.range >> 8) & 255 : t.mv, c0 = (sd.range >> 16) & 255, c1 = sd.range ? (sd.range >> 24) & 255 : t.nv;
+    p.vx = r >= r0 && r < r1; p.vy = r >= c0 && r < c1;
+    p.px = base + sd.a_off + t.ar + r + (int64_t)(k_lo + kq) * sd.lda;
+    p.py = base + sd.b_off + t.br + r + (int64_t)(k_lo + kq) * sd.ldb;
+    p.ldx = sd.lda; p.ldy = sd.ldb; p.krem = kn;
+    return 1;
+  }
+  return 0;
+}
+// requests the open piece's next batch into one slot and returns its k-steps (1 .. 8)
+__device__ __forceinline__ int upd_batch_request(upd_piece &p, int kq, double (&x)[8], double (&y)[8])
+{
+  const int kb = min(p.krem, 32), nk = (kb + 3) >> 2;
+  // ONE code path for full and partial batches: were there two, the compiler would see the second slot's full path as reachable from its partial
+  // one and guard the registers with a vmcnt(0) -- behind the first slot's requests
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    if (u < nk) {
+      const bool vk = 4 * u + kq < kb; // false in a partial batch's last k-step only
+      x[u] = (p.vx && vk) ? gload<true>(&p.px[(int64_t)(4 * u) * p.ldx]) : 0.0; y[u] = (p.vy && vk) ? gload<true>(&p.py[(int64_t)(4 * u) * p.ldy]) : 0.0;
+    }
+  }
+  p.px += 32 * (int64_t)p.ldx; p.py += 32 * (int64_t)p.ldy; p.krem -= kb;
+  return nk;
+}
+__device__ __forceinline__ d4 upd_batch_mfma(d4 acc, int nk, const double (&x)[8], const double (&y)[8])
+{ // nk = 0: an empty slot
+  if (nk == 8) {
+#pragma unroll
+    for (int u = 0; u < 8; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(y[u], x[u], acc, 0, 0, 0);
+  } else {
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      if (u >= nk) break;
+      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(y[u], x[u], acc, 0, 0, 0);
+    }
+  }
+  return acc;
+}
+// the sum over the wave's pieces.  TR (diagnostic instance of the program launch): *xstamp = the clock when st_done first covered every stage
+template <bool TR>
+__device__ __forceinline__ d4 upd_stream(const double *__restrict__ base, const chol_upd_task &t, const chol_upd_src *__restrict__ srcs, int s, int s_end, int step, int quarter,
+                                         int lane, const stage_waits &sw, int st_done, unsigned long long *xstamp)
+{
+  d4 acc = { 0.0, 0.0, 0.0, 0.0 };
+  const int kq = lane >> 4;
+  upd_piece p;
+  p.krem = 0;
+  double xa[8], ya[8], xb[8], yb[8];
+  for (;;) {
+    if (TR && xstamp && st_done >= sw.n) { if (lane == 0 && *xstamp == 0) *xstamp = __builtin_amdgcn_s_memrealtime(); xstamp = nullptr; } // the job's first look that covers them all
+    int na = 0, nb = 0, more = 1;
+    if (p.krem == 0) more = upd_piece_open(p, s, s_end, step, quarter, base, t, srcs, st_done, lane);
+    if (more > 0) {
+      na = upd_batch_request(p, kq, xa, ya);
+      if (p.krem == 0) more = upd_piece_open(p, s, s_end, step, quarter, base, t, srcs, st_done, lane);
+      if (more > 0) nb = upd_batch_request(p, kq, xb, yb);
+    }
+    acc = upd_batch_mfma(acc, na, xa, ya);
+    acc = upd_batch_mfma(acc, nb, xb, yb);
+    // every request of the pair has been multiplied, so nothing of it is in flight -- which the compiler cannot tell across the scalar branches of
+    // a partial batch: without this (free) s_waitcnt vmcnt(0) it protects the slots' registers against requests it believes pending with a
+    // vmcnt(0) of its own in front of the NEXT request, and the second slot's then waits for the first slot's loads: one batch per round trip
+    __builtin_amdgcn_s_waitcnt(0x0f70);
+    if (more == 0) break;
+    if (more < 0) st_done = max(wait_stage(sw, -more, lane), -more);
+  }
+  return acc;
+}
+// ------------------------------------------------------------------------------------------------
 // UPDATE: one workgroup (4 waves) per 16x16 output sub-tile of a target C tile.  The tile's sources
 // are walked in the reference's program order; the four waves split every source's K range, or -- from
 // four sources on -- the sources themselves (the tasks are latency bound: dependent descriptor ->
@@ -241,9 +318,10 @@ __device__ __forceinline__ int wait_stage(const stage_waits &sw, int need, int l
 // `live` = false: a placeholder that only keeps the workgroup's barrier count uniform.  `wait` (fused launch): the
 // counter of finished TRSM workgroups and the value it must reach before the sources may be read -- the task
 // descriptor and the C sub-tile are requested before that wait.
-template <bool PUB>
+template <bool PUB, bool TR = false>
 __device__ __forceinline__ void update_task_body(double *__restrict__ base, const chol_upd_task t, const chol_upd_src *__restrict__ srcs, double (*sAcc)[4][64],
-                                                 int wave, int lane, bool live, const int *wait, int wait_target, int *info, const stage_waits sw = stage_waits())
+                                                 int wave, int lane, bool live, const int *wait, int wait_target, int *info, const stage_waits sw = stage_waits(),
+                                                 unsigned long long *xstamp = nullptr)
 {
   // the C sub-tile is requested first (wave 0; clamped addresses, masked at the store): read at the end, each of
   // its four columns would be a memory round trip of its own on the tail of every task
@@ -261,25 +339,26 @@ __device__ __forceinline__ void update_task_body(double *__restrict__ base, cons
   d4 acc = { 0.0, 0.0, 0.0, 0.0 };
   const int nsrc = live ? t.src_end - t.src_begin : 0;
   int st_done = (PUB && sw.n > 0 && nsrc > 0) ? stages_holding(sw, lane) : 0;
-  if (nsrc >= 4) {
-    // many sources (a target high in the tree collects one per descendant): the waves take whole sources
-    // round-robin, so four descriptor -> operand load chains are in flight instead of one
+  // many sources (from four on: a target high in the tree collects one per descendant): the waves take whole sources round-robin, so
+  // four descriptor -> operand load chains are in flight instead of one; fewer: every wave takes its quarter of each source's K
+  if constexpr (PUB) {
+    const bool deal = nsrc >= 4;
+    acc = upd_stream<TR>(base, t, srcs, t.src_begin + (deal ? wave : 0), t.src_begin + nsrc, deal ? 4 : 1, deal ? -1 : wave, lane, sw, st_done, wave == 0 ? xstamp : nullptr);
+  } else if (nsrc >= 4) {
     for (int s = t.src_begin + wave; s < t.src_end; s += 4) {
       const chol_upd_src sd = srcs[s];
-      if (PUB && sd.stage > st_done) st_done = wait_stage(sw, sd.stage, lane);
       const int r0 = sd.range & 255, r1 = sd.range ? (sd.range >> 8) & 255 : t.mv, c0 = (sd.range >> 16) & 255, c1 = sd.range ? (sd.range >> 24) & 255 : t.nv;
-      acc = rank_k_16x16<PUB>(acc, base + sd.a_off + t.ar, sd.lda, r1, base + sd.b_off + t.br, sd.ldb, c1, sd.k, lane, r0, c0);
+      acc = rank_k_16x16(acc, base + sd.a_off + t.ar, sd.lda, r1, base + sd.b_off + t.br, sd.ldb, c1, sd.k, lane, r0, c0);
     }
   } else {
     for (int s = t.src_begin; s < t.src_end; ++s) {
       const chol_upd_src sd = srcs[s];
-      if (PUB && live && sd.stage > st_done) st_done = wait_stage(sw, sd.stage, lane);
       const int kc = ((((sd.k + 3) >> 2) + 3) >> 2) << 2; // K per wave, a multiple of 4
       const int k_lo = wave * kc;
       if (k_lo < sd.k) {
         const int kn = min(kc, sd.k - k_lo);
         const int r0 = sd.range & 255, r1 = sd.range ? (sd.range >> 8) & 255 : t.mv, c0 = (sd.range >> 16) & 255, c1 = sd.range ? (sd.range >> 24) & 255 : t.nv;
-        acc = rank_k_16x16<PUB>(acc, base + sd.a_off + t.ar + (int64_t)k_lo * sd.lda, sd.lda, r1,
+        acc = rank_k_16x16(acc, base + sd.a_off + t.ar + (int64_t)k_lo * sd.lda, sd.lda, r1,
                            base + sd.b_off + t.br + (int64_t)k_lo * sd.ldb, sd.ldb, c1, kn, lane, r0, c0);
       }
     }
@@ -300,22 +379,18 @@ __device__ __forceinline__ void update_task_body(double *__restrict__ base, cons
 }
 // the same task by ONE wave (program launch: twelve tasks of a job at a time, one per wave -- no K split, no LDS reduction,
 // no barrier; sources in program order, K in order: deterministic)
-template <bool PUB>
-__device__ __forceinline__ void update_task_wave(double *__restrict__ base, const chol_upd_task t, const chol_upd_src *__restrict__ srcs, int lane, const stage_waits sw = stage_waits())
+template <bool PUB, bool TR = false>
+__device__ __forceinline__ void update_task_wave(double *__restrict__ base, const chol_upd_task t, const chol_upd_src *__restrict__ srcs, int lane, const stage_waits sw = stage_waits(),
+                                                 unsigned long long *xstamp = nullptr)
 {
+  static_assert(PUB, "a role of the program launch");
   const int r = lane & 15, g = lane >> 4;
   double cv[4];
   double *C = base + t.c_off;
 #pragma unroll
   for (int q = 0; q < 4; ++q) cv[q] = gload<PUB>(C + min(r, t.mv - 1) + (int64_t)min(g + 4 * q, t.nv - 1) * t.ldc);
-  d4 acc = { 0.0, 0.0, 0.0, 0.0 };
-  int st_done = (PUB && sw.n > 0) ? stages_holding(sw, lane) : 0;
-  for (int s = t.src_begin; s < t.src_end; ++s) {
-    const chol_upd_src sd = srcs[s];
-    if (PUB && sd.stage > st_done) st_done = wait_stage(sw, sd.stage, lane);
-    const int r0 = sd.range & 255, r1 = sd.range ? (sd.range >> 8) & 255 : t.mv, c0 = (sd.range >> 16) & 255, c1 = sd.range ? (sd.range >> 24) & 255 : t.nv;
-    acc = rank_k_16x16<PUB>(acc, base + sd.a_off + t.ar, sd.lda, r1, base + sd.b_off + t.br, sd.ldb, c1, sd.k, lane, r0, c0);
-  }
+  const int st_done = sw.n > 0 ? stages_holding(sw, lane) : 0;
+  const d4 acc = upd_stream<TR>(base, t, srcs, t.src_begin, t.src_end, 1, -1, lane, sw, st_done, xstamp);
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int c = g + 4 * q;
@@ -2030,10 +2105,11 @@ __global__ __launch_bounds__(RR_THREADS) void k_program(double *__restrict__ bas
     } else {
       stage_waits sw;
       sw.w = waits + jb.wait_first + jb.n_pre; sw.n = jb.n_wait - jb.n_pre; sw.ctr = ctr; sw.ctr_total = ctr_total; sw.epoch = epoch; sw.info = info;
+      unsigned long long *const xs = TR && trace && wave == 0 ? &trace[4 * njobs + CHOL_TRACE_X * j] : nullptr; // wave 0 of the job: its last stage seen to hold
       if (jb.mode == 0) {
         for (int t0 = jb.first; t0 < jb.first + jb.n; t0 += RR_NW + 1) { // light tasks: one per wave
           const int tk = t0 + wave;
-          if (tk < jb.first + jb.n) update_task_wave<true>(base, t0 == jb.first ? tpre : tasks[tk], srcs, lane, sw);
+          if (tk < jb.first + jb.n) update_task_wave<true, TR>(base, t0 == jb.first ? tpre : tasks[tk], srcs, lane, sw, xs);
         }
       } else { // heavy tasks: three at a time, four waves each (K or the sources split, fixed-order LDS reduction)
         double (*sAcc)[3][3][4][64] = (double (*)[3][3][4][64])smem; // [parity of the round][group]
@@ -2041,7 +2117,7 @@ __global__ __launch_bounds__(RR_THREADS) void k_program(double *__restrict__ bas
         for (int t0 = jb.first; t0 < jb.first + jb.n; t0 += 3, ++round) {
           const int tk = t0 + grp;
           const bool live = tk < jb.first + jb.n;
-          update_task_body<true>(base, t0 == jb.first ? tpre : tasks[live ? tk : t0], srcs, sAcc[round & 1][grp], wave & 3, lane, live, nullptr, 0, info, sw);
+          update_task_body<true, TR>(base, t0 == jb.first ? tpre : tasks[live ? tk : t0], srcs, sAcc[round & 1][grp], wave & 3, lane, live, nullptr, 0, info, sw, xs);
         }
       }
     }

@@ -9,6 +9,8 @@ mkdir -p $out
 /opt/rocm/bin/hipcc -O3 -fPIC --offload-arch=gfx950 -Iinclude -Icholesky_amd/csrc -Wall -mllvm -pragma-unroll-threshold=100000 "$@" -c cholesky_amd/csrc/chol_kernels.hip -o $out/chol_kernels.o
 /opt/rocm/bin/hipcc -O3 -fPIC --offload-arch=gfx950 -Iinclude -Icholesky_amd/csrc -Wall "$@" -c cholesky_amd/csrc/chol_kernels_f32.hip -o $out/chol_kernels_f32.o
 gcc -O2 -fPIC -Wall -Wextra -std=gnu11 -Iinclude -Icholesky_amd/csrc "$@" -c cholesky_amd/csrc/chol_schedule.c -o $out/chol_schedule.o
-/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o $out/libcholamd.so cholesky_amd/lib/chol_ingest.o cholesky_amd/lib/chol_symbolic.o $out/chol_schedule.o \
-  cholesky_amd/lib/chol_generate.o $out/chol_kernels.o $out/chol_kernels_f32.o cholesky_amd/lib/chol_api.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+# every other object of the in-tree build (make first) goes in as it is
+rest=$(ls cholesky_amd/lib/*.o | grep -v -e '/chol_kernels\.o$' -e '/chol_kernels_f32\.o$' -e '/chol_schedule\.o$')
+/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o $out/libcholamd.so $rest $out/chol_schedule.o $out/chol_kernels.o $out/chol_kernels_f32.o \
+  -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 echo built $out/libcholamd.so

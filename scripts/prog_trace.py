@@ -22,6 +22,10 @@ for _ in range(3):
     dev.fill(a); dev.factor(a)
 dev.sync()
 dev.fill(a); dev.sync()
+follow_file = os.environ.get("CHOLAMD_TRACE_FOLLOW")
+if not follow_file:  # the update jobs' "last stage held" stamps come through the follow trace: a file of our own unless the caller names one
+    import tempfile
+    follow_file = os.environ["CHOLAMD_TRACE_FOLLOW"] = os.path.join(tempfile.mkdtemp(), "follow.txt")
 tr = dev.program_trace(a)
 us = tr[:, 1:4] * 0.01
 kind = tr[:, 0]
@@ -112,6 +116,26 @@ for sep in sorted(set(int(v) for v in jobs[jobs[:, 0] == 2, 1]), key=lambda s_: 
         d = us[gq]
         line += f"[jobs {gq[0]}-{gq[-1]} n={len(gq)} tasks={int(jobs[gq, 4].sum())} drawn {d[:, 0].min():.0f}-{d[:, 0].max():.0f} start {d[:, 1].min():.0f}-{d[:, 1].max():.0f} end {d[:, 2].min():.0f}-{d[:, 2].max():.0f}] "
     print(line)
+
+# update jobs per target panel: from "wave 0 saw the job's last staged wait hold" (slot 0 of the job's extra stamps) to the job's end --
+# what a transition pays after the last source of an extend-add job is readable
+held = {}
+if os.path.exists(follow_file):
+    for ln in open(follow_file):
+        w = ln.split()
+        if len(w) >= 6 and w[2] == "kind" and w[3] == "2" and w[4] == "last-stage-held":
+            held[int(w[1])] = float(w[5])
+print("update jobs per target panel, last stage held -> job ended (us): jobs stamped / all, min, quartiles, max; the last job to end")
+for sep in sorted(set(int(v) for v in jobs[jobs[:, 0] == 2, 1]), key=lambda s_: (heap_level[s_], s_), reverse=True):
+    js = [j for j in range(len(jobs)) if jobs[j, 0] == 2 and jobs[j, 1] == sep]
+    d = np.array([us[j, 2] - held[j] for j in js if j in held])
+    if len(d) == 0:
+        print(f"  panel {sep:2d} (level {heap_level[sep]}): {len(js):3d} jobs, none stamped")
+        continue
+    q = np.percentile(d, [0, 25, 50, 75, 100])
+    last = max(js, key=lambda j: us[j, 2])
+    tail = f"job {last} held {held[last]:.1f} end {us[last, 2]:.1f}" if last in held else f"job {last} end {us[last, 2]:.1f} (not stamped)"
+    print(f"  panel {sep:2d} (level {heap_level[sep]}): {len(d):3d} / {len(js):3d} jobs  {q[0]:5.1f} {q[1]:5.1f} {q[2]:5.1f} {q[3]:5.1f} {q[4]:5.1f}   last to end: {tail}")
 
 # TRACE_WAITS=lo:hi -- per job of the range: every wait (in list order = stage order) with the time its counter was complete
 if os.environ.get("TRACE_WAITS"):
