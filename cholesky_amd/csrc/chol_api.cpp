@@ -61,8 +61,9 @@ struct selinv_dev { // the lists of one tree level of the selected inversion (ch
   int max_nblk = 0;
 };
 struct schur_dev { dev_buf<chol_schur_desc> desc; int64_t n = -1; }; // n < 0: not built yet
-// the deterministic step lists of condense / expand cut at k kept levels (chol_build_schur_det), on the device; the steps stay on the host
-struct schur_det_dev { dev_buf<chol_mul_item> item[2]; dev_buf<chol_mul_src> src[2]; std::vector<chol_sdet_step> step[2]; bool ready = false; };
+// deterministic step lists (chol_sdet_lists: the whole tree's, or those of condense / expand cut at k kept levels) on the device; the steps stay on the
+// host: they are the launch sequence
+struct sdet_dev { dev_buf<chol_mul_item> item[2]; dev_buf<chol_mul_src> src[2]; std::vector<chol_sdet_step> step[2]; bool ready = false; };
 struct timed_launch { hipEvent_t a, b; int kind; };
 
 struct cholamd_device {
@@ -124,12 +125,12 @@ struct cholamd_device {
   chol_sched_opts opt;
   bool solve_reference_shape = false; // cholamd_solve with the per-call (deterministic) kernels of the BLAS-level entry points
   // option solve_deterministic: the streamed sweeps with owner gathers in place of the atomic kernels (chol_solve_det.hip).  The step lists of both
-  // directions (chol_sdet_lists) are built and uploaded at the first such solve; the steps themselves stay on the host (they are the launch sequence)
+  // directions (chol_sdet_lists) are built and uploaded at the first such solve
   bool solve_deterministic = false;
   // option solve_deterministic_block: under solve_deterministic (and without solve_reference_shape) the _nrhs entry points take the deterministic BLOCK path
-  // (solve_det_nrhs_t: the same step lists on chunks of 32 columns) instead of going column by column; no effect otherwise
+  // (solve_nrhs_t with the same step lists on chunks of 32 columns) instead of going column by column; no effect otherwise
   bool solve_deterministic_block = false;
-  dev_buf<chol_mul_item> sdet_item[2]; dev_buf<chol_mul_src> sdet_src[2]; std::vector<chol_sdet_step> sdet_step[2]; bool sdet_ready = false;
+  sdet_dev sdet;
   // block solve (cholamd_solve_nrhs): the permuted block of one chunk (n x CHOL_NRHS_W, row-major); refinement: the chunk's right-hand sides, residual and
   // correction (n x CHOL_NRHS_W, column-major) and the per-column partial sums of the residual kernel
   dev_buf<double> ynrhs, bnrhs, rnrhs, dxnrhs, pnrhs;
@@ -144,7 +145,7 @@ struct cholamd_device {
   // option schur_deterministic: condense / expand (single vector and _nrhs) walk the step lists cut at k (index k), built and uploaded at the first such
   // call with that k.  schur_launches: { atomic sweep, deterministic gather, deterministic span, pack / unpack } launches of the Schur sweeps so far
   bool schur_deterministic = false;
-  std::vector<schur_det_dev> scd;
+  std::vector<sdet_dev> scd;
   int64_t schur_launches[4] = { 0, 0, 0, 0 };
   // forward products (cholamd_multiply_half / cholamd_multiply / cholamd_factor_residual): the owner lists of the whole tree per direction, uploaded at the
   // first call; the intermediate vector of cholamd_multiply (permuted coordinates); the residual's per-workgroup partial sums and result words
@@ -790,7 +791,6 @@ static int build_solve(cholamd_device *d, int rank = 0, int world = 1)
 
 // first position of the shared top of the tree in the permuted vector (the separators above the cut are the last labels: a contiguous tail, as in the arena)
 static int64_t top_vec_offset(const cholamd_device *d) { return d->solve_world > 1 ? d->plan->sep_off[d->plan->nsep - (d->solve_world - 1) + 1] : d->plan->n; }
-// the streamed solve (every panel read once) with a factor of element type TL; vectors and arithmetic are fp64
 struct keep_inverses_scope { // set on the devices of a refinement after its first solve, cleared on every way out
   cholamd_device *const *devs; int n;
   keep_inverses_scope(cholamd_device *const *devs_, int n_) : devs(devs_), n(n_) { for (int g = 0; g < n; g++) devs[g]->keep_inverses = true; }
@@ -798,41 +798,91 @@ struct keep_inverses_scope { // set on the devices of a refinement after its fir
 };
 template <class TL> static int lsolve_trsv(cholamd_device *d, const TL *a, const chol_trsv_desc *t, int n, int mx, int mu, const double *W, double *y, int bw, const double *W256, hipStream_t st)
 { return chol_launch_solve_trsv(a, t, n, mx, mu, W, y, bw, d->step_flags, &d->step_gen, W256, d->step_xt, st); } // (the step launches' flags, counter and scratch are the device object's)
+// ---- the sweep helpers: every solve, half solve and Schur condense / expand below is a composition of these ----
+// which sweeps a body runs: one CHOLAMD_HALF_* sweep alone, or FORWARD then BACKWARD (the products: BACKWARD then FORWARD)
+#define CHOL_BOTH_SWEEPS (-1)
+// what a sweep works on: the permuted vector (n doubles), or the permuted row-major block of one chunk (n x CHOL_NRHS_W) with the chol_nrhs_* kernels
+struct sweep_rhs { double *y; bool block; };
+struct keep_restore { // keep_inverses for the chunks of one call, the caller's value back on every way out
+  cholamd_device *d; bool old;
+  explicit keep_restore(cholamd_device *d_) : d(d_), old(d_->keep_inverses) {}
+  ~keep_restore() { d->keep_inverses = old; }
+};
+// The inverses of the diagonal blocks of the levels lvl_lo .. levels - 1 from THIS arena (the factorisation's workspace belongs to the last arena factored): the
+// 16x16 ones, and with_spans the explicit span inverses of the wide top separators -- the atomic kernels read them, the deterministic ones do not.  The
+// caller decides whether they are due (keep_inverses; once per call in the block forms).
+template <class TL> static int form_inverses(cholamd_device *d, const TL *d_arena, int lvl_lo, bool with_spans, hipStream_t st)
+{
+  for (int lvl = lvl_lo; lvl < d->plan->levels; lvl++) {
+    const solve_dev &s = d->sv[lvl];
+    HIPCHK((hipError_t)chol_launch_solve_dinv(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, st));
+    if (with_spans && s.w256_off >= 0 && d->w256) HIPCHK((hipError_t)chol_launch_solve_inv256(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, d->w256 + s.w256_off, st));
+  }
+  return 0;
+}
+// One sweep of the atomic kernels over the levels lvl_lo .. lvl_hi.  Forward (mmat.rg:1395-1435) from lvl_hi down: TRSV per separator, then its panel into
+// the ancestors; backward (mmat.rg:1438-1479) from lvl_lo up: gather from the ancestors, then TRSV^T.  count (the Schur sweeps): 2 more per level.
+template <class TL> static int sweep_levels(cholamd_device *d, const TL *d_arena, sweep_rhs rhs, bool backward, int lvl_lo, int lvl_hi, int64_t *count, hipStream_t st)
+{
+  for (int i = 0; i <= lvl_hi - lvl_lo; i++) {
+    const solve_dev &s = d->sv[backward ? lvl_lo + i : lvl_hi - i];
+    const double *W256 = s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr;
+    const int *items = backward ? s.ibw : s.ifw;
+    const int n_items = backward ? s.n_ibw : s.n_ifw;
+    auto trsv = [&] {
+      return rhs.block ? chol_nrhs_launch_trsv(d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, W256, rhs.y, backward, st)
+                       : lsolve_trsv(d, d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, rhs.y, backward, W256, st);
+    };
+    if (!backward) HIPCHK((hipError_t)trsv());
+    HIPCHK((hipError_t)(rhs.block ? chol_nrhs_launch_offdiag(d_arena, s.bw, items, n_items, rhs.y, backward, st)
+                                  : chol_launch_solve_offdiag(d_arena, s.bw, items, n_items, rhs.y, backward, st)));
+    if (backward) HIPCHK((hipError_t)trsv());
+    if (count) *count += 2;
+  }
+  return 0;
+}
+// One sweep (q: CHOLAMD_HALF_*) of deterministic step lists: per step one gather launch where the step has items and one span launch where it has a span
+// (the kept lead step of the cut lists, level -1, is a gather alone).  counts (the Schur sweeps): a gather adds to [1], a span to [2].
+template <class TL> static int sweep_steps(cholamd_device *d, const TL *d_arena, const sdet_dev &c, int q, sweep_rhs rhs, int64_t *counts, hipStream_t st)
+{
+  const chol_mul_item *items = c.item[q];
+  for (const chol_sdet_step &t : c.step[q]) {
+    if (t.item_end > t.item_first) {
+      HIPCHK((hipError_t)(rhs.block ? chol_launch_solve_det_gather_nrhs(d_arena, items + t.item_first, t.item_end - t.item_first, c.src[q], q, rhs.y, st)
+                                    : chol_launch_solve_det_gather(d_arena, items + t.item_first, t.item_end - t.item_first, c.src[q], q, rhs.y, st)));
+      if (counts) counts[1]++;
+    }
+    if (t.col0 >= 0) {
+      const solve_dev &s = d->sv[t.level];
+      HIPCHK((hipError_t)(rhs.block ? chol_nrhs_launch_span(d_arena, s.trsv, s.n_trsv, d->ws_solve, rhs.y, t.col0, q, st)
+                                    : chol_launch_solve_span(d_arena, s.trsv, s.n_trsv, d->ws_solve, rhs.y, t.col0, q, st)));
+      if (counts) counts[2]++;
+    }
+  }
+  return 0;
+}
 // The streamed solve in three phases, so that a partitioned device can put the two vector reductions of the distributed solve between them:
 //   phase 0: y = P b (a rank of a partition: zero outside what it owns), the 16x16 inverses, forward sweep of the levels under the cut
 //            -> [sum of the shared top's part of y over the ranks]
 //   phase 1: forward and backward sweep of the levels above the cut (every rank: it holds the whole factored top), backward sweep under the cut;
 //            ranks other than 0 then clear the top's part again  -> [sum of y over the ranks: every rank has the whole permuted solution]
 //   phase 2: x = P^T y
-// A device that is not partitioned runs them back to back: the cut is at level 0.
+// A device that is not partitioned takes solve_t below, which launches the same with the cut at level 0 and nothing between the phases.
 template <class TL> static int solve_phase(cholamd_device *d, const TL *d_arena, const double *d_b, double *d_x, int phase, hipStream_t st)
 {
   const int L = d->plan->levels, n = d->plan->n, cut = d->solve_world > 1 ? chol_split_level(d->solve_world) : 0;
   double *y = d->ytmp;
+  const sweep_rhs rhs = { y, false };
+  int rc = 0;
   if (phase == 0) {
     HIPCHK((hipError_t)chol_launch_permute(d_b, d->perm, y, n, 0, st));
     if (d->n_zr_sub > 0) { hipLaunchKernelGGL(k_zero_ranges, dim3(16, d->n_zr_sub), dim3(256), 0, st, y, d->zr_sub, d->n_zr_sub); HIPCHK(hipGetLastError()); }
-    // the 16x16 inverses of this arena's diagonal blocks (the factorisation's workspace belongs to the last arena factored)
-    for (int lvl = 0; lvl < L && !d->keep_inverses; lvl++) {
-      const solve_dev &s = d->sv[lvl];
-      HIPCHK((hipError_t)chol_launch_solve_dinv(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, st));
-      if (s.w256_off >= 0 && d->w256) HIPCHK((hipError_t)chol_launch_solve_inv256(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, d->w256 + s.w256_off, st));
-    }
-  }
-  if (phase <= 1) {
-    const int hi = phase == 0 ? L - 1 : cut - 1, lo = phase == 0 ? cut : 0;
-    for (int lvl = hi; lvl >= lo; lvl--) { // forward, mmat.rg:1395-1435: TRSV per separator, then its panel into the ancestors
-      const solve_dev &s = d->sv[lvl];
-      HIPCHK((hipError_t)lsolve_trsv(d, d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, y, 0, s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr, st));
-      HIPCHK((hipError_t)chol_launch_solve_offdiag(d_arena, s.bw, s.ifw, s.n_ifw, y, 0, st));
-    }
+    if (!d->keep_inverses && (rc = form_inverses(d, d_arena, 0, true, st))) return rc;
+    if ((rc = sweep_levels(d, d_arena, rhs, false, cut, L - 1, nullptr, st))) return rc;
   }
   if (phase == 1) {
-    for (int lvl = 0; lvl < L; lvl++) { // backward, mmat.rg:1438-1479: gather from the ancestors, then TRSV^T
-      const solve_dev &s = d->sv[lvl];
-      HIPCHK((hipError_t)chol_launch_solve_offdiag(d_arena, s.bw, s.ibw, s.n_ibw, y, 1, st));
-      HIPCHK((hipError_t)lsolve_trsv(d, d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, y, 1, s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr, st));
-    }
+    if ((rc = sweep_levels(d, d_arena, rhs, false, 0, cut - 1, nullptr, st))) return rc;
+    if ((rc = sweep_levels(d, d_arena, rhs, true, 0, L - 1, nullptr, st))) return rc;
     if (d->solve_world > 1 && d->solve_rank != 0) { // the top's part of the solution is counted once in the sum that follows: rank 0's
       const int64_t t0 = top_vec_offset(d);
       HIPCHK(hipMemsetAsync(y + t0, 0, (size_t)(n - t0) * sizeof(double), st));
@@ -841,109 +891,111 @@ template <class TL> static int solve_phase(cholamd_device *d, const TL *d_arena,
   if (phase == 2) HIPCHK((hipError_t)chol_launch_permute(y, d->perm, d_x, n, 1, st));
   return 0;
 }
-template <class TL> static int solve_det_t(cholamd_device *d, const TL *d_arena, const double *d_b, double *d_x, int which, hipStream_t st);
-template <class TL> static int solve_streamed(cholamd_device *d, const TL *d_arena, const double *d_b, double *d_x, hipStream_t st)
+// ---------------------------------------------------------------------------------------------
+// The deterministic sweeps (option solve_deterministic; include/cholamd.h at "deterministic solve"): the step lists of chol_sdet_lists walked by sweep_steps
+// in place of the atomic kernels.  They need the solve lists of the whole tree (the spans' TRSV descriptors per level) and the 16x16 inverses alone.
+// ---------------------------------------------------------------------------------------------
+static int upload_sdet(sdet_dev &q, const chol_sdet_lists &w)
 {
-  if (d->solve_deterministic) return solve_det_t(d, d_arena, d_b, d_x, -1, st);
-  { int rc = build_solve(d); if (rc) return rc; } // the whole tree: the arena holds the complete factor (single GPU, or gathered on this rank)
-  for (int ph = 0; ph < 3; ph++) { int rc = solve_phase(d, d_arena, d_b, d_x, ph, st); if (rc) return rc; }
-  return 0;
+  int rc = 0;
+  for (int c = 0; c < 2 && !rc; c++) { // (an upload replaces what a call that failed half-way left)
+    rc = q.item[c].upload(w.item[c], (size_t)w.n_item[c]);
+    if (!rc) rc = q.src[c].upload(w.src[c], (size_t)w.n_src[c]);
+    q.step[c].assign(w.step[c], w.step[c] + w.n_step[c]);
+  }
+  q.ready = !rc;
+  return rc;
 }
-// ---------------------------------------------------------------------------------------------
-// The deterministic streamed solve (option solve_deterministic; include/cholamd.h at "deterministic solve"): the permute, the 16x16 inverses of THIS arena
-// unless a refinement keeps them, then per step of chol_sdet_lists one gather launch (where the step has items) and one span launch (where it has a span), and the permute back.
-// which: one CHOLAMD_HALF_* sweep, or -1: FORWARD then BACKWARD.  Needs the solve lists of the whole tree (the spans' TRSV descriptors per level).
-// ---------------------------------------------------------------------------------------------
 static int build_solve_det(cholamd_device *d)
 {
-  if (d->sdet_ready) return 0;
+  if (d->sdet.ready) return 0;
   chol_sdet_lists w;
   int rc = chol_build_solve_det(d->plan, &w);
   if (rc) return rc;
-  for (int q = 0; q < 2 && !rc; q++) { // (an upload replaces what a call that failed half-way left)
-    rc = d->sdet_item[q].upload(w.item[q], (size_t)w.n_item[q]);
-    if (!rc) rc = d->sdet_src[q].upload(w.src[q], (size_t)w.n_src[q]);
-    d->sdet_step[q].assign(w.step[q], w.step[q] + w.n_step[q]);
-  }
+  rc = upload_sdet(d->sdet, w);
   chol_sdet_lists_free(&w);
-  if (rc) return rc;
-  d->sdet_ready = true;
+  return rc;
+}
+// the sweeps `which` of the whole tree on rhs: the step lists (det) or the atomic kernels level by level
+template <class TL> static int sweep_tree(cholamd_device *d, const TL *d_arena, sweep_rhs rhs, int which, bool det, hipStream_t st)
+{
+  for (int q = 0; q < 2; q++) {
+    if (which != CHOL_BOTH_SWEEPS && which != q) continue;
+    int rc = det ? sweep_steps(d, d_arena, d->sdet, q, rhs, nullptr, st) : sweep_levels(d, d_arena, rhs, q == CHOLAMD_HALF_BACKWARD, 0, d->plan->levels - 1, nullptr, st);
+    if (rc) return rc;
+  }
   return 0;
 }
-template <class TL> static int solve_det_t(cholamd_device *d, const TL *d_arena, const double *d_b, double *d_x, int which, hipStream_t st)
+// The streamed solve of one vector on the whole tree (every panel read once; a factor of element type TL, vectors and arithmetic fp64): the arena holds the
+// complete factor (single GPU, or gathered on this rank).  x = A^-1 b (CHOL_BOTH_SWEEPS), P^T L^-1 P b (CHOLAMD_HALF_FORWARD) or P^T L^-T P b
+// (CHOLAMD_HALF_BACKWARD): the permute, the diagonal inverses of THIS arena unless the caller keeps them, the sweeps -- deterministic under option
+// solve_deterministic -- and the permute back: what solve_phase launches on a device that is not partitioned.
+template <class TL> static int solve_t(cholamd_device *d, const TL *d_arena, const double *d_b, double *d_x, int which, hipStream_t st)
 {
-  { int rc = build_solve(d); if (!rc) rc = build_solve_det(d); if (rc) return rc; }
-  const int L = d->plan->levels, n = d->plan->n;
+  const bool det = d->solve_deterministic;
+  { int rc = build_solve(d); if (!rc && det) rc = build_solve_det(d); if (rc) return rc; }
+  const int n = d->plan->n;
   double *y = d->ytmp;
   HIPCHK((hipError_t)chol_launch_permute(d_b, d->perm, y, n, 0, st));
-  for (int lvl = 0; lvl < L && !d->keep_inverses; lvl++) {
-    const solve_dev &s = d->sv[lvl];
-    HIPCHK((hipError_t)chol_launch_solve_dinv(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, st));
-  }
-  for (int q = 0; q < 2; q++) {
-    if (which >= 0 && which != q) continue;
-    const chol_mul_item *items = d->sdet_item[q];
-    for (const chol_sdet_step &t : d->sdet_step[q]) {
-      const solve_dev &s = d->sv[t.level];
-      if (t.item_end > t.item_first) HIPCHK((hipError_t)chol_launch_solve_det_gather(d_arena, items + t.item_first, t.item_end - t.item_first, d->sdet_src[q], q, y, st));
-      if (t.col0 >= 0) HIPCHK((hipError_t)chol_launch_solve_span(d_arena, s.trsv, s.n_trsv, d->ws_solve, y, t.col0, q, st));
-    }
-  }
+  if (!d->keep_inverses) { int rc = form_inverses(d, d_arena, 0, !det, st); if (rc) return rc; }
+  { int rc = sweep_tree(d, d_arena, { y, false }, which, det, st); if (rc) return rc; }
   HIPCHK((hipError_t)chol_launch_permute(y, d->perm, d_x, n, 1, st));
   return 0;
 }
-// The deterministic BLOCK solve (option solve_deterministic_block; include/cholamd.h at "deterministic solve"): the steps of solve_det_t on chunks of
-// CHOL_NRHS_W = 32 columns in the permuted row-major block of the block solve.  Per step one block gather (k_solve_det_gather_nrhs) where the step has items
-// and one k_nrhs_span launch in its substitution form where it has a span; the atomic kernels of the block solve (k_nrhs_panel, k_nrhs_offdiag) are never
-// launched.  EVERY chunk takes these kernels, whatever its column count: a column's bits must not depend on how many columns travel with it.
-static bool det_block(const cholamd_device *d) { return d->solve_deterministic && d->solve_deterministic_block && !d->solve_reference_shape; }
-template <class TL> static int solve_det_nrhs_t(cholamd_device *d, const TL *d_arena, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int nrhs, int which, hipStream_t st)
+// the same with the per-call kernels the BLAS-level entry points use (option solve_reference_shape: deterministic, slow at scale; fp64 factor only)
+static int solve_reference(cholamd_device *d, const double *d_arena, const double *d_b, double *d_x, int which, hipStream_t st)
 {
-  { int rc = build_solve(d); if (!rc) rc = build_solve_det(d); if (!rc) rc = d->ynrhs.ensure((size_t)d->plan->n * CHOL_NRHS_W); if (rc) return rc; }
-  const int L = d->plan->levels, n = d->plan->n;
-  double *Y = d->ynrhs;
-  for (int lvl = 0; lvl < L && !d->keep_inverses; lvl++) { // the 16x16 inverses of this arena once per call (a refinement keeps them)
-    const solve_dev &s = d->sv[lvl];
-    HIPCHK((hipError_t)chol_launch_solve_dinv(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, st));
-  }
-  for (int c0 = 0; c0 < nrhs; c0 += CHOL_NRHS_W) {
-    const int cols = std::min(CHOL_NRHS_W, nrhs - c0);
-    HIPCHK((hipError_t)chol_nrhs_launch_permute(d_B, ldb, d->perm, Y, nullptr, 0, n, c0, cols, 0, st));
-    for (int q = 0; q < 2; q++) {
-      if (which >= 0 && which != q) continue;
-      const chol_mul_item *items = d->sdet_item[q];
-      for (const chol_sdet_step &t : d->sdet_step[q]) {
-        const solve_dev &s = d->sv[t.level];
-        if (t.item_end > t.item_first) HIPCHK((hipError_t)chol_launch_solve_det_gather_nrhs(d_arena, items + t.item_first, t.item_end - t.item_first, d->sdet_src[q], q, Y, st));
-        if (t.col0 >= 0) HIPCHK((hipError_t)chol_nrhs_launch_span(d_arena, s.trsv, s.n_trsv, d->ws_solve, Y, t.col0, q, st));
-      }
-    }
-    HIPCHK((hipError_t)chol_nrhs_launch_permute(nullptr, 0, d->perm, Y, d_X, ldx, n, c0, cols, 1, st));
-  }
-  return 0;
-}
-extern "C" int cholamd_solve(cholamd_device *d, const double *d_arena, const double *d_b, double *d_x, void *stream)
-{
-  HIPCHK(hipSetDevice(d->dev));
   { int rc = build_solve(d); if (rc) return rc; }
-  hipStream_t st = (hipStream_t)stream;
-  if (!d->solve_reference_shape) return solve_streamed(d, d_arena, d_b, d_x, st);
-  // the per-call kernels the BLAS-level entry points use (deterministic, slow at scale)
   const int L = d->plan->levels, n = d->plan->n;
   double *y = d->ytmp;
   HIPCHK((hipError_t)chol_launch_permute(d_b, d->perm, y, n, 0, st));
-  for (int lvl = L - 1; lvl >= 0; lvl--) { // forward, mmat.rg:1395-1435
+  for (int lvl = L - 1; lvl >= 0 && which != CHOLAMD_HALF_BACKWARD; lvl--) { // forward, mmat.rg:1395-1435
     const solve_dev &s = d->sv[lvl];
     HIPCHK((hipError_t)chol_launch_trsv_fwd(d_arena, s.trsv, s.n_trsv, y, st));
     HIPCHK((hipError_t)chol_launch_gemv_fwd(d_arena, s.fw, s.grp_start, s.grp_rows, s.n_grp, y, st));
   }
-  for (int lvl = 0; lvl < L; lvl++) { // backward, mmat.rg:1438-1479
+  for (int lvl = 0; lvl < L && which != CHOLAMD_HALF_FORWARD; lvl++) { // backward, mmat.rg:1438-1479
     const solve_dev &s = d->sv[lvl];
     HIPCHK((hipError_t)chol_launch_bwd(d_arena, s.trsv, s.bw, s.bw_start, s.n_trsv, y, st));
   }
   HIPCHK((hipError_t)chol_launch_permute(y, d->perm, d_x, n, 1, st));
   return 0;
 }
+// One vector by the options in force, first match:
+//   solve_reference_shape, fp64 factor -> solve_reference (for an fp32 factor the option has no effect)
+//   solve_deterministic                -> solve_t with the step lists
+//   otherwise                          -> solve_t with the atomic kernels
+template <class TL> static int solve_any(cholamd_device *d, const TL *d_arena, const double *d_b, double *d_x, int which, hipStream_t st)
+{
+  if constexpr (std::is_same<TL, double>::value) { if (d->solve_reference_shape) return solve_reference(d, d_arena, d_b, d_x, which, st); }
+  return solve_t(d, d_arena, d_b, d_x, which, st);
+}
+static int half_which_ok(int which, const char *what)
+{
+  if (which == CHOLAMD_HALF_FORWARD || which == CHOLAMD_HALF_BACKWARD) return 0;
+  chol_set_error("%s: which = %d is neither CHOLAMD_HALF_FORWARD (0) nor CHOLAMD_HALF_BACKWARD (1)", what, which);
+  return CHOLAMD_ERR_ARG;
+}
+// cholamd_solve[_f32] (half = false: no argument checks, as ever) and cholamd_solve_half[_f32] (include/cholamd.h at cholamd_solve_half: M = P^T L P, so
+// M M^T = A in original dof order): the checks, the device, then solve_any's cascade
+template <class TL> static int solve_api(cholamd_device *d, const TL *d_arena, const double *d_b, double *d_x, bool half, int which, hipStream_t st, const char *what)
+{
+  if (half) {
+    if (!d) { chol_set_error("%s: NULL device", what); return CHOLAMD_ERR_ARG; }
+    { int rc = half_which_ok(which, what); if (rc) return rc; }
+    if (!d_arena || !d_b || !d_x) { chol_set_error("%s: NULL %s", what, !d_arena ? "arena" : !d_b ? "b" : "x"); return CHOLAMD_ERR_ARG; }
+  } else which = CHOL_BOTH_SWEEPS;
+  HIPCHK(hipSetDevice(d->dev));
+  return solve_any(d, d_arena, d_b, d_x, which, st);
+}
+extern "C" int cholamd_solve(cholamd_device *d, const double *d_arena, const double *d_b, double *d_x, void *stream)
+{ return solve_api(d, d_arena, d_b, d_x, false, 0, (hipStream_t)stream, "cholamd_solve"); }
+extern "C" int cholamd_solve_f32(cholamd_device *d, const float *d_arena32, const double *d_b, double *d_x, void *stream)
+{ return solve_api(d, d_arena32, d_b, d_x, false, 0, (hipStream_t)stream, "cholamd_solve_f32"); }
+extern "C" int cholamd_solve_half(cholamd_device *d, const double *d_arena, const double *d_b, double *d_x, int which, void *stream)
+{ return solve_api(d, d_arena, d_b, d_x, true, which, (hipStream_t)stream, "cholamd_solve_half"); }
+extern "C" int cholamd_solve_half_f32(cholamd_device *d, const float *d_arena32, const double *d_b, double *d_x, int which, void *stream)
+{ return solve_api(d, d_arena32, d_b, d_x, true, which, (hipStream_t)stream, "cholamd_solve_half_f32"); }
 
 // ---------------------------------------------------------------------------------------------
 // Mixed precision (BASELINE config 5): fp32 factor, fp64 iterative refinement of the solve.
@@ -994,12 +1046,6 @@ static int ensure_f32(cholamd_device *d, hipStream_t st)
     if (rc) { d->lv32.clear(); return rc; }
   }
   return 0;
-}
-extern "C" int cholamd_solve_f32(cholamd_device *d, const float *d_arena32, const double *d_b, double *d_x, void *stream)
-{
-  HIPCHK(hipSetDevice(d->dev));
-  { int rc = build_solve(d); if (rc) return rc; }
-  return solve_streamed(d, d_arena32, d_b, d_x, (hipStream_t)stream);
 }
 static int ensure_refine(cholamd_device *d)
 { // every buffer on its own: a call after a failure completes what is missing (csr_val is not uploaded twice: it follows cholamd_device_set_values)
@@ -1132,7 +1178,7 @@ extern "C" int cholamd_solve_refine(cholamd_device *d, const float *d_arena32, c
   const int n = d->plan->n;
   if (max_iter < 0) max_iter = 0;
   // x0 = M^-1 b with M = L32 L32^T; then x += M^-1 (b - A x) until ||b - A x|| <= tol ||b||
-  rc = solve_streamed(d, d_arena32, d_b, d_x, st);
+  rc = solve_t(d, d_arena32, d_b, d_x, CHOL_BOTH_SWEEPS, st);
   if (rc) return rc;
   keep_inverses_scope keep(&d, 1);
   double rel = 0.0;
@@ -1140,7 +1186,7 @@ extern "C" int cholamd_solve_refine(cholamd_device *d, const float *d_arena32, c
   for (;; ++it) {
     if ((rc = residual_norm(d, d_b, d_x, d->rvec, &rel, st))) return rc;
     if (!(rel > tol) || it >= max_iter) break; // also leaves on NaN
-    if ((rc = solve_streamed(d, d_arena32, d->rvec, d->dxvec, st))) return rc;
+    if ((rc = solve_t(d, d_arena32, d->rvec, d->dxvec, CHOL_BOTH_SWEEPS, st))) return rc;
     HIPCHK((hipError_t)chol_launch_axpy1(d_x, d->dxvec, n, st));
   }
   if (iters_out) *iters_out = it;
@@ -1177,182 +1223,68 @@ template <class TL> static constexpr int nrhs_min_block() { return sizeof(TL) ==
 // The same rule for one triangular half (cholamd_solve_half_nrhs): a half chunk and a half single solve both drop one of the two sweeps.  DESIGN.md section 10
 // records the measurement behind the value.
 template <class TL> static constexpr int half_nrhs_min_block() { return sizeof(TL) == sizeof(double) ? 4 : 6; }
-// One triangular half of the streamed solve on the whole tree, x = P^T L^-1 P b (CHOLAMD_HALF_FORWARD) or P^T L^-T P b (CHOLAMD_HALF_BACKWARD): the
-// launches of that sweep of solve_phase between the two permutes, the diagonal inverses of THIS arena first unless the caller keeps them.
-template <class TL> static int solve_half_streamed(cholamd_device *d, const TL *d_arena, const double *d_b, double *d_x, int which, hipStream_t st)
+// The block body: the diagonal inverses once per call (a caller that keeps them: not at all), then chunk by chunk the permute into the row-major block, the
+// sweeps `which` of the whole tree with the chol_nrhs_* kernels, and the permute back.
+//   det = false: the atomic kernels; a chunk under the threshold goes column by column through solve_t, which reuses the call's inverses
+//   det = true (option solve_deterministic_block; include/cholamd.h at "deterministic solve"): the step lists of solve_t's deterministic sweeps, one block gather
+//     (k_solve_det_gather_nrhs) and one k_nrhs_span launch in its substitution form per step; the atomic kernels (k_nrhs_panel, k_nrhs_offdiag) are never
+//     launched.  EVERY chunk takes these kernels, whatever its column count: a column's bits must not depend on how many columns travel with it.
+template <class TL> static int solve_nrhs_t(cholamd_device *d, const TL *d_arena, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int nrhs, int which, bool det, hipStream_t st)
 {
-  if (d->solve_deterministic) return solve_det_t(d, d_arena, d_b, d_x, which, st);
-  { int rc = build_solve(d); if (rc) return rc; }
-  const int L = d->plan->levels, n = d->plan->n;
-  double *y = d->ytmp;
-  HIPCHK((hipError_t)chol_launch_permute(d_b, d->perm, y, n, 0, st));
-  for (int lvl = 0; lvl < L && !d->keep_inverses; lvl++) {
-    const solve_dev &s = d->sv[lvl];
-    HIPCHK((hipError_t)chol_launch_solve_dinv(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, st));
-    if (s.w256_off >= 0 && d->w256) HIPCHK((hipError_t)chol_launch_solve_inv256(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, d->w256 + s.w256_off, st));
-  }
-  if (which == CHOLAMD_HALF_FORWARD)
-    for (int lvl = L - 1; lvl >= 0; lvl--) {
-      const solve_dev &s = d->sv[lvl];
-      HIPCHK((hipError_t)lsolve_trsv(d, d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, y, 0, s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr, st));
-      HIPCHK((hipError_t)chol_launch_solve_offdiag(d_arena, s.bw, s.ifw, s.n_ifw, y, 0, st));
-    }
-  else
-    for (int lvl = 0; lvl < L; lvl++) {
-      const solve_dev &s = d->sv[lvl];
-      HIPCHK((hipError_t)chol_launch_solve_offdiag(d_arena, s.bw, s.ibw, s.n_ibw, y, 1, st));
-      HIPCHK((hipError_t)lsolve_trsv(d, d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, y, 1, s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr, st));
-    }
-  HIPCHK((hipError_t)chol_launch_permute(y, d->perm, d_x, n, 1, st));
-  return 0;
-}
-struct keep_restore { // keep_inverses for the chunks of one call, the caller's value back on every way out
-  cholamd_device *d; bool old;
-  explicit keep_restore(cholamd_device *d_) : d(d_), old(d_->keep_inverses) {}
-  ~keep_restore() { d->keep_inverses = old; }
-};
-// which: CHOL_BOTH_SWEEPS (the solve), or one CHOLAMD_HALF_* sweep alone (cholamd_solve_half_nrhs)
-#define CHOL_BOTH_SWEEPS (-1)
-template <class TL> static int solve_nrhs_t(cholamd_device *d, const TL *d_arena, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int nrhs, hipStream_t st, int which = CHOL_BOTH_SWEEPS)
-{
-  { int rc = build_solve(d); if (rc) return rc; }
-  const int L = d->plan->levels, n = d->plan->n;
-  for (int lvl = 0; lvl < L && !d->keep_inverses; lvl++) { // the diagonal inverses once per call, as solve_phase
-    const solve_dev &s = d->sv[lvl];
-    HIPCHK((hipError_t)chol_launch_solve_dinv(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, st));
-    if (s.w256_off >= 0 && d->w256) HIPCHK((hipError_t)chol_launch_solve_inv256(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, d->w256 + s.w256_off, st));
-  }
+  { int rc = build_solve(d); if (!rc && det) rc = build_solve_det(d); if (rc) return rc; }
+  const int n = d->plan->n, min_block = det ? 1 : which == CHOL_BOTH_SWEEPS ? nrhs_min_block<TL>() : half_nrhs_min_block<TL>();
+  if (!d->keep_inverses) { int rc = form_inverses(d, d_arena, 0, !det, st); if (rc) return rc; }
   keep_restore kr(d);
-  d->keep_inverses = true; // (the column-by-column chunks: solve_streamed reuses them)
+  if (!det) d->keep_inverses = true; // (read by the column-by-column chunks alone)
   for (int c0 = 0; c0 < nrhs; c0 += CHOL_NRHS_W) {
     const int cols = std::min(CHOL_NRHS_W, nrhs - c0);
-    if (cols < (which == CHOL_BOTH_SWEEPS ? nrhs_min_block<TL>() : half_nrhs_min_block<TL>())) {
-      for (int j = c0; j < c0 + cols; j++) {
-        int rc = which == CHOL_BOTH_SWEEPS ? solve_streamed(d, d_arena, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, st)
-                                           : solve_half_streamed(d, d_arena, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, which, st);
-        if (rc) return rc;
-      }
+    if (cols < min_block) {
+      for (int j = c0; j < c0 + cols; j++) { int rc = solve_t(d, d_arena, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, which, st); if (rc) return rc; }
       continue;
     }
     { int rc = d->ynrhs.ensure((size_t)n * CHOL_NRHS_W); if (rc) return rc; }
     double *Y = d->ynrhs;
     HIPCHK((hipError_t)chol_nrhs_launch_permute(d_B, ldb, d->perm, Y, nullptr, 0, n, c0, cols, 0, st));
-    for (int lvl = L - 1; lvl >= 0 && which != CHOLAMD_HALF_BACKWARD; lvl--) { // forward: the separators' triangles, then their panels into the ancestors
-      const solve_dev &s = d->sv[lvl];
-      const double *W256 = s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr;
-      HIPCHK((hipError_t)chol_nrhs_launch_trsv(d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, W256, Y, 0, st));
-      HIPCHK((hipError_t)chol_nrhs_launch_offdiag(d_arena, s.bw, s.ifw, s.n_ifw, Y, 0, st));
-    }
-    for (int lvl = 0; lvl < L && which != CHOLAMD_HALF_FORWARD; lvl++) { // backward: gather from the ancestors, then the transposed triangles
-      const solve_dev &s = d->sv[lvl];
-      const double *W256 = s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr;
-      HIPCHK((hipError_t)chol_nrhs_launch_offdiag(d_arena, s.bw, s.ibw, s.n_ibw, Y, 1, st));
-      HIPCHK((hipError_t)chol_nrhs_launch_trsv(d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, W256, Y, 1, st));
-    }
+    { int rc = sweep_tree(d, d_arena, { Y, true }, which, det, st); if (rc) return rc; }
     HIPCHK((hipError_t)chol_nrhs_launch_permute(nullptr, 0, d->perm, Y, d_X, ldx, n, c0, cols, 1, st));
   }
   return 0;
 }
+static bool det_block(const cholamd_device *d) { return d->solve_deterministic && d->solve_deterministic_block && !d->solve_reference_shape; }
+// `cols` columns by the options in force (half: one of the half solves), first match:
+//   solve_deterministic and solve_deterministic_block, no solve_reference_shape -> solve_nrhs_t, det
+//   solve_reference_shape (fp64 factor) or solve_deterministic                  -> column by column through solve_any: both are deterministic there
+//   solve_reference_shape, fp32 factor, the full solve                          -> column by column through solve_any: the atomic solve_t (no per-call kernels)
+//   otherwise (also: solve_reference_shape, fp32 factor, a half solve)          -> solve_nrhs_t, atomic
+template <class TL> static int solve_nrhs_any(cholamd_device *d, const TL *d_arena, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int cols, bool half, int which, hipStream_t st)
+{
+  if (det_block(d)) return solve_nrhs_t(d, d_arena, d_B, ldb, d_X, ldx, cols, which, true, st);
+  if (d->solve_deterministic || (d->solve_reference_shape && (!half || std::is_same<TL, double>::value))) {
+    for (int j = 0; j < cols; j++) { int rc = solve_any(d, d_arena, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, which, st); if (rc) return rc; }
+    return 0;
+  }
+  return solve_nrhs_t(d, d_arena, d_B, ldb, d_X, ldx, cols, which, false, st);
+}
+// cholamd_solve_nrhs[_f32] and cholamd_solve_half_nrhs[_f32]: the checks (which before nrhs), the device, then solve_nrhs_any's cascade
+template <class TL> static int solve_nrhs_api(cholamd_device *d, const TL *d_arena, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int nrhs, bool half, int which, hipStream_t st, const char *what)
+{
+  if (half && d) { int rc = half_which_ok(which, what); if (rc) return rc; }
+  if (!half) which = CHOL_BOTH_SWEEPS;
+  { int rc = nrhs_check(d, d_arena, d_B, ldb, d_X, ldx, nrhs, what); if (rc) return rc > 0 ? 0 : rc; }
+  HIPCHK(hipSetDevice(d->dev));
+  return solve_nrhs_any(d, d_arena, d_B, ldb, d_X, ldx, nrhs, half, which, st);
+}
 extern "C" int cholamd_solve_nrhs(cholamd_device *d, const double *d_arena, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int nrhs, void *stream)
-{
-  { int rc = nrhs_check(d, d_arena, d_B, ldb, d_X, ldx, nrhs, "cholamd_solve_nrhs"); if (rc) return rc > 0 ? 0 : rc; }
-  HIPCHK(hipSetDevice(d->dev));
-  if (det_block(d)) return solve_det_nrhs_t(d, d_arena, d_B, ldb, d_X, ldx, nrhs, CHOL_BOTH_SWEEPS, (hipStream_t)stream);
-  if (d->solve_reference_shape || d->solve_deterministic) { // the deterministic kernels of either option, column by column
-    for (int j = 0; j < nrhs; j++) { int rc = cholamd_solve(d, d_arena, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, stream); if (rc) return rc; }
-    return 0;
-  }
-  return solve_nrhs_t(d, d_arena, d_B, ldb, d_X, ldx, nrhs, (hipStream_t)stream);
-}
+{ return solve_nrhs_api(d, d_arena, d_B, ldb, d_X, ldx, nrhs, false, 0, (hipStream_t)stream, "cholamd_solve_nrhs"); }
 extern "C" int cholamd_solve_nrhs_f32(cholamd_device *d, const float *d_arena32, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int nrhs, void *stream)
-{
-  { int rc = nrhs_check(d, d_arena32, d_B, ldb, d_X, ldx, nrhs, "cholamd_solve_nrhs_f32"); if (rc) return rc > 0 ? 0 : rc; }
-  HIPCHK(hipSetDevice(d->dev));
-  if (det_block(d)) return solve_det_nrhs_t(d, d_arena32, d_B, ldb, d_X, ldx, nrhs, CHOL_BOTH_SWEEPS, (hipStream_t)stream);
-  if (d->solve_reference_shape || d->solve_deterministic) {
-    for (int j = 0; j < nrhs; j++) { int rc = cholamd_solve_f32(d, d_arena32, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, stream); if (rc) return rc; }
-    return 0;
-  }
-  return solve_nrhs_t(d, d_arena32, d_B, ldb, d_X, ldx, nrhs, (hipStream_t)stream);
-}
-// ---------------------------------------------------------------------------------------------
-// One triangular half of the solve, and the factor's diagonal (include/cholamd.h at cholamd_solve_half): M = P^T L P, so M M^T = A in original dof order.
-// ---------------------------------------------------------------------------------------------
-static int half_which_ok(int which, const char *what)
-{
-  if (which == CHOLAMD_HALF_FORWARD || which == CHOLAMD_HALF_BACKWARD) return 0;
-  chol_set_error("%s: which = %d is neither CHOLAMD_HALF_FORWARD (0) nor CHOLAMD_HALF_BACKWARD (1)", what, which);
-  return CHOLAMD_ERR_ARG;
-}
-// the deterministic per-call kernels of cholamd_solve under option solve_reference_shape, one sweep of them (fp64 factor)
-static int solve_half_reference(cholamd_device *d, const double *d_arena, const double *d_b, double *d_x, int which, hipStream_t st)
-{
-  { int rc = build_solve(d); if (rc) return rc; }
-  const int L = d->plan->levels, n = d->plan->n;
-  double *y = d->ytmp;
-  HIPCHK((hipError_t)chol_launch_permute(d_b, d->perm, y, n, 0, st));
-  if (which == CHOLAMD_HALF_FORWARD)
-    for (int lvl = L - 1; lvl >= 0; lvl--) {
-      const solve_dev &s = d->sv[lvl];
-      HIPCHK((hipError_t)chol_launch_trsv_fwd(d_arena, s.trsv, s.n_trsv, y, st));
-      HIPCHK((hipError_t)chol_launch_gemv_fwd(d_arena, s.fw, s.grp_start, s.grp_rows, s.n_grp, y, st));
-    }
-  else
-    for (int lvl = 0; lvl < L; lvl++) {
-      const solve_dev &s = d->sv[lvl];
-      HIPCHK((hipError_t)chol_launch_bwd(d_arena, s.trsv, s.bw, s.bw_start, s.n_trsv, y, st));
-    }
-  HIPCHK((hipError_t)chol_launch_permute(y, d->perm, d_x, n, 1, st));
-  return 0;
-}
-static int half_check(cholamd_device *d, const void *arena, const double *b, const double *x, int which, const char *what)
-{
-  if (!d) { chol_set_error("%s: NULL device", what); return CHOLAMD_ERR_ARG; }
-  { int rc = half_which_ok(which, what); if (rc) return rc; }
-  if (!arena || !b || !x) { chol_set_error("%s: NULL %s", what, !arena ? "arena" : !b ? "b" : "x"); return CHOLAMD_ERR_ARG; }
-  return 0;
-}
-extern "C" int cholamd_solve_half(cholamd_device *d, const double *d_arena, const double *d_b, double *d_x, int which, void *stream)
-{
-  { int rc = half_check(d, d_arena, d_b, d_x, which, "cholamd_solve_half"); if (rc) return rc; }
-  HIPCHK(hipSetDevice(d->dev));
-  if (d->solve_reference_shape) return solve_half_reference(d, d_arena, d_b, d_x, which, (hipStream_t)stream);
-  return solve_half_streamed(d, d_arena, d_b, d_x, which, (hipStream_t)stream);
-}
-extern "C" int cholamd_solve_half_f32(cholamd_device *d, const float *d_arena32, const double *d_b, double *d_x, int which, void *stream)
-{
-  { int rc = half_check(d, d_arena32, d_b, d_x, which, "cholamd_solve_half_f32"); if (rc) return rc; }
-  HIPCHK(hipSetDevice(d->dev));
-  return solve_half_streamed(d, d_arena32, d_b, d_x, which, (hipStream_t)stream); // (as cholamd_solve_f32: the per-call kernels exist for the fp64 factor only)
-}
+{ return solve_nrhs_api(d, d_arena32, d_B, ldb, d_X, ldx, nrhs, false, 0, (hipStream_t)stream, "cholamd_solve_nrhs_f32"); }
 extern "C" int cholamd_solve_half_nrhs(cholamd_device *d, const double *d_arena, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int nrhs, int which, void *stream)
-{
-  if (d) { int rc = half_which_ok(which, "cholamd_solve_half_nrhs"); if (rc) return rc; }
-  { int rc = nrhs_check(d, d_arena, d_B, ldb, d_X, ldx, nrhs, "cholamd_solve_half_nrhs"); if (rc) return rc > 0 ? 0 : rc; }
-  HIPCHK(hipSetDevice(d->dev));
-  if (d->solve_reference_shape) {
-    for (int j = 0; j < nrhs; j++) { int rc = solve_half_reference(d, d_arena, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, which, (hipStream_t)stream); if (rc) return rc; }
-    return 0;
-  }
-  if (det_block(d)) return solve_det_nrhs_t(d, d_arena, d_B, ldb, d_X, ldx, nrhs, which, (hipStream_t)stream);
-  if (d->solve_deterministic) { // without option solve_deterministic_block: column by column, every column the single deterministic solve
-    for (int j = 0; j < nrhs; j++) { int rc = solve_det_t(d, d_arena, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, which, (hipStream_t)stream); if (rc) return rc; }
-    return 0;
-  }
-  return solve_nrhs_t(d, d_arena, d_B, ldb, d_X, ldx, nrhs, (hipStream_t)stream, which);
-}
+{ return solve_nrhs_api(d, d_arena, d_B, ldb, d_X, ldx, nrhs, true, which, (hipStream_t)stream, "cholamd_solve_half_nrhs"); }
 extern "C" int cholamd_solve_half_nrhs_f32(cholamd_device *d, const float *d_arena32, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int nrhs, int which, void *stream)
-{
-  if (d) { int rc = half_which_ok(which, "cholamd_solve_half_nrhs_f32"); if (rc) return rc; }
-  { int rc = nrhs_check(d, d_arena32, d_B, ldb, d_X, ldx, nrhs, "cholamd_solve_half_nrhs_f32"); if (rc) return rc > 0 ? 0 : rc; }
-  HIPCHK(hipSetDevice(d->dev));
-  if (det_block(d)) return solve_det_nrhs_t(d, d_arena32, d_B, ldb, d_X, ldx, nrhs, which, (hipStream_t)stream);
-  if (d->solve_deterministic) {
-    for (int j = 0; j < nrhs; j++) { int rc = solve_det_t(d, d_arena32, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, which, (hipStream_t)stream); if (rc) return rc; }
-    return 0;
-  }
-  return solve_nrhs_t(d, d_arena32, d_B, ldb, d_X, ldx, nrhs, (hipStream_t)stream, which);
-}
+{ return solve_nrhs_api(d, d_arena32, d_B, ldb, d_X, ldx, nrhs, true, which, (hipStream_t)stream, "cholamd_solve_half_nrhs_f32"); }
+// ---------------------------------------------------------------------------------------------
+// The factor's diagonal and determinant (include/cholamd.h at cholamd_factor_diag)
+// ---------------------------------------------------------------------------------------------
 template <class TL> static int factor_diag_t(cholamd_device *d, const TL *d_arena, double *d_diag, hipStream_t st, const char *what)
 {
   if (!d) { chol_set_error("%s: NULL device", what); return CHOLAMD_ERR_ARG; }
@@ -1690,81 +1622,60 @@ extern "C" int cholamd_schur(cholamd_device *d, const double *d_arena, int k, do
   HIPCHK((hipError_t)chol_launch_schur_gather(d_arena, d->sc[k].desc, d->sc[k].n, d_S, lds, (hipStream_t)stream));
   return 0;
 }
-// the 16x16 and span inverses of the levels under the cut, from this arena (the levels above it hold S, not a factor)
-template <class TL> static int schur_inverses(cholamd_device *d, const TL *d_arena, int k, hipStream_t st)
-{
-  for (int lvl = k; lvl < d->plan->levels; lvl++) {
-    const solve_dev &s = d->sv[lvl];
-    HIPCHK((hipError_t)chol_launch_solve_dinv(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, st));
-    if (s.w256_off >= 0 && d->w256) HIPCHK((hipError_t)chol_launch_solve_inv256(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, d->w256 + s.w256_off, st));
-  }
-  return 0;
-}
 // ---- option schur_deterministic: the step lists cut at k (chol_build_schur_det), per (device object, k), built at the first such call and kept
 static int build_schur_det(cholamd_device *d, int k)
 {
   if (d->scd.empty()) d->scd.resize(d->plan->levels);
-  schur_det_dev &q = d->scd[k];
-  if (q.ready) return 0;
+  if (d->scd[k].ready) return 0;
   chol_sdet_lists w;
   int rc = chol_build_schur_det(d->plan, k, &w);
   if (rc) return rc;
-  for (int c = 0; c < 2 && !rc; c++) { // (an upload replaces what a call that failed half-way left)
-    rc = q.item[c].upload(w.item[c], (size_t)w.n_item[c]);
-    if (!rc) rc = q.src[c].upload(w.src[c], (size_t)w.n_src[c]);
-    q.step[c].assign(w.step[c], w.step[c] + w.n_step[c]);
-  }
+  rc = upload_sdet(d->scd[k], w);
   chol_sdet_lists_free(&w);
-  if (rc) return rc;
-  q.ready = true;
-  return 0;
+  return rc;
 }
-// the 16x16 inverses of the levels under the cut alone: the deterministic sweeps use no span inverses
-template <class TL> static int schur_dinv(cholamd_device *d, const TL *d_arena, int k, hipStream_t st)
+// Condense, expand and their block forms by the one option they read, through the three helpers below:
+//   schur_deterministic -> the step lists cut at k (sweep_steps), the 16x16 inverses of the levels under the cut alone; every chunk of a block takes them
+//   otherwise           -> the atomic kernels over the levels k .. levels - 1 (sweep_levels), the span inverses too; a chunk of a block under
+//                          half_nrhs_min_block goes column by column through the single-vector body
+// The levels above the cut hold S, not a factor: no inverse is formed there.  Every launch is counted in schur_launches.
+static int schur_build(cholamd_device *d, int k)
 {
-  for (int lvl = k; lvl < d->plan->levels; lvl++) {
-    const solve_dev &s = d->sv[lvl];
-    HIPCHK((hipError_t)chol_launch_solve_dinv(d_arena, s.trsv, s.n_trsv, s.max_n, d->ws_solve, st));
-  }
-  return 0;
+  int rc = build_solve(d);
+  if (!rc && d->schur_deterministic) rc = build_schur_det(d, k);
+  return rc;
 }
-// one sweep of the cut lists on the permuted vector y, as solve_det_t walks the whole-tree lists; the kept lead step (level -1) is a gather alone
-template <class TL> static int schur_det_sweep(cholamd_device *d, const TL *d_arena, int k, int q, double *y, hipStream_t st)
+template <class TL> static int schur_inverses(cholamd_device *d, const TL *d_arena, int k, hipStream_t st) { return form_inverses(d, d_arena, k, !d->schur_deterministic, st); }
+template <class TL> static int schur_sweep(cholamd_device *d, const TL *d_arena, int k, bool backward, sweep_rhs rhs, hipStream_t st)
 {
-  const schur_det_dev &c = d->scd[k];
-  const chol_mul_item *items = c.item[q];
-  for (const chol_sdet_step &t : c.step[q]) {
-    if (t.item_end > t.item_first) {
-      HIPCHK((hipError_t)chol_launch_solve_det_gather(d_arena, items + t.item_first, t.item_end - t.item_first, c.src[q], q, y, st));
-      d->schur_launches[1]++;
-    }
-    if (t.col0 >= 0) {
-      const solve_dev &s = d->sv[t.level];
-      HIPCHK((hipError_t)chol_launch_solve_span(d_arena, s.trsv, s.n_trsv, d->ws_solve, y, t.col0, q, st));
-      d->schur_launches[2]++;
-    }
-  }
-  return 0;
+  return d->schur_deterministic ? sweep_steps(d, d_arena, d->scd[k], backward ? CHOLAMD_HALF_BACKWARD : CHOLAMD_HALF_FORWARD, rhs, d->schur_launches, st)
+                                : sweep_levels(d, d_arena, rhs, backward, k, d->plan->levels - 1, &d->schur_launches[0], st);
 }
-// the same on the permuted row-major block Y of one chunk, as solve_det_nrhs_t
-template <class TL> static int schur_det_sweep_nrhs(cholamd_device *d, const TL *d_arena, int k, int q, double *Y, hipStream_t st)
+// the single-vector bodies behind the checks (t0, m: chol_schur_range): the forward sweep under the cut in w, whose tail is g in Schur order ...
+template <class TL> static int schur_condense_t(cholamd_device *d, const TL *d_arena, int k, int t0, int m, const double *d_b, double *d_w, double *d_g, hipStream_t st)
 {
-  const schur_det_dev &c = d->scd[k];
-  const chol_mul_item *items = c.item[q];
-  for (const chol_sdet_step &t : c.step[q]) {
-    if (t.item_end > t.item_first) {
-      HIPCHK((hipError_t)chol_launch_solve_det_gather_nrhs(d_arena, items + t.item_first, t.item_end - t.item_first, c.src[q], q, Y, st));
-      d->schur_launches[1]++;
-    }
-    if (t.col0 >= 0) {
-      const solve_dev &s = d->sv[t.level];
-      HIPCHK((hipError_t)chol_nrhs_launch_span(d_arena, s.trsv, s.n_trsv, d->ws_solve, Y, t.col0, q, st));
-      d->schur_launches[2]++;
-    }
-  }
+  { int rc = schur_build(d, k); if (rc) return rc; }
+  const int n = d->plan->n;
+  HIPCHK((hipError_t)chol_launch_permute(d_b, d->perm, d_w, n, 0, st));
+  if (!d->keep_inverses) { int rc = schur_inverses(d, d_arena, k, st); if (rc) return rc; } // (kept: the column-by-column chunks of the block form)
+  { int rc = schur_sweep(d, d_arena, k, false, { d_w, false }, st); if (rc) return rc; }
+  if (m > 0) HIPCHK(hipMemcpyAsync(d_g, d_w + t0, (size_t)m * sizeof(double), hipMemcpyDeviceToDevice, st));
   return 0;
 }
-template <class TL> static int schur_condense_t(cholamd_device *d, const TL *d_arena, int k, const double *d_b, double *d_w, double *d_g, hipStream_t st, const char *what)
+// ... and the backward sweep under the cut from (w under the cut, xt above it); w stays as it is: the sweep runs in the device object's work vector
+template <class TL> static int schur_expand_t(cholamd_device *d, const TL *d_arena, int k, int t0, int m, const double *d_w, const double *d_xt, double *d_x, hipStream_t st)
+{
+  { int rc = schur_build(d, k); if (rc) return rc; }
+  const int n = d->plan->n;
+  double *y = d->ytmp;
+  if (t0 > 0) HIPCHK(hipMemcpyAsync(y, d_w, (size_t)t0 * sizeof(double), hipMemcpyDeviceToDevice, st));
+  if (m > 0) HIPCHK(hipMemcpyAsync(y + t0, d_xt, (size_t)m * sizeof(double), hipMemcpyDeviceToDevice, st));
+  if (!d->keep_inverses) { int rc = schur_inverses(d, d_arena, k, st); if (rc) return rc; } // as at the start of every half solve: the arena of the call before may have been another
+  { int rc = schur_sweep(d, d_arena, k, true, { y, false }, st); if (rc) return rc; }
+  HIPCHK((hipError_t)chol_launch_permute(y, d->perm, d_x, n, 1, st));
+  return 0;
+}
+template <class TL> static int schur_condense_api(cholamd_device *d, const TL *d_arena, int k, const double *d_b, double *d_w, double *d_g, hipStream_t st, const char *what)
 {
   int t0 = 0;
   const int m = schur_args(d, k, what, &t0);
@@ -1777,25 +1688,9 @@ template <class TL> static int schur_condense_t(cholamd_device *d, const TL *d_a
     return CHOLAMD_ERR_ARG;
   }
   HIPCHK(hipSetDevice(d->dev));
-  { int rc = build_solve(d); if (rc) return rc; }
-  const int L = d->plan->levels, n = d->plan->n;
-  HIPCHK((hipError_t)chol_launch_permute(d_b, d->perm, d_w, n, 0, st));
-  if (d->schur_deterministic) {
-    { int rc = build_schur_det(d, k); if (!rc && !d->keep_inverses) rc = schur_dinv(d, d_arena, k, st); if (!rc) rc = schur_det_sweep(d, d_arena, k, CHOLAMD_HALF_FORWARD, d_w, st); if (rc) return rc; }
-    if (m > 0) HIPCHK(hipMemcpyAsync(d_g, d_w + t0, mb, hipMemcpyDeviceToDevice, st));
-    return 0;
-  }
-  if (!d->keep_inverses) { int rc = schur_inverses(d, d_arena, k, st); if (rc) return rc; } // (kept: the column-by-column chunks of the block form)
-  for (int lvl = L - 1; lvl >= k; lvl--) { // forward sweep under the cut: TRSV per separator, then its panel into the ancestors (the kept ones included)
-    const solve_dev &s = d->sv[lvl];
-    d->schur_launches[0] += 2;
-    HIPCHK((hipError_t)lsolve_trsv(d, d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, d_w, 0, s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr, st));
-    HIPCHK((hipError_t)chol_launch_solve_offdiag(d_arena, s.bw, s.ifw, s.n_ifw, d_w, 0, st));
-  }
-  if (m > 0) HIPCHK(hipMemcpyAsync(d_g, d_w + t0, mb, hipMemcpyDeviceToDevice, st)); // the tail of the permuted vector is g, in Schur order
-  return 0;
+  return schur_condense_t(d, d_arena, k, t0, m, d_b, d_w, d_g, st);
 }
-template <class TL> static int schur_expand_t(cholamd_device *d, const TL *d_arena, int k, const double *d_w, const double *d_xt, double *d_x, hipStream_t st, const char *what)
+template <class TL> static int schur_expand_api(cholamd_device *d, const TL *d_arena, int k, const double *d_w, const double *d_xt, double *d_x, hipStream_t st, const char *what)
 {
   int t0 = 0;
   const int m = schur_args(d, k, what, &t0);
@@ -1807,34 +1702,16 @@ template <class TL> static int schur_expand_t(cholamd_device *d, const TL *d_are
     return CHOLAMD_ERR_ARG;
   }
   HIPCHK(hipSetDevice(d->dev));
-  { int rc = build_solve(d); if (rc) return rc; }
-  const int L = d->plan->levels, n = d->plan->n;
-  double *y = d->ytmp; // w stays as it is: the sweep runs in the device object's work vector
-  if (t0 > 0) HIPCHK(hipMemcpyAsync(y, d_w, (size_t)t0 * sizeof(double), hipMemcpyDeviceToDevice, st));
-  if (m > 0) HIPCHK(hipMemcpyAsync(y + t0, d_xt, mb, hipMemcpyDeviceToDevice, st));
-  if (d->schur_deterministic) {
-    { int rc = build_schur_det(d, k); if (!rc && !d->keep_inverses) rc = schur_dinv(d, d_arena, k, st); if (!rc) rc = schur_det_sweep(d, d_arena, k, CHOLAMD_HALF_BACKWARD, y, st); if (rc) return rc; }
-    HIPCHK((hipError_t)chol_launch_permute(y, d->perm, d_x, n, 1, st));
-    return 0;
-  }
-  if (!d->keep_inverses) { int rc = schur_inverses(d, d_arena, k, st); if (rc) return rc; } // as at the start of every half solve: the arena of the call before may have been another
-  for (int lvl = k; lvl < L; lvl++) { // backward sweep under the cut: gather from the ancestors, then TRSV^T
-    const solve_dev &s = d->sv[lvl];
-    d->schur_launches[0] += 2;
-    HIPCHK((hipError_t)chol_launch_solve_offdiag(d_arena, s.bw, s.ibw, s.n_ibw, y, 1, st));
-    HIPCHK((hipError_t)lsolve_trsv(d, d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, y, 1, s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr, st));
-  }
-  HIPCHK((hipError_t)chol_launch_permute(y, d->perm, d_x, n, 1, st));
-  return 0;
+  return schur_expand_t(d, d_arena, k, t0, m, d_w, d_xt, d_x, st);
 }
 extern "C" int cholamd_schur_condense(cholamd_device *d, const double *d_arena, int k, const double *d_b, double *d_w, double *d_g, void *stream)
-{ return schur_condense_t(d, d_arena, k, d_b, d_w, d_g, (hipStream_t)stream, "cholamd_schur_condense"); }
+{ return schur_condense_api(d, d_arena, k, d_b, d_w, d_g, (hipStream_t)stream, "cholamd_schur_condense"); }
 extern "C" int cholamd_schur_condense_f32(cholamd_device *d, const float *d_arena32, int k, const double *d_b, double *d_w, double *d_g, void *stream)
-{ return schur_condense_t(d, d_arena32, k, d_b, d_w, d_g, (hipStream_t)stream, "cholamd_schur_condense_f32"); }
+{ return schur_condense_api(d, d_arena32, k, d_b, d_w, d_g, (hipStream_t)stream, "cholamd_schur_condense_f32"); }
 extern "C" int cholamd_schur_expand(cholamd_device *d, const double *d_arena, int k, const double *d_w, const double *d_xt, double *d_x, void *stream)
-{ return schur_expand_t(d, d_arena, k, d_w, d_xt, d_x, (hipStream_t)stream, "cholamd_schur_expand"); }
+{ return schur_expand_api(d, d_arena, k, d_w, d_xt, d_x, (hipStream_t)stream, "cholamd_schur_expand"); }
 extern "C" int cholamd_schur_expand_f32(cholamd_device *d, const float *d_arena32, int k, const double *d_w, const double *d_xt, double *d_x, void *stream)
-{ return schur_expand_t(d, d_arena32, k, d_w, d_xt, d_x, (hipStream_t)stream, "cholamd_schur_expand_f32"); }
+{ return schur_expand_api(d, d_arena32, k, d_w, d_xt, d_x, (hipStream_t)stream, "cholamd_schur_expand_f32"); }
 
 // ---- block forms (include/cholamd.h at cholamd_schur_condense_nrhs): chunks of CHOL_NRHS_W columns through the permuted row-major block ynrhs; the pack /
 // unpack kernels of chol_schur.hip stand where the block solve has its permutes.  a, b, c: the call's three blocks with their rows and names
@@ -1852,8 +1729,18 @@ static int schur_nrhs_args(const cholamd_device *d, const void *arena, int k, co
   for (const schur_blk &b : x) if (!b.p) { chol_set_error("%s: NULL %s", what, b.name); return CHOLAMD_ERR_ARG; }
   return m;
 }
-template <class TL> static int schur_condense_nrhs_t(cholamd_device *d, const TL *d_arena, int k, const double *d_B, int64_t ldb, double *d_W, int64_t ldw, double *d_G, int64_t ldg,
-                                                     int nrhs, hipStream_t st, const char *what)
+// what both block forms do between their checks and their chunks: the device, the lists, the chunk's block, and the inverses once per call -- whatever
+// keep_inverses says; it is then set for the column-by-column chunks (keep_restore in the callers)
+template <class TL> static int schur_nrhs_begin(cholamd_device *d, const TL *d_arena, int k, hipStream_t st)
+{
+  HIPCHK(hipSetDevice(d->dev));
+  int rc = schur_build(d, k);
+  if (!rc) rc = d->ynrhs.ensure((size_t)d->plan->n * CHOL_NRHS_W);
+  if (!rc) rc = schur_inverses(d, d_arena, k, st);
+  return rc;
+}
+template <class TL> static int schur_condense_nrhs_api(cholamd_device *d, const TL *d_arena, int k, const double *d_B, int64_t ldb, double *d_W, int64_t ldw, double *d_G, int64_t ldg,
+                                                       int nrhs, hipStream_t st, const char *what)
 {
   if (!d) { chol_set_error("%s: NULL device", what); return CHOLAMD_ERR_ARG; }
   const int n = d->plan->n;
@@ -1870,39 +1757,28 @@ template <class TL> static int schur_condense_nrhs_t(cholamd_device *d, const TL
     for (int j = i + 1; j < 3 && !bad; j++) bad = x[j].rows > 0 && ranges_overlap(x[i].p, blk_bytes(x[i], nrhs), x[j].p, blk_bytes(x[j], nrhs));
     if (bad) { chol_set_error("%s: B, W, G and the arena must not overlap each other", what); return CHOLAMD_ERR_ARG; }
   }
-  HIPCHK(hipSetDevice(d->dev));
-  { int rc = build_solve(d); if (!rc && d->schur_deterministic) rc = build_schur_det(d, k); if (!rc) rc = d->ynrhs.ensure((size_t)n * CHOL_NRHS_W); if (rc) return rc; }
-  const int L = d->plan->levels;
-  { int rc = d->schur_deterministic ? schur_dinv(d, d_arena, k, st) : schur_inverses(d, d_arena, k, st); if (rc) return rc; } // once per call
+  { int rc = schur_nrhs_begin(d, d_arena, k, st); if (rc) return rc; }
   keep_restore kr(d);
-  d->keep_inverses = true; // (the column-by-column chunks reuse them)
+  d->keep_inverses = true;
   double *Y = d->ynrhs;
   for (int c0 = 0; c0 < nrhs; c0 += CHOL_NRHS_W) {
     const int cols = std::min(CHOL_NRHS_W, nrhs - c0);
     if (!d->schur_deterministic && cols < half_nrhs_min_block<TL>()) {
       for (int j = c0; j < c0 + cols; j++) {
-        int rc = schur_condense_t(d, d_arena, k, d_B + (int64_t)j * ldb, d_W + (int64_t)j * ldw, d_G + (int64_t)j * ldg, st, what);
+        int rc = schur_condense_t(d, d_arena, k, t0, m, d_B + (int64_t)j * ldb, d_W + (int64_t)j * ldw, d_G + (int64_t)j * ldg, st);
         if (rc) return rc;
       }
       continue;
     }
     HIPCHK((hipError_t)chol_nrhs_launch_permute(d_B, ldb, d->perm, Y, nullptr, 0, n, c0, cols, 0, st));
-    if (d->schur_deterministic) { int rc = schur_det_sweep_nrhs(d, d_arena, k, CHOLAMD_HALF_FORWARD, Y, st); if (rc) return rc; }
-    else
-      for (int lvl = L - 1; lvl >= k; lvl--) { // forward under the cut: the separators' triangles, then their panels into the ancestors (the kept ones included)
-        const solve_dev &s = d->sv[lvl];
-        const double *W256 = s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr;
-        HIPCHK((hipError_t)chol_nrhs_launch_trsv(d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, W256, Y, 0, st));
-        HIPCHK((hipError_t)chol_nrhs_launch_offdiag(d_arena, s.bw, s.ifw, s.n_ifw, Y, 0, st));
-        d->schur_launches[0] += 2;
-      }
+    { int rc = schur_sweep(d, d_arena, k, false, { Y, true }, st); if (rc) return rc; }
     HIPCHK((hipError_t)chol_launch_schur_unpack(Y, n, t0, c0, cols, d_W, ldw, d_G, ldg, st));
     d->schur_launches[3]++;
   }
   return 0;
 }
-template <class TL> static int schur_expand_nrhs_t(cholamd_device *d, const TL *d_arena, int k, const double *d_W, int64_t ldw, const double *d_XT, int64_t ldxt, double *d_X, int64_t ldx,
-                                                   int nrhs, hipStream_t st, const char *what)
+template <class TL> static int schur_expand_nrhs_api(cholamd_device *d, const TL *d_arena, int k, const double *d_W, int64_t ldw, const double *d_XT, int64_t ldxt, double *d_X, int64_t ldx,
+                                                     int nrhs, hipStream_t st, const char *what)
 {
   if (!d) { chol_set_error("%s: NULL device", what); return CHOLAMD_ERR_ARG; }
   const int n = d->plan->n;
@@ -1917,10 +1793,7 @@ template <class TL> static int schur_expand_nrhs_t(cholamd_device *d, const TL *
     chol_set_error("%s: X must not overlap W, XT or the arena", what);
     return CHOLAMD_ERR_ARG;
   }
-  HIPCHK(hipSetDevice(d->dev));
-  { int rc = build_solve(d); if (!rc && d->schur_deterministic) rc = build_schur_det(d, k); if (!rc) rc = d->ynrhs.ensure((size_t)n * CHOL_NRHS_W); if (rc) return rc; }
-  const int L = d->plan->levels;
-  { int rc = d->schur_deterministic ? schur_dinv(d, d_arena, k, st) : schur_inverses(d, d_arena, k, st); if (rc) return rc; }
+  { int rc = schur_nrhs_begin(d, d_arena, k, st); if (rc) return rc; }
   keep_restore kr(d);
   d->keep_inverses = true;
   double *Y = d->ynrhs;
@@ -1928,34 +1801,26 @@ template <class TL> static int schur_expand_nrhs_t(cholamd_device *d, const TL *
     const int cols = std::min(CHOL_NRHS_W, nrhs - c0);
     if (!d->schur_deterministic && cols < half_nrhs_min_block<TL>()) {
       for (int j = c0; j < c0 + cols; j++) {
-        int rc = schur_expand_t(d, d_arena, k, d_W + (int64_t)j * ldw, d_XT + (int64_t)j * ldxt, d_X + (int64_t)j * ldx, st, what);
+        int rc = schur_expand_t(d, d_arena, k, t0, m, d_W + (int64_t)j * ldw, d_XT + (int64_t)j * ldxt, d_X + (int64_t)j * ldx, st);
         if (rc) return rc;
       }
       continue;
     }
     HIPCHK((hipError_t)chol_launch_schur_pack(d_W, ldw, d_XT, ldxt, n, t0, c0, cols, Y, st));
     d->schur_launches[3]++;
-    if (d->schur_deterministic) { int rc = schur_det_sweep_nrhs(d, d_arena, k, CHOLAMD_HALF_BACKWARD, Y, st); if (rc) return rc; }
-    else
-      for (int lvl = k; lvl < L; lvl++) { // backward under the cut: gather from the ancestors, then the transposed triangles
-        const solve_dev &s = d->sv[lvl];
-        const double *W256 = s.w256_off >= 0 && d->w256 ? d->w256 + s.w256_off : nullptr;
-        HIPCHK((hipError_t)chol_nrhs_launch_offdiag(d_arena, s.bw, s.ibw, s.n_ibw, Y, 1, st));
-        HIPCHK((hipError_t)chol_nrhs_launch_trsv(d_arena, s.trsv, s.n_trsv, s.max_n, s.max_under, d->ws_solve, W256, Y, 1, st));
-        d->schur_launches[0] += 2;
-      }
+    { int rc = schur_sweep(d, d_arena, k, true, { Y, true }, st); if (rc) return rc; }
     HIPCHK((hipError_t)chol_nrhs_launch_permute(nullptr, 0, d->perm, Y, d_X, ldx, n, c0, cols, 1, st));
   }
   return 0;
 }
 extern "C" int cholamd_schur_condense_nrhs(cholamd_device *d, const double *d_arena, int k, const double *d_B, int64_t ldb, double *d_W, int64_t ldw, double *d_G, int64_t ldg, int nrhs, void *stream)
-{ return schur_condense_nrhs_t(d, d_arena, k, d_B, ldb, d_W, ldw, d_G, ldg, nrhs, (hipStream_t)stream, "cholamd_schur_condense_nrhs"); }
+{ return schur_condense_nrhs_api(d, d_arena, k, d_B, ldb, d_W, ldw, d_G, ldg, nrhs, (hipStream_t)stream, "cholamd_schur_condense_nrhs"); }
 extern "C" int cholamd_schur_condense_nrhs_f32(cholamd_device *d, const float *d_arena32, int k, const double *d_B, int64_t ldb, double *d_W, int64_t ldw, double *d_G, int64_t ldg, int nrhs, void *stream)
-{ return schur_condense_nrhs_t(d, d_arena32, k, d_B, ldb, d_W, ldw, d_G, ldg, nrhs, (hipStream_t)stream, "cholamd_schur_condense_nrhs_f32"); }
+{ return schur_condense_nrhs_api(d, d_arena32, k, d_B, ldb, d_W, ldw, d_G, ldg, nrhs, (hipStream_t)stream, "cholamd_schur_condense_nrhs_f32"); }
 extern "C" int cholamd_schur_expand_nrhs(cholamd_device *d, const double *d_arena, int k, const double *d_W, int64_t ldw, const double *d_XT, int64_t ldxt, double *d_X, int64_t ldx, int nrhs, void *stream)
-{ return schur_expand_nrhs_t(d, d_arena, k, d_W, ldw, d_XT, ldxt, d_X, ldx, nrhs, (hipStream_t)stream, "cholamd_schur_expand_nrhs"); }
+{ return schur_expand_nrhs_api(d, d_arena, k, d_W, ldw, d_XT, ldxt, d_X, ldx, nrhs, (hipStream_t)stream, "cholamd_schur_expand_nrhs"); }
 extern "C" int cholamd_schur_expand_nrhs_f32(cholamd_device *d, const float *d_arena32, int k, const double *d_W, int64_t ldw, const double *d_XT, int64_t ldxt, double *d_X, int64_t ldx, int nrhs, void *stream)
-{ return schur_expand_nrhs_t(d, d_arena32, k, d_W, ldw, d_XT, ldxt, d_X, ldx, nrhs, (hipStream_t)stream, "cholamd_schur_expand_nrhs_f32"); }
+{ return schur_expand_nrhs_api(d, d_arena32, k, d_W, ldw, d_XT, ldxt, d_X, ldx, nrhs, (hipStream_t)stream, "cholamd_schur_expand_nrhs_f32"); }
 extern "C" int cholamd_device_schur_launches(const cholamd_device *d, int64_t out[4])
 {
   if (!d || !out) { chol_set_error("cholamd_device_schur_launches: NULL %s", !d ? "device" : "out"); return CHOLAMD_ERR_ARG; }
@@ -1978,15 +1843,9 @@ static int residual_nrhs(cholamd_device *d, const double *d_B, int64_t ldb, cons
   }
   return 0;
 }
-// M^-1 B for `cols` columns with M = L32 L32^T: the block solve, the deterministic block solve (option solve_deterministic_block), or column by column under
-// option solve_reference_shape or solve_deterministic
+// M^-1 B for `cols` columns with M = L32 L32^T: what cholamd_solve_nrhs_f32 runs under the options in force
 static int refine_solve(cholamd_device *d, const float *d_arena32, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int cols, hipStream_t st)
-{
-  if (det_block(d)) return solve_det_nrhs_t(d, d_arena32, d_B, ldb, d_X, ldx, cols, CHOL_BOTH_SWEEPS, st);
-  if (!d->solve_reference_shape && !d->solve_deterministic) return solve_nrhs_t(d, d_arena32, d_B, ldb, d_X, ldx, cols, st);
-  for (int j = 0; j < cols; j++) { int rc = solve_streamed(d, d_arena32, d_B + (int64_t)j * ldb, d_X + (int64_t)j * ldx, st); if (rc) return rc; }
-  return 0;
-}
+{ return solve_nrhs_any(d, d_arena32, d_B, ldb, d_X, ldx, cols, false, CHOL_BOTH_SWEEPS, st); }
 extern "C" int cholamd_solve_refine_nrhs(cholamd_device *d, const float *d_arena32, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int nrhs, int max_iter,
                                          double tol, int *iters_out, double *relres_out, void *stream)
 {
@@ -3229,7 +3088,7 @@ static int gather_factor_bytes(cholamd_device *const *devs, void *const *arenas,
 template <class TL> static int solve_sharded_t(cholamd_device *d, const TL *d_arena, const double *d_b, double *d_x, cholamd_comm *c, hipStream_t st)
 {
   HIPCHK(hipSetDevice(d->dev));
-  if (d->world == 1) return solve_streamed(d, d_arena, d_b, d_x, st);
+  if (d->world == 1) return solve_t(d, d_arena, d_b, d_x, CHOL_BOTH_SWEEPS, st);
   int rc = build_solve(d, d->rank, d->world);
   if (rc) return rc;
   if (comm_matches(d, c)) return CHOLAMD_ERR_ARG;
@@ -3310,7 +3169,7 @@ template <class TL> static int solve_multi_t(cholamd_device *const *devs, const 
                                              int n, void *const *streams)
 {
   if (n < 1) { chol_set_error("no devices"); return CHOLAMD_ERR_ARG; }
-  if (n == 1) { HIPCHK(hipSetDevice(devs[0]->dev)); return solve_streamed(devs[0], arenas[0], bs[0], xs[0], stream_of(streams, 0)); }
+  if (n == 1) { HIPCHK(hipSetDevice(devs[0]->dev)); return solve_t(devs[0], arenas[0], bs[0], xs[0], CHOL_BOTH_SWEEPS, stream_of(streams, 0)); }
   local_group *G = comms[0] ? comms[0]->local : nullptr;
   for (int g = 0; g < n; g++) {
     if (devs[g]->world != n || devs[g]->rank != g) { chol_set_error("device %d is not partitioned as rank %d of %d", g, g, n); return CHOLAMD_ERR_ARG; }
