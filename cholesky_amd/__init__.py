@@ -9,6 +9,7 @@ torch.distributed (RCCL).  Nothing here computes on the CPU.
 from ._lib import CholamdError, Filled, Op, Region, load  # noqa: F401
 from .plan import Plan, Problem  # noqa: F401
 from .device import HALF_BACKWARD, HALF_FORWARD, Comm, Device  # noqa: F401
+from .lowrank import LowRank  # noqa: F401
 from . import blas  # noqa: F401
 
-__all__ = ["Plan", "Problem", "Device", "Comm", "blas", "CholamdError", "Filled", "Op", "Region", "load", "HALF_FORWARD", "HALF_BACKWARD"]
+__all__ = ["Plan", "Problem", "Device", "Comm", "LowRank", "blas", "CholamdError", "Filled", "Op", "Region", "load", "HALF_FORWARD", "HALF_BACKWARD"]

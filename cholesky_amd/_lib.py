@@ -245,6 +245,21 @@ def load():
     L.cholamd_dsyrk_dev.argtypes = [ci, ci, vp, ci, vp, ci, vp]
     L.cholamd_dtrsv_dev.argtypes = [ci, ci, vp, ci, vp, vp]
     L.cholamd_dgemv_dev.argtypes = [ci, ci, ci, vp, ci, vp, vp, vp]
+    L.cholamd_lowrank_create.argtypes = [vp, ci, C.POINTER(vp)]
+    L.cholamd_lowrank_destroy.argtypes = [vp]
+    L.cholamd_lowrank_destroy.restype = None
+    L.cholamd_lowrank_set.argtypes = [vp, vp, vp, i64, ci, ci, vp]
+    L.cholamd_lowrank_state.argtypes = [vp, vp]
+    L.cholamd_lowrank_solve.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.cholamd_lowrank_solve_nrhs.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, ci, vp]
+    L.cholamd_lowrank_project.argtypes = [vp, vp, i64, vp, vp, vp, vp]
+    L.cholamd_lowrank_diag.argtypes = [vp, vp, vp]
+    L.cholamd_lowrank_logdet.argtypes = [vp, C.POINTER(cd)]
+    L.cholamd_lowrank_factor.argtypes = [vp, vp, ci]
+    L.cholamd_lowrank_block.argtypes = [vp, C.POINTER(vp), C.POINTER(i64)]
+    L.cholamd_lowrank_slabs.argtypes = [i64, vp, i64]
+    L.cholamd_lowrank_tprod_host.argtypes = [i64, ci, ci, vp, i64, vp, i64, vp, i64]
+    L.cholamd_lowrank_rprod_host.argtypes = [i64, ci, ci, cd, cd, vp, i64, vp, i64, vp, i64]
     _lib = L
     return L
 

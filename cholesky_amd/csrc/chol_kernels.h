@@ -109,6 +109,15 @@ template <class TL> int chol_nrhs_launch_span(const TL *base, const chol_trsv_de
 template <class TL> int chol_launch_multiply_nrhs(const TL *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, const double *Zp, double *Y, const int *perm,
                                                   int64_t ldy, int c0, int cols, hipStream_t st);
 int chol_launch_multiply_resid(const int64_t *ptr, const int *col, const double *val, const double *z, const double *w, int n, double *part, int64_t *ipart, int64_t *res, hipStream_t st);
+/* low-rank corrections (chol_lowrank.hip; partition in chol_plan.h at CHOL_LR_SLAB): column-major blocks, k <= CHOL_LR_MAX, no atomics, the same bits every call.
+ * tprod: T (k x m) = P^T Q over n rows in two launches per 32 columns of Q (P == Q, ldp == ldq, m == k: the Gram matrix in two launches, lower tiles
+ * mirrored); ws: chol_lr_ws_doubles(n, k) doubles.  rprod: X (n x m) = alpha X + beta V T, V n x k, T k x m; X == V with m == k allowed; alpha == 0: X is
+ * not read.  rowsq: w[i] = sum_j W(i, j)^2.  small: what = 0: A = I + mode A (mode 0: unchanged), 1: A = I, 2: A -= B, on k x cols */
+int64_t chol_lr_ws_doubles(int64_t n, int kmax);
+int chol_launch_lr_tprod(int64_t n, int k, int m, const double *P, int64_t ldp, const double *Q, int64_t ldq, double *ws, double *T, int64_t ldt, hipStream_t st);
+int chol_launch_lr_rprod(int64_t n, int k, int m, double alpha, double beta, const double *V, int64_t ldv, const double *T, int64_t ldt, double *X, int64_t ldx, hipStream_t st);
+int chol_launch_lr_rowsq(int64_t n, int k, const double *W, int64_t ldw, double *w, hipStream_t st);
+int chol_launch_lr_small(int what, int k, int cols, int mode, double *A, int64_t lda, const double *B, int64_t ldb, hipStream_t st);
 /* diagnostic instance of the program launch (k_program<true>): 4 stamps per job, then CHOL_TRACE_X per job -- [0] follower: own tiles' wait over / update job: wave 0 saw the job's last staged wait hold,
  * [1] its items, [2 + i] round of item i begun; [48 + k] POTRF job: column k published / TRSM job (first strip): column tile k on its channel;
  * [72 + k] POTRF job: the factor wave starts column k / TRSM job: the POTRF's column k seen */

@@ -517,6 +517,33 @@ CHOL_HD int64_t chol_muln_elem(const chol_mul_src *q, int backward, int nv, int 
   return q->a_off + (backward ? (int64_t)kc + (int64_t)lc * q->ld : (int64_t)lc + (int64_t)kc * q->ld);
 }
 
+/* ---- low-rank corrections on the finished factor (cholamd_lowrank_*; chol_lowrank.hip, chol_lowrank_host.c): the partition of the three tall-skinny
+ * kernels, shared by the kernels and their host restatements.
+ *   T = P^T Q (n rows summed away): the rows are cut into SLABS of CHOL_LR_SLAB rows, slab s = rows [s CHOL_LR_SLAB, min(n, (s + 1) CHOL_LR_SLAB)) -- a
+ *     function of n alone, never of k, m or the grid.  One workgroup per slab walks it in blocks of CHOL_LR_STAGE rows (staged in LDS, four rows per MFMA
+ *     step) and keeps the slab's partial 16 x 16 tiles in registers: tile number `id` of a call belongs to wave id % CHOL_LR_WAVES, slot id / CHOL_LR_WAVES.
+ *     The tiles of the Gram form (P == Q) are the lower ones in row-major order of the triangle (chol_lr_gram_tile), those of the general form (m <= 32
+ *     columns per call) tile id = (id / mt, id % mt).  A second launch adds the partials of an element in slab order.
+ *   X = alpha X + beta V T: one workgroup per chunk of CHOL_LR_ROWS rows; wave w takes the 32-column chunks w, w + 4, ... of X.  A call of at most 32 columns
+ *     (the corrected solves) shares its one chunk instead: the k / 4 reduction steps are cut into CHOL_LR_RWAVES consecutive ranges
+ *     of ceil(steps / CHOL_LR_RWAVES), one per wave, and the waves' partial tiles are added in wave order.
+ *   w_i = sum_j W_ij^2: one thread per row, j ascending. */
+#define CHOL_LR_MAX 256      /* most columns of U (CHOLAMD_LOWRANK_MAX) */
+#define CHOL_LR_SLAB 1024    /* rows of a slab of the transposed product */
+#define CHOL_LR_STAGE 32     /* rows staged in LDS at a time (8 MFMA steps) */
+#define CHOL_LR_WAVES 16     /* waves of a slab's workgroup */
+#define CHOL_LR_SLOTS 9      /* tiles a wave can own: ceil(136 / 16), 136 = lower tiles of a 256 x 256 Gram matrix */
+#define CHOL_LR_ROWS 16      /* rows of a chunk of the row-owned product */
+#define CHOL_LR_RWAVES 4     /* waves of its workgroup */
+CHOL_HD int64_t chol_lr_slabs(int64_t n) { return (n + CHOL_LR_SLAB - 1) / CHOL_LR_SLAB; }
+CHOL_HD int chol_lr_gram_tiles(int kt) { return kt * (kt + 1) / 2; }
+CHOL_HD void chol_lr_gram_tile(int id, int *ti, int *tj)
+{ /* id = ti (ti + 1) / 2 + tj, tj <= ti */
+  int r = 0;
+  while ((r + 1) * (r + 2) / 2 <= id) r++;
+  *ti = r; *tj = id - r * (r + 1) / 2;
+}
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,10 @@
  *        writer's format: n lines, original dof order, %0.8g or %.17g under --full-precision; fp64 factor only),
  *        --schur K FILE (after the factorisation: the Schur complement of A on the K kept tree levels -- cholamd_schur_factor + cholamd_schur on a second,
  *        freshly filled arena -- as a Matrix-Market dense `array` file, %.17g, column by column, and the Schur dofs, 1-based, one per line, as FILE.dofs;
- *        single GPU, fp64 only).
+ *        single GPU, fp64 only),
+ *        --lowrank FILE K [--lowrank-mode update|downdate|constraint] (FILE: a Matrix-Market dense `array` n x K, the columns of U; after the factorisation
+ *        cholamd_lowrank_set on device 0; the solve of -b becomes the corrected solve of A + U U^T (update, the default), A - U U^T (downdate) or of A under
+ *        U^T x = 0 (constraint); with --logdet one more line "logdet C: %.17g" after the logdet line: log det(A +- U U^T) = logdet + logdet C; fp64 only).
  * Unknown flags (the reference passes -fflow/-ll:cpu/-fcuda/-ll:csize through to Legion) are ignored.
  *
  * Flow = main() of mmat.rg:1056-1496 with the numeric phase on the GPU.  Progress lines keep the
@@ -38,8 +41,8 @@ static double now_s(void)
 int main(int argc, char **argv)
 {
   const char *matrix_file = "", *separator_file = "", *clusters_file = "", *b_file = "", *solution_file = "", *factor_file = "",
-             *permuted_file = "", *debug_path = "", *invdiag_file = "", *schur_file = "";
-  int debug = 0, iterations = 1, gpu = 0, full = 0, gpus = 1, want_logdet = 0, want_check = 0, schur_k = 0, det_solve = 0;
+             *permuted_file = "", *debug_path = "", *invdiag_file = "", *schur_file = "", *lowrank_file = "", *lowrank_mode = "update";
+  int debug = 0, iterations = 1, gpu = 0, full = 0, gpus = 1, want_logdet = 0, want_check = 0, schur_k = 0, det_solve = 0, lowrank_k = 0;
   const char *precision = "fp64";
   for (int i = 0; i < argc; i++) {
     const char *next = i + 1 < argc ? argv[i + 1] : "";
@@ -62,6 +65,8 @@ int main(int argc, char **argv)
     else if (!strcmp(argv[i], "--deterministic-solve")) det_solve = 1; /* device option solve_deterministic for the solve of -b: the same bits in every run */
     else if (!strcmp(argv[i], "--invdiag")) invdiag_file = next;
     else if (!strcmp(argv[i], "--schur")) { schur_k = atoi(next); schur_file = i + 2 < argc ? argv[i + 2] : ""; if (!*schur_file) DIE("--schur K FILE"); }
+    else if (!strcmp(argv[i], "--lowrank")) { lowrank_file = next; lowrank_k = i + 2 < argc ? atoi(argv[i + 2]) : 0; if (!*lowrank_file || lowrank_k < 1) DIE("--lowrank FILE K"); }
+    else if (!strcmp(argv[i], "--lowrank-mode")) lowrank_mode = next;
   }
   printf("Iterations: %d\n", iterations);
   if (!*matrix_file || !*separator_file || !*clusters_file) DIE("usage: %s -i A.mtx -s ord.txt -c clust.txt [-b B.mtx -o x.txt] [-m L.mtx] [-p PAPt.mtx] [-d dir] [--iterations n]", argv[0]);
@@ -97,6 +102,10 @@ int main(int argc, char **argv)
   if (mixed && *invdiag_file) DIE("--invdiag needs the fp64 factor (--precision fp64)");
   if (*schur_file && (mixed || gpus > 1)) DIE("--schur is a single-GPU fp64 path");
   if (*schur_file && cholamd_plan_schur_size(plan, schur_k) < 0) DIE("--schur: %s", cholamd_last_error());
+  const int lr_mode = !strcmp(lowrank_mode, "update") ? CHOLAMD_LOWRANK_UPDATE : !strcmp(lowrank_mode, "downdate") ? CHOLAMD_LOWRANK_DOWNDATE : CHOLAMD_LOWRANK_CONSTRAINT;
+  if (*lowrank_file && mixed) DIE("--lowrank needs the fp64 factor (--precision fp64)");
+  if (*lowrank_file && lr_mode == CHOLAMD_LOWRANK_CONSTRAINT && strcmp(lowrank_mode, "constraint")) DIE("--lowrank-mode %s: update, downdate or constraint", lowrank_mode);
+  if (*lowrank_file && (lowrank_k > CHOLAMD_LOWRANK_MAX || (int64_t)n * lowrank_k > 2147483647)) DIE("--lowrank: K = %d (at most %d, and n K must fit an int)", lowrank_k, CHOLAMD_LOWRANK_MAX);
   if (gpus < 1 || gpus > 64 || (gpus & (gpus - 1))) DIE("--gpus must be a power of two");
   if (cholamd_device_count() < gpu + gpus) DIE("--gpus %d from device %d: only %d HIP devices are visible", gpus, gpu, cholamd_device_count());
   /* one device object + arena per GPU; devs[0] ends up with the complete factor */
@@ -142,10 +151,26 @@ int main(int argc, char **argv)
   fprintf(stderr, "[cholamd] %d GPU(s), symbolic %.3f ms, numeric factorisation %.3f ms, F_ref %.6g flop, %.3f GF/s, B_alg %ld bytes\n",
           gpus, 1e3 * t_sym, 1e3 * t_factor, flops, flops / t_factor * 1e-9, (long)cholamd_plan_alg_bytes(plan));
 
+  cholamd_lowrank *lr = NULL;
+  if (*lowrank_file) { /* the complete factor is on device 0 */
+    const int64_t nk = (int64_t)n * lowrank_k;
+    double *U = malloc((size_t)nk * sizeof(double)), *d_U = NULL;
+    if (!U) DIE("out of memory");
+    if (cholamd_read_vector(lowrank_file, (int)nk, U)) DIE("%s", cholamd_last_error());
+    if (cholamd_device_alloc(dev, nk, &d_U) || cholamd_device_upload(dev, d_U, U, nk, NULL)) DIE("%s", cholamd_last_error());
+    if (cholamd_lowrank_create(dev, lowrank_k, &lr) || cholamd_lowrank_set(lr, d_arena, d_U, n, lowrank_k, lr_mode, NULL)) DIE("lowrank: %s", cholamd_last_error());
+    cholamd_device_free(dev, d_U);
+    free(U);
+  }
   if (want_logdet) { /* the complete factor is on device 0 */
     double logdet = 0.0;
     if (mixed ? cholamd_factor_logdet_f32(dev, (const float *)d_arena, &logdet, NULL) : cholamd_factor_logdet(dev, d_arena, &logdet, NULL)) DIE("logdet: %s", cholamd_last_error());
     printf(mixed ? "logdet(fp32 factor): %.17g\n" : "logdet: %.17g\n", logdet);
+    if (lr) {
+      double logdet_c = 0.0;
+      if (cholamd_lowrank_logdet(lr, &logdet_c)) DIE("lowrank: %s", cholamd_last_error());
+      printf("logdet C: %.17g\n", logdet_c);
+    }
   }
   if (want_check) { /* the complete factor is on device 0; the probe is the right-hand side */
     double *z = malloc((size_t)n * sizeof(double)), *d_z = NULL, rel = 0.0;
@@ -215,7 +240,7 @@ int main(int argc, char **argv)
       if (cholamd_solve_refine(dev, (const float *)d_arena, d_b, d_x, 30, 1e-14, &iters, &rel, NULL)) DIE("solve: %s", cholamd_last_error());
       fprintf(stderr, "[cholamd] iterative refinement: %d corrections, ||b - A x|| / ||b|| = %.3e\n", iters, rel);
       if (cholamd_device_download(dev, x, d_x, n, NULL)) DIE("solve: %s", cholamd_last_error());
-    } else if (cholamd_solve(dev, d_arena, d_b, d_x, NULL) || cholamd_device_download(dev, x, d_x, n, NULL)) DIE("solve: %s", cholamd_last_error());
+    } else if ((lr ? cholamd_lowrank_solve(lr, d_arena, d_b, NULL, d_x, NULL) : cholamd_solve(dev, d_arena, d_b, d_x, NULL)) || cholamd_device_download(dev, x, d_x, n, NULL)) DIE("solve: %s", cholamd_last_error());
     printf("Done solve.\n");
     if (*solution_file) {
       printf("Saving solution to: %s\n", solution_file);
@@ -224,6 +249,7 @@ int main(int argc, char **argv)
     cholamd_device_free(dev, d_b); cholamd_device_free(dev, d_x);
     free(b); free(x);
   }
+  cholamd_lowrank_destroy(lr);
   for (int g = 0; g < gpus; g++) {
     cholamd_comm_destroy(comms[g]);
     cholamd_device_free(devs[g], arenas[g]);

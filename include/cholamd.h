@@ -913,6 +913,73 @@ int cholamd_dsyrk_dev(int n, int k, const double *d_a, int lda, double *d_c, int
 int cholamd_dtrsv_dev(int trans, int n, const double *d_a, int lda, double *d_x, void *stream);
 int cholamd_dgemv_dev(int trans, int m, int n, const double *d_a, int lda, const double *d_x, double *d_y, void *stream);
 
+/* ---- low-rank corrections on the finished factor (not in the reference): solves, log det and variances of A + U U^T, A - U U^T and of A under the linear
+ * constraints U^T x = e, with U a few dense columns (n x k, column-major, ORIGINAL dof order, 1 <= k <= CHOLAMD_LOWRANK_MAX), without touching the factor's
+ * pattern.  CONVENTIONS: M = P^T L P, M M^T = A (the half solves above); Y = M^-1 U; G = Y^T Y = U^T A^-1 U; the CAPACITANCE matrix C = L_C L_C^T (k x k) is
+ *     CHOLAMD_LOWRANK_UPDATE     (A + U U^T) x = b                      C = I + G
+ *     CHOLAMD_LOWRANK_DOWNDATE   (A - U U^T) x = b, A - U U^T SPD       C = I - G
+ *     CHOLAMD_LOWRANK_CONSTRAINT A x + U lambda = b, U^T x = e          C = G
+ * V = M^-T Y = A^-1 U, and the object stores W = V L_C^-T (n x k).  Then A'^-1 = A^-1 - sigma W W^T with sigma = -1 for a downdate and +1 otherwise:
+ *     corrected solve   x0 = A^-1 b, t = W^T b (constraint mode: t = W^T b - L_C^-1 e), x = x0 - sigma W t
+ *     determinant       log det(A +- U U^T) = log det A + log det C, log det C = 2 sum_i log (L_C)_ii        (cholamd_lowrank_logdet)
+ *     diagonal          diag(A'^-1) = diag(A^-1) - sigma w, w_i = sum_j W_ij^2: subtract from (add to, for a downdate) cholamd_selinv_diag; in constraint
+ *                       mode these are the marginal variances under the constraints                              (cholamd_lowrank_diag)
+ *     projection        x* = x - W L_C^-1 (U^T x - e) puts a sample x ~ N(mu, A^-1) on the constraint set         (cholamd_lowrank_project)
+ * After cholamd_lowrank_set a corrected solve is one plain solve plus two passes over W (2 n k doubles): no triangular solve with C (its inverse factor
+ * R = L_C^-T is kept, k x k) and no pass over L per column of U.
+ * cholamd_lowrank_create: an object for up to kmax columns on device object d: ONE n x kmax block, four kmax x kmax / kmax x 32 matrices and the workspace of
+ *   the transposed product, all from the device object's allocator (CHOLAMD_POISON and the guard tails apply, cholamd_debug_live_buffers counts them).  The
+ *   object refers to d: destroy it first.
+ * cholamd_lowrank_set: U is copied into the block; Y by cholamd_solve_half_nrhs(FORWARD) in place; G by the transposed-product kernel; C formed and factored
+ *   by cholamd_dpotrf_dev; V by cholamd_solve_half_nrhs(BACKWARD) in place; R = L_C^-T by cholamd_dtrsm_dev on a k x k identity; W = V R in place by the
+ *   row-owned product kernel.  The half solves honour the device's solve options: under "solve_deterministic" + "solve_deterministic_block" two calls give
+ *   the same bits of W and L_C (everything else in the chain is deterministic whatever the options).  SYNCHRONISES (it returns info).  C not positive
+ *   definite -- a downdate too large, dependent or zero constraint columns -- returns CHOLAMD_ERR_ARG, cholamd_last_error names the failing leading minor
+ *   (info > 0 in cholamd_lowrank_state) and the object is left UNSET.  k < 1, k > kmax, ldu < n, a NULL pointer, a mode other than the three, a
+ *   partitioned device object of rank != 0: CHOLAMD_ERR_ARG, the object keeps the state it had.
+ * Any use of an unset object (solve, solve_nrhs, project, diag, logdet, factor, block) returns CHOLAMD_ERR_ARG and writes nothing.
+ * cholamd_lowrank_state: out = { k (0: unset), mode, info of the last set }.
+ * cholamd_lowrank_solve / _solve_nrhs: the corrected solve, asynchronous on `stream`.  d_e / d_E (k doubles / k x nrhs, lde >= k) are read in constraint mode
+ *   only, NULL = zero.  In place (x == b; X == B with ldx == ldb) is allowed: t is taken before the plain solve overwrites b.  The argument rules of
+ *   cholamd_solve_nrhs hold verbatim (nrhs == 0 returns 0 and touches nothing; nrhs < 0, ldb < n, ldx < n, a NULL pointer with nrhs > 0: CHOLAMD_ERR_ARG; rows
+ *   n .. ld - 1 and columns >= nrhs of X are never written).  Columns go in chunks of 32: per chunk t, then cholamd_solve_nrhs on the chunk (cholamd_solve for
+ *   the single vector) with every solve_* option in force, then the correction.  The correction X - X0 of column j depends on column j of B and E alone,
+ *   whatever nrhs, the column's chunk and the other columns hold (a NaN there never reaches it), and has the same bits every call.
+ * cholamd_lowrank_project: d_xout = d_x - W L_C^-1 (U^T d_x - e) with the caller's U (the object keeps W, not U); constraint mode only; d_e NULL = zero;
+ *   d_xout == d_x allowed.  cholamd_lowrank_diag: d_w[i] = sum_j W_ij^2 (n doubles).  cholamd_lowrank_logdet: *logdet_C_out (HOST) = log det C, summed on the
+ *   host in index order at set time.  cholamd_lowrank_factor: h_LC (HOST, k x k, ldl >= k) = L_C, the strict upper triangle zero.  cholamd_lowrank_block:
+ *   the stored W on the device, read-only, valid until the next set or destroy.
+ * DETERMINISM of the kernels (chol_lowrank.hip): T = P^T Q sums the rows in SLABS of 1024 rows -- a partition of n alone, never of k, m or the grid: one
+ *   workgroup per slab keeps the slab's partial 16 x 16 tiles (v_mfma_f64_16x16x4_f64) and stores them, a second launch adds an element's partials in slab
+ *   order; X = alpha X + beta V T owns rows in chunks of 16; w_i sums j ascending.  One owner per element, no floating-point atomics, no flags, no waits inside
+ *   a launch; ragged sizes are masked by selection, never by multiplying with zero.
+ * SCOPE: the COMPLETE fp64 factor in the arena: a single-GPU device object, or rank 0's after a gather; another rank: CHOLAMD_ERR_ARG.  There are no _f32 and
+ *   no sharded forms.  W belongs to the arena's VALUES at set time: after a refactorisation call cholamd_lowrank_set again -- NOTHING detects a stale W.  One
+ *   call at a time per object and per device object.
+ * Host restatements (no device) of the kernels' partition: cholamd_lowrank_slabs returns the number of slabs of n rows and writes their first rows
+ *   (first_row NULL: the count only; at most cap entries); cholamd_lowrank_tprod_host: T (k x m, ldt >= k) = P^T Q, P n x k, Q n x m, slab by slab;
+ *   cholamd_lowrank_rprod_host: X (n x m) = alpha X + beta V T, V n x k, T k x m, in 16-row chunks read whole before they are written (X == V with m == k
+ *   allowed; alpha == 0: X is not read).  Leading dimensions at least the row counts (and 1), k <= CHOLAMD_LOWRANK_MAX; k == 0 or m == 0 touches nothing. */
+typedef struct cholamd_lowrank cholamd_lowrank;
+#define CHOLAMD_LOWRANK_MAX 256
+#define CHOLAMD_LOWRANK_UPDATE 1
+#define CHOLAMD_LOWRANK_DOWNDATE (-1)
+#define CHOLAMD_LOWRANK_CONSTRAINT 0
+int  cholamd_lowrank_create(cholamd_device *d, int kmax, cholamd_lowrank **out);
+void cholamd_lowrank_destroy(cholamd_lowrank *lr);
+int  cholamd_lowrank_set(cholamd_lowrank *lr, const double *d_arena, const double *d_U, int64_t ldu, int k, int mode, void *stream);
+int  cholamd_lowrank_state(const cholamd_lowrank *lr, int out[3]);
+int  cholamd_lowrank_solve(cholamd_lowrank *lr, const double *d_arena, const double *d_b, const double *d_e, double *d_x, void *stream);
+int  cholamd_lowrank_solve_nrhs(cholamd_lowrank *lr, const double *d_arena, const double *d_B, int64_t ldb, const double *d_E, int64_t lde, double *d_X, int64_t ldx, int nrhs, void *stream);
+int  cholamd_lowrank_project(cholamd_lowrank *lr, const double *d_U, int64_t ldu, const double *d_x, const double *d_e, double *d_xout, void *stream);
+int  cholamd_lowrank_diag(cholamd_lowrank *lr, double *d_w, void *stream);
+int  cholamd_lowrank_logdet(cholamd_lowrank *lr, double *logdet_C_out);
+int  cholamd_lowrank_factor(cholamd_lowrank *lr, double *h_LC, int ldl);
+int  cholamd_lowrank_block(cholamd_lowrank *lr, const double **d_W, int64_t *ldw);
+int  cholamd_lowrank_slabs(int64_t n, int64_t *first_row, int64_t cap);
+int  cholamd_lowrank_tprod_host(int64_t n, int k, int m, const double *P, int64_t ldp, const double *Q, int64_t ldq, double *T, int64_t ldt);
+int  cholamd_lowrank_rprod_host(int64_t n, int k, int m, double alpha, double beta, const double *V, int64_t ldv, const double *T, int64_t ldt, double *X, int64_t ldx);
+
 #ifdef __cplusplus
 }
 #endif
