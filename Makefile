@@ -13,7 +13,7 @@ HIPFLAGS:= -O3 -fPIC --offload-arch=$(ARCH) -Iinclude -I$(CSRC) -Wall
 $(OUT)/chol_kernels.o: KERNFLAGS := -mllvm -pragma-unroll-threshold=100000
 
 HOST_OBJS := $(OUT)/chol_ingest.o $(OUT)/chol_symbolic.o $(OUT)/chol_schedule.o $(OUT)/chol_generate.o $(OUT)/chol_lowrank_host.o
-HIP_OBJS  := $(OUT)/chol_kernels.o $(OUT)/chol_kernels_f32.o $(OUT)/chol_solve_nrhs.o $(OUT)/chol_factor_query.o $(OUT)/chol_selinv.o $(OUT)/chol_schur.o $(OUT)/chol_multiply.o $(OUT)/chol_multiply_nrhs.o $(OUT)/chol_solve_det.o $(OUT)/chol_lowrank.o $(OUT)/chol_api.o
+HIP_OBJS  := $(OUT)/chol_kernels.o $(OUT)/chol_kernels_f32.o $(OUT)/chol_solve_nrhs.o $(OUT)/chol_factor_query.o $(OUT)/chol_selinv.o $(OUT)/chol_schur.o $(OUT)/chol_multiply.o $(OUT)/chol_multiply_nrhs.o $(OUT)/chol_solve_det.o $(OUT)/chol_lowrank.o $(OUT)/chol_values_grad.o $(OUT)/chol_api.o
 
 all: $(OUT)/libcholamd.so $(BIN)/cholamd_mmat oracle
 
@@ -57,7 +57,7 @@ $(ASAN_OUT)/%.o: $(CSRC)/%.c $(CSRC)/chol_plan.h include/cholamd.h
 $(ASAN_OUT)/chol_api.o: $(CSRC)/chol_api.cpp $(CSRC)/chol_devbuf.h $(CSRC)/chol_plan.h $(CSRC)/chol_kernels.h include/cholamd.h
 	@mkdir -p $(ASAN_OUT)
 	$(HIPCC) $(HIPFLAGS) -O1 $(SAN) -fno-sanitize=function -fno-gpu-sanitize -x hip -c $< -o $@
-$(ASAN_OUT)/libcholamd.so: $(ASAN_HOST_OBJS) $(ASAN_OUT)/chol_api.o $(OUT)/chol_kernels.o $(OUT)/chol_kernels_f32.o $(OUT)/chol_solve_nrhs.o $(OUT)/chol_factor_query.o $(OUT)/chol_selinv.o $(OUT)/chol_schur.o $(OUT)/chol_multiply.o $(OUT)/chol_multiply_nrhs.o $(OUT)/chol_solve_det.o $(OUT)/chol_lowrank.o
+$(ASAN_OUT)/libcholamd.so: $(ASAN_HOST_OBJS) $(ASAN_OUT)/chol_api.o $(OUT)/chol_kernels.o $(OUT)/chol_kernels_f32.o $(OUT)/chol_solve_nrhs.o $(OUT)/chol_factor_query.o $(OUT)/chol_selinv.o $(OUT)/chol_schur.o $(OUT)/chol_multiply.o $(OUT)/chol_multiply_nrhs.o $(OUT)/chol_solve_det.o $(OUT)/chol_lowrank.o $(OUT)/chol_values_grad.o
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) $(SAN) -fno-gpu-sanitize -o $@ $^ -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 # leak detection: ON, in a process of its own without an interpreter (tests/native/host_leak.c: plans, schedules of every level and
 # world size, the program builder and its self-check, the generator, error paths); the only suppression is the HIP runtime's own
@@ -119,3 +119,11 @@ lowrank_host: $(ASAN_OUT)/lowrank_host
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 LSAN_OPTIONS=suppressions=$(abspath scripts/lsan.supp):print_suppressions=0 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
 	$(ASAN_OUT)/lowrank_host
 .PHONY: lowrank_host
+# the host restatements of the values-gradient kernels under the sanitizers, in a process of its own (tests/native/values_grad_host.c: it generates its
+# inputs): `make values_grad_host` builds and runs this program alone
+$(ASAN_OUT)/values_grad_host: tests/native/values_grad_host.c $(ASAN_OUT)/libcholamd.so
+	$(HIPCC) -x c -O1 -Iinclude $(SAN) -fno-sanitize=function -o $@ $< -L$(ASAN_OUT) -lcholamd -Wl,-rpath,$(abspath $(ASAN_OUT)) -lm
+values_grad_host: $(ASAN_OUT)/values_grad_host
+	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 LSAN_OPTIONS=suppressions=$(abspath scripts/lsan.supp):print_suppressions=0 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
+	$(ASAN_OUT)/values_grad_host
+.PHONY: values_grad_host

@@ -192,6 +192,12 @@ def load():
     L.cholamd_selinv_entries.argtypes = [vp, vp, vp, i64, vp]
     L.cholamd_plan_selinv_blocks.argtypes = [vp, ci]
     L.cholamd_plan_selinv_front.argtypes = [vp, ci, ci, ci, vp, vp, vp]
+    L.cholamd_values_grad_pairs.argtypes = [vp, vp, i64, vp, i64, ci, cd, cd, vp, i64, vp]
+    L.cholamd_values_grad_logdet.argtypes = [vp, vp, cd, cd, vp, i64, vp]
+    L.cholamd_plan_values_grad_pairs_host.argtypes = [vp, vp, i64, vp, i64, ci, cd, cd, vp, i64]
+    L.cholamd_plan_values_grad_logdet_host.argtypes = [vp, vp, cd, cd, vp, i64]
+    L.cholamd_plan_duplicate_entries.argtypes = [vp]
+    L.cholamd_plan_duplicate_entries.restype = i64
     L.cholamd_plan_schur_size.argtypes = [vp, ci]
     L.cholamd_plan_schur_dofs.argtypes = [vp, ci, vp]
     L.cholamd_plan_schur_list.argtypes = [vp, ci, i64, vp]

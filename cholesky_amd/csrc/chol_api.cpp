@@ -97,6 +97,7 @@ struct cholamd_device {
   // new values of A (cholamd_device_set_values): the index lists of the gather and the entries' classes (uploaded at the first call), the status words of
   // the last call on the device ([4]), their start values ([4], device) and where they are read back to (pinned host, two slots of four)
   dev_buf<int> a_src, csr_src; dev_buf<unsigned char> e_cls;
+  dev_buf<int> e_row, e_col; // the entry list itself (cholamd_values_grad_pairs / _logdet: uploaded at the first call)
   dev_buf<int64_t> vs_dev, vs_init; pinned_words vs_host;
   int64_t vs_last[4] = { 0, 0, 0, 0 };  // the last call's status words as read back
   bool vs_called = false, vs_last_valid = false;
@@ -1404,6 +1405,66 @@ extern "C" int cholamd_selinv_entries(cholamd_device *d, const double *d_zarena,
   HIPCHK(hipSetDevice(d->dev));
   if (!d->a_src) { int rc = d->a_src.upload(p->a_src, (size_t)p->nnz_a); if (rc) return rc; } // the index list of cholamd_device_set_values
   HIPCHK((hipError_t)chol_launch_selinv_entries(d_zarena, d->a_dst, d->a_src, p->nnz_a, d_vals, count, (hipStream_t)stream));
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Gradients with respect to the value array (include/cholamd.h at cholamd_values_grad_pairs; kernels in chol_values_grad.hip, host restatements in
+// chol_symbolic.c).  The entry list and the entries' classes go to the device at the first call on a device object; later calls allocate nothing.
+// ---------------------------------------------------------------------------------------------
+static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb);
+// the rules both calls share: the plan's (count, dropped, duplicates) and the single-GPU object; then the lists
+static int values_grad_ready(cholamd_device *d, int64_t count, const char *what)
+{
+  const cholamd_plan *p = d->plan;
+  { int rc = chol_values_grad_plan_ok(p, count, what); if (rc) return rc; }
+  if (d->world > 1) {
+    chol_set_error("%s: the device object is rank %d of a partition of %d; gradients are taken on a single-GPU object", what, d->rank, d->world);
+    return CHOLAMD_ERR_ARG;
+  }
+  return 0;
+}
+static int values_grad_lists(cholamd_device *d)
+{
+  const cholamd_plan *p = d->plan;
+  int rc = 0;
+  if (!d->e_row) rc = d->e_row.upload(p->e_row, (size_t)p->nz_file);
+  if (!rc && !d->e_col) rc = d->e_col.upload(p->e_col, (size_t)p->nz_file);
+  if (!rc && !d->e_cls) rc = d->e_cls.upload(p->e_cls, (size_t)p->nz_file); // (cholamd_device_set_values may have brought it)
+  if (!rc && !d->a_src) rc = d->a_src.upload(p->a_src, (size_t)p->nnz_a);
+  return rc;
+}
+extern "C" int cholamd_values_grad_pairs(cholamd_device *d, const double *d_P, int64_t ldp, const double *d_Q, int64_t ldq, int nrhs, double alpha, double beta,
+                                         double *d_g, int64_t count, void *stream)
+{
+  const char *what = "cholamd_values_grad_pairs";
+  if (!d) { chol_set_error("%s: NULL device", what); return CHOLAMD_ERR_ARG; }
+  { int rc = values_grad_ready(d, count, what); if (rc) return rc; }
+  const cholamd_plan *p = d->plan;
+  const int n = p->n;
+  if (nrhs < 0) { chol_set_error("%s: nrhs = %d < 0", what, nrhs); return CHOLAMD_ERR_ARG; }
+  if (ldp < n || ldq < n) { chol_set_error("%s: leading dimensions ldp = %lld, ldq = %lld must be at least n = %d", what, (long long)ldp, (long long)ldq, n); return CHOLAMD_ERR_ARG; }
+  if (nrhs == 0) return 0;
+  if (!d_P || !d_Q || !d_g) { chol_set_error("%s: NULL %s", what, !d_P ? "P" : !d_Q ? "Q" : "g"); return CHOLAMD_ERR_ARG; }
+  const size_t gb = (size_t)count * sizeof(double);
+  const size_t pb = ((size_t)(nrhs - 1) * (size_t)ldp + (size_t)n) * sizeof(double), qb = ((size_t)(nrhs - 1) * (size_t)ldq + (size_t)n) * sizeof(double);
+  if (ranges_overlap(d_g, gb, d_P, pb) || ranges_overlap(d_g, gb, d_Q, qb)) { chol_set_error("%s: g overlaps P or Q", what); return CHOLAMD_ERR_ARG; }
+  HIPCHK(hipSetDevice(d->dev));
+  { int rc = values_grad_lists(d); if (rc) return rc; }
+  HIPCHK((hipError_t)chol_launch_values_grad_pairs(d_P, ldp, d_Q, ldq, nrhs, d->e_row, d->e_col, d->e_cls, count, alpha, beta, d_g, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int cholamd_values_grad_logdet(cholamd_device *d, const double *d_zarena, double alpha, double beta, double *d_g, int64_t count, void *stream)
+{
+  const char *what = "cholamd_values_grad_logdet";
+  if (!d) { chol_set_error("%s: NULL device", what); return CHOLAMD_ERR_ARG; }
+  { int rc = values_grad_ready(d, count, what); if (rc) return rc; }
+  if (!d_zarena || !d_g) { chol_set_error("%s: NULL %s", what, !d_zarena ? "Z arena" : "g"); return CHOLAMD_ERR_ARG; }
+  const cholamd_plan *p = d->plan;
+  if (ranges_overlap(d_g, (size_t)count * sizeof(double), d_zarena, (size_t)p->arena * sizeof(double))) { chol_set_error("%s: g overlaps the Z arena", what); return CHOLAMD_ERR_ARG; }
+  HIPCHK(hipSetDevice(d->dev));
+  { int rc = values_grad_lists(d); if (rc) return rc; }
+  HIPCHK((hipError_t)chol_launch_values_grad_logdet(d_zarena, d->a_dst, d->a_src, p->nnz_a, d->e_row, d->e_col, d->e_cls, count, alpha, beta, d_g, (hipStream_t)stream));
   return 0;
 }
 

@@ -118,6 +118,14 @@ int chol_launch_lr_tprod(int64_t n, int k, int m, const double *P, int64_t ldp, 
 int chol_launch_lr_rprod(int64_t n, int k, int m, double alpha, double beta, const double *V, int64_t ldv, const double *T, int64_t ldt, double *X, int64_t ldx, hipStream_t st);
 int chol_launch_lr_rowsq(int64_t n, int k, const double *W, int64_t ldw, double *w, hipStream_t st);
 int chol_launch_lr_small(int what, int k, int cols, int mode, double *A, int64_t lda, const double *B, int64_t ldb, hipStream_t st);
+/* gradients with respect to the value array (chol_values_grad.hip): g[k] = alpha s_k + beta g[k] for every k < nz, one owner per entry, no atomics, a fixed
+ * order of the sum; beta == 0: g is not read.  pairs: s_k = sum_c (P[i, c] Q[j, c] + P[j, c] Q[i, c]) (one product on the diagonal), (i, j) = (e_row[k],
+ * e_col[k]), P and Q column-major in original dof order.  logdet: s_k = m_k Z[a_dst[e]] for the scatter entry e with a_src[e] == k (no two of them share a
+ * k: the caller refuses plans with duplicate entries).  Entries with e_cls != CHOL_ENTRY_IN: s_k = 0 */
+int chol_launch_values_grad_pairs(const double *P, int64_t ldp, const double *Q, int64_t ldq, int nrhs, const int *e_row, const int *e_col, const unsigned char *e_cls,
+                                  int64_t nz, double alpha, double beta, double *g, hipStream_t st);
+int chol_launch_values_grad_logdet(const double *Z, const int64_t *a_dst, const int *a_src, int64_t nnz, const int *e_row, const int *e_col, const unsigned char *e_cls,
+                                   int64_t nz, double alpha, double beta, double *g, hipStream_t st);
 /* diagnostic instance of the program launch (k_program<true>): 4 stamps per job, then CHOL_TRACE_X per job -- [0] follower: own tiles' wait over / update job: wave 0 saw the job's last staged wait hold,
  * [1] its items, [2 + i] round of item i begun; [48 + k] POTRF job: column k published / TRSM job (first strip): column tile k on its channel;
  * [72 + k] POTRF job: the factor wave starts column k / TRSM job: the POTRF's column k seen */

@@ -343,6 +343,9 @@ struct cholamd_plan {
    * triangles point at the same index); e_cls[k]: what became of entry k -- outside the pattern (0.0 at creation: in neither list), in the
    * scatter list and the CSR, or dropped by the ordering (CSR only) */
   int *e_row, *e_col, *a_src, *csr_src; unsigned char *e_cls;
+  /* in-pattern entries that share their arena position with the entry before them in the sorted scatter list (the scatter overwrites, the CSR sums: the
+   * values-gradient calls refuse such a plan), and the value-array index of the first one (-1: none) */
+  int64_t duplicates; int dup_first;
   /* fill snapshots per interval label */
   int64_t *snap_n; cholamd_filled **snap;
   /* reference-order BLAS call list */
@@ -354,6 +357,9 @@ struct cholamd_plan {
 };
 
 /* chol_symbolic.c */
+/* the plan rules of the values-gradient calls (include/cholamd.h at cholamd_values_grad_pairs): count == nz, no dropped and no duplicate entries; 0 or
+ * CHOLAMD_ERR_ARG with the message set */
+int chol_values_grad_plan_ok(const struct cholamd_plan *p, int64_t count, const char *what);
 int chol_plan_finish(struct cholamd_plan *p, int nz, const int *a_row, const int *a_col, const double *a_val);
 const chol_block *chol_plan_block(const struct cholamd_plan *p, int r, int c);
 int chol_ntiles(const struct cholamd_plan *p, int sep, int interval);

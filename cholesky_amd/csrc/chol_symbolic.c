@@ -12,6 +12,7 @@
  */
 #define _GNU_SOURCE
 #include <errno.h>
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -473,6 +474,12 @@ int chol_plan_finish(plan_t *p, int nz, const int *a_row, const int *a_col, cons
     for (int64_t e = 0; e < p->nnz_a; e++) { p->a_dst[e] = t[e].d; p->a_val[e] = t[e].v; p->a_src[e] = t[e].s; }
     free(t);
   }
+  /* two in-pattern entries at one position are neighbours now (cholamd_plan_duplicate_entries) */
+  p->duplicates = 0; p->dup_first = -1;
+  for (int64_t e = 1; e < p->nnz_a; e++)
+    if (p->a_dst[e] == p->a_dst[e - 1]) {
+      if (p->duplicates++ == 0) p->dup_first = p->a_src[e] > p->a_src[e - 1] ? p->a_src[e] : p->a_src[e - 1];
+    }
   return 0;
 }
 
@@ -708,6 +715,70 @@ int cholamd_plan_fill_host_values(const cholamd_plan *p, const double *vals, int
   if (!vals || count != p->nz_file) { chol_set_error("value array of %lld entries, the plan has %d", (long long)count, p->nz_file); return CHOLAMD_ERR_ARG; }
   memset(arena, 0, (size_t)p->arena * sizeof(double));
   for (int64_t e = 0; e < p->nnz_a; e++) arena[p->a_dst[e]] = vals[p->a_src[e]];
+  return 0;
+}
+
+/* ---- gradients with respect to the value array (include/cholamd.h at cholamd_values_grad_pairs): the host restatements of chol_values_grad.hip.  They
+ * walk the same lists in the same order with fma() from <math.h>, never with a * b + c (which the compiler may or may not contract): the device's bits. */
+int64_t cholamd_plan_duplicate_entries(const cholamd_plan *p) { return p->duplicates; }
+int chol_values_grad_plan_ok(const cholamd_plan *p, int64_t count, const char *what)
+{
+  if (count != p->nz_file) { chol_set_error("%s: room for %lld entries, the plan has %d", what, (long long)count, p->nz_file); return CHOLAMD_ERR_ARG; }
+  if (p->dropped > 0) {
+    int k = 0;
+    while (k < p->nz_file && p->e_cls[k] != CHOL_ENTRY_DROPPED) k++;
+    chol_set_error("%s: the ordering dropped %lld entr%s of A, the first one entry %d at (%d, %d): the arena does not factor A(v)", what, (long long)p->dropped,
+                   p->dropped == 1 ? "y" : "ies", k, p->e_row[k], p->e_col[k]);
+    return CHOLAMD_ERR_ARG;
+  }
+  if (p->duplicates > 0) {
+    const int k = p->dup_first;
+    chol_set_error("%s: %lld entr%s of the value array repeat%s the position of another one, the first one entry %d at (%d, %d): the scatter overwrites where "
+                   "the residual operator sums, so A(v) is not linear in such a pair", what, (long long)p->duplicates, p->duplicates == 1 ? "y" : "ies",
+                   p->duplicates == 1 ? "s" : "", k, p->e_row[k], p->e_col[k]);
+    return CHOLAMD_ERR_ARG;
+  }
+  return 0;
+}
+static double grad_scale(double alpha, double t, double beta, const double *g) /* beta == 0: *g is not read */
+{
+  return beta == 0.0 ? alpha * t : fma(alpha, t, beta * *g);
+}
+int cholamd_plan_values_grad_pairs_host(const cholamd_plan *p, const double *P, int64_t ldp, const double *Q, int64_t ldq, int nrhs,
+                                        double alpha, double beta, double *g, int64_t count)
+{
+  const char *what = "cholamd_plan_values_grad_pairs_host";
+  if (!p) { chol_set_error("%s: NULL plan", what); return CHOLAMD_ERR_ARG; }
+  { int rc = chol_values_grad_plan_ok(p, count, what); if (rc) return rc; }
+  if (nrhs < 0) { chol_set_error("%s: nrhs = %d < 0", what, nrhs); return CHOLAMD_ERR_ARG; }
+  if (ldp < p->n || ldq < p->n) { chol_set_error("%s: leading dimensions ldp = %lld, ldq = %lld must be at least n = %d", what, (long long)ldp, (long long)ldq, p->n); return CHOLAMD_ERR_ARG; }
+  if (nrhs == 0) return 0;
+  if (!P || !Q || !g) { chol_set_error("%s: NULL %s", what, !P ? "P" : !Q ? "Q" : "g"); return CHOLAMD_ERR_ARG; }
+  for (int k = 0; k < p->nz_file; k++) {
+    if (p->e_cls[k] != CHOL_ENTRY_IN) { g[k] = beta == 0.0 ? 0.0 : beta * g[k]; continue; } /* A(v) does not depend on v_k */
+    const int64_t i = p->e_row[k], j = p->e_col[k];
+    double acc = 0.0;
+    for (int64_t c = 0; c < nrhs; c++) {
+      acc = fma(P[i + c * ldp], Q[j + c * ldq], acc);
+      if (i != j) acc = fma(P[j + c * ldp], Q[i + c * ldq], acc);
+    }
+    g[k] = grad_scale(alpha, acc, beta, &g[k]);
+  }
+  return 0;
+}
+int cholamd_plan_values_grad_logdet_host(const cholamd_plan *p, const double *zarena_host, double alpha, double beta, double *g, int64_t count)
+{
+  const char *what = "cholamd_plan_values_grad_logdet_host";
+  if (!p) { chol_set_error("%s: NULL plan", what); return CHOLAMD_ERR_ARG; }
+  { int rc = chol_values_grad_plan_ok(p, count, what); if (rc) return rc; }
+  if (!zarena_host || !g) { chol_set_error("%s: NULL %s", what, !zarena_host ? "Z arena" : "g"); return CHOLAMD_ERR_ARG; }
+  for (int k = 0; k < p->nz_file; k++)
+    if (p->e_cls[k] != CHOL_ENTRY_IN) g[k] = beta == 0.0 ? 0.0 : beta * g[k];
+  for (int64_t e = 0; e < p->nnz_a; e++) {
+    const int k = p->a_src[e];
+    const double m = p->e_row[k] == p->e_col[k] ? 1.0 : 2.0;
+    g[k] = grad_scale(alpha, m * zarena_host[p->a_dst[e]], beta, &g[k]);
+  }
   return 0;
 }
 

@@ -391,6 +391,38 @@ class Device:
         check(self.L.cholamd_selinv_entries(self.h, self.ptr(zarena), self.ptr(out), self.plan.nz, _stream_ptr(stream)), "cholamd_selinv_entries")
         return out
 
+    # -- gradients with respect to the value array: the contraction of an adjoint onto the entries of A(v) ---------------------------------
+    def values_grad_pairs(self, P, Q, alpha=1.0, beta=0.0, out=None, stream=None):
+        """out[k] = alpha * sum_c (P[i, c] Q[j, c] + P[j, c] Q[i, c]) + beta * out[k] for every entry k at (i, j) of plan.entries() (one product on the
+        diagonal, 0 outside the pattern): cholamd_values_grad_pairs.  P, Q: n x nrhs column-major (as solve_nrhs takes them; P may be Q); out: plan.nz
+        doubles, allocated when None (then beta must be 0), returned.  With X = A^-1 B and Lam = A^-1 dloss/dX: dloss/dvalues = values_grad_pairs(Lam,
+        X, alpha=-1).  Asynchronous on `stream`; deterministic.  Refuses plans with dropped or duplicate entries (CholamdError)."""
+        import torch
+        (ldp, k), (ldq, kq) = self._block(P, "P", self.plan.n), self._block(Q, "Q", self.plan.n)
+        if kq != k:
+            raise ValueError(f"P has {k} columns, Q has {kq}")
+        if out is None:
+            if beta != 0.0:
+                raise ValueError("beta != 0 needs the array to accumulate into (out)")
+            out = (torch.empty if k else torch.zeros)(self.plan.nz, dtype=torch.float64, device=f"cuda:{self.device_id}")  # (no columns: the call touches nothing)
+        self._f64_vec(out, "out", self.plan.nz)
+        check(self.L.cholamd_values_grad_pairs(self.h, self.ptr(P), ldp, self.ptr(Q), ldq, k, float(alpha), float(beta), self.ptr(out), self.plan.nz,
+                                               _stream_ptr(stream)), "cholamd_values_grad_pairs")
+        return out
+
+    def values_grad_logdet(self, zarena, alpha=1.0, beta=0.0, out=None, stream=None):
+        """out[k] = alpha * m_k (A^-1)(i, j) + beta * out[k] = alpha * d(log det A)/dvalues[k] + beta * out[k] from the Z arena of selinv (m_k = 2 off
+        the diagonal, 1 on it; 0 outside the pattern): cholamd_values_grad_logdet.  out as for values_grad_pairs.  Asynchronous; deterministic."""
+        import torch
+        if out is None:
+            if beta != 0.0:
+                raise ValueError("beta != 0 needs the array to accumulate into (out)")
+            out = torch.empty(self.plan.nz, dtype=torch.float64, device=f"cuda:{self.device_id}")
+        self._f64_vec(out, "out", self.plan.nz)
+        check(self.L.cholamd_values_grad_logdet(self.h, self.ptr(zarena), float(alpha), float(beta), self.ptr(out), self.plan.nz, _stream_ptr(stream)),
+              "cholamd_values_grad_logdet")
+        return out
+
     # -- Schur complement on the top k levels of the tree: S = A_TT - A_TI A_II^-1 A_IT, condense, expand ---------------------------
     def schur_factor(self, arena, k, stream=None):
         """Eliminate the tree levels levels - 1 .. k of a filled fp64 arena by the per-level launches (cholamd_schur_factor): the blocks of the k kept

@@ -156,6 +156,41 @@ class Plan:
             check(self.L.cholamd_plan_fill_host_values(self.h, v.ctypes.data, v.size, a.ctypes.data), "cholamd_plan_fill_host_values")
         return a
 
+    @property
+    def duplicate_entries(self):
+        """In-pattern entries that repeat the position of another one (cholamd_plan_duplicate_entries): the values-gradient calls refuse such a plan."""
+        return int(self.L.cholamd_plan_duplicate_entries(self.h))
+
+    def values_grad_pairs_host(self, P, Q, alpha=1.0, beta=0.0, g=None, ldp=None, ldq=None):
+        """Device.values_grad_pairs on the CPU (cholamd_plan_values_grad_pairs_host): the same walk with fma(), the device's bits.  P, Q: n x nrhs
+        arrays (Q may be P itself: then one buffer is handed over twice); g: plan.nz doubles to accumulate into (a copy is returned), NaN-filled when
+        None.  ldp / ldq: leading dimensions of the column-major copies handed to the library (default n); the rows behind are -3.0 and never read."""
+        P = np.asarray(P, dtype=np.float64)
+        assert P.ndim == 2 and P.shape[0] == self.n
+        k = P.shape[1]
+        ldp, ldq = int(ldp or self.n), int(ldq or self.n)
+        pb = self._colmajor(P, self.n, ldp, -3.0)
+        if Q is P:
+            assert ldq == ldp
+            qb = pb
+        else:
+            Q = np.asarray(Q, dtype=np.float64)
+            assert Q.shape == P.shape
+            qb = self._colmajor(Q, self.n, ldq, -3.0)
+        out = np.full(max(self.nz, 1), np.nan) if g is None else np.array(g, dtype=np.float64)
+        check(self.L.cholamd_plan_values_grad_pairs_host(self.h, pb.ctypes.data, ldp, qb.ctypes.data, ldq, k, float(alpha), float(beta), out.ctypes.data, self.nz),
+              "cholamd_plan_values_grad_pairs_host")
+        return out[:self.nz]
+
+    def values_grad_logdet_host(self, zarena, alpha=1.0, beta=0.0, g=None):
+        """Device.values_grad_logdet on the CPU from a host copy of the Z arena (cholamd_plan_values_grad_logdet_host); g as for values_grad_pairs_host."""
+        zarena = np.ascontiguousarray(zarena, dtype=np.float64)
+        assert zarena.size == self.arena_doubles
+        out = np.full(max(self.nz, 1), np.nan) if g is None else np.array(g, dtype=np.float64)
+        check(self.L.cholamd_plan_values_grad_logdet_host(self.h, zarena.ctypes.data, float(alpha), float(beta), out.ctypes.data, self.nz),
+              "cholamd_plan_values_grad_logdet_host")
+        return out[:self.nz]
+
     def fill_host_part(self, rank, world):
         """Host arena as rank `rank` of `world` starts from (A's shared-top entries on rank 0 only) and
         the offset of the shared tail of the arena."""

@@ -640,6 +640,35 @@ int cholamd_selinv_diag(cholamd_device *d, const double *d_zarena, double *d_dia
 int cholamd_selinv_entries(cholamd_device *d, const double *d_zarena, double *d_vals, int64_t count, void *stream);
 int cholamd_plan_selinv_blocks(const cholamd_plan *p, int sep);
 int cholamd_plan_selinv_front(const cholamd_plan *p, int sep, int block, int cap, int cols[2], int *pos, int64_t *off);
+/* ---- gradients with respect to the value array (not in the reference): the contraction of an adjoint onto the entries of A, for callers who hold the value
+ * array of cholamd_device_set_values as the variable of an optimisation.  The matrix is the linear function of the value array v that the residual operator
+ * implements,  A(v) = sum_k v_k E_k,  E_k = e_i e_j^T + e_j e_i^T for an off-diagonal entry k at (i, j) = (row_k, col_k) of cholamd_plan_entries and
+ * E_k = e_i e_i^T for a diagonal one: multiplicity m_k = 2 off the diagonal, 1 on it.  Both calls compute  g[k] = alpha s_k + beta g[k]  for every k:
+ *   cholamd_values_grad_pairs:   s_k = sum_c p_c^T E_k q_c = sum_c (P[i, c] Q[j, c] + P[j, c] Q[i, c])  (sum_c P[i, c] Q[i, c] on the diagonal), P and Q
+ *     column-major n x nrhs on the device in original dof order, ldp, ldq >= n.  With X = A^-1 B and Lam = A^-1 (dloss / dX) the gradient of the loss with
+ *     respect to v is the call with P = Lam, Q = X, alpha = -1; d_P == d_Q is allowed (alpha = 1: d(x^T A x) / dv).
+ *   cholamd_values_grad_logdet:  s_k = tr(A^-1 E_k) = m_k (A^-1)(i, j) = d(log det A) / dv_k, read from the Z arena of cholamd_selinv.
+ * Entries outside the pattern (0.0 when the plan was made) are ignored by everything the library computes, so their derivative is zero: s_k = 0, they
+ * receive beta g[k] -- never NaN.  beta == 0: g is not read (g[k] = alpha s_k; 0.0 outside the pattern), so a NaN-filled or uninitialised g comes out finite.
+ * THE ORDER OF THE SUM is part of the contract: acc = 0; for c = 0 .. nrhs - 1: acc = fma(P[i, c], Q[j, c], acc), then, off the diagonal,
+ * acc = fma(P[j, c], Q[i, c], acc); g = beta == 0 ? alpha acc : fma(alpha, acc, beta g).  One owner per entry, no atomics: the same bits every call, and
+ * the bits of the host restatements below.
+ * REFUSED PLANS (CHOLAMD_ERR_ARG, the message names the first offending entry): a plan with cholamd_plan_dropped_entries() > 0 (the arena does not factor
+ * A) and a plan with cholamd_plan_duplicate_entries() > 0 -- two in-pattern entries at one position: the scatter overwrites where the residual operator
+ * sums, so A(v) is not the sum above.  cholamd_plan_duplicate_entries: the in-pattern entries that repeat the position of another one, counted when the
+ * plan is made.
+ * Both device calls are asynchronous on `stream`.  nrhs == 0 returns 0 and touches nothing.  CHOLAMD_ERR_ARG with nothing written: count !=
+ * cholamd_plan_nz(), a NULL pointer, nrhs < 0, ldp < n or ldq < n, d_g overlapping P, Q (their full extents (nrhs - 1) ld + n) or the Z arena, a
+ * partitioned device object (world > 1).  The first call on a device object uploads the entry list; later calls allocate nothing.  fp64 only.
+ * cholamd_plan_values_grad_pairs_host / _logdet_host: the same on the CPU with host arrays (zarena_host: a host copy of the Z arena), walking the same lists
+ * in the same order with fma(): the device's bits. */
+int cholamd_values_grad_pairs(cholamd_device *d, const double *d_P, int64_t ldp, const double *d_Q, int64_t ldq, int nrhs,
+                              double alpha, double beta, double *d_g, int64_t count, void *stream);
+int cholamd_values_grad_logdet(cholamd_device *d, const double *d_zarena, double alpha, double beta, double *d_g, int64_t count, void *stream);
+int cholamd_plan_values_grad_pairs_host(const cholamd_plan *p, const double *P, int64_t ldp, const double *Q, int64_t ldq, int nrhs,
+                                        double alpha, double beta, double *g, int64_t count);
+int cholamd_plan_values_grad_logdet_host(const cholamd_plan *p, const double *zarena_host, double alpha, double beta, double *g, int64_t count);
+int64_t cholamd_plan_duplicate_entries(const cholamd_plan *p);
 /* ---- Schur complement on the top of the tree, with condense and expand (not in the reference; the "Schur complement" / "partial factorisation" option of
  * MUMPS and PARDISO): eliminate the interior dofs I, keep the interface dofs T, and receive  S = A_TT - A_TI A_II^-1 A_IT  -- substructuring, domain
  * decomposition, static condensation, constrained Gaussian Markov random fields.  The caller assembles or solves the interface problem, then recovers the interior.
