@@ -1022,6 +1022,16 @@ __device__ __forceinline__ void lds_set(int *flag, int value, int lane)
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // this wave's LDS writes have landed
   if (lane == 0) __hip_atomic_store(flag, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
+// a flag that goes from 0 to non-zero once (the strips' column tiles, trsm_rr_body): bounded like wait_progress -- a mistake in the protocol fails the
+// factorisation through info and falls through instead of hanging the workgroup
+__device__ __forceinline__ void lds_wait_set(int *flag, int *info, int lane)
+{
+  for (int it = 0; __builtin_amdgcn_readfirstlane(__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) == 0; ++it) {
+    if (it >= (1 << 25)) { if (lane == 0) report_stall(info); break; } // x ~0.06 us per poll
+    __builtin_amdgcn_s_sleep(1);
+  }
+  asm volatile("" ::: "memory"); // later LDS reads stay behind the poll (LDS executes a wave's accesses in order)
+}
 __device__ __forceinline__ void lds_inc(int *cnt, int lane)
 {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1821,12 +1831,18 @@ __global__ __launch_bounds__(64) void k_dinv(const double *__restrict__ Lp, int 
 // BAND (program launch, a banded leaf pivot factored as ONE block of up to CHOL_RR_MAXN columns): tile (J2, J) of the block's L is zero for
 // J2 - J > d.band (<= 4), so step J touches at most one tile per wave (J2 = wave mod 4 within (J, J + band]): the L prefetch ring
 // holds ONE tile per step instead of one per slot -- what lets a strip of seventeen column tiles fit the registers.
-template <bool PUB, int SLOTS, bool BAND = false, bool TR = false>
+template <bool PUB, int SLOTS, bool BAND = false, bool TR = false, bool FLAG = false>
 __device__ __forceinline__ void trsm_rr_body(double *__restrict__ base, const double *__restrict__ ws, const chol_trsm_desc d, double (*sX)[TS * TS],
                                              int wave, int lane, const int *__restrict__ progress, int progress_base, int *__restrict__ info,
-                                             int *__restrict__ chan = nullptr, unsigned long long *xst = nullptr)
+                                             int *__restrict__ chan = nullptr, unsigned long long *xst = nullptr, int *xflag = nullptr)
 { // chan (program launch): the strip's rows are followed by a POTRF workgroup -- counter chan[J] is raised once column tile J
   // of the strip has been stored (follow_external)
+  // FLAG (program launch): no barrier in the step loop.  Every X_J has an LDS slot of its own for the whole job (sX[J], no ring: nothing is
+  // overwritten, so there is no write-after-read to order) and a flag xflag[J] of the strip's group (zero when the body starts), set by the
+  // solving wave behind its LDS writes; a wave that needs X_J waits for that flag alone.  The solving wave's global stores, their drain
+  // (vmcnt(0)) and the channel's raise come after the flag, on that wave alone: the other waves of the strip -- and the job's other strips,
+  // which no longer count the same barriers -- go on with the next column tile meanwhile.  Same MFMAs, same accumulators, same order.
+  if (FLAG && d.m <= 0) return; // a placeholder group has nothing to solve and nobody waits for it
   const double *Lm = base + d.l_off;
   const double *W = ws + d.dinv_off;
   double *B = base + d.b_off;
@@ -1874,12 +1890,22 @@ __device__ __forceinline__ void trsm_rr_body(double *__restrict__ base, const do
     if (PUB) seen = wait_progress(progress, progress_base + (J_) + 1, seen, info);                      \
     _Pragma("unroll") for (int st = 0; st < 4; ++st) buf_[st] = gload<PUB>(&W[(int64_t)(J_) * TS * TS + (4 * st + g) * TS + r15]); \
   }
+#define XS(J_) (FLAG ? (J_) : (J_) % 3) /* LDS slot of X_J */
 #define PUBLISH_X(J_, x_)                                                                               \
   {                                                                                                     \
-    _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                     \
-      const int col_ = (J_) * TS + g + 4 * q;                                                           \
-      sX[(J_) % 3][q * 64 + lp] = x_[q];                                                                \
-      if (vrow && col_ < n) gstore<PUB>(&B[r15 + (int64_t)col_ * ldb], x_[q]);                          \
+    if constexpr (FLAG) { /* LDS first, then the flag: the strip's other waves go on while this one stores and drains */ \
+      _Pragma("unroll") for (int q = 0; q < 4; ++q) sX[XS(J_)][q * 64 + lp] = x_[q];                    \
+      lds_set(&xflag[J_], 1, lane);                                                                     \
+      _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                   \
+        const int col_ = (J_) * TS + g + 4 * q;                                                         \
+        if (vrow && col_ < n) gstore<PUB>(&B[r15 + (int64_t)col_ * ldb], x_[q]);                        \
+      }                                                                                                 \
+    } else {                                                                                            \
+      _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                   \
+        const int col_ = (J_) * TS + g + 4 * q;                                                         \
+        sX[XS(J_)][q * 64 + lp] = x_[q];                                                                \
+        if (vrow && col_ < n) gstore<PUB>(&B[r15 + (int64_t)col_ * ldb], x_[q]);                        \
+      }                                                                                                 \
     }                                                                                                   \
     if (PUB && chan && m > 0) { /* this wave stored the whole column tile: tell the follower once it has landed */ \
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                  \
@@ -1891,7 +1917,7 @@ __device__ __forceinline__ void trsm_rr_body(double *__restrict__ base, const do
   {                                                                                                     \
     d4 acc_ = tile[s_];                                                                                 \
     _Pragma("unroll") for (int st = 0; st < 4; ++st)                                                    \
-      acc_ = __builtin_amdgcn_mfma_f64_16x16x4f64(lpre[(JX_) % 3][LS(s_)][st], -sX[(JX_) % 3][st * 64 + lp], acc_, 0, 0, 0); \
+      acc_ = __builtin_amdgcn_mfma_f64_16x16x4f64(lpre[(JX_) % 3][LS(s_)][st], -sX[XS(JX_)][st * 64 + lp], acc_, 0, 0, 0); \
     tile[s_] = acc_;                                                                                    \
   }
   // operands are fetched two steps ahead; vmcnt retires in order, so the inverse the next solve waits
@@ -1924,7 +1950,9 @@ __device__ __forceinline__ void trsm_rr_body(double *__restrict__ base, const do
     if (J < T) {
       STAMP(0);
       const bool next_owner = (J + 1 < T) && (((J + 1) & 3) == wave);
-      lds_barrier(); // X_J visible
+      if constexpr (FLAG) {
+        if ((J & 3) != wave) lds_wait_set(&xflag[J], info, lane); // X_J visible (its owner wrote it itself)
+      } else lds_barrier(); // X_J visible
       STAMP(1);
       if (next_owner) {
         // critical chain: bring tile J+1 up to date, solve it, publish it -- nothing else before the
@@ -1962,6 +1990,7 @@ __device__ __forceinline__ void trsm_rr_body(double *__restrict__ base, const do
 #undef LOAD_W
 #undef PUBLISH_X
 #undef APPLY_X
+#undef XS
 #undef LS
 #undef VOFF
 }
@@ -2038,6 +2067,11 @@ __global__ __launch_bounds__(RR_THREADS) void k_potrf_trsm(double *__restrict__ 
 // are ahead of it in the queue or for the strips of a source that the queue places within reach of the resident
 // workgroups (checked on the host: chol_program_check); every spin is bounded and fails the factorisation through info.
 // ------------------------------------------------------------------------------------------------
+// LDS image of a strip job (kind 1): three groups x RR_MAXT solved column tiles of 2 KB, then one flag per group and column tile
+#define PROG_XFLAGS 32 /* flags per group: 4 x the most column tiles per wave (the unrolled step loop's range), rounded up */
+#define PROG_OFF_XFLAG (3 * RR_MAXT * TS * TS)
+static_assert(PROG_XFLAGS >= 4 * ((CHOL_RR_MAXN / TS + 3) / 4) && PROG_XFLAGS >= 4 * FUSED_SLOTS && PROG_OFF_XFLAG + (3 * PROG_XFLAGS + 1) / 2 <= RR_SMEM_DOUBLES, "the strips' slots and flags fit the image");
+static_assert(CHOL_RR_MAXN <= RR_MAXT * TS && CHOL_FUSE_MAXN <= CHOL_RR_MAXN, "one slot per column tile of the widest strip");
 template <bool TR>
 __global__ __launch_bounds__(RR_THREADS) void k_program(double *__restrict__ base, double *__restrict__ ws, const chol_job *__restrict__ jobs, int njobs,
                                                         const chol_wait *__restrict__ waits, const chol_potrf_desc *__restrict__ pdescs,
@@ -2070,6 +2104,11 @@ __global__ __launch_bounds__(RR_THREADS) void k_program(double *__restrict__ bas
     if (j >= njobs) break; // every workgroup draws exactly one job index past the end: head advances by njobs + gridDim.x per launch
     const chol_job jb = jobs[j];
     if (TR && trace && tid == 0) { trace[4 * j] = __builtin_amdgcn_s_memrealtime(); trace[4 * j + 3] = blockIdx.x; }
+    // a strip job's column-tile flags (trsm_rr_body, FLAG form) are cleared here, ahead of the job's waits: the barrier behind the waits
+    // (or the one in front of the strips, for a job without) is the one between the clearing and the first use
+    int *const xflags = (int *)(smem + PROG_OFF_XFLAG);
+    if (jb.kind == 1 && tid < 3 * PROG_XFLAGS) xflags[tid] = 0;
+    bool fenced = false;
     // ONE wave polls (hundreds of blocked workgroups are resident at a time: twelve polling waves each would sit on the L2 the
     // working jobs hand their data through); the others park at the barrier
     // A job is usually drawn long before it may run: what does not depend on the wait is fetched ahead of it -- the first
@@ -2085,6 +2124,7 @@ __global__ __launch_bounds__(RR_THREADS) void k_program(double *__restrict__ bas
     if (jb.n_pre > 0 && !(jb.kind == 0 && jb.n_ext > 0)) { // a follower looks at its waits itself (potrf_rr_body); an extend-add job's staged waits are its tasks' business
       if (wave == 0) wait_list(waits + jb.wait_first, jb.n_pre, ctr, ctr_total, epoch, lane, info);
       lds_barrier();
+      fenced = true;
     }
     if (TR && trace && tid == 0) trace[4 * j + 1] = __builtin_amdgcn_s_memrealtime(); // a follower overwrites it when its followed columns are in
     if (jb.kind == 0) {
@@ -2093,15 +2133,16 @@ __global__ __launch_bounds__(RR_THREADS) void k_program(double *__restrict__ bas
       fa.ext = exts + jb.ext_first; fa.n_ext = jb.n_ext; fa.ctr = ctr; fa.ctr_total = ctr_total; fa.epoch = epoch; fa.wl = waits + jb.wait_first; fa.n_wl = jb.n_wait; fa.stamp = TR && trace ? &trace[4 * j + 1] : nullptr; fa.xstamp = TR && trace ? &trace[4 * njobs + CHOL_TRACE_X * j] : nullptr;
       potrf_rr_body<true, true, TR>(base, ws, pd, info, ctr + pd.ctr, epoch * ctr_total[pd.ctr], smem, pdescs[jb.first].sky, fa, tid);
     } else if (jb.kind == 1) {
-      double (*sX)[3][TS * TS] = (double (*)[3][TS * TS])smem;
+      double (*sX)[RR_MAXT][TS * TS] = (double (*)[RR_MAXT][TS * TS])smem; // [group][column tile]: one slot per solved tile
       chol_trsm_desc d = tdescs[jb.first + min(grp, jb.n - 1)];
-      if (grp >= jb.n) d.m = 0; // every group runs the same number of barriers: the strips of a job share one pivot block
+      if (grp >= jb.n) d.m = 0; // a placeholder group: the strips of a job are independent of each other (flag form), it leaves at once
+      if (!fenced) lds_barrier(); // the flags are clear
       if (d.band > 0) // a banded leaf pivot factored as one block (up to CHOL_RR_MAXN columns: (CHOL_RR_MAXN / 16 + 3) / 4 column tiles per wave)
-        trsm_rr_body<true, (CHOL_RR_MAXN / TS + 3) / 4, true, TR>(base, ws, d, sX[grp], wave & 3, lane, ctr + d.flag, epoch * ctr_total[d.flag], info, d.chan >= 0 ? ctr + d.chan : nullptr,
-                                                                   TR && trace && grp == 0 ? &trace[4 * njobs + CHOL_TRACE_X * j] : nullptr);
+        trsm_rr_body<true, (CHOL_RR_MAXN / TS + 3) / 4, true, TR, true>(base, ws, d, sX[grp], wave & 3, lane, ctr + d.flag, epoch * ctr_total[d.flag], info, d.chan >= 0 ? ctr + d.chan : nullptr,
+                                                                         TR && trace && grp == 0 ? &trace[4 * njobs + CHOL_TRACE_X * j] : nullptr, xflags + grp * PROG_XFLAGS);
       else
-        trsm_rr_body<true, FUSED_SLOTS, false, TR>(base, ws, d, sX[grp], wave & 3, lane, ctr + d.flag, epoch * ctr_total[d.flag], info, d.chan >= 0 ? ctr + d.chan : nullptr,
-                                                   TR && trace && grp == 0 ? &trace[4 * njobs + CHOL_TRACE_X * j] : nullptr);
+        trsm_rr_body<true, FUSED_SLOTS, false, TR, true>(base, ws, d, sX[grp], wave & 3, lane, ctr + d.flag, epoch * ctr_total[d.flag], info, d.chan >= 0 ? ctr + d.chan : nullptr,
+                                                         TR && trace && grp == 0 ? &trace[4 * njobs + CHOL_TRACE_X * j] : nullptr, xflags + grp * PROG_XFLAGS);
     } else {
       stage_waits sw;
       sw.w = waits + jb.wait_first + jb.n_pre; sw.n = jb.n_wait - jb.n_pre; sw.ctr = ctr; sw.ctr_total = ctr_total; sw.epoch = epoch; sw.info = info;

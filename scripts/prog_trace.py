@@ -137,6 +137,32 @@ for sep in sorted(set(int(v) for v in jobs[jobs[:, 0] == 2, 1]), key=lambda s_: 
     tail = f"job {last} held {held[last]:.1f} end {us[last, 2]:.1f}" if last in held else f"job {last} end {us[last, 2]:.1f} (not stamped)"
     print(f"  panel {sep:2d} (level {heap_level[sep]}): {len(d):3d} / {len(js):3d} jobs  {q[0]:5.1f} {q[1]:5.1f} {q[2]:5.1f} {q[3]:5.1f} {q[4]:5.1f}   last to end: {tail}")
 
+# followed strips, column tile by column tile: when the pivot block's POTRF published column tile k and when its strip jobs (first strip of
+# each) had put tile k on the channel -- the lag of the first and of the last tile says whether the strips keep the pivot's pace
+def _stamps(line, title):
+    part = line.split(title)[1].split("|")[0] if title in line else ""
+    return {int(kv.split(":")[0]): float(kv.split(":")[1]) for kv in part.split()}
+
+
+pub, chn = {}, {}
+if os.path.exists(follow_file):
+    for ln in open(follow_file):
+        w = ln.split()
+        if len(w) >= 4 and w[2] == "kind" and w[3] == "0":
+            pub[int(w[1])] = _stamps(ln, "column published:")
+        elif len(w) >= 4 and w[2] == "kind" and w[3] == "1":
+            chn[int(w[1])] = _stamps(ln, "column tile on the channel:")
+print("followed strips per source pivot block: POTRF published tile k at / latest strip job put tile k on the channel at / lag (us)")
+for (sep, col0, ch), js in sorted(seen.items(), key=lambda kv: us[pot[kv[0][:2]], 2]):
+    pj = pot[(sep, col0)]
+    tiles = sorted(set(pub.get(pj, {})) & set.intersection(*(set(chn.get(q, {})) for q in js)))
+    if not tiles:
+        continue
+    p = [pub[pj][k] for k in tiles]
+    c = [max(chn[q][k] for q in js) for k in tiles]
+    print(f"  sep {sep:2d} (level {heap_level[sep]}) col0 {col0:3d} jobs {js[0]}-{js[-1]}: tiles {tiles[0]}..{tiles[-1]}  lag first {c[0] - p[0]:4.1f} last {c[-1] - p[-1]:4.1f}\n"
+          f"      published  {' '.join(f'{v:6.1f}' for v in p)}\n      on channel {' '.join(f'{v:6.1f}' for v in c)}")
+
 # TRACE_WAITS=lo:hi -- per job of the range: every wait (in list order = stage order) with the time its counter was complete
 if os.environ.get("TRACE_WAITS"):
     lo, hi = (int(v) for v in os.environ["TRACE_WAITS"].split(":"))
