@@ -64,17 +64,9 @@ $(ASAN_OUT)/libcholamd.so: $(ASAN_HOST_OBJS) $(ASAN_OUT)/chol_api.o $(OUT)/chol_
 # process-lifetime state (scripts/lsan.supp).  Under pytest the interpreter's and torch's allocations would drown (or, suppressed by
 # frame, hide) the library's, so that run keeps detect_leaks=0.
 G := tests/golden
-$(ASAN_OUT)/host_leak: tests/native/host_leak.c $(ASAN_OUT)/libcholamd.so
-	$(HIPCC) -x c -O1 -Iinclude $(SAN) -fno-sanitize=function -o $@ $< -L$(ASAN_OUT) -lcholamd -Wl,-rpath,$(abspath $(ASAN_OUT)) -lm
-$(ASAN_OUT)/schur_host: tests/native/schur_host.c $(ASAN_OUT)/libcholamd.so
-	$(HIPCC) -x c -O1 -Iinclude $(SAN) -fno-sanitize=function -o $@ $< -L$(ASAN_OUT) -lcholamd -Wl,-rpath,$(abspath $(ASAN_OUT)) -lm
-$(ASAN_OUT)/multiply_host: tests/native/multiply_host.c $(ASAN_OUT)/libcholamd.so
-	$(HIPCC) -x c -O1 -Iinclude $(SAN) -fno-sanitize=function -o $@ $< -L$(ASAN_OUT) -lcholamd -Wl,-rpath,$(abspath $(ASAN_OUT)) -lm
-$(ASAN_OUT)/multiply_nrhs_host: tests/native/multiply_nrhs_host.c $(ASAN_OUT)/libcholamd.so
-	$(HIPCC) -x c -O1 -Iinclude $(SAN) -fno-sanitize=function -o $@ $< -L$(ASAN_OUT) -lcholamd -Wl,-rpath,$(abspath $(ASAN_OUT)) -lm
-$(ASAN_OUT)/solve_det_host: tests/native/solve_det_host.c $(ASAN_OUT)/libcholamd.so
-	$(HIPCC) -x c -O1 -Iinclude $(SAN) -fno-sanitize=function -o $@ $< -L$(ASAN_OUT) -lcholamd -Wl,-rpath,$(abspath $(ASAN_OUT)) -lm
-$(ASAN_OUT)/solve_det_nrhs_host: tests/native/solve_det_nrhs_host.c $(ASAN_OUT)/libcholamd.so
+# every tests/native/*.c program links against the sanitized library in the same way
+NATIVE_PROGS := host_leak schur_host multiply_host multiply_nrhs_host solve_det_host solve_det_nrhs_host schur_solve_host lowrank_host values_grad_host
+$(NATIVE_PROGS:%=$(ASAN_OUT)/%): $(ASAN_OUT)/%: tests/native/%.c $(ASAN_OUT)/libcholamd.so
 	$(HIPCC) -x c -O1 -Iinclude $(SAN) -fno-sanitize=function -o $@ $< -L$(ASAN_OUT) -lcholamd -Wl,-rpath,$(abspath $(ASAN_OUT)) -lm
 # the owning device buffers of the glue over a host allocator that can be told to fail (tests/native/devbuf_host.cpp): no library, no HIP runtime
 $(ASAN_OUT)/devbuf_host: tests/native/devbuf_host.cpp $(CSRC)/chol_devbuf.h
@@ -105,24 +97,18 @@ asan: $(ASAN_OUT)/libcholamd.so $(ASAN_OUT)/host_leak $(ASAN_OUT)/schur_host $(A
 .PHONY: asan
 # the host restatement of the block Schur condense / expand under the sanitizers, in a process of its own (tests/native/schur_solve_host.c: it generates
 # its input): `make schur_solve_host` builds and runs this program alone
-$(ASAN_OUT)/schur_solve_host: tests/native/schur_solve_host.c $(ASAN_OUT)/libcholamd.so
-	$(HIPCC) -x c -O1 -Iinclude $(SAN) -fno-sanitize=function -o $@ $< -L$(ASAN_OUT) -lcholamd -Wl,-rpath,$(abspath $(ASAN_OUT)) -lm
 schur_solve_host: $(ASAN_OUT)/schur_solve_host
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 LSAN_OPTIONS=suppressions=$(abspath scripts/lsan.supp):print_suppressions=0 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
 	$(ASAN_OUT)/schur_solve_host
 .PHONY: schur_solve_host
 # the host restatements of the low-rank kernels' partition under the sanitizers, in a process of its own (tests/native/lowrank_host.c: it generates its
 # inputs): `make lowrank_host` builds and runs this program alone
-$(ASAN_OUT)/lowrank_host: tests/native/lowrank_host.c $(ASAN_OUT)/libcholamd.so
-	$(HIPCC) -x c -O1 -Iinclude $(SAN) -fno-sanitize=function -o $@ $< -L$(ASAN_OUT) -lcholamd -Wl,-rpath,$(abspath $(ASAN_OUT)) -lm
 lowrank_host: $(ASAN_OUT)/lowrank_host
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 LSAN_OPTIONS=suppressions=$(abspath scripts/lsan.supp):print_suppressions=0 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
 	$(ASAN_OUT)/lowrank_host
 .PHONY: lowrank_host
 # the host restatements of the values-gradient kernels under the sanitizers, in a process of its own (tests/native/values_grad_host.c: it generates its
 # inputs): `make values_grad_host` builds and runs this program alone
-$(ASAN_OUT)/values_grad_host: tests/native/values_grad_host.c $(ASAN_OUT)/libcholamd.so
-	$(HIPCC) -x c -O1 -Iinclude $(SAN) -fno-sanitize=function -o $@ $< -L$(ASAN_OUT) -lcholamd -Wl,-rpath,$(abspath $(ASAN_OUT)) -lm
 values_grad_host: $(ASAN_OUT)/values_grad_host
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 LSAN_OPTIONS=suppressions=$(abspath scripts/lsan.supp):print_suppressions=0 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
 	$(ASAN_OUT)/values_grad_host

@@ -163,6 +163,12 @@ static int no_device_error()
   chol_set_error("no usable HIP device (libcholamd has no CPU fallback)");
   return CHOLAMD_ERR_NO_DEVICE;
 }
+// do [a, a + na) and [b, b + nb) share a byte?  (the argument checks of the gradients, the products and the Schur entry points)
+static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+  const char *pa = (const char *)a, *pb = (const char *)b;
+  return pa < pb + nb && pb < pa + na;
+}
 
 extern "C" int cholamd_device_count(void)
 {
@@ -1168,6 +1174,35 @@ extern "C" int cholamd_residual(cholamd_device *d, const double *d_b, const doub
   if (rc) return rc;
   return residual_norm(d, d_b, d_x, d_r, relres_out, (hipStream_t)stream);
 }
+static hipStream_t stream_of(void *const *streams, int g) { return streams ? (hipStream_t)streams[g] : nullptr; }
+static int refine_nan_error() { chol_set_error("iterative refinement produced NaN (fp32 factorisation broke down)"); return CHOLAMD_ERR_ARG; }
+// The refinement of one vector, written once over n rank objects (1: the single and the sharded form; every rank holds the same b and the same iterate):
+// x0 = M^-1 b with M = L32 L32^T; then x += M^-1 (b - A x) until ||b - A x|| <= tol ||b||.  solve(rhs, out) applies M^-1 on every rank.  The callers
+// have made their checks and pass the ranks' residual and correction vectors (rv[g] = devs[g]->rvec, dx[g] = devs[g]->dxvec) as the arrays solve takes.
+template <class Solve> static int refine_loop(cholamd_device *const *devs, int n, const double *const *bs, double *const *xs, const double *const *rv, double *const *dx,
+                                              void *const *streams, int max_iter, double tol, int *iters_out, double *relres_out, Solve solve)
+{
+  if (max_iter < 0) max_iter = 0;
+  int rc = solve(bs, xs);
+  if (rc) return rc;
+  keep_inverses_scope keep(devs, n);
+  double rel = 0.0;
+  int it = 0;
+  for (;; ++it) {
+    for (int g = 0; g < n; g++) { // every rank forms the residual of its own (identical) iterate
+      double rg = 0.0;
+      HIPCHK(hipSetDevice(devs[g]->dev));
+      if ((rc = residual_norm(devs[g], bs[g], xs[g], devs[g]->rvec, &rg, stream_of(streams, g)))) return rc;
+      if (g == 0) rel = rg;
+    }
+    if (!(rel > tol) || it >= max_iter) break; // also leaves on NaN (the same decision on every rank: the iterates are identical)
+    if ((rc = solve(rv, dx))) return rc;
+    for (int g = 0; g < n; g++) { HIPCHK(hipSetDevice(devs[g]->dev)); HIPCHK((hipError_t)chol_launch_axpy1(xs[g], devs[g]->dxvec, devs[g]->plan->n, stream_of(streams, g))); }
+  }
+  if (iters_out) *iters_out = it;
+  if (relres_out) *relres_out = rel;
+  return rel != rel ? refine_nan_error() : 0;
+}
 extern "C" int cholamd_solve_refine(cholamd_device *d, const float *d_arena32, const double *d_b, double *d_x, int max_iter, double tol,
                                     int *iters_out, double *relres_out, void *stream)
 {
@@ -1175,25 +1210,10 @@ extern "C" int cholamd_solve_refine(cholamd_device *d, const float *d_arena32, c
   int rc = ensure_refine(d);
   if (!rc) rc = build_solve(d);
   if (rc) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  const int n = d->plan->n;
-  if (max_iter < 0) max_iter = 0;
-  // x0 = M^-1 b with M = L32 L32^T; then x += M^-1 (b - A x) until ||b - A x|| <= tol ||b||
-  rc = solve_t(d, d_arena32, d_b, d_x, CHOL_BOTH_SWEEPS, st);
-  if (rc) return rc;
-  keep_inverses_scope keep(&d, 1);
-  double rel = 0.0;
-  int it = 0;
-  for (;; ++it) {
-    if ((rc = residual_norm(d, d_b, d_x, d->rvec, &rel, st))) return rc;
-    if (!(rel > tol) || it >= max_iter) break; // also leaves on NaN
-    if ((rc = solve_t(d, d_arena32, d->rvec, d->dxvec, CHOL_BOTH_SWEEPS, st))) return rc;
-    HIPCHK((hipError_t)chol_launch_axpy1(d_x, d->dxvec, n, st));
-  }
-  if (iters_out) *iters_out = it;
-  if (relres_out) *relres_out = rel;
-  if (rel != rel) { chol_set_error("iterative refinement produced NaN (fp32 factorisation broke down)"); return CHOLAMD_ERR_ARG; }
-  return 0;
+  const double *rv = d->rvec;
+  double *dx = d->dxvec;
+  return refine_loop(&d, 1, &d_b, &d_x, &rv, &dx, &stream, max_iter, tol, iters_out, relres_out,
+                     [&](const double *const *r, double *const *o) { return solve_t(d, d_arena32, r[0], o[0], CHOL_BOTH_SWEEPS, (hipStream_t)stream); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1412,7 +1432,6 @@ extern "C" int cholamd_selinv_entries(cholamd_device *d, const double *d_zarena,
 // Gradients with respect to the value array (include/cholamd.h at cholamd_values_grad_pairs; kernels in chol_values_grad.hip, host restatements in
 // chol_symbolic.c).  The entry list and the entries' classes go to the device at the first call on a device object; later calls allocate nothing.
 // ---------------------------------------------------------------------------------------------
-static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb);
 // the rules both calls share: the plan's (count, dropped, duplicates) and the single-GPU object; then the lists
 static int values_grad_ready(cholamd_device *d, int64_t count, const char *what)
 {
@@ -1474,7 +1493,6 @@ extern "C" int cholamd_values_grad_logdet(cholamd_device *d, const double *d_zar
 // permute of z into the work vector and ONE launch over the whole tree, which writes y in original dof order; the full product puts the BACKWARD launch
 // between them, into the object's second vector (permuted coordinates throughout).
 // ---------------------------------------------------------------------------------------------
-static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb);
 static int build_multiply(cholamd_device *d)
 {
   if (d->mul_ready) return 0;
@@ -1634,11 +1652,6 @@ extern "C" int cholamd_factor_residual_f32(cholamd_device *d, const float *d_are
 // S = A_TT - A_TI A_II^-1 A_IT.  Condense and expand are the streamed solve cut at level k instead of at the partition's level: the same launches over
 // a level range, the levels above the cut never read as a factor.
 // ---------------------------------------------------------------------------------------------
-static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-  const char *pa = (const char *)a, *pb = (const char *)b;
-  return pa < pb + nb && pb < pa + na;
-}
 // the checks every Schur entry point shares; returns m (the kept dofs) and *t0 = n - m, or the error
 static int schur_args(const cholamd_device *d, int k, const char *what, int *t0)
 {
@@ -1953,8 +1966,7 @@ extern "C" int cholamd_solve_refine_nrhs(cholamd_device *d, const float *d_arena
   }
   if (relres_out) for (int j = c0; j < nrhs; j++) relres_out[j] = std::nan(""); // (after a NaN: the chunks not reached)
   if (iters_out) *iters_out = it_max;
-  if (nan) { chol_set_error("iterative refinement produced NaN (fp32 factorisation broke down)"); return CHOLAMD_ERR_ARG; }
-  return 0;
+  return nan ? refine_nan_error() : 0;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2946,7 +2958,6 @@ template <class T> __global__ void k_sum_ranks(ptr_pack P, int n, T *dst, int64_
     dst[i] = s;
   }
 }
-static hipStream_t stream_of(void *const *streams, int g) { return streams ? (hipStream_t)streams[g] : nullptr; }
 template <class T> static int local_exchange(cholamd_device *const *devs, T *const *arenas, const std::vector<level_dev> &lv0, local_group *G, int n, void *const *streams)
 {
   std::vector<xpiece> px;
@@ -3175,23 +3186,10 @@ extern "C" int cholamd_solve_refine_sharded(cholamd_device *d, const float *d_ar
   HIPCHK(hipSetDevice(d->dev));
   int rc = ensure_refine(d);
   if (rc) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  const int n = d->plan->n;
-  if (max_iter < 0) max_iter = 0;
-  if ((rc = solve_sharded_t<float>(d, d_arena32, d_b, d_x, c, st))) return rc;
-  keep_inverses_scope keep(&d, 1);
-  double rel = 0.0;
-  int it = 0;
-  for (;; ++it) {
-    if ((rc = residual_norm(d, d_b, d_x, d->rvec, &rel, st))) return rc;
-    if (!(rel > tol) || it >= max_iter) break; // also leaves on NaN (the same decision on every rank: the iterates are identical)
-    if ((rc = solve_sharded_t<float>(d, d_arena32, d->rvec, d->dxvec, c, st))) return rc;
-    HIPCHK((hipError_t)chol_launch_axpy1(d_x, d->dxvec, n, st));
-  }
-  if (iters_out) *iters_out = it;
-  if (relres_out) *relres_out = rel;
-  if (rel != rel) { chol_set_error("iterative refinement produced NaN (fp32 factorisation broke down)"); return CHOLAMD_ERR_ARG; }
-  return 0;
+  const double *rv = d->rvec;
+  double *dx = d->dxvec;
+  return refine_loop(&d, 1, &d_b, &d_x, &rv, &dx, &stream, max_iter, tol, iters_out, relres_out,
+                     [&](const double *const *r, double *const *o) { return solve_sharded_t<float>(d, d_arena32, r[0], o[0], c, (hipStream_t)stream); });
 }
 // one process driving n ranks: the two sums as an ordered device-side sum on rank 0's stream and peer copies back (local communicator), or grouped
 // ncclAllReduce calls (cholamd_comm_create_all)
@@ -3260,31 +3258,12 @@ extern "C" int cholamd_solve_refine_multi(cholamd_device *const *devs, const flo
                                           int *iters_out, double *relres_out, cholamd_comm *const *comms, int n, void *const *streams)
 {
   if (n < 1) { chol_set_error("no devices"); return CHOLAMD_ERR_ARG; }
-  if (max_iter < 0) max_iter = 0;
   for (int g = 0; g < n; g++) { HIPCHK(hipSetDevice(devs[g]->dev)); int rc = ensure_refine(devs[g]); if (rc) return rc; }
-  int rc = solve_multi_t<float>(devs, arenas32, bs, xs, comms, n, streams);
-  if (rc) return rc;
   std::vector<const double *> rv(n);
   std::vector<double *> dx(n);
   for (int g = 0; g < n; g++) { rv[g] = devs[g]->rvec; dx[g] = devs[g]->dxvec; }
-  keep_inverses_scope keep(devs, n);
-  double rel = 0.0;
-  int it = 0;
-  for (;; ++it) {
-    for (int g = 0; g < n; g++) { // every rank forms the residual of its own (identical) iterate
-      double rg = 0.0;
-      HIPCHK(hipSetDevice(devs[g]->dev));
-      if ((rc = residual_norm(devs[g], bs[g], xs[g], devs[g]->rvec, &rg, stream_of(streams, g)))) return rc;
-      if (g == 0) rel = rg;
-    }
-    if (!(rel > tol) || it >= max_iter) break;
-    if ((rc = solve_multi_t<float>(devs, arenas32, rv.data(), dx.data(), comms, n, streams))) return rc;
-    for (int g = 0; g < n; g++) { HIPCHK(hipSetDevice(devs[g]->dev)); HIPCHK((hipError_t)chol_launch_axpy1(xs[g], devs[g]->dxvec, devs[g]->plan->n, stream_of(streams, g))); }
-  }
-  if (iters_out) *iters_out = it;
-  if (relres_out) *relres_out = rel;
-  if (rel != rel) { chol_set_error("iterative refinement produced NaN (fp32 factorisation broke down)"); return CHOLAMD_ERR_ARG; }
-  return 0;
+  return refine_loop(devs, n, bs, xs, rv.data(), dx.data(), streams, max_iter, tol, iters_out, relres_out,
+                     [&](const double *const *r, double *const *o) { return solve_multi_t<float>(devs, arenas32, r, o, comms, n, streams); });
 }
 
 // ---------------------------------------------------------------------------------------------
