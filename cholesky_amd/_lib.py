@@ -161,6 +161,13 @@ def load():
     L.cholamd_solve_nrhs.argtypes = [vp, vp, vp, i64, vp, i64, ci, vp]
     L.cholamd_solve_nrhs_f32.argtypes = [vp, vp, vp, i64, vp, i64, ci, vp]
     L.cholamd_solve_refine_nrhs.argtypes = [vp, vp, vp, i64, vp, i64, ci, ci, cd, C.POINTER(ci), vp, vp]
+    L.cholamd_apply.argtypes = [vp, vp, vp, vp]
+    L.cholamd_apply_nrhs.argtypes = [vp, vp, i64, vp, i64, ci, vp]
+    L.cholamd_plan_apply_host.argtypes = [vp, vp, vp, vp]
+    for name in ("cholamd_solve_pcg", "cholamd_solve_pcg_f32"):
+        getattr(L, name).argtypes = [vp, vp, vp, vp, ci, cd, ci, vp, vp, vp, vp]
+    for name in ("cholamd_solve_pcg_nrhs", "cholamd_solve_pcg_nrhs_f32"):
+        getattr(L, name).argtypes = [vp, vp, vp, i64, vp, i64, ci, ci, cd, ci, vp, vp, vp, vp]
     L.cholamd_solve_half.argtypes = [vp, vp, vp, vp, ci, vp]
     L.cholamd_solve_half_f32.argtypes = [vp, vp, vp, vp, ci, vp]
     L.cholamd_solve_half_nrhs.argtypes = [vp, vp, vp, i64, vp, i64, ci, ci, vp]

@@ -126,6 +126,27 @@ int chol_launch_values_grad_pairs(const double *P, int64_t ldp, const double *Q,
                                   int64_t nz, double alpha, double beta, double *g, hipStream_t st);
 int chol_launch_values_grad_logdet(const double *Z, const int64_t *a_dst, const int *a_src, int64_t nnz, const int *e_row, const int *e_col, const unsigned char *e_cls,
                                    int64_t nz, double alpha, double beta, double *g, hipStream_t st);
+/* preconditioned conjugate gradients and y = A x (chol_pcg.hip): column-major blocks of `cols` <= CHOL_NRHS_W columns, 256 rows per workgroup, no atomics.
+ * A partial array holds one double per (column, workgroup) at [j * nb + workgroup], nb = (n + 255) / 256.  rec: one record per column in device memory; the
+ * vector kernels read alpha / beta from it (0: the column is not written / p = z), chol_launch_pcg_scalars adds the column's partials in ascending
+ * workgroup order and moves the record on by `stage` (INIT, VERIFY and FINAL read the (r^2, b^2) pairs of chol_nrhs_launch_residual).
+ *   apply:     Q = A P, partial (may be NULL) = p_i q_i        update: X += alpha P, R -= alpha Q, partial = r_i^2        dot: partial = r_i z_i
+ *   direction: P = Z + beta P                                  take:   R = T in the columns of state RESTART */
+#define CHOL_PCG_APPLY_G 8 /* columns per lane of the block apply kernel: DESIGN.md section 17 */
+enum { CHOL_PCG_CONVERGED = 0, CHOL_PCG_MAXITER = 1, CHOL_PCG_BREAKDOWN = 2, CHOL_PCG_NAN = 3, /* what the caller sees */
+       CHOL_PCG_RUNNING = 4, CHOL_PCG_CLAIM = 5 /* rr <= tol^2 bb: the true residual decides */, CHOL_PCG_RESTART = 6 /* runs on from the true residual: p = z */,
+       CHOL_PCG_ZERO_B = 7 /* b = 0: x = 0 */ };
+enum { CHOL_PCG_STAGE_INIT, CHOL_PCG_STAGE_RHO, CHOL_PCG_STAGE_SIGMA, CHOL_PCG_STAGE_RR, CHOL_PCG_STAGE_VERIFY, CHOL_PCG_STAGE_FINAL };
+typedef struct chol_pcg_rec {
+  double rho, sigma, alpha, beta, rr, bb, rel; /* r^T z, p^T A p, their quotients, ||r||^2 (recurrence, or true after INIT / VERIFY), ||b||^2, true ||b - A x|| / ||b|| */
+  int state, iters, what, pad;                 /* iters: applications of A to p; what: 1 = r^T z, 2 = p^T A p broke down */
+} chol_pcg_rec;
+int chol_launch_pcg_apply(const int64_t *ptr, const int *col, const double *val, const double *P, int64_t ldp, double *Q, int64_t ldq, int n, int cols, double *partial, hipStream_t st);
+int chol_launch_pcg_update(const chol_pcg_rec *rec, const double *P, const double *Q, double *X, int64_t ldx, double *R, int64_t ld, int n, int cols, double *partial, hipStream_t st);
+int chol_launch_pcg_dot(const double *R, const double *Z, int64_t ld, int n, int cols, double *partial, hipStream_t st);
+int chol_launch_pcg_direction(const chol_pcg_rec *rec, const double *Z, double *P, int64_t ld, int n, int cols, hipStream_t st);
+int chol_launch_pcg_take(const chol_pcg_rec *rec, const double *T, double *R, int64_t ld, int n, int cols, hipStream_t st);
+int chol_launch_pcg_scalars(chol_pcg_rec *rec, const double *partial, int n, int cols, int stage, double tol, hipStream_t st);
 /* diagnostic instance of the program launch (k_program<true>): 4 stamps per job, then CHOL_TRACE_X per job -- [0] follower: own tiles' wait over / update job: wave 0 saw the job's last staged wait hold,
  * [1] its items, [2 + i] round of item i begun; [48 + k] POTRF job: column k published / TRSM job (first strip): column tile k on its channel;
  * [72 + k] POTRF job: the factor wave starts column k / TRSM job: the POTRF's column k seen */

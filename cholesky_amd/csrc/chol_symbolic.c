@@ -718,6 +718,20 @@ int cholamd_plan_fill_host_values(const cholamd_plan *p, const double *vals, int
   return 0;
 }
 
+/* y = A x on the host (include/cholamd.h at cholamd_apply): the CSR of the residual operator row by row, e ascending, fma() from 0.0 -- the device's bits.
+ * vals != NULL: the plan's pattern with the value array of cholamd_device_set_values (entry k of the CSR reads vals[csr_src[k]]) */
+int cholamd_plan_apply_host(const cholamd_plan *p, const double *vals, const double *x, double *y)
+{
+  if (!p || !x || !y) { chol_set_error("cholamd_plan_apply_host: NULL %s", !p ? "plan" : !x ? "x" : "y"); return CHOLAMD_ERR_ARG; }
+  if (x == y) { chol_set_error("cholamd_plan_apply_host: y is x (there is no in-place form)"); return CHOLAMD_ERR_ARG; }
+  for (int i = 0; i < p->n; i++) {
+    double acc = 0.0;
+    for (int64_t e = p->csr_ptr[i]; e < p->csr_ptr[i + 1]; e++) acc = fma(vals ? vals[p->csr_src[e]] : p->csr_val[e], x[p->csr_col[e]], acc);
+    y[i] = acc;
+  }
+  return 0;
+}
+
 /* ---- gradients with respect to the value array (include/cholamd.h at cholamd_values_grad_pairs): the host restatements of chol_values_grad.hip.  They
  * walk the same lists in the same order with fma() from <math.h>, never with a * b + c (which the compiler may or may not contract): the device's bits. */
 int64_t cholamd_plan_duplicate_entries(const cholamd_plan *p) { return p->duplicates; }

@@ -16,7 +16,9 @@
  *        single GPU, fp64 only),
  *        --lowrank FILE K [--lowrank-mode update|downdate|constraint] (FILE: a Matrix-Market dense `array` n x K, the columns of U; after the factorisation
  *        cholamd_lowrank_set on device 0; the solve of -b becomes the corrected solve of A + U U^T (update, the default), A - U U^T (downdate) or of A under
- *        U^T x = 0 (constraint); with --logdet one more line "logdet C: %.17g" after the logdet line: log det(A +- U U^T) = logdet + logdet C; fp64 only).
+ *        U^T x = 0 (constraint); with --logdet one more line "logdet C: %.17g" after the logdet line: log det(A +- U U^T) = logdet + logdet C; fp64 only),
+ *        --pcg (needs -b: the solve of either --precision goes through cholamd_solve_pcg / _f32 -- conjugate gradients preconditioned with the factor, 30
+ *        iterations, 1e-14 -- and one stderr line "[cholamd] pcg: %d iterations, ||b - A x|| / ||b|| = %.3e", and one more with the status where that is not 0; not with --lowrank or --gpus > 1).
  * Unknown flags (the reference passes -fflow/-ll:cpu/-fcuda/-ll:csize through to Legion) are ignored.
  *
  * Flow = main() of mmat.rg:1056-1496 with the numeric phase on the GPU.  Progress lines keep the
@@ -42,7 +44,7 @@ int main(int argc, char **argv)
 {
   const char *matrix_file = "", *separator_file = "", *clusters_file = "", *b_file = "", *solution_file = "", *factor_file = "",
              *permuted_file = "", *debug_path = "", *invdiag_file = "", *schur_file = "", *lowrank_file = "", *lowrank_mode = "update";
-  int debug = 0, iterations = 1, gpu = 0, full = 0, gpus = 1, want_logdet = 0, want_check = 0, schur_k = 0, det_solve = 0, lowrank_k = 0;
+  int debug = 0, iterations = 1, gpu = 0, full = 0, gpus = 1, want_logdet = 0, want_check = 0, schur_k = 0, det_solve = 0, lowrank_k = 0, pcg = 0;
   const char *precision = "fp64";
   for (int i = 0; i < argc; i++) {
     const char *next = i + 1 < argc ? argv[i + 1] : "";
@@ -63,6 +65,7 @@ int main(int argc, char **argv)
     else if (!strcmp(argv[i], "--logdet")) want_logdet = 1;
     else if (!strcmp(argv[i], "--check")) want_check = 1;
     else if (!strcmp(argv[i], "--deterministic-solve")) det_solve = 1; /* device option solve_deterministic for the solve of -b: the same bits in every run */
+    else if (!strcmp(argv[i], "--pcg")) pcg = 1;
     else if (!strcmp(argv[i], "--invdiag")) invdiag_file = next;
     else if (!strcmp(argv[i], "--schur")) { schur_k = atoi(next); schur_file = i + 2 < argc ? argv[i + 2] : ""; if (!*schur_file) DIE("--schur K FILE"); }
     else if (!strcmp(argv[i], "--lowrank")) { lowrank_file = next; lowrank_k = i + 2 < argc ? atoi(argv[i + 2]) : 0; if (!*lowrank_file || lowrank_k < 1) DIE("--lowrank FILE K"); }
@@ -104,6 +107,9 @@ int main(int argc, char **argv)
   if (*schur_file && cholamd_plan_schur_size(plan, schur_k) < 0) DIE("--schur: %s", cholamd_last_error());
   const int lr_mode = !strcmp(lowrank_mode, "update") ? CHOLAMD_LOWRANK_UPDATE : !strcmp(lowrank_mode, "downdate") ? CHOLAMD_LOWRANK_DOWNDATE : CHOLAMD_LOWRANK_CONSTRAINT;
   if (*lowrank_file && mixed) DIE("--lowrank needs the fp64 factor (--precision fp64)");
+  if (pcg && *lowrank_file) DIE("--pcg does not take a low-rank object (--lowrank)");
+  if (pcg && !*b_file) DIE("--pcg is a form of the solve: it needs -b");
+  if (pcg && gpus > 1) DIE("--pcg is a single-GPU path");
   if (*lowrank_file && lr_mode == CHOLAMD_LOWRANK_CONSTRAINT && strcmp(lowrank_mode, "constraint")) DIE("--lowrank-mode %s: update, downdate or constraint", lowrank_mode);
   if (*lowrank_file && (lowrank_k > CHOLAMD_LOWRANK_MAX || (int64_t)n * lowrank_k > 2147483647)) DIE("--lowrank: K = %d (at most %d, and n K must fit an int)", lowrank_k, CHOLAMD_LOWRANK_MAX);
   if (gpus < 1 || gpus > 64 || (gpus & (gpus - 1))) DIE("--gpus must be a power of two");
@@ -235,7 +241,14 @@ int main(int argc, char **argv)
     if (cholamd_read_vector(b_file, n, b)) DIE("%s", cholamd_last_error());
     if (cholamd_device_alloc(dev, n, &d_b) || cholamd_device_alloc(dev, n, &d_x) || cholamd_device_upload(dev, d_b, b, n, NULL)) DIE("%s", cholamd_last_error());
     printf("Forward Substitution\nBackward Substitution\n");
-    if (mixed) {
+    if (pcg) {
+      int iters = 0, status = 0; double rel = 0.0;
+      if (mixed ? cholamd_solve_pcg_f32(dev, (const float *)d_arena, d_b, d_x, 30, 1e-14, 0, &iters, &rel, &status, NULL)
+                : cholamd_solve_pcg(dev, d_arena, d_b, d_x, 30, 1e-14, 0, &iters, &rel, &status, NULL)) DIE("solve: %s", cholamd_last_error());
+      fprintf(stderr, "[cholamd] pcg: %d iterations, ||b - A x|| / ||b|| = %.3e\n", iters, rel);
+      if (status) fprintf(stderr, "[cholamd] pcg: status %d, not converged to 1e-14 in 30 iterations\n", status);
+      if (cholamd_device_download(dev, x, d_x, n, NULL)) DIE("solve: %s", cholamd_last_error());
+    } else if (mixed) {
       int iters = 0; double rel = 0.0;
       if (cholamd_solve_refine(dev, (const float *)d_arena, d_b, d_x, 30, 1e-14, &iters, &rel, NULL)) DIE("solve: %s", cholamd_last_error());
       fprintf(stderr, "[cholamd] iterative refinement: %d corrections, ||b - A x|| / ||b|| = %.3e\n", iters, rel);

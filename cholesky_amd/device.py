@@ -531,6 +531,48 @@ class Device:
                                                C.byref(it), rel.ctypes.data, _stream_ptr(stream)), "cholamd_solve_refine_nrhs")
         return int(it.value), rel[:k]
 
+    # -- y = A x and conjugate gradients preconditioned with the factor at hand (include/cholamd.h at cholamd_solve_pcg) ----------------
+    PCG_X0 = 1  # CHOLAMD_PCG_X0
+
+    def apply(self, x, y, stream=None):
+        """y = A x with the values in force (cholamd_apply): the fma order of Plan.apply_host; asynchronous; y must not overlap x."""
+        check(self.L.cholamd_apply(self.h, self.ptr(x), self.ptr(y), _stream_ptr(stream)), "cholamd_apply")
+
+    def apply_nrhs(self, X, Y, stream=None):
+        """Y = A X for the k columns of X (n x k, column-major, as solve_nrhs takes them): cholamd_apply_nrhs."""
+        ldx, ldy, k = self._blocks(X, Y)
+        check(self.L.cholamd_apply_nrhs(self.h, self.ptr(X), ldx, self.ptr(Y), ldy, k, _stream_ptr(stream)), "cholamd_apply_nrhs")
+
+    def _pcg(self, fn, what, args, k):
+        it, st = np.zeros(max(k, 1), dtype=np.int32), np.zeros(max(k, 1), dtype=np.int32)
+        rel = np.zeros(max(k, 1), dtype=np.float64)
+        rc = fn(*args, it.ctypes.data, rel.ctypes.data, st.ctypes.data)
+        try:
+            check(rc, what)
+        except Exception as e:  # a breakdown (status 2) or NaN (3) in some column: the per-column results travel with the exception
+            e.iters, e.relres, e.status = it[:k], rel[:k], st[:k]
+            raise
+        return it[:k], rel[:k], st[:k]
+
+    def solve_pcg(self, arena, b, x, max_iter=50, tol=1e-12, x0=False, stream=None):
+        """A x = b for the values IN FORCE (set_values) by conjugate gradients preconditioned with the factor in `arena` -- the factor of other values
+        on the pattern, or an fp32 one (cholamd_solve_pcg / _f32 by the arena's element type).  x0: start from the caller's x instead of zero.  x may
+        be b.  Returns (iters, relres, status): applications of A, the true ||b - A x|| / ||b||, 0 converged / 1 max_iter reached.  A breakdown
+        (status 2: A or the factor is not positive definite) or NaN (3) raises CholamdError, which carries .iters, .relres and .status."""
+        fn = self.L.cholamd_solve_pcg_f32 if self._is_f32(arena) else self.L.cholamd_solve_pcg
+        args = (self.h, self.ptr(arena), self.ptr(b), self.ptr(x), int(max_iter), float(tol), self.PCG_X0 if x0 else 0)
+        it, rel, st = self._pcg(lambda *a: fn(*a, _stream_ptr(stream)), "cholamd_solve_pcg", args, 1)
+        return int(it[0]), float(rel[0]), int(st[0])
+
+    def solve_pcg_nrhs(self, arena, B, X, max_iter=50, tol=1e-12, x0=False, stream=None):
+        """The same for the k columns of B (n x k, column-major, as solve_nrhs takes them) in chunks of 32, every column with its own scalars, count
+        and status: cholamd_solve_pcg_nrhs / _f32.  Returns the arrays (iters, relres, status).  Under option solve_deterministic a column has the
+        bits of solve_pcg on it; with solve_deterministic_block too it depends on its own column of B alone."""
+        ldb, ldx, k = self._blocks(B, X)
+        fn = self.L.cholamd_solve_pcg_nrhs_f32 if self._is_f32(arena) else self.L.cholamd_solve_pcg_nrhs
+        args = (self.h, self.ptr(arena), self.ptr(B), ldb, self.ptr(X), ldx, k, int(max_iter), float(tol), self.PCG_X0 if x0 else 0)
+        return self._pcg(lambda *a: fn(*a, _stream_ptr(stream)), "cholamd_solve_pcg_nrhs", args, k)
+
     def residual(self, b, x, r=None, stream=None):
         """||b - A x|| / ||b|| in fp64 on the device (A = the matrix file's entries)."""
         rel = C.c_double(0.0)

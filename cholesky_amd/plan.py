@@ -411,6 +411,19 @@ class Plan:
         check(self.L.cholamd_plan_schur_det_lists(self.h, int(k), int(which), steps.ctypes.data, items.ctypes.data, srcs.ctypes.data), "cholamd_plan_schur_det_lists")
         return steps[:c["steps"]], items[:c["items"]], srcs[:c["sources"]]
 
+    def apply_host(self, x, values=None):
+        """y = A x on the CPU in the device's fma order (cholamd_plan_apply_host): bit for bit what Device.apply returns.  values: a value array of
+        plan.nz doubles as Device.set_values takes it (None: the plan's own values)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        assert x.shape == (self.n,)
+        if values is not None:
+            values = np.ascontiguousarray(values, dtype=np.float64)
+            if values.shape != (self.nz,):
+                raise ValueError(f"values must hold plan.nz = {self.nz} doubles; got {values.shape}")
+        y = np.full(max(self.n, 1), np.nan, dtype=np.float64)
+        check(self.L.cholamd_plan_apply_host(self.h, values.ctypes.data if values is not None else None, x.ctypes.data, y.ctypes.data), "cholamd_plan_apply_host")
+        return y[:self.n]
+
     def multiply_host(self, arena, which, z):
         """y = M z (which = 0) or y = M^T z (1) on the CPU from a host arena (cholamd_plan_multiply_host): the owner lists of Device.multiply_half
         walked on the host -- the lower triangles and the stored row runs only.  z and the result: n doubles in original dof order."""

@@ -507,6 +507,50 @@ int cholamd_solve_nrhs(cholamd_device *d, const double *d_arena, const double *d
 int cholamd_solve_nrhs_f32(cholamd_device *d, const float *d_arena32, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int nrhs, void *stream);
 int cholamd_solve_refine_nrhs(cholamd_device *d, const float *d_arena32, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int nrhs, int max_iter,
                               double tol, int *iters_out, double *relres_out /* nrhs doubles, may be NULL */, void *stream);
+/* ---- y = A x, and conjugate gradients preconditioned with the factor at hand (not in the reference).  A is the matrix with the values IN FORCE on the
+ * device object: the plan's, or those of the last cholamd_device_set_values.  The factor in the arena may be that of OTHER values on the same pattern (the
+ * previous Newton step's, the last time step's) or of lower precision (an fp32 arena): M = L L^T only has to be symmetric positive definite, and the loop
+ * solves A x = b with the values in force to `tol` in a number of steps set by the spectrum of M^-1 A -- one where A = c M, m + 1 after a change of rank m,
+ * a handful for a drift of a few per cent -- where the stationary iteration of cholamd_solve_refine may diverge (A = 3 M: iteration matrix -2 I).
+ *   cholamd_apply / _nrhs: y = A x (vectors in original dof order; blocks column-major with leading dimensions >= n, rows n .. ld - 1 never written), per row
+ *     acc = fma(a_ie, x_e, acc) over the row's entries in the order of the plan's CSR from 0.0; asynchronous; y overlapping x: CHOLAMD_ERR_ARG.
+ *     cholamd_plan_apply_host is the same order on the host (bit for bit); values == NULL: the plan's values, otherwise a value array of cholamd_plan_nz()
+ *     doubles as cholamd_device_set_values takes it (entries that were explicit zeros when the plan was made are not part of the operator).
+ *   cholamd_solve_pcg / _f32 / _nrhs / _nrhs_f32: standard PCG, M^-1 = what cholamd_solve / _f32 (the one-vector forms) or cholamd_solve_nrhs / _f32 run under
+ *     the options in force.  Start: x = 0, r = b; flags = CHOLAMD_PCG_X0: the caller's x, r = b - A x.  b is copied to a workspace first: x == b is allowed.
+ *     A column claims convergence when the recurrence's ||r||^2 <= tol^2 ||b||^2; the TRUE residual b - A x is then formed, and if ||b - A x|| <= tol ||b||
+ *     the column ends (status 0); otherwise the true residual replaces r, p = M^-1 r, and the column runs on (that step counts as no iteration).
+ *     Outputs per column (HOST arrays of nrhs entries, one entry in the one-vector forms; each may be NULL): iters = applications of A to p, relres = the TRUE
+ *     ||b - A x|| / ||b|| of the x returned, status = 0 converged | 1 max_iter reached (return code 0, as for the refinement) | 2 breakdown: p^T A p <= 0
+ *     or r^T M^-1 r <= 0 -- the values in force are not positive definite, or the factor is broken; x keeps the last iterate | 3 NaN or inf.  Status 2 or 3
+ *     in any column: CHOLAMD_ERR_ARG after ALL columns have been worked on, cholamd_last_error names the first such column and the quantity.  b = 0: x = 0,
+ *     0 iterations, relres 0, status 0.  The calls synchronise `stream` once per iteration (one read-back of the columns' states); every scalar of the
+ *     iteration stays in device memory.  Workspaces (five n x 32 blocks, partial sums, the records) belong to the device object and are allocated at the
+ *     first call; ONE CALL AT A TIME per device object.  The blocks have their full width of 32 columns whatever nrhs is, the one-vector forms included (with
+ *     the residual block they share with cholamd_solve_refine_nrhs: 6 * 32 * 8 n bytes, 1.5 GB at n = 10^6), so that no later call allocates; cholamd_apply /
+ *     _nrhs need the CSR operator alone.  A column that has finished stays in its chunk's launches until the chunk ends (alpha = beta = 0 select no write):
+ *     a chunk costs what its slowest column costs.
+ *     Arguments: those of cholamd_solve_nrhs (nrhs == 0 returns 0 and touches nothing; nrhs < 0, a small ld, a NULL pointer with nrhs > 0: CHOLAMD_ERR_ARG),
+ *     unknown flags, tol negative or not finite: CHOLAMD_ERR_ARG, nothing written.  Columns go in chunks of 32; a chunk's loop ends when none of its columns runs.
+ *     SCOPE: the complete factor -- a single-GPU device object, or rank 0 after a gather; another rank of a partitioned object: CHOLAMD_ERR_ARG.  Follow-ups,
+ *     not here: low-rank objects (cholamd_lowrank_*), the sharded and multi-rank forms, autograd.
+ *   BITS.  The vector kernels have one owner per element, no atomics, and sum in a fixed order, so the loop is as reproducible as the solve inside it:
+ *     (a) option solve_deterministic: two calls return the same iters, relres, status and bits of x;
+ *     (b) solve_deterministic without solve_deterministic_block: column j of an _nrhs call has the bits and the iteration count of the one-vector call on it;
+ *     (c) both options: column j depends on column j of B alone (and of X under CHOLAMD_PCG_X0) -- not on nrhs, on its chunk, or on a NaN next to it;
+ *     (d) on the atomic solve paths nothing is promised beyond the tolerances. */
+#define CHOLAMD_PCG_X0 1
+int cholamd_apply(cholamd_device *d, const double *d_x, double *d_y, void *stream);
+int cholamd_apply_nrhs(cholamd_device *d, const double *d_X, int64_t ldx, double *d_Y, int64_t ldy, int nrhs, void *stream);
+int cholamd_plan_apply_host(const cholamd_plan *p, const double *values /* or NULL */, const double *x, double *y);
+int cholamd_solve_pcg(cholamd_device *d, const double *d_arena, const double *d_b, double *d_x, int max_iter, double tol, int flags,
+                      int *iters_out, double *relres_out, int *status_out, void *stream);
+int cholamd_solve_pcg_f32(cholamd_device *d, const float *d_arena32, const double *d_b, double *d_x, int max_iter, double tol, int flags,
+                          int *iters_out, double *relres_out, int *status_out, void *stream);
+int cholamd_solve_pcg_nrhs(cholamd_device *d, const double *d_arena, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int nrhs, int max_iter, double tol, int flags,
+                           int *iters_out, double *relres_out, int *status_out, void *stream);
+int cholamd_solve_pcg_nrhs_f32(cholamd_device *d, const float *d_arena32, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int nrhs, int max_iter, double tol, int flags,
+                               int *iters_out, double *relres_out, int *status_out, void *stream);
 /* ---- one triangular half of the solve, the factor's diagonal and log det A (not in the reference; CHOLMOD's CHOLMOD_L / CHOLMOD_Lt systems and the logdet
  * every sparse Cholesky offers).  THE SQUARE ROOT these calls speak about is M = P^T L P in ORIGINAL dof order (P the plan's permutation, L the factor in
  * the arena): M M^T = A, A^-1 = M^-T M^-1, and no caller ever sees permuted coordinates.  M y = b whitens b (b^T A^-1 b = ||y||^2); M^T x = z turns white
