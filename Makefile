@@ -13,7 +13,12 @@ HIPFLAGS:= -O3 -fPIC --offload-arch=$(ARCH) -Iinclude -I$(CSRC) -Wall
 $(OUT)/chol_kernels.o: KERNFLAGS := -mllvm -pragma-unroll-threshold=100000
 
 HOST_OBJS := $(OUT)/chol_ingest.o $(OUT)/chol_symbolic.o $(OUT)/chol_schedule.o $(OUT)/chol_generate.o $(OUT)/chol_lowrank_host.o
-HIP_OBJS  := $(OUT)/chol_kernels.o $(OUT)/chol_kernels_f32.o $(OUT)/chol_solve_nrhs.o $(OUT)/chol_factor_query.o $(OUT)/chol_selinv.o $(OUT)/chol_schur.o $(OUT)/chol_multiply.o $(OUT)/chol_multiply_nrhs.o $(OUT)/chol_solve_det.o $(OUT)/chol_lowrank.o $(OUT)/chol_values_grad.o $(OUT)/chol_pcg.o $(OUT)/chol_api.o
+KERNEL_OBJS := $(OUT)/chol_kernels.o $(OUT)/chol_kernels_f32.o $(OUT)/chol_solve_nrhs.o $(OUT)/chol_factor_query.o $(OUT)/chol_selinv.o $(OUT)/chol_schur.o $(OUT)/chol_multiply.o $(OUT)/chol_multiply_nrhs.o $(OUT)/chol_solve_det.o $(OUT)/chol_lowrank.o $(OUT)/chol_values_grad.o $(OUT)/chol_pcg.o
+# the C-ABI glue: one file per family of entry points over the internal header chol_device.h
+GLUE      := chol_api chol_api_schur chol_api_blas chol_api_lowrank
+GLUE_HDRS := $(CSRC)/chol_device.h $(CSRC)/chol_devbuf.h $(CSRC)/chol_plan.h $(CSRC)/chol_kernels.h include/cholamd.h
+GLUE_OBJS := $(GLUE:%=$(OUT)/%.o)
+HIP_OBJS  := $(KERNEL_OBJS) $(GLUE_OBJS)
 
 all: $(OUT)/libcholamd.so $(BIN)/cholamd_mmat oracle
 
@@ -25,7 +30,7 @@ $(OUT)/%.o: $(CSRC)/%.hip $(CSRC)/chol_plan.h $(CSRC)/chol_kernels.h
 	@mkdir -p $(OUT)
 	$(HIPCC) $(HIPFLAGS) $(KERNFLAGS) -c $< -o $@
 
-$(OUT)/chol_api.o: $(CSRC)/chol_api.cpp $(CSRC)/chol_devbuf.h $(CSRC)/chol_plan.h $(CSRC)/chol_kernels.h include/cholamd.h
+$(GLUE_OBJS): $(OUT)/%.o: $(CSRC)/%.cpp $(GLUE_HDRS)
 	@mkdir -p $(OUT)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
@@ -54,10 +59,10 @@ ASAN_HOST_OBJS := $(ASAN_OUT)/chol_ingest.o $(ASAN_OUT)/chol_symbolic.o $(ASAN_O
 $(ASAN_OUT)/%.o: $(CSRC)/%.c $(CSRC)/chol_plan.h include/cholamd.h
 	@mkdir -p $(ASAN_OUT)
 	$(CC) $(CFLAGS) -O1 $(SAN) -c $< -o $@
-$(ASAN_OUT)/chol_api.o: $(CSRC)/chol_api.cpp $(CSRC)/chol_devbuf.h $(CSRC)/chol_plan.h $(CSRC)/chol_kernels.h include/cholamd.h
+$(GLUE:%=$(ASAN_OUT)/%.o): $(ASAN_OUT)/%.o: $(CSRC)/%.cpp $(GLUE_HDRS)
 	@mkdir -p $(ASAN_OUT)
 	$(HIPCC) $(HIPFLAGS) -O1 $(SAN) -fno-sanitize=function -fno-gpu-sanitize -x hip -c $< -o $@
-$(ASAN_OUT)/libcholamd.so: $(ASAN_HOST_OBJS) $(ASAN_OUT)/chol_api.o $(OUT)/chol_kernels.o $(OUT)/chol_kernels_f32.o $(OUT)/chol_solve_nrhs.o $(OUT)/chol_factor_query.o $(OUT)/chol_selinv.o $(OUT)/chol_schur.o $(OUT)/chol_multiply.o $(OUT)/chol_multiply_nrhs.o $(OUT)/chol_solve_det.o $(OUT)/chol_lowrank.o $(OUT)/chol_values_grad.o $(OUT)/chol_pcg.o
+$(ASAN_OUT)/libcholamd.so: $(ASAN_HOST_OBJS) $(GLUE:%=$(ASAN_OUT)/%.o) $(KERNEL_OBJS)
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) $(SAN) -fno-gpu-sanitize -o $@ $^ -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 # leak detection: ON, in a process of its own without an interpreter (tests/native/host_leak.c: plans, schedules of every level and
 # world size, the program builder and its self-check, the generator, error paths); the only suppression is the HIP runtime's own

@@ -1,174 +1,15 @@
 // C ABI glue of libcholamd: device objects, the level schedule, the task-level (fused_*) and the
 // BLAS-level entry points.  Compiled with hipcc; everything exported is extern "C" (include/cholamd.h).
 // There is no CPU fallback: every compute entry point needs a HIP device and fails loudly otherwise.
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
+#include "chol_device.h"
 
-#include <cstdio>
-#include <algorithm>
-#include <cstdlib>
-#include <cfloat>
-#include <cmath>
-#include <cctype>
-#include <cstring>
-#include <string>
-#include <type_traits>
-#include <vector>
-
-#include <atomic>
-#include "chol_devbuf.h"
-#include "chol_kernels.h"
-#include "chol_plan.h"
-#include "cholamd.h"
-
-#define HIPCHK(call)                                                                                  \
-  do {                                                                                                \
-    hipError_t e_ = (call);                                                                           \
-    if (e_ != hipSuccess) {                                                                           \
-      chol_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__);     \
-      return (e_ == hipErrorNoDevice || e_ == hipErrorInvalidDevice) ? CHOLAMD_ERR_NO_DEVICE : CHOLAMD_ERR_HIP; \
-    }                                                                                                 \
-  } while (0)
-
-struct pinned_words { // pinned host memory, owned like a dev_buf: where status words are read back to
-  int64_t *p = nullptr;
-  pinned_words() = default; pinned_words(const pinned_words &) = delete; pinned_words &operator=(const pinned_words &) = delete;
-  ~pinned_words() { if (p) (void)hipHostFree(p); }
-  operator int64_t *() const { return p; }
-  int ensure(size_t n) { if (!p) HIPCHK(hipHostMalloc((void **)&p, n * sizeof(int64_t))); return 0; }
-};
-struct sum_desc;
-
-struct level_dev {
-  int n_potrf = 0, n_trsm = 0, n_task = 0, n_src = 0;
-  std::vector<chol_phase> phase; // launches of the level in order (big pivots are factored in column blocks)
-  dev_buf<chol_potrf_desc> potrf; dev_buf<chol_trsm_desc> trsm; // (potrf: with the role tables behind the descriptors, upload_level)
-  dev_buf<chol_upd_task> task, task_mt; dev_buf<chol_upd_src> src;
-  std::vector<chol_bcast> bcast;  // distributed top levels: the column blocks a phase of kind 6 broadcasts
-};
-struct solve_dev {
-  int n_trsv = 0, n_grp = 0, n_fw = 0, n_bw = 0;
-  dev_buf<chol_trsv_desc> trsv; dev_buf<chol_gemv_desc> fw, bw;
-  dev_buf<int> grp_start, grp_rows, bw_start;
-  int n_ifw = 0, n_ibw = 0, max_n = 0, max_under = 0;
-  int64_t w256_off = -1; // this level's explicit span inverses in cholamd_device::w256 (levels of at most 8 separators wider than a span); -1: none
-  dev_buf<int> ifw, ibw;
-};
-struct selinv_dev { // the lists of one tree level of the selected inversion (chol_selinv_level) on the device
-  std::vector<chol_selinv_sep> host; // the separator descriptors, for the launch geometry of every step
-  dev_buf<chol_selinv_sep> sep; dev_buf<chol_selinv_tile> tile;
-  dev_buf<int> chain_ld, chain_pos0; dev_buf<int64_t> rowoff;
-  int max_nblk = 0;
-};
-struct schur_dev { dev_buf<chol_schur_desc> desc; int64_t n = -1; }; // n < 0: not built yet
-// deterministic step lists (chol_sdet_lists: the whole tree's, or those of condense / expand cut at k kept levels) on the device; the steps stay on the
-// host: they are the launch sequence
-struct sdet_dev { dev_buf<chol_mul_item> item[2]; dev_buf<chol_mul_src> src[2]; std::vector<chol_sdet_step> step[2]; bool ready = false; };
-struct timed_launch { hipEvent_t a, b; int kind; };
-
-struct cholamd_device {
-  struct vmm_arena { void *va; size_t total; std::vector<hipMemGenericAllocationHandle_t> handles; };
-  std::vector<vmm_arena> vmm; // sharded arenas of this rank (cholamd_device_alloc_arena)
-
-  const cholamd_plan *plan = nullptr;
-  int dev = 0, rank = 0, world = 1;
-  std::vector<level_dev> lv;
-  std::vector<solve_dev> sv;
-  bool solve_ready = false;
-  int solve_rank = 0, solve_world = 1; // the partition the solve lists were built for
-  dev_buf<int> zr_sub; int n_zr_sub = 0; // distributed solve: (offset, length) ranges of the permuted vector this rank starts from zero in (other ranks' subtrees; the shared top on ranks other than 0)
-  dev_buf<double> ws;
-  dev_buf<double> ws_solve; // 16x16 inverses of the diagonal blocks of the arena being solved with
-  dev_buf<int> step_flags;     // flags of the step launches of the wide top separators' span chains (k_solve_step): one per separator of a level, 64 ints
-  int step_gen = 0;           // ... and the number of the last such launch (a flag equal to it: the launch's span is solved)
-  dev_buf<double> w256;       // explicit inverses of the 256-column diagonal spans of the wide top separators (k_solve_inv256, recomputed with the 16x16 inverses)
-  dev_buf<double> step_xt;    // 8 x 256 doubles: a step launch's x_k before it replaces the right-hand side
-  bool keep_inverses = false; // the correction solves of a refinement: same factor as the solve before them, its diagonal inverses (16x16, spans) are kept
-  dev_buf<int> info;        // [0] first failing column, [1] separator; two slots of two ints: the program launch alternates between them (each launch clears the other
-                            // one for the next: no memset node per factorisation), every other path uses slot 0
-  int *info_last = nullptr; // the slot of the most recent factorisation (cholamd_factor_info)
-  int info_parity = 0; bool info_foreign = false; // program path: slot of the next launch; slot 0 was used by another path since
-  dev_buf<int> progress;    // fused launches: columns published per pivot block (epoch * 64 + columns); [nsep + 1] = TRSM workgroups finished
-  int epoch = 0, done_total = 0;
-  dev_buf<int64_t> a_dst; dev_buf<double> a_val; dev_buf<int> perm; dev_buf<double> ytmp;
-  // distributed top levels: the entries of A in the column blocks of the shared top THIS rank owns ([0]: by the fp64 schedule's blocks, [1]: the fp32 one's)
-  // top_val is gathered on the device from a_val through top_e (the entries' positions in the scatter list), so that it follows cholamd_device_set_values
-  dev_buf<int64_t> top_dst[2]; dev_buf<double> top_val[2]; dev_buf<int> top_e[2]; int64_t top_n[2] = { 0, 0 }; int top_gen[2] = { -1, -1 };
-  // new values of A (cholamd_device_set_values): the index lists of the gather and the entries' classes (uploaded at the first call), the status words of
-  // the last call on the device ([4]), their start values ([4], device) and where they are read back to (pinned host, two slots of four)
-  dev_buf<int> a_src, csr_src; dev_buf<unsigned char> e_cls;
-  dev_buf<int> e_row, e_col; // the entry list itself (cholamd_values_grad_pairs / _logdet: uploaded at the first call)
-  dev_buf<int64_t> vs_dev, vs_init; pinned_words vs_host;
-  int64_t vs_last[4] = { 0, 0, 0, 0 };  // the last call's status words as read back
-  bool vs_called = false, vs_last_valid = false;
-  bool vs_in_force = false; // the values in force come from set_values: the fp32 range verdict comes from the status words, not from the plan's values
-  bool f32_pending = false; // ... and has not been read back yet (the last call was asynchronous)
-  bool timing = false;
-  std::vector<timed_launch> tl;
-  std::vector<hipEvent_t> pool;
-  // the one-launch program of the whole factorisation (single GPU, small problems: chol_build_program / k_program)
-  level_dev prog;
-  dev_buf<chol_job> jobs; dev_buf<chol_wait> pwaits; dev_buf<chol_ext> exts;
-  dev_buf<int> pctr, pctr_total; // counters (last one: the queue head) and what one factorisation adds to each
-  int n_job = 0, n_pctr = 0, prog_grid = 0, prog_epoch = 0, prog_epoch_limit = 0;
-  bool prog_ready = false;
-  unsigned long long *trace = nullptr; // diagnostic: per-job clock stamps of the next program launches (cholamd_device_program_trace, which owns them)
-  std::vector<chol_job> jobs_host;
-  // mixed precision (fp32 factor + fp64 refinement): work lists of the fp32 kernels, their workspace, A as a device CSR
-  std::vector<level_dev> lv32;
-  dev_buf<float> ws32;
-  int f32_range = -1; int64_t f32_bad = -1; // A's entries all zero or normal floats (1), or not (0: f32_bad = the first entry that is not); -1: not checked yet
-  dev_buf<int64_t> csr_ptr; dev_buf<int> csr_col; dev_buf<double> csr_val;
-  dev_buf<double> rvec, dxvec, partial;
-  // extend-add exchange under the distributed top levels: staging of the copies received for the owned column blocks, descriptors of the sum
-  dev_buf<char> xstage; size_t xstage_bytes = 0; dev_buf<sum_desc> xdesc; int xdesc_gen = -1, xdesc_elem = 0, sched_gen = 0;
-  // switches, read from the environment once at cholamd_device_create (cholamd_device_set_option changes them later)
-  chol_sched_opts opt;
-  bool solve_reference_shape = false; // cholamd_solve with the per-call (deterministic) kernels of the BLAS-level entry points
-  // option solve_deterministic: the streamed sweeps with owner gathers in place of the atomic kernels (chol_solve_det.hip).  The step lists of both
-  // directions (chol_sdet_lists) are built and uploaded at the first such solve
-  bool solve_deterministic = false;
-  // option solve_deterministic_block: under solve_deterministic (and without solve_reference_shape) the _nrhs entry points take the deterministic BLOCK path
-  // (solve_nrhs_t with the same step lists on chunks of 32 columns) instead of going column by column; no effect otherwise
-  bool solve_deterministic_block = false;
-  sdet_dev sdet;
-  // block solve (cholamd_solve_nrhs): the permuted block of one chunk (n x CHOL_NRHS_W, row-major); refinement: the chunk's right-hand sides, residual and
-  // correction (n x CHOL_NRHS_W, column-major) and the per-column partial sums of the residual kernel
-  dev_buf<double> ynrhs, bnrhs, rnrhs, dxnrhs, pnrhs;
-  // factor queries (cholamd_factor_diag / _logdet): the TRSV descriptors of the whole tree in one list ordered by permuted position and the prefix of their
-  // column counts (built with the solve lists of rank 0 of 1); the logdet's per-workgroup partial sums, their integer companions and the three result words
-  dev_buf<chol_trsv_desc> dg_desc; dev_buf<int> dg_prefix; int n_dg = 0;
-  dev_buf<double> ld_part; dev_buf<int64_t> ld_ipart, ld_res;
-  // selected inversion (cholamd_selinv): the gather lists of every level and the workspace of the widest level, built at the first call
-  std::vector<selinv_dev> si; dev_buf<double> si_ws; bool si_ready = false;
-  // Schur complement (cholamd_schur): the gather kernel's piece list per number of kept levels k (index k), uploaded at the first call with that k
-  std::vector<schur_dev> sc;
-  // option schur_deterministic: condense / expand (single vector and _nrhs) walk the step lists cut at k (index k), built and uploaded at the first such
-  // call with that k.  schur_launches: { atomic sweep, deterministic gather, deterministic span, pack / unpack } launches of the Schur sweeps so far
-  bool schur_deterministic = false;
-  std::vector<sdet_dev> scd;
-  int64_t schur_launches[4] = { 0, 0, 0, 0 };
-  // forward products (cholamd_multiply_half / cholamd_multiply / cholamd_factor_residual): the owner lists of the whole tree per direction, uploaded at the
-  // first call; the intermediate vector of cholamd_multiply (permuted coordinates); the residual's per-workgroup partial sums and result words
-  dev_buf<chol_mul_item> mul_item[2]; dev_buf<chol_mul_src> mul_src[2]; int n_mul_item[2] = { 0, 0 }; bool mul_ready = false;
-  dev_buf<double> mvec, mr_part; dev_buf<int64_t> mr_ipart, mr_res;
-  // their block form (cholamd_multiply_half_nrhs / cholamd_multiply_nrhs): the two permuted blocks of one chunk (n x CHOL_NRHS_W, row-major), allocated at the
-  // first chunk that takes the block kernel; option multiply_nrhs_min: chunks of fewer columns go column by column (<= 0: the measured default)
-  dev_buf<double> mznrhs, mwnrhs;
-  int multiply_nrhs_min = 0;
-  // preconditioned conjugate gradients (cholamd_solve_pcg*): the chunk's right-hand sides, p, q, r, z (n x CHOL_NRHS_W, column-major), one partial per
-  // (column, workgroup), the columns' scalar records and where they are read back to; allocated at the first call
-  dev_buf<double> pcg_b, pcg_p, pcg_q, pcg_r, pcg_z, pcg_part;
-  dev_buf<chol_pcg_rec> pcg_rec; pinned_words pcg_host;
-};
-
-static int no_device_error()
+int no_device_error()
 {
   chol_set_error("no usable HIP device (libcholamd has no CPU fallback)");
   return CHOLAMD_ERR_NO_DEVICE;
 }
 // do [a, a + na) and [b, b + nb) share a byte?  (the argument checks of the gradients, the products and the Schur entry points)
-static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
+bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
 {
   const char *pa = (const char *)a, *pb = (const char *)b;
   return pa < pb + nb && pb < pa + na;
@@ -570,24 +411,13 @@ extern "C" int cholamd_device_free_arena(cholamd_device *d, void *dptr)
 }
 
 // ---- timing helpers -------------------------------------------------------------------------
-static hipEvent_t get_event(cholamd_device *d)
+hipEvent_t get_event(cholamd_device *d)
 {
   if (!d->pool.empty()) { hipEvent_t e = d->pool.back(); d->pool.pop_back(); return e; }
   hipEvent_t e;
   (void)hipEventCreate(&e);
   return e;
 }
-struct scoped_timer {
-  cholamd_device *d; hipStream_t st; int kind; hipEvent_t a{}, b{}; bool on;
-  scoped_timer(cholamd_device *d_, hipStream_t st_, int kind_, bool active) : d(d_), st(st_), kind(kind_), on(d_->timing && active)
-  {
-    if (on) { a = get_event(d); b = get_event(d); (void)hipEventRecord(a, st); }
-  }
-  ~scoped_timer()
-  {
-    if (on) { (void)hipEventRecord(b, st); d->tl.push_back({ a, b, kind }); }
-  }
-};
 
 extern "C" int cholamd_device_set_timing(cholamd_device *d, int on)
 {
@@ -734,7 +564,7 @@ __global__ void k_zero_ranges(double *y, const int *ranges, int nr)
 }
 // the solve lists of the whole tree (rank 0 of 1: cholamd_solve / cholamd_solve_refine, also on a partitioned device whose arena holds the gathered
 // factor) or of one rank's share (the distributed solve); one set is kept, rebuilt when the other is asked for
-static int build_solve(cholamd_device *d, int rank = 0, int world = 1)
+int build_solve(cholamd_device *d, int rank, int world)
 {
   const int L = d->plan->levels;
   if (d->solve_ready && d->solve_rank == rank && d->solve_world == world) return 0;
@@ -802,27 +632,13 @@ static int build_solve(cholamd_device *d, int rank = 0, int world = 1)
 
 // first position of the shared top of the tree in the permuted vector (the separators above the cut are the last labels: a contiguous tail, as in the arena)
 static int64_t top_vec_offset(const cholamd_device *d) { return d->solve_world > 1 ? d->plan->sep_off[d->plan->nsep - (d->solve_world - 1) + 1] : d->plan->n; }
-struct keep_inverses_scope { // set on the devices of a refinement after its first solve, cleared on every way out
-  cholamd_device *const *devs; int n;
-  keep_inverses_scope(cholamd_device *const *devs_, int n_) : devs(devs_), n(n_) { for (int g = 0; g < n; g++) devs[g]->keep_inverses = true; }
-  ~keep_inverses_scope() { for (int g = 0; g < n; g++) devs[g]->keep_inverses = false; }
-};
 template <class TL> static int lsolve_trsv(cholamd_device *d, const TL *a, const chol_trsv_desc *t, int n, int mx, int mu, const double *W, double *y, int bw, const double *W256, hipStream_t st)
 { return chol_launch_solve_trsv(a, t, n, mx, mu, W, y, bw, d->step_flags, &d->step_gen, W256, d->step_xt, st); } // (the step launches' flags, counter and scratch are the device object's)
 // ---- the sweep helpers: every solve, half solve and Schur condense / expand below is a composition of these ----
-// which sweeps a body runs: one CHOLAMD_HALF_* sweep alone, or FORWARD then BACKWARD (the products: BACKWARD then FORWARD)
-#define CHOL_BOTH_SWEEPS (-1)
-// what a sweep works on: the permuted vector (n doubles), or the permuted row-major block of one chunk (n x CHOL_NRHS_W) with the chol_nrhs_* kernels
-struct sweep_rhs { double *y; bool block; };
-struct keep_restore { // keep_inverses for the chunks of one call, the caller's value back on every way out
-  cholamd_device *d; bool old;
-  explicit keep_restore(cholamd_device *d_) : d(d_), old(d_->keep_inverses) {}
-  ~keep_restore() { d->keep_inverses = old; }
-};
 // The inverses of the diagonal blocks of the levels lvl_lo .. levels - 1 from THIS arena (the factorisation's workspace belongs to the last arena factored): the
 // 16x16 ones, and with_spans the explicit span inverses of the wide top separators -- the atomic kernels read them, the deterministic ones do not.  The
 // caller decides whether they are due (keep_inverses; once per call in the block forms).
-template <class TL> static int form_inverses(cholamd_device *d, const TL *d_arena, int lvl_lo, bool with_spans, hipStream_t st)
+template <class TL> int form_inverses(cholamd_device *d, const TL *d_arena, int lvl_lo, bool with_spans, hipStream_t st)
 {
   for (int lvl = lvl_lo; lvl < d->plan->levels; lvl++) {
     const solve_dev &s = d->sv[lvl];
@@ -833,7 +649,7 @@ template <class TL> static int form_inverses(cholamd_device *d, const TL *d_aren
 }
 // One sweep of the atomic kernels over the levels lvl_lo .. lvl_hi.  Forward (mmat.rg:1395-1435) from lvl_hi down: TRSV per separator, then its panel into
 // the ancestors; backward (mmat.rg:1438-1479) from lvl_lo up: gather from the ancestors, then TRSV^T.  count (the Schur sweeps): 2 more per level.
-template <class TL> static int sweep_levels(cholamd_device *d, const TL *d_arena, sweep_rhs rhs, bool backward, int lvl_lo, int lvl_hi, int64_t *count, hipStream_t st)
+template <class TL> int sweep_levels(cholamd_device *d, const TL *d_arena, sweep_rhs rhs, bool backward, int lvl_lo, int lvl_hi, int64_t *count, hipStream_t st)
 {
   for (int i = 0; i <= lvl_hi - lvl_lo; i++) {
     const solve_dev &s = d->sv[backward ? lvl_lo + i : lvl_hi - i];
@@ -854,7 +670,7 @@ template <class TL> static int sweep_levels(cholamd_device *d, const TL *d_arena
 }
 // One sweep (q: CHOLAMD_HALF_*) of deterministic step lists: per step one gather launch where the step has items and one span launch where it has a span
 // (the kept lead step of the cut lists, level -1, is a gather alone).  counts (the Schur sweeps): a gather adds to [1], a span to [2].
-template <class TL> static int sweep_steps(cholamd_device *d, const TL *d_arena, const sdet_dev &c, int q, sweep_rhs rhs, int64_t *counts, hipStream_t st)
+template <class TL> int sweep_steps(cholamd_device *d, const TL *d_arena, const sdet_dev &c, int q, sweep_rhs rhs, int64_t *counts, hipStream_t st)
 {
   const chol_mul_item *items = c.item[q];
   for (const chol_sdet_step &t : c.step[q]) {
@@ -906,7 +722,7 @@ template <class TL> static int solve_phase(cholamd_device *d, const TL *d_arena,
 // The deterministic sweeps (option solve_deterministic; include/cholamd.h at "deterministic solve"): the step lists of chol_sdet_lists walked by sweep_steps
 // in place of the atomic kernels.  They need the solve lists of the whole tree (the spans' TRSV descriptors per level) and the 16x16 inverses alone.
 // ---------------------------------------------------------------------------------------------
-static int upload_sdet(sdet_dev &q, const chol_sdet_lists &w)
+int upload_sdet(sdet_dev &q, const chol_sdet_lists &w)
 {
   int rc = 0;
   for (int c = 0; c < 2 && !rc; c++) { // (an upload replaces what a call that failed half-way left)
@@ -1012,9 +828,22 @@ extern "C" int cholamd_solve_half_f32(cholamd_device *d, const float *d_arena32,
 // Mixed precision (BASELINE config 5): fp32 factor, fp64 iterative refinement of the solve.
 // The fp32 arena has the element layout of the fp64 one (cholamd_plan_arena_doubles() floats).
 // ---------------------------------------------------------------------------------------------
+static void take_f32_verdict(cholamd_device *d, const int64_t *status)
+{
+  d->f32_range = status[0] == 0; d->f32_bad = status[0] ? status[1] : -1; d->f32_pending = false;
+}
+// the status words of the last (asynchronous) call, which are those of the values in force: one synchronisation of `st`
+static int read_values_status(cholamd_device *d, hipStream_t st)
+{
+  HIPCHK(hipMemcpyAsync(d->vs_host, d->vs_dev, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  std::memcpy(d->vs_last, d->vs_host, sizeof d->vs_last);
+  d->vs_last_valid = true;
+  take_f32_verdict(d, d->vs_last);
+  return 0;
+}
 // the fp32 factor converts A to float: an entry beyond FLT_MAX would become inf, one below FLT_MIN a denormal or zero, and the pivot checks do not see
 // what that does to the factor.  Such a matrix is refused (include/cholamd.h); checked once per device object.
-static int read_values_status(cholamd_device *d, hipStream_t st);
 static int f32_range_ok(cholamd_device *d, hipStream_t st)
 {
   const cholamd_plan *p = d->plan;
@@ -1098,20 +927,6 @@ static int ensure_values(cholamd_device *d)
   if (!rc) rc = d->vs_host.ensure(8);
   if (!rc) rc = d->vs_dev.alloc(4);
   return rc;
-}
-static void take_f32_verdict(cholamd_device *d, const int64_t *status)
-{
-  d->f32_range = status[0] == 0; d->f32_bad = status[0] ? status[1] : -1; d->f32_pending = false;
-}
-// the status words of the last (asynchronous) call, which are those of the values in force: one synchronisation of `st`
-static int read_values_status(cholamd_device *d, hipStream_t st)
-{
-  HIPCHK(hipMemcpyAsync(d->vs_host, d->vs_dev, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  std::memcpy(d->vs_last, d->vs_host, sizeof d->vs_last);
-  d->vs_last_valid = true;
-  take_f32_verdict(d, d->vs_last);
-  return 0;
 }
 extern "C" int cholamd_device_set_values(cholamd_device *d, const double *d_vals, int64_t count, int flags, void *stream)
 {
@@ -1250,7 +1065,7 @@ static int block_check(cholamd_device *d, bool with_arena, const void *arena, co
   if (no_arena || !B || !X) { chol_set_error("%s: NULL %s", what, no_arena ? "arena" : !B ? in : out); return CHOLAMD_ERR_ARG; }
   return 0;
 }
-static int nrhs_check(cholamd_device *d, const void *arena, const double *B, int64_t ldb, const double *X, int64_t ldx, int nrhs, const char *what, const char *in = "B", const char *out = "X")
+int nrhs_check(cholamd_device *d, const void *arena, const double *B, int64_t ldb, const double *X, int64_t ldx, int nrhs, const char *what, const char *in, const char *out)
 {
   return block_check(d, true, arena, B, ldb, X, ldx, nrhs, what, in, out);
 }
@@ -1258,9 +1073,6 @@ static int nrhs_check(cholamd_device *d, const void *arena, const double *B, int
 // chunk of fewer columns than this is solved column by column with the single-vector path.  Measured on one MI355X: a block chunk
 // takes 3.0 - 3.3 single fp64 solves and 5.0 single fp32-factor solves.
 template <class TL> static constexpr int nrhs_min_block() { return sizeof(TL) == sizeof(double) ? 4 : 6; }
-// The same rule for one triangular half (cholamd_solve_half_nrhs): a half chunk and a half single solve both drop one of the two sweeps.  DESIGN.md section 10
-// records the measurement behind the value.
-template <class TL> static constexpr int half_nrhs_min_block() { return sizeof(TL) == sizeof(double) ? 4 : 6; }
 // The block body: the diagonal inverses once per call (a caller that keeps them: not at all), then chunk by chunk the permute into the row-major block, the
 // sweeps `which` of the whole tree with the chol_nrhs_* kernels, and the permute back.
 //   det = false: the atomic kernels; a chunk under the threshold goes column by column through solve_t, which reuses the call's inverses
@@ -1663,262 +1475,6 @@ extern "C" int cholamd_factor_residual(cholamd_device *d, const double *d_arena,
 extern "C" int cholamd_factor_residual_f32(cholamd_device *d, const float *d_arena32, const double *d_z, double *rel_out, void *stream)
 { return factor_residual_t(d, d_arena32, d_z, rel_out, (hipStream_t)stream, "cholamd_factor_residual_f32"); }
 
-// ---------------------------------------------------------------------------------------------
-// Schur complement on the top k levels of the tree (include/cholamd.h at cholamd_schur; the gather kernel in chol_schur.hip).  The factorisation is
-// right-looking: after the levels levels - 1 .. k every contribution of the eliminated separators sits in the blocks of the kept ones, which then hold
-// S = A_TT - A_TI A_II^-1 A_IT.  Condense and expand are the streamed solve cut at level k instead of at the partition's level: the same launches over
-// a level range, the levels above the cut never read as a factor.
-// ---------------------------------------------------------------------------------------------
-// the checks every Schur entry point shares; returns m (the kept dofs) and *t0 = n - m, or the error
-static int schur_args(const cholamd_device *d, int k, const char *what, int *t0)
-{
-  if (!d) { chol_set_error("%s: NULL device", what); return CHOLAMD_ERR_ARG; }
-  if (d->world > 1) { chol_set_error("%s: the device object is partitioned (rank %d of %d); there are no sharded variants", what, d->rank, d->world); return CHOLAMD_ERR_ARG; }
-  return chol_schur_range(d->plan, k, t0);
-}
-extern "C" int cholamd_schur_factor(cholamd_device *d, double *d_arena, int k, void *stream)
-{
-  const int m = schur_args(d, k, "cholamd_schur_factor", nullptr);
-  if (m < 0) return m;
-  if (!d_arena) { chol_set_error("cholamd_schur_factor: NULL arena"); return CHOLAMD_ERR_ARG; }
-  return cholamd_factor_levels(d, d_arena, d->plan->levels - 1, k, stream); // the per-level launches, never the program
-}
-static int build_schur(cholamd_device *d, int k)
-{
-  if (d->sc.empty()) d->sc.resize(d->plan->levels);
-  schur_dev &q = d->sc[k];
-  if (q.n >= 0) return 0;
-  const int64_t cnt = chol_schur_pieces(d->plan, k, 1, CHOL_SCHUR_CHUNK, 0, nullptr);
-  if (cnt < 0) return (int)cnt;
-  std::vector<chol_schur_desc> h((size_t)cnt);
-  chol_schur_pieces(d->plan, k, 1, CHOL_SCHUR_CHUNK, cnt, h.data());
-  int rc = q.desc.upload(h.data(), (size_t)cnt);
-  if (rc) return rc;
-  q.n = cnt;
-  return 0;
-}
-extern "C" int cholamd_schur(cholamd_device *d, const double *d_arena, int k, double *d_S, int64_t lds, void *stream)
-{
-  const int m = schur_args(d, k, "cholamd_schur", nullptr);
-  if (m < 0) return m;
-  if (!d_arena || !d_S) { chol_set_error("cholamd_schur: NULL %s", !d_arena ? "arena" : "S"); return CHOLAMD_ERR_ARG; }
-  if (lds < m) { chol_set_error("cholamd_schur: lds = %lld < m = %d", (long long)lds, m); return CHOLAMD_ERR_ARG; }
-  if (m == 0) return 0;
-  if (ranges_overlap(d_S, ((size_t)(m - 1) * (size_t)lds + (size_t)m) * sizeof(double), d_arena, (size_t)d->plan->arena * sizeof(double))) {
-    chol_set_error("cholamd_schur: S overlaps the arena");
-    return CHOLAMD_ERR_ARG;
-  }
-  HIPCHK(hipSetDevice(d->dev));
-  { int rc = build_schur(d, k); if (rc) return rc; }
-  HIPCHK((hipError_t)chol_launch_schur_gather(d_arena, d->sc[k].desc, d->sc[k].n, d_S, lds, (hipStream_t)stream));
-  return 0;
-}
-// ---- option schur_deterministic: the step lists cut at k (chol_build_schur_det), per (device object, k), built at the first such call and kept
-static int build_schur_det(cholamd_device *d, int k)
-{
-  if (d->scd.empty()) d->scd.resize(d->plan->levels);
-  if (d->scd[k].ready) return 0;
-  chol_sdet_lists w;
-  int rc = chol_build_schur_det(d->plan, k, &w);
-  if (rc) return rc;
-  rc = upload_sdet(d->scd[k], w);
-  chol_sdet_lists_free(&w);
-  return rc;
-}
-// Condense, expand and their block forms by the one option they read, through the three helpers below:
-//   schur_deterministic -> the step lists cut at k (sweep_steps), the 16x16 inverses of the levels under the cut alone; every chunk of a block takes them
-//   otherwise           -> the atomic kernels over the levels k .. levels - 1 (sweep_levels), the span inverses too; a chunk of a block under
-//                          half_nrhs_min_block goes column by column through the single-vector body
-// The levels above the cut hold S, not a factor: no inverse is formed there.  Every launch is counted in schur_launches.
-static int schur_build(cholamd_device *d, int k)
-{
-  int rc = build_solve(d);
-  if (!rc && d->schur_deterministic) rc = build_schur_det(d, k);
-  return rc;
-}
-template <class TL> static int schur_inverses(cholamd_device *d, const TL *d_arena, int k, hipStream_t st) { return form_inverses(d, d_arena, k, !d->schur_deterministic, st); }
-template <class TL> static int schur_sweep(cholamd_device *d, const TL *d_arena, int k, bool backward, sweep_rhs rhs, hipStream_t st)
-{
-  return d->schur_deterministic ? sweep_steps(d, d_arena, d->scd[k], backward ? CHOLAMD_HALF_BACKWARD : CHOLAMD_HALF_FORWARD, rhs, d->schur_launches, st)
-                                : sweep_levels(d, d_arena, rhs, backward, k, d->plan->levels - 1, &d->schur_launches[0], st);
-}
-// the single-vector bodies behind the checks (t0, m: chol_schur_range): the forward sweep under the cut in w, whose tail is g in Schur order ...
-template <class TL> static int schur_condense_t(cholamd_device *d, const TL *d_arena, int k, int t0, int m, const double *d_b, double *d_w, double *d_g, hipStream_t st)
-{
-  { int rc = schur_build(d, k); if (rc) return rc; }
-  const int n = d->plan->n;
-  HIPCHK((hipError_t)chol_launch_permute(d_b, d->perm, d_w, n, 0, st));
-  if (!d->keep_inverses) { int rc = schur_inverses(d, d_arena, k, st); if (rc) return rc; } // (kept: the column-by-column chunks of the block form)
-  { int rc = schur_sweep(d, d_arena, k, false, { d_w, false }, st); if (rc) return rc; }
-  if (m > 0) HIPCHK(hipMemcpyAsync(d_g, d_w + t0, (size_t)m * sizeof(double), hipMemcpyDeviceToDevice, st));
-  return 0;
-}
-// ... and the backward sweep under the cut from (w under the cut, xt above it); w stays as it is: the sweep runs in the device object's work vector
-template <class TL> static int schur_expand_t(cholamd_device *d, const TL *d_arena, int k, int t0, int m, const double *d_w, const double *d_xt, double *d_x, hipStream_t st)
-{
-  { int rc = schur_build(d, k); if (rc) return rc; }
-  const int n = d->plan->n;
-  double *y = d->ytmp;
-  if (t0 > 0) HIPCHK(hipMemcpyAsync(y, d_w, (size_t)t0 * sizeof(double), hipMemcpyDeviceToDevice, st));
-  if (m > 0) HIPCHK(hipMemcpyAsync(y + t0, d_xt, (size_t)m * sizeof(double), hipMemcpyDeviceToDevice, st));
-  if (!d->keep_inverses) { int rc = schur_inverses(d, d_arena, k, st); if (rc) return rc; } // as at the start of every half solve: the arena of the call before may have been another
-  { int rc = schur_sweep(d, d_arena, k, true, { y, false }, st); if (rc) return rc; }
-  HIPCHK((hipError_t)chol_launch_permute(y, d->perm, d_x, n, 1, st));
-  return 0;
-}
-template <class TL> static int schur_condense_api(cholamd_device *d, const TL *d_arena, int k, const double *d_b, double *d_w, double *d_g, hipStream_t st, const char *what)
-{
-  int t0 = 0;
-  const int m = schur_args(d, k, what, &t0);
-  if (m < 0) return m;
-  if (!d_arena || !d_b || !d_w || !d_g) { chol_set_error("%s: NULL %s", what, !d_arena ? "arena" : !d_b ? "b" : !d_w ? "w" : "g"); return CHOLAMD_ERR_ARG; }
-  const size_t nb = (size_t)d->plan->n * sizeof(double), mb = (size_t)m * sizeof(double), ab = (size_t)d->plan->arena * sizeof(TL);
-  if (ranges_overlap(d_w, nb, d_b, nb) || ranges_overlap(d_w, nb, d_g, mb) || ranges_overlap(d_g, mb, d_b, nb) || ranges_overlap(d_w, nb, d_arena, ab) ||
-      ranges_overlap(d_g, mb, d_arena, ab)) {
-    chol_set_error("%s: b, w, g and the arena must not overlap each other", what);
-    return CHOLAMD_ERR_ARG;
-  }
-  HIPCHK(hipSetDevice(d->dev));
-  return schur_condense_t(d, d_arena, k, t0, m, d_b, d_w, d_g, st);
-}
-template <class TL> static int schur_expand_api(cholamd_device *d, const TL *d_arena, int k, const double *d_w, const double *d_xt, double *d_x, hipStream_t st, const char *what)
-{
-  int t0 = 0;
-  const int m = schur_args(d, k, what, &t0);
-  if (m < 0) return m;
-  if (!d_arena || !d_w || !d_xt || !d_x) { chol_set_error("%s: NULL %s", what, !d_arena ? "arena" : !d_w ? "w" : !d_xt ? "xt" : "x"); return CHOLAMD_ERR_ARG; }
-  const size_t nb = (size_t)d->plan->n * sizeof(double), mb = (size_t)m * sizeof(double), ab = (size_t)d->plan->arena * sizeof(TL);
-  if (ranges_overlap(d_x, nb, d_w, nb) || ranges_overlap(d_x, nb, d_xt, mb) || ranges_overlap(d_x, nb, d_arena, ab)) {
-    chol_set_error("%s: x must not overlap w, xt or the arena", what);
-    return CHOLAMD_ERR_ARG;
-  }
-  HIPCHK(hipSetDevice(d->dev));
-  return schur_expand_t(d, d_arena, k, t0, m, d_w, d_xt, d_x, st);
-}
-extern "C" int cholamd_schur_condense(cholamd_device *d, const double *d_arena, int k, const double *d_b, double *d_w, double *d_g, void *stream)
-{ return schur_condense_api(d, d_arena, k, d_b, d_w, d_g, (hipStream_t)stream, "cholamd_schur_condense"); }
-extern "C" int cholamd_schur_condense_f32(cholamd_device *d, const float *d_arena32, int k, const double *d_b, double *d_w, double *d_g, void *stream)
-{ return schur_condense_api(d, d_arena32, k, d_b, d_w, d_g, (hipStream_t)stream, "cholamd_schur_condense_f32"); }
-extern "C" int cholamd_schur_expand(cholamd_device *d, const double *d_arena, int k, const double *d_w, const double *d_xt, double *d_x, void *stream)
-{ return schur_expand_api(d, d_arena, k, d_w, d_xt, d_x, (hipStream_t)stream, "cholamd_schur_expand"); }
-extern "C" int cholamd_schur_expand_f32(cholamd_device *d, const float *d_arena32, int k, const double *d_w, const double *d_xt, double *d_x, void *stream)
-{ return schur_expand_api(d, d_arena32, k, d_w, d_xt, d_x, (hipStream_t)stream, "cholamd_schur_expand_f32"); }
-
-// ---- block forms (include/cholamd.h at cholamd_schur_condense_nrhs): chunks of CHOL_NRHS_W columns through the permuted row-major block ynrhs; the pack /
-// unpack kernels of chol_schur.hip stand where the block solve has its permutes.  a, b, c: the call's three blocks with their rows and names
-struct schur_blk { const double *p; int64_t ld; int rows; const char *name; };
-static size_t blk_bytes(const schur_blk &x, int nrhs) { return ((size_t)(nrhs - 1) * (size_t)x.ld + (size_t)x.rows) * sizeof(double); }
-static int schur_nrhs_args(const cholamd_device *d, const void *arena, int k, const schur_blk (&x)[3], int nrhs, const char *what, int *t0)
-{ // m, or the error; *t0 < 0: nothing to do
-  const int m = schur_args(d, k, what, t0);
-  if (m < 0) return m;
-  if (nrhs < 0) { chol_set_error("%s: nrhs = %d < 0", what, nrhs); return CHOLAMD_ERR_ARG; }
-  for (const schur_blk &b : x)
-    if (b.ld < (b.rows == 0 ? m : b.rows)) { chol_set_error("%s: leading dimension of %s = %lld is less than its %d rows", what, b.name, (long long)b.ld, b.rows == 0 ? m : b.rows); return CHOLAMD_ERR_ARG; }
-  if (nrhs == 0) { *t0 = -1; return m; }
-  if (!arena) { chol_set_error("%s: NULL arena", what); return CHOLAMD_ERR_ARG; }
-  for (const schur_blk &b : x) if (!b.p) { chol_set_error("%s: NULL %s", what, b.name); return CHOLAMD_ERR_ARG; }
-  return m;
-}
-// what both block forms do between their checks and their chunks: the device, the lists, the chunk's block, and the inverses once per call -- whatever
-// keep_inverses says; it is then set for the column-by-column chunks (keep_restore in the callers)
-template <class TL> static int schur_nrhs_begin(cholamd_device *d, const TL *d_arena, int k, hipStream_t st)
-{
-  HIPCHK(hipSetDevice(d->dev));
-  int rc = schur_build(d, k);
-  if (!rc) rc = d->ynrhs.ensure((size_t)d->plan->n * CHOL_NRHS_W);
-  if (!rc) rc = schur_inverses(d, d_arena, k, st);
-  return rc;
-}
-template <class TL> static int schur_condense_nrhs_api(cholamd_device *d, const TL *d_arena, int k, const double *d_B, int64_t ldb, double *d_W, int64_t ldw, double *d_G, int64_t ldg,
-                                                       int nrhs, hipStream_t st, const char *what)
-{
-  if (!d) { chol_set_error("%s: NULL device", what); return CHOLAMD_ERR_ARG; }
-  const int n = d->plan->n;
-  int t0 = 0;
-  schur_blk x[3] = { { d_B, ldb, n, "B" }, { d_W, ldw, n, "W" }, { d_G, ldg, 0, "G" } };
-  const int m = schur_nrhs_args(d, d_arena, k, x, nrhs, what, &t0);
-  if (m < 0) return m;
-  if (t0 < 0) return 0;
-  x[2].rows = m;
-  const size_t ab = (size_t)d->plan->arena * sizeof(TL);
-  for (int i = 0; i < 3; i++) {
-    if (x[i].rows == 0) continue; // (m = 0: G has no element)
-    bool bad = ranges_overlap(x[i].p, blk_bytes(x[i], nrhs), d_arena, ab);
-    for (int j = i + 1; j < 3 && !bad; j++) bad = x[j].rows > 0 && ranges_overlap(x[i].p, blk_bytes(x[i], nrhs), x[j].p, blk_bytes(x[j], nrhs));
-    if (bad) { chol_set_error("%s: B, W, G and the arena must not overlap each other", what); return CHOLAMD_ERR_ARG; }
-  }
-  { int rc = schur_nrhs_begin(d, d_arena, k, st); if (rc) return rc; }
-  keep_restore kr(d);
-  d->keep_inverses = true;
-  double *Y = d->ynrhs;
-  for (int c0 = 0; c0 < nrhs; c0 += CHOL_NRHS_W) {
-    const int cols = std::min(CHOL_NRHS_W, nrhs - c0);
-    if (!d->schur_deterministic && cols < half_nrhs_min_block<TL>()) {
-      for (int j = c0; j < c0 + cols; j++) {
-        int rc = schur_condense_t(d, d_arena, k, t0, m, d_B + (int64_t)j * ldb, d_W + (int64_t)j * ldw, d_G + (int64_t)j * ldg, st);
-        if (rc) return rc;
-      }
-      continue;
-    }
-    HIPCHK((hipError_t)chol_nrhs_launch_permute(d_B, ldb, d->perm, Y, nullptr, 0, n, c0, cols, 0, st));
-    { int rc = schur_sweep(d, d_arena, k, false, { Y, true }, st); if (rc) return rc; }
-    HIPCHK((hipError_t)chol_launch_schur_unpack(Y, n, t0, c0, cols, d_W, ldw, d_G, ldg, st));
-    d->schur_launches[3]++;
-  }
-  return 0;
-}
-template <class TL> static int schur_expand_nrhs_api(cholamd_device *d, const TL *d_arena, int k, const double *d_W, int64_t ldw, const double *d_XT, int64_t ldxt, double *d_X, int64_t ldx,
-                                                     int nrhs, hipStream_t st, const char *what)
-{
-  if (!d) { chol_set_error("%s: NULL device", what); return CHOLAMD_ERR_ARG; }
-  const int n = d->plan->n;
-  int t0 = 0;
-  schur_blk x[3] = { { d_W, ldw, n, "W" }, { d_XT, ldxt, 0, "XT" }, { d_X, ldx, n, "X" } };
-  const int m = schur_nrhs_args(d, d_arena, k, x, nrhs, what, &t0);
-  if (m < 0) return m;
-  if (t0 < 0) return 0;
-  x[1].rows = m;
-  const size_t ab = (size_t)d->plan->arena * sizeof(TL), xb = blk_bytes(x[2], nrhs);
-  if (ranges_overlap(d_X, xb, d_W, blk_bytes(x[0], nrhs)) || (m > 0 && ranges_overlap(d_X, xb, d_XT, blk_bytes(x[1], nrhs))) || ranges_overlap(d_X, xb, d_arena, ab)) {
-    chol_set_error("%s: X must not overlap W, XT or the arena", what);
-    return CHOLAMD_ERR_ARG;
-  }
-  { int rc = schur_nrhs_begin(d, d_arena, k, st); if (rc) return rc; }
-  keep_restore kr(d);
-  d->keep_inverses = true;
-  double *Y = d->ynrhs;
-  for (int c0 = 0; c0 < nrhs; c0 += CHOL_NRHS_W) {
-    const int cols = std::min(CHOL_NRHS_W, nrhs - c0);
-    if (!d->schur_deterministic && cols < half_nrhs_min_block<TL>()) {
-      for (int j = c0; j < c0 + cols; j++) {
-        int rc = schur_expand_t(d, d_arena, k, t0, m, d_W + (int64_t)j * ldw, d_XT + (int64_t)j * ldxt, d_X + (int64_t)j * ldx, st);
-        if (rc) return rc;
-      }
-      continue;
-    }
-    HIPCHK((hipError_t)chol_launch_schur_pack(d_W, ldw, d_XT, ldxt, n, t0, c0, cols, Y, st));
-    d->schur_launches[3]++;
-    { int rc = schur_sweep(d, d_arena, k, true, { Y, true }, st); if (rc) return rc; }
-    HIPCHK((hipError_t)chol_nrhs_launch_permute(nullptr, 0, d->perm, Y, d_X, ldx, n, c0, cols, 1, st));
-  }
-  return 0;
-}
-extern "C" int cholamd_schur_condense_nrhs(cholamd_device *d, const double *d_arena, int k, const double *d_B, int64_t ldb, double *d_W, int64_t ldw, double *d_G, int64_t ldg, int nrhs, void *stream)
-{ return schur_condense_nrhs_api(d, d_arena, k, d_B, ldb, d_W, ldw, d_G, ldg, nrhs, (hipStream_t)stream, "cholamd_schur_condense_nrhs"); }
-extern "C" int cholamd_schur_condense_nrhs_f32(cholamd_device *d, const float *d_arena32, int k, const double *d_B, int64_t ldb, double *d_W, int64_t ldw, double *d_G, int64_t ldg, int nrhs, void *stream)
-{ return schur_condense_nrhs_api(d, d_arena32, k, d_B, ldb, d_W, ldw, d_G, ldg, nrhs, (hipStream_t)stream, "cholamd_schur_condense_nrhs_f32"); }
-extern "C" int cholamd_schur_expand_nrhs(cholamd_device *d, const double *d_arena, int k, const double *d_W, int64_t ldw, const double *d_XT, int64_t ldxt, double *d_X, int64_t ldx, int nrhs, void *stream)
-{ return schur_expand_nrhs_api(d, d_arena, k, d_W, ldw, d_XT, ldxt, d_X, ldx, nrhs, (hipStream_t)stream, "cholamd_schur_expand_nrhs"); }
-extern "C" int cholamd_schur_expand_nrhs_f32(cholamd_device *d, const float *d_arena32, int k, const double *d_W, int64_t ldw, const double *d_XT, int64_t ldxt, double *d_X, int64_t ldx, int nrhs, void *stream)
-{ return schur_expand_nrhs_api(d, d_arena32, k, d_W, ldw, d_XT, ldxt, d_X, ldx, nrhs, (hipStream_t)stream, "cholamd_schur_expand_nrhs_f32"); }
-extern "C" int cholamd_device_schur_launches(const cholamd_device *d, int64_t out[4])
-{
-  if (!d || !out) { chol_set_error("cholamd_device_schur_launches: NULL %s", !d ? "device" : "out"); return CHOLAMD_ERR_ARG; }
-  for (int i = 0; i < 4; i++) out[i] = d->schur_launches[i];
-  return 0;
-}
-
 // one chunk's residuals: R = B - A X (column-major, ld n), rel[j] = ||r_j|| / ||b_j||
 static int residual_nrhs(cholamd_device *d, const double *d_B, int64_t ldb, const double *d_X, int64_t ldx, int cols, double *rel, hipStream_t st)
 {
@@ -2130,604 +1686,13 @@ extern "C" int cholamd_solve_pcg_nrhs_f32(cholamd_device *d, const float *d_aren
 { return pcg_t(d, d_arena32, d_B, ldb, d_X, ldx, nrhs, max_iter, tol, flags, iters_out, relres_out, status_out, false, (hipStream_t)stream, "cholamd_solve_pcg_nrhs_f32"); }
 
 // ---------------------------------------------------------------------------------------------
-// L-A / L-B: stand-alone batched launches with pointer-valued descriptors (base = nullptr)
-// ---------------------------------------------------------------------------------------------
-static inline int64_t poff(const void *p) { return (int64_t)((uintptr_t)p / sizeof(double)); }
-
-struct scratch { // per-call device scratch, freed at scope exit after the stream has been synchronised
-  std::vector<dev_buf<char>> bufs;
-  template <class T> int get(T **dptr, size_t n, int floating_point = std::is_floating_point<T>::value)
-  {
-    bufs.emplace_back();
-    int rc = bufs.back().alloc_bytes((n ? n : 1) * sizeof(T), floating_point);
-    *dptr = (T *)bufs.back().get();
-    return rc;
-  }
-  template <class T> int put(T **dptr, const T *h, size_t n, hipStream_t st)
-  {
-    *dptr = nullptr;
-    if (n == 0) return 0;
-    int rc = get(dptr, n, 0); // uploads: plain memory
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(*dptr, h, n * sizeof(T), hipMemcpyHostToDevice, st));
-    return 0;
-  }
-};
-
-static int check_ptr(const void *p, const char *what)
-{
-  if (!p || ((uintptr_t)p & 7)) { chol_set_error("%s must be a non-null, 8-byte aligned pointer", what); return CHOLAMD_ERR_ARG; }
-  return 0;
-}
-static int have_device()
-{
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return no_device_error();
-  return 0;
-}
-
-static void add_update_tasks(std::vector<chol_upd_task> &tasks, int src_begin, int src_end, double *c, int ldc, int m, int n, bool syrk)
-{
-  const int tr = (m + 15) / 16, tc = (n + 15) / 16;
-  for (int a = 0; a < tr; a++)
-    for (int b = 0; b < tc; b++) {
-      if (syrk && b > a) continue;
-      chol_upd_task t;
-      std::memset(&t, 0, sizeof t);
-      t.c_off = poff(c) + a * 16 + (int64_t)b * 16 * ldc;
-      t.ldc = ldc;
-      t.mv = (short)(m - a * 16 < 16 ? m - a * 16 : 16);
-      t.nv = (short)(n - b * 16 < 16 ? n - b * 16 : 16);
-      t.lower = (syrk && a == b);
-      t.src_begin = src_begin; t.src_end = src_end; t.ar = a * 16; t.br = b * 16;
-      tasks.push_back(t);
-    }
-}
-
-static int run_updates(std::vector<chol_upd_task> &tasks, std::vector<chol_upd_src> &srcs, hipStream_t st)
-{
-  if (tasks.empty()) return 0;
-  scratch sc;
-  chol_upd_task *dt; chol_upd_src *ds;
-  int rc = sc.put(&dt, tasks.data(), tasks.size(), st);
-  if (!rc) rc = sc.put(&ds, srcs.data(), srcs.size(), st);
-  if (rc) return rc;
-  HIPCHK((hipError_t)chol_launch_update((double *)nullptr, dt, ds, (int)tasks.size(), st));
-  HIPCHK(hipStreamSynchronize(st));
-  return 0;
-}
-
-// B tiles (rows m_i of width n) <- B L^-T for one pivot L (n x n, ld ldl)
-static int run_trsm(const double *Lp, int n, int ldl, const std::vector<chol_trsm_desc> &rows, hipStream_t st)
-{
-  if (rows.empty() || n == 0) return 0;
-  scratch sc;
-  double *W; chol_trsm_desc *dd;
-  const size_t nb = (size_t)(n + CHOL_NB - 1) / CHOL_NB;
-  int rc = sc.get(&W, nb * CHOL_NB * CHOL_NB);
-  if (rc) return rc;
-  HIPCHK((hipError_t)chol_launch_dinv(Lp, n, ldl, W, st));
-  std::vector<chol_trsm_desc> v;
-  for (const auto &r : rows)
-    for (int r0 = 0; r0 < r.m; r0 += CHOL_TRSM_ROWS) {
-      chol_trsm_desc t = r;
-      t.l_off = poff(Lp); t.dinv_off = poff(W); t.b_off = r.b_off + r0;
-      t.m = r.m - r0 < CHOL_TRSM_ROWS ? r.m - r0 : CHOL_TRSM_ROWS;
-      v.push_back(t);
-    }
-  rc = sc.put(&dd, v.data(), v.size(), st);
-  if (rc) return rc;
-  if (n <= CHOL_TRSM_W_MAXN) HIPCHK((hipError_t)chol_launch_trsm_w(nullptr, nullptr, dd, (int)v.size(), st));
-  else if (n <= CHOL_RR_MAXN) HIPCHK((hipError_t)chol_launch_trsm((double *)nullptr, nullptr, dd, (int)v.size(), st));
-  else HIPCHK((hipError_t)chol_launch_trsm_big(nullptr, nullptr, dd, (int)v.size(), st));
-  HIPCHK(hipStreamSynchronize(st));
-  return 0;
-}
-
-static int run_potrf(const std::vector<chol_potrf_desc> &v, hipStream_t st, int *info_out, int *sep_out)
-{
-  if (info_out) *info_out = 0;
-  if (v.empty()) return 0;
-  scratch sc;
-  size_t wsz = 0;
-  std::vector<chol_potrf_desc> dv;
-  for (const auto &p : v) if (p.n <= CHOL_RR_MAXN) dv.push_back(p);
-  const int n_small = (int)dv.size();
-  for (const auto &p : v) if (p.n > CHOL_RR_MAXN) dv.push_back(p);
-  for (auto &p : dv) { p.dinv_off = (int64_t)wsz; wsz += (size_t)((p.n + CHOL_NB - 1) / CHOL_NB) * CHOL_NB * CHOL_NB; }
-  double *W; int *info; chol_potrf_desc *dd;
-  int rc = sc.get(&W, wsz);
-  if (!rc) rc = sc.get(&info, (size_t)2);
-  if (rc) return rc;
-  HIPCHK(hipMemsetAsync(info, 0, 2 * sizeof(int), st));
-  rc = sc.put(&dd, dv.data(), dv.size(), st);
-  if (rc) return rc;
-  HIPCHK((hipError_t)chol_launch_potrf(nullptr, W, dd, n_small, info, st));
-  HIPCHK((hipError_t)chol_launch_potrf_big(nullptr, W, dd + n_small, (int)dv.size() - n_small, info, st));
-  int h[2] = { 0, 0 };
-  HIPCHK(hipMemcpyAsync(h, info, sizeof h, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (info_out) *info_out = h[0];
-  if (sep_out) *sep_out = h[1];
-  return 0;
-}
-
-// ---- L-B: fused leaf tasks -------------------------------------------------------------------
-static double *tile_ptr(const cholamd_region *r, const cholamd_filled *f)
-{ // get_raw_ptr_2d, blas.rg:35-43; a row-compacted block instance stores only the 16-row tiles its filled tiles touch (tile_row)
-  const int row = f->lo_x - r->lo_x;
-  const int64_t srow = r->tile_row ? (int64_t)r->tile_row[row / CHOL_NB] * CHOL_NB + row % CHOL_NB : row;
-  return r->ptr + srow + (int64_t)(f->lo_y - r->lo_y) * r->ld;
-}
-static int region_ok(const cholamd_region *r, const char *name)
-{
-  if (!r) { chol_set_error("region %s is null", name); return CHOLAMD_ERR_ARG; }
-  return check_ptr(r->ptr, name);
-}
-static int tile_inside(const cholamd_region *r, const cholamd_filled *f)
-{
-  if (f->lo_x < r->lo_x || f->lo_y < r->lo_y || f->hi_x > r->hi_x || f->hi_y > r->hi_y) {
-    chol_set_error("tile (%d,%d,%d) lies outside its region", f->sep_x, f->sep_y, f->cluster);
-    return CHOLAMD_ERR_ARG;
-  }
-  if (r->tile_row) // every row of the tile must have storage, consecutively
-    for (int t = (f->lo_x - r->lo_x) / CHOL_NB; t <= (f->hi_x - r->lo_x) / CHOL_NB; t++)
-      if (r->tile_row[t] < 0 || (t > (f->lo_x - r->lo_x) / CHOL_NB && r->tile_row[t] != r->tile_row[t - 1] + 1)) {
-        chol_set_error("tile (%d,%d,%d) touches rows its region does not store", f->sep_x, f->sep_y, f->cluster);
-        return CHOLAMD_ERR_ARG;
-      }
-  return 0;
-}
-
-extern "C" int cholamd_plan_region(const cholamd_plan *p, double *d_arena, int r, int c, cholamd_region *out)
-{
-  const chol_block *B = chol_plan_block(p, r, c);
-  if (!B || !out) { chol_set_error("no block (%d, %d)", r, c); return CHOLAMD_ERR_ARG; }
-  cholamd_region rg = { d_arena + B->off, B->ld, B->lo_x, B->lo_y, B->hi_x, B->hi_y, B->tmap };
-  *out = rg;
-  return 0;
-}
-
-extern "C" int cholamd_fused_dpotrf(const cholamd_region *rA, const cholamd_filled *fa, int nA, int level, int interval, int debug, void *stream)
-{
-  int rc = have_device();
-  if (!rc) rc = region_ok(rA, "rA");
-  if (rc) return rc;
-  std::vector<chol_potrf_desc> v;
-  for (int i = 0; i < nA; i++) {
-    if ((rc = tile_inside(rA, &fa[i]))) return rc;
-    const int m = fa[i].hi_x - fa[i].lo_x + 1;
-    if (debug)
-      printf("POTRF: {'A': (%d, %d, %d), 'A_Lo': (%d, %d), 'A_Hi': (%d, %d), 'SizeA': (%d, %d), 'Block': (%d, %d), 'Level': %d, 'Interval': %d}\n",
-             fa[i].sep_x, fa[i].sep_y, fa[i].cluster, fa[i].lo_x, fa[i].lo_y, fa[i].hi_x, fa[i].hi_y, m, fa[i].hi_y - fa[i].lo_y + 1,
-             fa[i].sep_x, fa[i].sep_y, level, interval);
-    if (m == 0) continue; // blas.rg:68
-    chol_potrf_desc p = { poff(tile_ptr(rA, &fa[i])), 0, m, rA->ld, fa[i].sep_x, 0, 0, 0, { 0 } };
-    v.push_back(p);
-  }
-  int info = 0;
-  rc = run_potrf(v, (hipStream_t)stream, &info, nullptr);
-  return rc ? rc : info;
-}
-
-extern "C" int cholamd_fused_dtrsm(const cholamd_region *rA, const cholamd_region *rB, const cholamd_filled *fa, int nA,
-                                   const cholamd_filled *fb, int nB, int level, int interval, int debug, void *stream)
-{
-  int rc = have_device();
-  if (!rc) rc = region_ok(rA, "rA");
-  if (!rc) rc = region_ok(rB, "rB");
-  if (rc) return rc;
-  for (int i = 0; i < nA; i++) {
-    if ((rc = tile_inside(rA, &fa[i]))) return rc;
-    const double *Lp = tile_ptr(rA, &fa[i]);
-    std::vector<chol_trsm_desc> rows;
-    int n = 0;
-    for (int j = 0; j < nB; j++) {
-      if ((rc = tile_inside(rB, &fb[j]))) return rc;
-      const int m = fb[j].hi_x - fb[j].lo_x + 1;
-      n = fb[j].hi_y - fb[j].lo_y + 1;
-      if (debug)
-        printf("TRSM: {'A': (%d, %d, %d), 'A_Lo': (%d, %d), 'A_Hi': (%d, %d), 'SizeA': (%d, %d), 'B': (%d, %d, %d), 'B_Lo': (%d, %d), 'B_Hi': (%d, %d), 'SizeB': (%d, %d), 'Block': (%d, %d), 'Level': %d, 'Interval': %d}\n",
-               fa[i].sep_x, fa[i].sep_y, fa[i].cluster, fa[i].lo_x, fa[i].lo_y, fa[i].hi_x, fa[i].hi_y, fa[i].hi_x - fa[i].lo_x + 1, fa[i].hi_y - fa[i].lo_y + 1,
-               fb[j].sep_x, fb[j].sep_y, fb[j].cluster, fb[j].lo_x, fb[j].lo_y, fb[j].hi_x, fb[j].hi_y, m, n, fb[j].sep_x, fb[j].sep_y, level, interval);
-      if (n != fa[i].hi_x - fa[i].lo_x + 1) { chol_set_error("TRSM: B tile width %d != pivot size %d", n, fa[i].hi_x - fa[i].lo_x + 1); return CHOLAMD_ERR_ARG; }
-      chol_trsm_desc t = { 0, 0, poff(tile_ptr(rB, &fb[j])), n, rA->ld, m, rB->ld };
-      rows.push_back(t);
-    }
-    if ((rc = run_trsm(Lp, n, rA->ld, rows, (hipStream_t)stream))) return rc;
-  }
-  return 0;
-}
-
-static int fused_update(const cholamd_region *rA, const cholamd_region *rB, const cholamd_region *rC,
-                        const cholamd_filled *fa, int nA, const cholamd_filled *fb, int nB, const cholamd_filled *fc, int nC,
-                        int ccs, int level, int interval, int debug, void *stream, bool is_syrk)
-{
-  int rc = have_device();
-  if (!rc) rc = region_ok(rA, "rA");
-  if (!rc) rc = region_ok(rB, "rB");
-  if (!rc) rc = region_ok(rC, "rC");
-  if (rc) return rc;
-  std::vector<chol_upd_task> tasks;
-  std::vector<chol_upd_src> srcs;
-  for (int i = 0; i < nA; i++) {
-    const cholamd_filled &a = fa[i];
-    if ((rc = tile_inside(rA, &a))) return rc;
-    const int row = a.cluster, sAx = a.hi_x - a.lo_x + 1, sAy = a.hi_y - a.lo_y + 1;
-    for (int j = 0; j < nB; j++) {
-      const cholamd_filled &b = fb[j];
-      if ((rc = tile_inside(rB, &b))) return rc;
-      const int col = b.cluster, sBx = b.hi_x - b.lo_x + 1;
-      const int cz = row * ccs + col;
-      const cholamd_filled *c = nullptr;
-      for (int k = 0; k < nC; k++) // the reference's linear search, blas.rg:385-392 / 468-475
-        if (fc[k].sep_x == a.sep_x && fc[k].sep_y == b.sep_x && fc[k].cluster == cz) { c = &fc[k]; break; }
-      if (!c) continue;
-      if ((rc = tile_inside(rC, c))) return rc;
-      const int sCx = c->hi_x - c->lo_x + 1, sCy = c->hi_y - c->lo_y + 1;
-      if (sCx <= 0 || sCy <= 0) continue;
-      if (is_syrk && col > row) continue;
-      if (debug)
-        printf("GEMM: {'A': (%d, %d, %d), 'A_Lo': (%d, %d), 'A_Hi': (%d, %d), 'sizeA': (%d, %d), 'B': (%d, %d, %d), 'B_Lo': (%d, %d), 'B_Hi': (%d, %d), 'sizeB': (%d, %d), 'C': (%d, %d, %d), 'C_Lo': (%d, %d), 'C_Hi': (%d, %d), 'sizeC': (%d, %d), 'Block': (%d, %d), 'Level': %d, 'Interval': %d}\n",
-               a.sep_x, a.sep_y, a.cluster, a.lo_x, a.lo_y, a.hi_x, a.hi_y, sAx, sAy, b.sep_x, b.sep_y, b.cluster, b.lo_x, b.lo_y, b.hi_x, b.hi_y, sBx, b.hi_y - b.lo_y + 1,
-               c->sep_x, c->sep_y, c->cluster, c->lo_x, c->lo_y, c->hi_x, c->hi_y, sCx, sCy, c->sep_x, c->sep_y, level, interval);
-      const bool syrk = is_syrk && col == row;
-      chol_upd_src s = { poff(tile_ptr(rA, &a)), poff(tile_ptr(rB, &b)), rA->ld, rB->ld, sAy, 0, 0, 0 };
-      srcs.push_back(s);
-      // distinct (a, b) pairs address distinct C tiles inside one fused task, so one source per task group
-      add_update_tasks(tasks, (int)srcs.size() - 1, (int)srcs.size(), tile_ptr(rC, c), rC->ld, syrk ? sCx : sAx, syrk ? sCx : sBx, syrk);
-    }
-  }
-  return run_updates(tasks, srcs, (hipStream_t)stream);
-}
-
-extern "C" int cholamd_fused_dsyrk(const cholamd_region *rA, const cholamd_region *rB, const cholamd_region *rC,
-                                   const cholamd_filled *fa, int nA, const cholamd_filled *fb, int nB, const cholamd_filled *fc, int nC,
-                                   int ccs, int level, int interval, int debug, void *stream)
-{
-  return fused_update(rA, rB, rC, fa, nA, fb, nB, fc, nC, ccs, level, interval, debug, stream, true);
-}
-extern "C" int cholamd_fused_dgemm(const cholamd_region *rA, const cholamd_region *rB, const cholamd_region *rC,
-                                   const cholamd_filled *fa, int nA, const cholamd_filled *fb, int nB, const cholamd_filled *fc, int nC,
-                                   int ccs, int level, int interval, int debug, void *stream)
-{
-  return fused_update(rA, rB, rC, fa, nA, fb, nB, fc, nC, ccs, level, interval, debug, stream, false);
-}
-
-// ---- the reference's debug mode: the main loop of mmat.rg:1227-1355 literally, one fused task at a time, with write_blocks dumps
-static int debug_dump(cholamd_device *d, const double *d_arena, std::vector<double> &host, const char *dir, int level, const char *op,
-                      int ax, int ay, int bx, int by, int cx, int cy, int full)
-{
-  const cholamd_plan *p = d->plan;
-  HIPCHK(hipMemcpy(host.data(), d_arena, (size_t)p->arena * sizeof(double), hipMemcpyDeviceToHost));
-  char stem[1100], file[1200], header[200];
-  if (!std::strcmp(op, "POTRF")) { snprintf(stem, sizeof stem, "%s/potrf_lvl%d_a%d%d", dir, level, ax, ay); snprintf(header, sizeof header, "Level: %d POTRF A=(%d, %d)", level, ax, ay); }
-  else if (!std::strcmp(op, "TRSM")) { snprintf(stem, sizeof stem, "%s/trsm_lvl%d_a%d%d_b%d%d", dir, level, ax, ay, bx, by); snprintf(header, sizeof header, "Level: %d TRSM A=(%d, %d) B=(%d, %d)", level, ax, ay, bx, by); }
-  else { snprintf(stem, sizeof stem, "%s/gemm_lvl%d_a%d%d_b%d%d_c%d%d", dir, level, ax, ay, bx, by, cx, cy); snprintf(header, sizeof header, "Level: %d GEMM A=(%d, %d) B=(%d, %d) C=(%d, %d)", level, ax, ay, bx, by, cx, cy); }
-  snprintf(file, sizeof file, "%s.mtx", stem);
-  printf("filename: %s\n", file);
-  printf("saving matrix to: %s\n\n", file);
-  int rc = cholamd_plan_write_matrix(p, host.data(), file, full);
-  if (rc) return rc;
-  snprintf(file, sizeof file, "%s.txt", stem);
-  printf("filename: %s\n", file);
-  return cholamd_plan_write_blocks_txt(p, host.data(), file, header);
-}
-extern "C" int cholamd_factor_debug(cholamd_device *d, double *d_arena, const char *dir, int full_precision, void *stream)
-{
-  HIPCHK(hipSetDevice(d->dev));
-  const cholamd_plan *p = d->plan;
-  const int L = p->levels, ns = p->nsep;
-  std::vector<double> host((size_t)p->arena);
-  auto region_of = [&](int r, int c) {
-    const chol_block *B = chol_plan_block(p, r, c);
-    cholamd_region rg = { d_arena + B->off, B->ld, B->lo_x, B->lo_y, B->hi_x, B->hi_y, B->tmap };
-    return rg;
-  };
-  for (int lvl = L - 1; lvl >= 0; lvl--) {
-    const int lbl = L - 1 - lvl;
-    // filled tiles of the level's snapshot, grouped by block (the snapshot is ordered by (row label, col label, cluster))
-    std::vector<std::vector<cholamd_filled>> fl((size_t)(ns + 1) * (ns + 1));
-    for (int64_t i = 0; i < p->snap_n[lbl]; i++) fl[(size_t)p->snap[lbl][i].sep_x * (ns + 1) + p->snap[lbl][i].sep_y].push_back(p->snap[lbl][i]);
-    auto F = [&](int r, int c) -> std::vector<cholamd_filled> & { return fl[(size_t)r * (ns + 1) + c]; };
-    const int h0 = 1 << lvl, h1 = (1 << (lvl + 1)) - 1;
-    for (int h = h0; h <= h1; h++) { // POTRF sweep, mmat.rg:1240-1257
-      const int s = p->tree[h];
-      cholamd_region rA = region_of(s, s);
-      int rc = cholamd_fused_dpotrf(&rA, F(s, s).data(), (int)F(s, s).size(), lvl, lbl, 1, stream);
-      if (rc < 0) return rc;
-      if (rc > 0) { int h2[2] = { rc, s }; HIPCHK(hipMemcpy(d->info, h2, sizeof h2, hipMemcpyHostToDevice)); d->info_last = d->info; d->info_foreign = true; }
-      if ((rc = debug_dump(d, d_arena, host, dir, lvl, "POTRF", s, s, 0, 0, 0, 0, full_precision))) return rc;
-    }
-    for (int h = h0; h <= h1; h++) { // TRSM sweep, mmat.rg:1259-1291
-      const int s = p->tree[h];
-      for (int hp = h / 2; hp >= 1; hp /= 2) {
-        const int par = p->tree[hp];
-        cholamd_region rA = region_of(s, s), rB = region_of(par, s);
-        int rc = cholamd_fused_dtrsm(&rA, &rB, F(s, s).data(), (int)F(s, s).size(), F(par, s).data(), (int)F(par, s).size(), lvl, lbl, 1, stream);
-        if (rc) return rc;
-        if ((rc = debug_dump(d, d_arena, host, dir, lvl, "TRSM", s, s, par, s, 0, 0, full_precision))) return rc;
-      }
-    }
-    for (int h = h0; h <= h1; h++) { // SYRK / GEMM sweep, mmat.rg:1293-1347
-      const int s = p->tree[h];
-      for (int hp = h / 2; hp >= 1; hp /= 2) {
-        const int par = p->tree[hp];
-        const int ccs = cholamd_plan_ntiles_at_level(p, par, lvl);
-        for (int hg = hp; hg >= 1; hg /= 2) {
-          const int gp = p->tree[hg];
-          cholamd_region rA = region_of(gp, s), rB = region_of(par, s), rC = region_of(gp, par);
-          int rc = (gp == par ? cholamd_fused_dsyrk : cholamd_fused_dgemm)(&rA, &rB, &rC, F(gp, s).data(), (int)F(gp, s).size(), F(par, s).data(), (int)F(par, s).size(),
-                                                                             F(gp, par).data(), (int)F(gp, par).size(), ccs, lvl, lbl, 1, stream);
-          if (rc) return rc;
-          if ((rc = debug_dump(d, d_arena, host, dir, lvl, "GEMM", gp, s, par, s, gp, par, full_precision))) return rc;
-        }
-      }
-    }
-  }
-  return 0;
-}
-
-// ---- L-A: device-pointer BLAS ----------------------------------------------------------------
-extern "C" int cholamd_dpotrf_dev(int n, double *d_a, int lda, int *d_info, void *stream)
-{
-  int rc = have_device();
-  if (rc) return rc;
-  if (n < 0 || lda < (n > 1 ? n : 1)) { chol_set_error("dpotrf: bad n/lda"); return CHOLAMD_ERR_ARG; }
-  if (n == 0) return 0;
-  if ((rc = check_ptr(d_a, "a"))) return rc;
-  std::vector<chol_potrf_desc> v(1);
-  v[0] = { poff(d_a), 0, n, lda, 0, 0 };
-  int info = 0;
-  rc = run_potrf(v, (hipStream_t)stream, &info, nullptr);
-  if (rc) return rc;
-  if (d_info) HIPCHK(hipMemcpy(d_info, &info, sizeof(int), hipMemcpyHostToDevice));
-  return info;
-}
-extern "C" int cholamd_dtrsm_dev(int m, int n, const double *d_a, int lda, double *d_b, int ldb, void *stream)
-{
-  int rc = have_device();
-  if (rc) return rc;
-  if (m < 0 || n < 0 || lda < (n > 1 ? n : 1) || ldb < (m > 1 ? m : 1)) { chol_set_error("dtrsm: bad sizes"); return CHOLAMD_ERR_ARG; }
-  if (m == 0 || n == 0) return 0;
-  if ((rc = check_ptr(d_a, "a")) || (rc = check_ptr(d_b, "b"))) return rc;
-  std::vector<chol_trsm_desc> rows(1);
-  rows[0] = { 0, 0, poff(d_b), n, lda, m, ldb };
-  return run_trsm(d_a, n, lda, rows, (hipStream_t)stream);
-}
-extern "C" int cholamd_dgemm_dev(int m, int n, int k, const double *d_a, int lda, const double *d_b, int ldb, double *d_c, int ldc, void *stream)
-{
-  int rc = have_device();
-  if (rc) return rc;
-  if (m < 0 || n < 0 || k < 0 || lda < (m > 1 ? m : 1) || ldb < (n > 1 ? n : 1) || ldc < (m > 1 ? m : 1)) { chol_set_error("dgemm: bad sizes"); return CHOLAMD_ERR_ARG; }
-  if (m == 0 || n == 0 || k == 0) return 0;
-  if ((rc = check_ptr(d_a, "a")) || (rc = check_ptr(d_b, "b")) || (rc = check_ptr(d_c, "c"))) return rc;
-  std::vector<chol_upd_task> tasks;
-  std::vector<chol_upd_src> srcs(1);
-  srcs[0] = { poff(d_a), poff(d_b), lda, ldb, k, 0 };
-  add_update_tasks(tasks, 0, 1, d_c, ldc, m, n, false);
-  return run_updates(tasks, srcs, (hipStream_t)stream);
-}
-extern "C" int cholamd_dsyrk_dev(int n, int k, const double *d_a, int lda, double *d_c, int ldc, void *stream)
-{
-  int rc = have_device();
-  if (rc) return rc;
-  if (n < 0 || k < 0 || lda < (n > 1 ? n : 1) || ldc < (n > 1 ? n : 1)) { chol_set_error("dsyrk: bad sizes"); return CHOLAMD_ERR_ARG; }
-  if (n == 0 || k == 0) return 0;
-  if ((rc = check_ptr(d_a, "a")) || (rc = check_ptr(d_c, "c"))) return rc;
-  std::vector<chol_upd_task> tasks;
-  std::vector<chol_upd_src> srcs(1);
-  srcs[0] = { poff(d_a), poff(d_a), lda, lda, k, 0 };
-  add_update_tasks(tasks, 0, 1, d_c, ldc, n, n, true);
-  return run_updates(tasks, srcs, (hipStream_t)stream);
-}
-extern "C" int cholamd_dtrsv_dev(int trans, int n, const double *d_a, int lda, double *d_x, void *stream)
-{
-  int rc = have_device();
-  if (rc) return rc;
-  if (n < 0 || lda < (n > 1 ? n : 1) || (trans != CholamdNoTrans && trans != CholamdTrans)) { chol_set_error("dtrsv: bad arguments"); return CHOLAMD_ERR_ARG; }
-  if (n == 0) return 0;
-  if ((rc = check_ptr(d_a, "a")) || (rc = check_ptr(d_x, "x"))) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  scratch sc;
-  chol_trsv_desc t = { poff(d_a), n, lda, 0, 0 };
-  chol_trsv_desc *dt;
-  if ((rc = sc.put(&dt, &t, 1, st))) return rc;
-  if (trans == CholamdNoTrans) {
-    HIPCHK((hipError_t)chol_launch_trsv_fwd(nullptr, dt, 1, d_x, st));
-  } else {
-    int zero2[2] = { 0, 0 };
-    int *ds;
-    if ((rc = sc.put(&ds, zero2, 2, st))) return rc;
-    HIPCHK((hipError_t)chol_launch_bwd(nullptr, dt, nullptr, ds, 1, d_x, st));
-  }
-  HIPCHK(hipStreamSynchronize(st));
-  return 0;
-}
-extern "C" int cholamd_dgemv_dev(int trans, int m, int n, const double *d_a, int lda, const double *d_x, double *d_y, void *stream)
-{
-  int rc = have_device();
-  if (rc) return rc;
-  if (m < 0 || n < 0 || lda < (m > 1 ? m : 1) || (trans != CholamdNoTrans && trans != CholamdTrans)) { chol_set_error("dgemv: bad arguments"); return CHOLAMD_ERR_ARG; }
-  if (m == 0 || n == 0) return 0;
-  if ((rc = check_ptr(d_a, "a")) || (rc = check_ptr(d_x, "x")) || (rc = check_ptr(d_y, "y"))) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  scratch sc;
-  if (trans == CholamdNoTrans) { // y(m) -= A x(n): the forward kernel with pointer-valued offsets
-    std::vector<chol_gemv_desc> g;
-    std::vector<int> gs, gr;
-    for (int row0 = 0; row0 < m; row0 += 256) {
-      gs.push_back((int)g.size());
-      gr.push_back(row0); gr.push_back(0);
-      chol_gemv_desc d = { poff(d_a), m, n, lda, 0, 0 };
-      g.push_back(d);
-    }
-    gs.push_back((int)g.size());
-    // vectors are addressed relative to y: x_off = x - y in doubles
-    for (auto &d : g) d.x_off = (int)(poff(d_x) - poff(d_y));
-    chol_gemv_desc *dg; int *dgs, *dgr;
-    if ((rc = sc.put(&dg, g.data(), g.size(), st)) || (rc = sc.put(&dgs, gs.data(), gs.size(), st)) || (rc = sc.put(&dgr, gr.data(), gr.size(), st))) return rc;
-    if (poff(d_x) - poff(d_y) != (int64_t)(int)(poff(d_x) - poff(d_y))) { chol_set_error("dgemv: x and y too far apart"); return CHOLAMD_ERR_ARG; }
-    HIPCHK((hipError_t)chol_launch_gemv_fwd(nullptr, dg, dgs, dgr, (int)gs.size() - 1, d_y, st));
-  } else { // y(n) -= A^T x(m): the backward kernel with an empty triangle (n = 0) does only the gather
-    chol_trsv_desc t = { 0, 0, 1, 0, 0 };
-    chol_gemv_desc d = { poff(d_a), m, n, lda, (int)(poff(d_x) - poff(d_y)), 0 };
-    if (poff(d_x) - poff(d_y) != (int64_t)d.x_off) { chol_set_error("dgemv: x and y too far apart"); return CHOLAMD_ERR_ARG; }
-    int start[2] = { 0, 1 };
-    chol_trsv_desc *dt; chol_gemv_desc *dg; int *ds;
-    if ((rc = sc.put(&dt, &t, 1, st)) || (rc = sc.put(&dg, &d, 1, st)) || (rc = sc.put(&ds, start, 2, st))) return rc;
-    HIPCHK((hipError_t)chol_launch_bwd(nullptr, dt, dg, ds, 1, d_y, st));
-  }
-  HIPCHK(hipStreamSynchronize(st));
-  return 0;
-}
-
-// ---- L-A: host-pointer CBLAS / LAPACKE replacements -------------------------------------------
-static thread_local int g_blas_status = 0;
-extern "C" int cholamd_blas_status(void) { return g_blas_status; }
-extern "C" void cholamd_openblas_set_num_threads(int) {} // mmat.rg:1057: parallelism is the GPU's
-
-struct host_mat { // a host matrix mirrored on the device for the duration of one call
-  dev_buf<double> d; double *h = nullptr; int rows = 0, cols = 0, ld = 0; bool writeback = false;
-  int up(const double *hp, int r, int c, int ldh, bool wb)
-  {
-    h = const_cast<double *>(hp); rows = r; cols = c; ld = ldh; writeback = wb;
-    if (r == 0 || c == 0) return 0;
-    { int rc = d.alloc((size_t)ld * cols); if (rc) return rc; }
-    HIPCHK(hipMemcpy(d, h, ((size_t)ld * (cols - 1) + rows) * sizeof(double), hipMemcpyHostToDevice));
-    return 0;
-  }
-  int down()
-  {
-    if (d && writeback) HIPCHK(hipMemcpy2D(h, (size_t)ld * sizeof(double), d, (size_t)ld * sizeof(double), (size_t)rows * sizeof(double), cols, hipMemcpyDeviceToHost));
-    return 0;
-  }
-};
-
-extern "C" int cholamd_LAPACKE_dpotrf(int layout, char uplo, int n, double *a, int lda)
-{
-  g_blas_status = 0;
-  if (layout != CholamdColMajor || (uplo != 'L' && uplo != 'l')) { chol_set_error("LAPACKE_dpotrf: only ColMajor/'L' (blas.rg:71)"); return g_blas_status = CHOLAMD_ERR_ARG; }
-  int rc = have_device();
-  if (rc) return g_blas_status = rc;
-  if (n == 0) return 0;
-  host_mat A;
-  if ((rc = A.up(a, n, n, lda, true))) return g_blas_status = rc;
-  int info = cholamd_dpotrf_dev(n, A.d, lda, nullptr, nullptr);
-  if (info < 0) return g_blas_status = info;
-  if ((rc = A.down())) return g_blas_status = rc;
-  return info;
-}
-extern "C" void cholamd_cblas_dtrsm(int layout, int side, int uplo, int transa, int diag, int m, int n, double alpha,
-                                    const double *a, int lda, double *b, int ldb)
-{
-  g_blas_status = 0;
-  if (layout != CholamdColMajor || side != CholamdRight || uplo != CholamdLower || transa != CholamdTrans || diag != CholamdNonUnit || alpha != 1.0) {
-    chol_set_error("cblas_dtrsm: only ColMajor/Right/Lower/Trans/NonUnit/alpha=1 (blas.rg:99)");
-    g_blas_status = CHOLAMD_ERR_ARG; return;
-  }
-  int rc = have_device();
-  if (rc) { g_blas_status = rc; return; }
-  host_mat A, B;
-  if ((rc = A.up(a, n, n, lda, false)) || (rc = B.up(b, m, n, ldb, true))) { g_blas_status = rc; return; }
-  if ((rc = cholamd_dtrsm_dev(m, n, A.d, lda, B.d, ldb, nullptr)) || (rc = B.down())) g_blas_status = rc;
-}
-extern "C" void cholamd_cblas_dgemm(int layout, int transa, int transb, int m, int n, int k, double alpha, const double *a, int lda,
-                                    const double *b, int ldb, double beta, double *c, int ldc)
-{
-  g_blas_status = 0;
-  if (layout != CholamdColMajor || transa != CholamdNoTrans || transb != CholamdTrans || alpha != -1.0 || beta != 1.0) {
-    chol_set_error("cblas_dgemm: only ColMajor/NoTrans/Trans/alpha=-1/beta=1 (blas.rg:139)");
-    g_blas_status = CHOLAMD_ERR_ARG; return;
-  }
-  int rc = have_device();
-  if (rc) { g_blas_status = rc; return; }
-  host_mat A, B, C;
-  if ((rc = A.up(a, m, k, lda, false)) || (rc = B.up(b, n, k, ldb, false)) || (rc = C.up(c, m, n, ldc, true))) { g_blas_status = rc; return; }
-  if ((rc = cholamd_dgemm_dev(m, n, k, A.d, lda, B.d, ldb, C.d, ldc, nullptr)) || (rc = C.down())) g_blas_status = rc;
-}
-extern "C" void cholamd_cblas_dsyrk(int layout, int uplo, int trans, int n, int k, double alpha, const double *a, int lda,
-                                    double beta, double *c, int ldc)
-{
-  g_blas_status = 0;
-  if (layout != CholamdColMajor || uplo != CholamdLower || trans != CholamdNoTrans || alpha != -1.0 || beta != 1.0) {
-    chol_set_error("cblas_dsyrk: only ColMajor/Lower/NoTrans/alpha=-1/beta=1 (blas.rg:187)");
-    g_blas_status = CHOLAMD_ERR_ARG; return;
-  }
-  int rc = have_device();
-  if (rc) { g_blas_status = rc; return; }
-  host_mat A, C;
-  if ((rc = A.up(a, n, k, lda, false)) || (rc = C.up(c, n, n, ldc, true))) { g_blas_status = rc; return; }
-  if ((rc = cholamd_dsyrk_dev(n, k, A.d, lda, C.d, ldc, nullptr)) || (rc = C.down())) g_blas_status = rc;
-}
-extern "C" void cholamd_cblas_dtrsv(int layout, int uplo, int transa, int diag, int n, const double *a, int lda, double *x, int incx)
-{
-  g_blas_status = 0;
-  if (layout != CholamdColMajor || uplo != CholamdLower || diag != CholamdNonUnit || incx != 1 || (transa != CholamdNoTrans && transa != CholamdTrans)) {
-    chol_set_error("cblas_dtrsv: only ColMajor/Lower/NonUnit/incx=1 (blas.rg:226)");
-    g_blas_status = CHOLAMD_ERR_ARG; return;
-  }
-  int rc = have_device();
-  if (rc) { g_blas_status = rc; return; }
-  host_mat A, X;
-  if ((rc = A.up(a, n, n, lda, false)) || (rc = X.up(x, n, 1, n > 1 ? n : 1, true))) { g_blas_status = rc; return; }
-  if ((rc = cholamd_dtrsv_dev(transa, n, A.d, lda, X.d, nullptr)) || (rc = X.down())) g_blas_status = rc;
-}
-extern "C" void cholamd_cblas_dgemv(int layout, int trans, int m, int n, double alpha, const double *a, int lda, const double *x, int incx,
-                                    double beta, double *y, int incy)
-{
-  g_blas_status = 0;
-  if (layout != CholamdColMajor || alpha != -1.0 || beta != 1.0 || incx != 1 || incy != 1 || (trans != CholamdNoTrans && trans != CholamdTrans)) {
-    chol_set_error("cblas_dgemv: only ColMajor/alpha=-1/beta=1/inc=1 (blas.rg:263)");
-    g_blas_status = CHOLAMD_ERR_ARG; return;
-  }
-  int rc = have_device();
-  if (rc) { g_blas_status = rc; return; }
-  const int lx = trans == CholamdNoTrans ? n : m, ly = trans == CholamdNoTrans ? m : n;
-  if (m == 0 || n == 0) return;
-  // x and y share one device buffer so that 32-bit relative offsets always suffice
-  dev_buf<double> xy;
-  if (xy.alloc((size_t)(lx + ly))) { g_blas_status = CHOLAMD_ERR_HIP; return; }
-  host_mat A;
-  rc = A.up(a, m, n, lda, false);
-  if (!rc && hipMemcpy(xy, x, (size_t)lx * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = CHOLAMD_ERR_HIP;
-  if (!rc && hipMemcpy(xy + lx, y, (size_t)ly * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = CHOLAMD_ERR_HIP;
-  if (!rc) rc = cholamd_dgemv_dev(trans, m, n, A.d, lda, xy, xy + lx, nullptr);
-  if (!rc && hipMemcpy(y, xy + lx, (size_t)ly * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = CHOLAMD_ERR_HIP;
-  g_blas_status = rc;
-}
-
-// ---------------------------------------------------------------------------------------------
 // Multi-GPU: subtree sharding + ONE extend-add exchange over RCCL.
 // The separator tree is cut at level d = log2(world): rank g owns the subtrees under its level-d separator and
 // factors them locally; contributions to the shared top of the tree accumulate in the rank's own copy of the
 // arena tail (the top panels are the contiguous tail of the arena: chol_plan.h); one ncclAllReduce(sum) over
 // that tail is the exchange; the top levels follow on every rank.
 // ---------------------------------------------------------------------------------------------
-// A LOCAL communicator (cholamd_comm_create_local) joins rank objects of ONE process without RCCL: the exchange is a device-side
-// ordered sum of the tails and peer copies, events order the ranks' streams.  The ranks may share a device (how the one-GPU test
-// box runs world 2 ... 8); usable through cholamd_factor_multi only, which sees every rank's arena.
 #define CHOL_LOCAL_MAX 64
-struct local_group {
-  int n = 0, refs = 0;
-  std::vector<int> dev;
-  std::vector<hipEvent_t> ev; // [g]: rank g's stream has reached the exchange; [n + g]: rank g's part of the exchange is enqueued
-};
-struct cholamd_comm {
-  ncclComm_t comm = nullptr;
-  int world = 1, rank = 0;
-  bool owned = true;
-  local_group *local = nullptr;
-};
-#define NCCLCHK(call)                                                                                 \
-  do {                                                                                                \
-    ncclResult_t r_ = (call);                                                                         \
-    if (r_ != ncclSuccess) {                                                                          \
-      chol_set_error("%s failed: %s (%s:%d)", #call, ncclGetErrorString(r_), __FILE__, __LINE__);     \
-      return CHOLAMD_ERR_COMM;                                                                        \
-    }                                                                                                 \
-  } while (0)
-
 extern "C" int cholamd_comm_unique_id(char id[CHOLAMD_UNIQUE_ID_BYTES])
 {
   static_assert(sizeof(ncclUniqueId) <= CHOLAMD_UNIQUE_ID_BYTES, "unique id size");
@@ -2904,7 +1869,6 @@ static int top_entries(cholamd_device *d, int f32, int64_t *below, const int64_t
   else { *tdst = d->top_dst[f32]; *tval = d->top_val[f32]; *ntop = d->top_n[f32]; }
   return 0;
 }
-struct sum_desc { int64_t off, count, stage; unsigned contrib, pad; };
 template <class T> __global__ void k_sum_owned(T *arena, const T *stage, const sum_desc *desc, int world, int rank)
 { // arena[off + i] = sum over the ranks in rank order; rank r's copy: this rank's own arena for r == rank, else -- if r contributes -- the next staging slot
   const sum_desc d = desc[blockIdx.y];
@@ -3281,15 +2245,6 @@ extern "C" int cholamd_gather_to_root(cholamd_device *d, void *d_arena, int elem
   NCCLCHK(ncclGroupEnd());
   return 0;
 }
-static int gather_factor_bytes(cholamd_device *const *devs, void *const *arenas, int n, void *const *streams, int elem_bytes);
-extern "C" int cholamd_gather_factor(cholamd_device *const *devs, double *const *arenas, int n, void *const *streams)
-{
-  return gather_factor_bytes(devs, (void *const *)arenas, n, streams, 8);
-}
-extern "C" int cholamd_gather_factor_f32(cholamd_device *const *devs, float *const *arenas32, int n, void *const *streams)
-{
-  return gather_factor_bytes(devs, (void *const *)arenas32, n, streams, 4);
-}
 static int gather_factor_bytes(cholamd_device *const *devs, void *const *arenas, int n, void *const *streams, int elem_bytes)
 { // the panels of the subtrees ranks 1..n-1 own -> device 0's arena (peer copies), so that it holds the complete factor
   const cholamd_plan *p = devs[0]->plan;
@@ -3306,6 +2261,14 @@ static int gather_factor_bytes(cholamd_device *const *devs, void *const *arenas,
     HIPCHK(hipMemcpyPeerAsync((char *)arenas[0] + (size_t)off * elem_bytes, devs[0]->dev, (const char *)arenas[g] + (size_t)off * elem_bytes, devs[g]->dev, (size_t)len * elem_bytes, streams ? (hipStream_t)streams[0] : nullptr));
   }
   return 0;
+}
+extern "C" int cholamd_gather_factor(cholamd_device *const *devs, double *const *arenas, int n, void *const *streams)
+{
+  return gather_factor_bytes(devs, (void *const *)arenas, n, streams, 8);
+}
+extern "C" int cholamd_gather_factor_f32(cholamd_device *const *devs, float *const *arenas32, int n, void *const *streams)
+{
+  return gather_factor_bytes(devs, (void *const *)arenas32, n, streams, 4);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3426,203 +2389,10 @@ extern "C" int cholamd_solve_refine_multi(cholamd_device *const *devs, const flo
                      [&](const double *const *r, double *const *o) { return solve_multi_t<float>(devs, arenas32, r, o, comms, n, streams); });
 }
 
-// ---------------------------------------------------------------------------------------------
-// Low-rank corrections on the finished factor (include/cholamd.h at "low-rank corrections"; kernels in chol_lowrank.hip).  The object owns W = A^-1 U L_C^-T
-// (n x kmax, leading dimension n), the capacitance factor C -> L_C and R = L_C^-T (kmax x kmax), two k x 32 blocks for t and the stage-1 workspace of
-// the transposed product.  Everything else goes through the public entry points of the device object it refers to.
-// ---------------------------------------------------------------------------------------------
-struct cholamd_lowrank {
-  cholamd_device *d = nullptr;
-  int kmax = 0, k = 0, mode = 0, info = 0; // k == 0: unset
-  int64_t ldw = 0;
-  double logdet = 0.0;
-  dev_buf<double> W, C, R, T, T2, ws;
-  std::vector<double> LC; // L_C on the host (k x k, the upper triangle zero), read back by set
-};
-static int lowrank_rank_ok(const cholamd_device *d, const char *what)
-{
-  if (d->world > 1 && d->rank != 0) { chol_set_error("%s: rank %d of %d holds no complete factor (gather to rank 0 and use its device object)", what, d->rank, d->world); return CHOLAMD_ERR_ARG; }
-  return 0;
-}
-static int lowrank_is_set(const cholamd_lowrank *lr, const char *what)
-{
-  if (!lr) { chol_set_error("%s: NULL object", what); return CHOLAMD_ERR_ARG; }
-  if (lr->k <= 0) { chol_set_error("%s: the object is unset (no successful cholamd_lowrank_set)", what); return CHOLAMD_ERR_ARG; }
-  return 0;
-}
-extern "C" int cholamd_lowrank_create(cholamd_device *d, int kmax, cholamd_lowrank **out)
-{
-  const char *what = "cholamd_lowrank_create";
-  if (out) *out = nullptr;
-  if (!d || !out) { chol_set_error("%s: NULL %s", what, !d ? "device" : "out"); return CHOLAMD_ERR_ARG; }
-  if (kmax < 1 || kmax > CHOLAMD_LOWRANK_MAX) { chol_set_error("%s: kmax = %d is not in 1 .. %d", what, kmax, CHOLAMD_LOWRANK_MAX); return CHOLAMD_ERR_ARG; }
-  { int rc = lowrank_rank_ok(d, what); if (rc) return rc; }
-  HIPCHK(hipSetDevice(d->dev));
-  cholamd_lowrank *lr = new cholamd_lowrank;
-  lr->d = d; lr->kmax = kmax; lr->ldw = d->plan->n;
-  const size_t n = (size_t)d->plan->n, kk = (size_t)kmax * kmax, kt = (size_t)kmax * CHOL_NRHS_W;
-  int rc = lr->W.alloc(n * kmax);
-  if (!rc) rc = lr->C.alloc(kk);
-  if (!rc) rc = lr->R.alloc(kk);
-  if (!rc) rc = lr->T.alloc(kt);
-  if (!rc) rc = lr->T2.alloc(kt);
-  if (!rc) rc = lr->ws.alloc((size_t)chol_lr_ws_doubles(d->plan->n, kmax));
-  if (rc) { delete lr; return rc; }
-  *out = lr;
-  return 0;
-}
-extern "C" void cholamd_lowrank_destroy(cholamd_lowrank *lr) { delete lr; }
-extern "C" int cholamd_lowrank_state(const cholamd_lowrank *lr, int out[3])
-{
-  if (!lr || !out) { chol_set_error("cholamd_lowrank_state: NULL %s", !lr ? "object" : "out"); return CHOLAMD_ERR_ARG; }
-  out[0] = lr->k; out[1] = lr->mode; out[2] = lr->info;
-  return 0;
-}
-extern "C" int cholamd_lowrank_set(cholamd_lowrank *lr, const double *d_arena, const double *d_U, int64_t ldu, int k, int mode, void *stream)
-{
-  const char *what = "cholamd_lowrank_set";
-  hipStream_t st = (hipStream_t)stream;
-  if (!lr) { chol_set_error("%s: NULL object", what); return CHOLAMD_ERR_ARG; }
-  cholamd_device *d = lr->d;
-  const int n = d->plan->n, kmax = lr->kmax;
-  if (!d_arena || !d_U) { chol_set_error("%s: NULL %s", what, !d_arena ? "arena" : "U"); return CHOLAMD_ERR_ARG; }
-  if (k < 1 || k > kmax) { chol_set_error("%s: k = %d is not in 1 .. kmax = %d", what, k, kmax); return CHOLAMD_ERR_ARG; }
-  if (ldu < n) { chol_set_error("%s: ldu = %lld must be at least n = %d", what, (long long)ldu, n); return CHOLAMD_ERR_ARG; }
-  if (mode != CHOLAMD_LOWRANK_UPDATE && mode != CHOLAMD_LOWRANK_DOWNDATE && mode != CHOLAMD_LOWRANK_CONSTRAINT) {
-    chol_set_error("%s: mode = %d is none of CHOLAMD_LOWRANK_UPDATE (1), _DOWNDATE (-1), _CONSTRAINT (0)", what, mode);
-    return CHOLAMD_ERR_ARG;
-  }
-  { int rc = lowrank_rank_ok(d, what); if (rc) return rc; }
-  HIPCHK(hipSetDevice(d->dev));
-  lr->k = 0; lr->mode = mode; lr->info = 0;
-  double *W = lr->W, *C = lr->C, *R = lr->R;
-  const int64_t ldw = lr->ldw;
-  HIPCHK(hipMemcpy2DAsync(W, (size_t)ldw * sizeof(double), d_U, (size_t)ldu * sizeof(double), (size_t)n * sizeof(double), (size_t)k, hipMemcpyDeviceToDevice, st));
-  { int rc = cholamd_solve_half_nrhs(d, d_arena, W, ldw, W, ldw, k, CHOLAMD_HALF_FORWARD, st); if (rc) return rc; }         // Y = M^-1 U
-  HIPCHK((hipError_t)chol_launch_lr_tprod(n, k, k, W, ldw, W, ldw, lr->ws, C, kmax, st));                                   // G = Y^T Y
-  HIPCHK((hipError_t)chol_launch_lr_small(0, k, k, mode, C, kmax, nullptr, 0, st));                                         // C = I +- G, or G
-  const int info = cholamd_dpotrf_dev(k, C, kmax, nullptr, st);                                                             // C = L_C L_C^T (synchronises)
-  if (info < 0) return info;
-  if (info > 0) {
-    lr->info = info;
-    chol_set_error("%s: the capacitance matrix %s is not positive definite at leading minor %d%s", what, mode > 0 ? "I + U^T A^-1 U" : mode < 0 ? "I - U^T A^-1 U" : "U^T A^-1 U", info,
-                   mode < 0 ? " (A - U U^T is not positive definite)" : mode == 0 ? " (the constraint columns are dependent or zero)" : "");
-    return CHOLAMD_ERR_ARG;
-  }
-  { int rc = cholamd_solve_half_nrhs(d, d_arena, W, ldw, W, ldw, k, CHOLAMD_HALF_BACKWARD, st); if (rc) return rc; }        // V = M^-T Y
-  HIPCHK((hipError_t)chol_launch_lr_small(1, k, k, 0, R, kmax, nullptr, 0, st));
-  { int rc = cholamd_dtrsm_dev(k, k, C, kmax, R, kmax, st); if (rc) return rc; }                                            // R = I L_C^-T
-  HIPCHK((hipError_t)chol_launch_lr_rprod(n, k, k, 0.0, 1.0, W, ldw, R, kmax, W, ldw, st));                                 // W = V R, in place
-  lr->LC.assign((size_t)k * k, 0.0);
-  HIPCHK(hipMemcpy2DAsync(lr->LC.data(), (size_t)k * sizeof(double), C, (size_t)kmax * sizeof(double), (size_t)k * sizeof(double), (size_t)k, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  double sum = 0.0;
-  for (int j = 0; j < k; j++) {
-    for (int i = 0; i < j; i++) lr->LC[i + (size_t)j * k] = 0.0;
-    sum += std::log(lr->LC[j + (size_t)j * k]);
-  }
-  lr->logdet = 2.0 * sum;
-  lr->k = k;
-  return 0;
-}
-// t (k x cols, leading dimension kmax, in lr->T) of one chunk: W^T B, in constraint mode minus L_C^-1 E = R^T E
-static int lowrank_t(cholamd_lowrank *lr, const double *B, int64_t ldb, const double *E, int64_t lde, int cols, hipStream_t st)
-{
-  const int n = lr->d->plan->n, k = lr->k, kmax = lr->kmax;
-  HIPCHK((hipError_t)chol_launch_lr_tprod(n, k, cols, lr->W, lr->ldw, B, ldb, lr->ws, lr->T, kmax, st));
-  if (lr->mode == CHOLAMD_LOWRANK_CONSTRAINT && E) {
-    HIPCHK((hipError_t)chol_launch_lr_tprod(k, k, cols, lr->R, kmax, E, lde, lr->ws, lr->T2, kmax, st));
-    HIPCHK((hipError_t)chol_launch_lr_small(2, k, cols, 0, lr->T, kmax, lr->T2, kmax, st));
-  }
-  return 0;
-}
-static double lowrank_sigma(const cholamd_lowrank *lr) { return lr->mode == CHOLAMD_LOWRANK_DOWNDATE ? -1.0 : 1.0; }
-extern "C" int cholamd_lowrank_solve(cholamd_lowrank *lr, const double *d_arena, const double *d_b, const double *d_e, double *d_x, void *stream)
-{
-  const char *what = "cholamd_lowrank_solve";
-  hipStream_t st = (hipStream_t)stream;
-  { int rc = lowrank_is_set(lr, what); if (rc) return rc; }
-  if (!d_arena || !d_b || !d_x) { chol_set_error("%s: NULL %s", what, !d_arena ? "arena" : !d_b ? "b" : "x"); return CHOLAMD_ERR_ARG; }
-  cholamd_device *d = lr->d;
-  const int n = d->plan->n;
-  { int rc = lowrank_rank_ok(d, what); if (rc) return rc; }
-  HIPCHK(hipSetDevice(d->dev));
-  { int rc = lowrank_t(lr, d_b, n, d_e, lr->k, 1, st); if (rc) return rc; }
-  { int rc = cholamd_solve(d, d_arena, d_b, d_x, st); if (rc) return rc; }
-  HIPCHK((hipError_t)chol_launch_lr_rprod(n, lr->k, 1, 1.0, -lowrank_sigma(lr), lr->W, lr->ldw, lr->T, lr->kmax, d_x, n, st));
-  return 0;
-}
-extern "C" int cholamd_lowrank_solve_nrhs(cholamd_lowrank *lr, const double *d_arena, const double *d_B, int64_t ldb, const double *d_E, int64_t lde, double *d_X, int64_t ldx, int nrhs,
-                                          void *stream)
-{
-  const char *what = "cholamd_lowrank_solve_nrhs";
-  hipStream_t st = (hipStream_t)stream;
-  { int rc = lowrank_is_set(lr, what); if (rc) return rc; }
-  cholamd_device *d = lr->d;
-  { int rc = nrhs_check(d, d_arena, d_B, ldb, d_X, ldx, nrhs, what); if (rc) return rc > 0 ? 0 : rc; }
-  const bool with_e = lr->mode == CHOLAMD_LOWRANK_CONSTRAINT && d_E;
-  if (with_e && lde < lr->k) { chol_set_error("%s: lde = %lld must be at least k = %d", what, (long long)lde, lr->k); return CHOLAMD_ERR_ARG; }
-  { int rc = lowrank_rank_ok(d, what); if (rc) return rc; }
-  HIPCHK(hipSetDevice(d->dev));
-  const int n = d->plan->n;
-  for (int c0 = 0; c0 < nrhs; c0 += CHOL_NRHS_W) {
-    const int cols = std::min(CHOL_NRHS_W, nrhs - c0);
-    const double *B = d_B + (int64_t)c0 * ldb;
-    double *X = d_X + (int64_t)c0 * ldx;
-    { int rc = lowrank_t(lr, B, ldb, with_e ? d_E + (int64_t)c0 * lde : nullptr, lde, cols, st); if (rc) return rc; }
-    { int rc = cholamd_solve_nrhs(d, d_arena, B, ldb, X, ldx, cols, st); if (rc) return rc; }
-    HIPCHK((hipError_t)chol_launch_lr_rprod(n, lr->k, cols, 1.0, -lowrank_sigma(lr), lr->W, lr->ldw, lr->T, lr->kmax, X, ldx, st));
-  }
-  return 0;
-}
-extern "C" int cholamd_lowrank_project(cholamd_lowrank *lr, const double *d_U, int64_t ldu, const double *d_x, const double *d_e, double *d_xout, void *stream)
-{
-  const char *what = "cholamd_lowrank_project";
-  hipStream_t st = (hipStream_t)stream;
-  { int rc = lowrank_is_set(lr, what); if (rc) return rc; }
-  cholamd_device *d = lr->d;
-  const int n = d->plan->n, k = lr->k, kmax = lr->kmax;
-  if (lr->mode != CHOLAMD_LOWRANK_CONSTRAINT) { chol_set_error("%s: the object is not in constraint mode", what); return CHOLAMD_ERR_ARG; }
-  if (!d_U || !d_x || !d_xout) { chol_set_error("%s: NULL %s", what, !d_U ? "U" : !d_x ? "x" : "xout"); return CHOLAMD_ERR_ARG; }
-  if (ldu < n) { chol_set_error("%s: ldu = %lld must be at least n = %d", what, (long long)ldu, n); return CHOLAMD_ERR_ARG; }
-  HIPCHK(hipSetDevice(d->dev));
-  HIPCHK((hipError_t)chol_launch_lr_tprod(n, k, 1, d_U, ldu, d_x, n, lr->ws, lr->T, kmax, st));                   // U^T x
-  if (d_e) HIPCHK((hipError_t)chol_launch_lr_small(2, k, 1, 0, lr->T, kmax, d_e, k, st));                        // - e
-  HIPCHK((hipError_t)chol_launch_lr_tprod(k, k, 1, lr->R, kmax, lr->T, kmax, lr->ws, lr->T2, kmax, st));          // L_C^-1 (U^T x - e)
-  if (d_xout != d_x) HIPCHK(hipMemcpyAsync(d_xout, d_x, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
-  HIPCHK((hipError_t)chol_launch_lr_rprod(n, k, 1, 1.0, -1.0, lr->W, lr->ldw, lr->T2, kmax, d_xout, n, st));
-  return 0;
-}
-extern "C" int cholamd_lowrank_diag(cholamd_lowrank *lr, double *d_w, void *stream)
-{
-  const char *what = "cholamd_lowrank_diag";
-  { int rc = lowrank_is_set(lr, what); if (rc) return rc; }
-  if (!d_w) { chol_set_error("%s: NULL w", what); return CHOLAMD_ERR_ARG; }
-  HIPCHK(hipSetDevice(lr->d->dev));
-  HIPCHK((hipError_t)chol_launch_lr_rowsq(lr->d->plan->n, lr->k, lr->W, lr->ldw, d_w, (hipStream_t)stream));
-  return 0;
-}
-extern "C" int cholamd_lowrank_logdet(cholamd_lowrank *lr, double *logdet_C_out)
-{
-  const char *what = "cholamd_lowrank_logdet";
-  { int rc = lowrank_is_set(lr, what); if (rc) return rc; }
-  if (!logdet_C_out) { chol_set_error("%s: NULL logdet_C_out", what); return CHOLAMD_ERR_ARG; }
-  *logdet_C_out = lr->logdet;
-  return 0;
-}
-extern "C" int cholamd_lowrank_factor(cholamd_lowrank *lr, double *h_LC, int ldl)
-{
-  const char *what = "cholamd_lowrank_factor";
-  { int rc = lowrank_is_set(lr, what); if (rc) return rc; }
-  if (!h_LC || ldl < lr->k) { chol_set_error("%s: %s", what, !h_LC ? "NULL h_LC" : "ldl < k"); return CHOLAMD_ERR_ARG; }
-  for (int j = 0; j < lr->k; j++) std::memcpy(h_LC + (size_t)j * ldl, lr->LC.data() + (size_t)j * lr->k, (size_t)lr->k * sizeof(double));
-  return 0;
-}
-extern "C" int cholamd_lowrank_block(cholamd_lowrank *lr, const double **d_W, int64_t *ldw)
-{
-  const char *what = "cholamd_lowrank_block";
-  { int rc = lowrank_is_set(lr, what); if (rc) return rc; }
-  if (!d_W || !ldw) { chol_set_error("%s: NULL %s", what, !d_W ? "d_W" : "ldw"); return CHOLAMD_ERR_ARG; }
-  *d_W = lr->W; *ldw = lr->ldw;
-  return 0;
-}
+// the sweep templates that chol_api_schur.cpp calls (chol_device.h), for the two element types of the arena
+template int form_inverses<double>(cholamd_device *, const double *, int, bool, hipStream_t);
+template int sweep_levels<double>(cholamd_device *, const double *, sweep_rhs, bool, int, int, int64_t *, hipStream_t);
+template int sweep_steps<double>(cholamd_device *, const double *, const sdet_dev &, int, sweep_rhs, int64_t *, hipStream_t);
+template int form_inverses<float>(cholamd_device *, const float *, int, bool, hipStream_t);
+template int sweep_levels<float>(cholamd_device *, const float *, sweep_rhs, bool, int, int, int64_t *, hipStream_t);
+template int sweep_steps<float>(cholamd_device *, const float *, const sdet_dev &, int, sweep_rhs, int64_t *, hipStream_t);

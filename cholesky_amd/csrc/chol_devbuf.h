@@ -1,4 +1,4 @@
-// Owning device buffers of the C ABI glue (chol_api.cpp only).  A dev_buf<T> holds one device allocation of the library's own: it starts empty, is
+// Owning device buffers of the C ABI glue (the chol_api*.cpp files only, through chol_device.h).  A dev_buf<T> holds one device allocation of the library's own: it starts empty, is
 // move-only and releases what it holds when it goes out of scope or takes something else.  Whatever can fail returns the library's error code with
 // the error text set and leaves the buffer EMPTY: "non-empty" always means "allocated and initialised as asked".  No HIP here: memory comes and goes
 // through the four functions below, which chol_api.cpp defines over the HIP runtime and tests/native/devbuf_host.cpp over malloc.
