@@ -56,7 +56,15 @@ int chol_dev_acquire(void **p, size_t bytes, int floating_point)
   return 0;
 }
 void chol_dev_release(void *p) { (void)hipFree(p); g_live_buffers--; }
-int chol_dev_zero(void *p, size_t bytes) { HIPCHK(hipMemset(p, 0, bytes)); return 0; }
+// The clearing runs on the null stream, and a caller's stream may be non-blocking (torch's pool streams are): it does not wait for the null stream, and
+// the buffer is used by kernels on the caller's stream in the same call.  So the device is synchronised, like the poison fill: ordered before work on any
+// stream.  Creation and first use only (the "repeated calls allocate nothing" tests keep it off the hot path).
+int chol_dev_zero(void *p, size_t bytes)
+{
+  HIPCHK(hipMemset(p, 0, bytes));
+  HIPCHK(hipDeviceSynchronize());
+  return 0;
+}
 int chol_dev_copy_in(void *p, const void *host, size_t bytes) { HIPCHK(hipMemcpy(p, host, bytes, hipMemcpyHostToDevice)); return 0; }
 extern "C" int64_t cholamd_debug_live_buffers(void) { return g_live_buffers.load(); }
 

@@ -296,6 +296,11 @@ int cholamd_device_free(cholamd_device *d, double *dptr);
 int cholamd_device_upload(cholamd_device *d, double *d_dst, const double *h_src, int64_t doubles, void *stream);
 int cholamd_device_download(cholamd_device *d, double *h_dst, const double *d_src, int64_t doubles, void *stream);
 int cholamd_device_sync(cholamd_device *d, void *stream);
+/* STREAMS.  `stream` is a hipStream_t (NULL: the null stream).  Everything a call enqueues goes to that stream, and where a call "synchronises" it waits
+ * for that stream alone.  "Asynchronous on `stream`" describes a WARM call: the first call of a family on a device object also builds, uploads and
+ * clears that family's lists, scratch and status words with blocking copies on the null stream, and a clearing synchronises the whole device once, so
+ * that it is ordered before work on any stream (a non-blocking stream does not wait for the null stream); later calls allocate nothing and only enqueue.
+ * A device object serves ONE stream of work at a time: its scratch and its counters are shared by all its calls. */
 /* A scatter on the device (fill_block, mmat.rg:1216-1224): zero d_arena, scatter tril(A).  A partitioned device (cholamd_device_set_partition)
  * scatters every entry under the cut and, of the shared top of the tree, the entries exactly one rank must start from: all of them on rank 0 when the
  * top levels are replicated, those of the column blocks the rank OWNS when they are distributed (option dist_top) -- fill after set_partition /
