@@ -137,6 +137,10 @@ def load():
     L.cholamd_follow_rounds.argtypes = [ci, ci, ci, vp, vp]
     L.cholamd_plan_program_followers.argtypes = [vp, i64, vp]
     L.cholamd_plan_program_followers.restype = i64
+    L.cholamd_plan_program_follow_own.argtypes = [vp, ci, ci, ci, ci, ci, i64, vp]
+    L.cholamd_plan_program_follow_own.restype = i64
+    L.cholamd_plan_program_check_follow.argtypes = [vp, ci, ci, ci, ci, ci, ci]
+    L.cholamd_plan_program_hazards.argtypes = [vp, ci, ci, ci, ci, ci, vp]
     L.cholamd_factor_multi_f32.argtypes = [vp, vp, vp, ci, vp]
     L.cholamd_gather_factor_f32.argtypes = [vp, vp, ci, vp]
     L.cholamd_device_alloc.argtypes = [vp, i64, C.POINTER(vp)]

@@ -1092,7 +1092,8 @@ __device__ __forceinline__ bool wait_list_holds(const chol_wait *__restrict__ wl
     if (b0 + lane < n) { const chol_wait wt = wl[b0 + lane]; ok = ok && __hip_atomic_load(&ctr[wt.ctr], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= wt.value + epoch * ctr_total[wt.ctr]; }
   return !__ballot(!ok);
 }
-struct follow_args { const chol_ext *ext; int n_ext; const int *ctr; const int *ctr_total; int epoch; const chol_wait *wl; int n_wl; unsigned long long *stamp, *xstamp; };
+struct follow_args { const chol_ext *ext; int n_ext; const int *ctr; const int *ctr_total; int epoch; const chol_wait *wl; int n_wl; unsigned long long *stamp, *xstamp;
+                     int own_at; /* the item in front of whose round the follower's own tiles are added (chol_job.mode; n_ext: after the last item) */ };
 // followed column tiles from item `from` on whose strips have all published: every lane polls one item's counter (one round trip)
 __device__ __forceinline__ int ext_ready(const follow_args &f, int from, int lane)
 {
@@ -1109,11 +1110,13 @@ template <bool UPD, bool PUB, bool TR = false>
 __device__ __forceinline__ void follow_external(const double *__restrict__ base, const follow_args f, int T, int n, double *sE, d4 (&tile)[11], d4 (&stage)[3],
                                                 const int (&ijp)[12], int w, int lane, int tid, int *info, const double *A, int lda, int r15, int g, int *sReady)
 { // sReady: LDS word (0 at entry): leading items the factor wave has seen published
+  // a follower that adds its own tiles LAST leaves them in tile[FOLLOW_SLOTS ..] (free across the followed columns), requested and not waited for
+  // -- columns 0 / 1 in the first three, the register tiles behind: the caller adds and parks the first three while the others are still on their way
   const int lp = lane; // accumulator layout: register q of lane l at q * 64 + l
   int buf = 0;
   // Column tiles are consumed in the order of the list, TWO per round where two fit an LDS buffer (T <= 8) -- a column tile of a wide
   // follower is 16 KB handed over by other workgroups, and one memory round trip per tile is what bounds a follower that has fallen
-  // behind its sources -- except the last two, which go one by one (the follower's start hangs on them).  The grouping is a function
+  // behind its sources (the last items too: CHOL_FOLLOW_SINGLE_TAIL is 0).  The grouping is a function
   // of the list alone: every wave takes the same rounds (they poll for themselves), and a pair is the same sequence of MFMAs on the
   // same accumulators as two single rounds.  `ready` = leading items known to be published; the poll for more is issued before the
   // barrier and update of the round at hand and read after them, and the loads of the next round are issued before the update
@@ -1123,15 +1126,22 @@ __device__ __forceinline__ void follow_external(const double *__restrict__ base,
 #ifndef FOLLOW_OWN_SLEEP
 #define FOLLOW_OWN_SLEEP 4
 #endif
-#ifndef FOLLOW_OWN_LAST_MAX
-#define FOLLOW_OWN_LAST_MAX 0 /* followers with at most this many items add their own tiles after the last one (3: lapl_3375 unchanged, lapl_400 45.8 -> 48.9 us) */
-#endif
   static_assert(CHOL_FOLLOW_PAIR_MAXT == RR_MAXT, "a pair of followed column tiles shares one LDS buffer of RR_MAXT tiles");
-  // where the follower's own tiles go in: before the last FOLLOW_OWN_BEFORE items (their round trip hides behind the wait for those) -- or,
-  // for a follower with one source and a tail only (the next column block of a split pivot: its early jobs hang on the same strips as
-  // its tail, they end after the tail has arrived), after the last item
-  // (rounds and the own tiles' place: chol_follow_round / chol_follow_own_at in chol_plan.h -- functions of the list alone, checked on the host)
-  const int own_at = f.n_ext <= FOLLOW_OWN_LAST_MAX ? f.n_ext : chol_follow_own_at(f.n_ext, T);
+  // where the follower's own tiles go in is the schedule's choice, per follower (chol_job.mode, option follow_own): in front of the round of
+  // the last FOLLOW_OWN_BEFORE items (chol_follow_own_at: their round trip hides behind the wait for those) where the own tiles are ready
+  // early -- or after the last item where early update jobs write the follower's diagonal block: those end a few column steps before the last
+  // followed column tile arrives, and a wait for them in front of the last round holds that round up although it is on the channel.
+  // Fixed by the plan, never by what has been published: the waves count barriers by it, and it is a position in the sum
+  // (rounds: chol_follow_round in chol_plan.h -- a function of the list alone; both checked on the host)
+  const int own_at = f.own_at;
+  // own tiles last: the factor wave has nothing to do while the tile waves update, so it looks at its waits then (one load next to the round's poll,
+  // the entries fetched here) -- by the last round they have usually been seen to hold, and the blocking poll behind it is skipped.  What it sees
+  // changes neither the barriers it counts nor any sum
+  const bool own_last = f.n_wl > 0 && own_at >= f.n_ext;
+  bool own_ok = false;
+  int own_c = 0, own_need = 0, own_v = 0;
+  const bool own_look = !UPD && own_last && f.n_wl <= 64;
+  if (own_look && lane < f.n_wl) { const chol_wait wt = f.wl[lane]; own_c = wt.ctr; own_need = wt.value + f.epoch * f.ctr_total[wt.ctr]; }
 #define EXT_ROUND(I_) chol_follow_round(I_, f.n_ext, T)
 #define EXT_LOAD(I_, V_)                                                                                             \
   {                                                                                                                  \
@@ -1160,7 +1170,7 @@ __device__ __forceinline__ void follow_external(const double *__restrict__ base,
   }
 #define OWN_TILES()                                                                                                  \
   {                                                                                                                  \
- /* the follower's own tiles, before the last two followed column tiles (their round trip hides behind the wait for those) */ \
+ /* the follower's own tiles (columns 0 and 1 first: the first Cholesky waits for tile (0,0) only) */ \
       if (!UPD) wait_list<FOLLOW_OWN_SLEEP>(f.wl, f.n_wl, f.ctr, f.ctr_total, f.epoch, lane, info); /* the factor wave polls: a follower waiting for its own tiles IS on the critical path */ \
       if (TR && !UPD && f.xstamp && lane == 0) f.xstamp[0] = __builtin_amdgcn_s_memrealtime(); \
       lds_barrier(); \
@@ -1227,7 +1237,10 @@ __device__ __forceinline__ void follow_external(const double *__restrict__ base,
       polled = true;
       if (j + lane < f.n_ext) { const int c = f.ext[j + lane].ctr; pv = __hip_atomic_load(&f.ctr[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); pneed = f.epoch * f.ctr_total[c] + f.ext[j + lane].need; }
     }
+    const bool look = own_look && !own_ok;
+    if (look && lane < f.n_wl) own_v = __hip_atomic_load(&f.ctr[own_c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     lds_barrier();
+    if (look) own_ok = !__ballot(lane < f.n_wl && own_v < own_need);
     if (UPD) {
 #pragma unroll
       for (int it = 0; it < 3; ++it) { // the tiles of columns 0 and 1 (parked in LDS by the prologue later on)
@@ -1249,7 +1262,26 @@ __device__ __forceinline__ void follow_external(const double *__restrict__ base,
     }
     i = j;
   }
-  if (f.n_wl > 0 && own_at >= f.n_ext) OWN_TILES();
+  if (own_last) { // after the last item: everything is requested at once and handed to the caller in flight
+    if (!UPD && !own_ok) wait_list<FOLLOW_OWN_SLEEP>(f.wl, f.n_wl, f.ctr, f.ctr_total, f.epoch, lane, info);
+    if (TR && !UPD && f.xstamp && lane == 0) f.xstamp[0] = __builtin_amdgcn_s_memrealtime();
+    lds_barrier(); // the waits hold; every wave has read the last followed column tiles
+    if (UPD) {
+      int rx = r15, gx = g;
+      asm volatile("" : "+v"(rx), "+v"(gx));
+#pragma unroll
+      for (int it = 0; it < 3; ++it) { // columns 0 and 1 first: the first Cholesky waits for tile (0,0) only
+        const int u = min(w + it * RR_NW, 2 * T - 2);
+        tile[FOLLOW_SLOTS + it] = load_tile<PUB>(A, lda, n, u < T ? u : u - T + 1, u < T ? 0 : 1, rx, gx);
+      }
+#pragma unroll
+      for (int s = 0; s < FOLLOW_SLOTS; ++s) {
+        const d4 zero4 = { 0.0, 0.0, 0.0, 0.0 };
+        tile[FOLLOW_SLOTS + 3 + s] = zero4;
+        if (ijp[s] != 0xffff) tile[FOLLOW_SLOTS + 3 + s] = load_tile<PUB>(A, lda, n, ijp[s] & 0xff, ijp[s] >> 8, rx, gx);
+      }
+    }
+  }
 #undef OWN_TILES
 #undef EXT_LOAD_ROUND
 #undef EXT_ROUND
@@ -1297,6 +1329,7 @@ __device__ __forceinline__ void potrf_rr_body(double *__restrict__ base, double 
   PSTAMP(0);
   // a block that follows nobody requests its tiles of columns 0 and 1 before anything else: their round trip runs under the arrival of the role tables
   d4 stage[3];
+  const bool own_pending = FOLLOW && fa.n_ext > 0 && fa.n_wl > 0 && fa.own_at >= fa.n_ext;
   const bool stage_early = !(FOLLOW && fa.n_ext > 0) && wave != 0;
   if (stage_early) {
 #pragma unroll
@@ -1467,7 +1500,8 @@ __device__ __forceinline__ void potrf_rr_body(double *__restrict__ base, double 
       // followed contributions on top.  One with waits starts from ZERO accumulators, consumes its children's columns as they
       // arrive, and adds its own tiles just before the last TWO followed column tiles (follow_external: there its waits must hold;
       // the load hides behind the wait for that column): it does not sit idle until its grandchildren's extend-add is through.
-      // Which of the two is fixed by the schedule, not by timing: the summation order is the same in every run.
+      // Which of the two is fixed by the schedule, not by timing: the summation order is the same in every run.  (Where early update jobs
+      // write the follower's diagonal block the own tiles go in after the LAST followed column tile: chol_job.mode, option follow_own.)
       const bool early = fa.n_wl == 0;
       const d4 zero4 = { 0.0, 0.0, 0.0, 0.0 };
 #pragma unroll
@@ -1483,9 +1517,11 @@ __device__ __forceinline__ void potrf_rr_body(double *__restrict__ base, double 
         tile[s] = v;
       }
       follow_external<true, PUB, TR>(base, fa, T, n, smem + RR_OFF_SOL, tile, stage, ijp, w, lane, tid, info, A, lda, r15, g, &sFlag[5]);
-#pragma unroll
-      for (int s = FOLLOW_SLOTS; s < RR_RSLOTS; ++s) tile[s] = zero4; // not live across the followed columns
       lds_barrier();
+      if (own_pending) { // own tiles last: they are on their way in tile[FOLLOW_SLOTS ..]; columns 0 and 1 are added and parked as they land, the register tiles behind them
+#pragma unroll
+        for (int it = 0; it < 3; ++it) stage[it] += tile[FOLLOW_SLOTS + it];
+      }
     } else {
     PSTAMP(6);
 #pragma unroll
@@ -1508,6 +1544,17 @@ __device__ __forceinline__ void potrf_rr_body(double *__restrict__ base, double 
         if (ti == 1) lds_set(tj == 0 ? fA : fD, 1, lane);
         if (tj == 0 && ti > 0) lds_inc(cRaw, lane);
       }
+    }
+    if (FOLLOW && fa.n_ext > 0) {
+      static_assert(FOLLOW_SLOTS + 3 + FOLLOW_SLOTS <= RR_RSLOTS, "a follower's own tiles in flight fit the register tiles it does not use");
+      if (own_pending) {
+        __builtin_amdgcn_sched_barrier(0); // behind the parking: these wait for the last of the requests
+#pragma unroll
+        for (int s = 0; s < FOLLOW_SLOTS; ++s) tile[s] += tile[FOLLOW_SLOTS + 3 + s];
+      }
+      const d4 zero4 = { 0.0, 0.0, 0.0, 0.0 };
+#pragma unroll
+      for (int s = FOLLOW_SLOTS; s < RR_RSLOTS; ++s) tile[s] = zero4; // not live across the followed columns
     }
     if (ijp[RR_RSLOTS] != 0xffff) { // heavy waves only (rr_owner)
       const d4 v = load_tile<PUB>(A, lda, n, ijp[RR_RSLOTS] & 0xff, ijp[RR_RSLOTS] >> 8, r15, g);
@@ -2130,7 +2177,7 @@ __global__ __launch_bounds__(RR_THREADS) void k_program(double *__restrict__ bas
     if (jb.kind == 0) {
       const chol_potrf_desc pd = pdescs[jb.first];
       follow_args fa;
-      fa.ext = exts + jb.ext_first; fa.n_ext = jb.n_ext; fa.ctr = ctr; fa.ctr_total = ctr_total; fa.epoch = epoch; fa.wl = waits + jb.wait_first; fa.n_wl = jb.n_wait; fa.stamp = TR && trace ? &trace[4 * j + 1] : nullptr; fa.xstamp = TR && trace ? &trace[4 * njobs + CHOL_TRACE_X * j] : nullptr;
+      fa.ext = exts + jb.ext_first; fa.n_ext = jb.n_ext; fa.ctr = ctr; fa.ctr_total = ctr_total; fa.epoch = epoch; fa.wl = waits + jb.wait_first; fa.n_wl = jb.n_wait; fa.own_at = jb.mode; fa.stamp = TR && trace ? &trace[4 * j + 1] : nullptr; fa.xstamp = TR && trace ? &trace[4 * njobs + CHOL_TRACE_X * j] : nullptr;
       potrf_rr_body<true, true, TR>(base, ws, pd, info, ctr + pd.ctr, epoch * ctr_total[pd.ctr], smem, pdescs[jb.first].sky, fa, tid);
     } else if (jb.kind == 1) {
       double (*sX)[RR_MAXT][TS * TS] = (double (*)[RR_MAXT][TS * TS])smem; // [group][column tile]: one slot per solved tile

@@ -181,7 +181,8 @@ typedef struct {
   int ext_first, n_ext;/* POTRF: the external panels it follows (chol_ext), none = plain POTRF */
   int mode, n_pre;     /* n_pre: the leading waits that gate the whole job; the others are STAGED (update jobs of the extend-add: one per source
                         * pivot block in expected order of completion, chol_upd_src.stage) and are looked at by the tasks.  mode: update: 0 = one wave per task (light tasks, twelve at a time), 1 = four waves per task splitting K / the sources
-                        * (heavy tasks, three at a time) */
+                        * (heavy tasks, three at a time); POTRF job that follows and has waits: the followed item in front of whose round its own tiles
+                        * are added, n_ext = after the last item (chosen by the schedule, option follow_own; a start of a round or n_ext) */
 } chol_job;
 typedef struct {       /* one followed column tile: (rows of the follower's block) x (16 columns of a source pivot block).  A follower's items are
                         * queued in the order their columns are EXPECTED to arrive (position of the column in its source's pivot chain: the
@@ -196,7 +197,9 @@ typedef struct {       /* one followed column tile: (rows of the follower's bloc
  * disagreed).  Shared by the kernel and the host-side check (cholamd_follow_rounds, tests/test_host.py). */
 #define CHOL_FOLLOW_PAIR_MAXT 17   /* two column tiles share an LDS buffer of this many tiles */
 #define CHOL_FOLLOW_SINGLE_TAIL 0  /* last items of a list that go one by one (0 / 1 / 2 measured: 189.5 / 190.4 / 190.2 us on lapl_3375) */
-#define CHOL_FOLLOW_OWN_BEFORE 2   /* the follower's own tiles go in at the last round that starts at or before item n - CHOL_FOLLOW_OWN_BEFORE */
+#define CHOL_FOLLOW_OWN_BEFORE 2   /* the follower's own tiles go in at the last round that starts at or before item n - CHOL_FOLLOW_OWN_BEFORE (the default
+                                    * place, chol_follow_own_at; the place in force is chol_job.mode, see option follow_own) */
+#define CHOL_FOLLOW_OWN 1          /* default of option follow_own */
 #if defined(__HIPCC__)
 #define CHOL_HD __host__ __device__ __forceinline__
 #else
@@ -277,6 +280,12 @@ typedef struct {
                              * in front of their first entry, the columns of a source in front of its rows' first entries (identical results) */
   int super_blocks;         /* column blocks per super-block of a wide pivot: the trailing matrix beyond a super-block gets one update of
                              * rank super_blocks * (block width) instead of one per block */
+  int follow_own;           /* program launch: where a follower with waits adds its own tiles (chol_job.mode).  0: in front of the round
+                             * chol_follow_own_at names, everywhere; 1: after the last followed item where early update jobs write the follower's
+                             * diagonal block (they end after the last early column tile is on the channel, a few column steps before the last
+                             * followed one: the wait for them is over late, and in front of the last round it would hold that round up), at
+                             * chol_follow_own_at everywhere else; 2: after the last item for every follower with waits.  Fixed by the plan,
+                             * never by what has been published: the waves count barriers by it, and it is a position in the sum */
 } chol_sched_opts;
 #define CHOL_SUPER_BLOCKS 3
 #define CHOL_STAGE_CHUNK 0

@@ -125,7 +125,7 @@ static int env_int(const char *name, int dflt) { const char *e = getenv(name); r
 void chol_sched_opts_default(chol_sched_opts *o)
 {
   o->split_min = CHOL_SPLIT_MIN; o->split_nb = CHOL_SPLIT_NB; o->fuse = 1; o->fuse_update_max = CHOL_FUSE_UPDATE_MAX;
-  o->mt_min_tiles = CHOL_MT_MIN_TILES; o->trsm_wt_min = CHOL_TRSM_WT_MIN; o->trsm_group = 0; o->cells = 1; o->program = 1; o->follow = 1; o->super_blocks = CHOL_SUPER_BLOCKS; o->dist_top = 2; o->follow_tail = CHOL_FOLLOW_TAIL; o->follow_tail_split = CHOL_FOLLOW_TAIL; o->staged = 1; o->fine_upd = 1; o->skyline = 1; o->stage_chunk = CHOL_STAGE_CHUNK; o->merge_targets = 1; o->leaf_envelope = 1;
+  o->mt_min_tiles = CHOL_MT_MIN_TILES; o->trsm_wt_min = CHOL_TRSM_WT_MIN; o->trsm_group = 0; o->cells = 1; o->program = 1; o->follow = 1; o->super_blocks = CHOL_SUPER_BLOCKS; o->dist_top = 2; o->follow_tail = CHOL_FOLLOW_TAIL; o->follow_tail_split = CHOL_FOLLOW_TAIL; o->staged = 1; o->fine_upd = 1; o->skyline = 1; o->stage_chunk = CHOL_STAGE_CHUNK; o->merge_targets = 1; o->leaf_envelope = 1; o->follow_own = CHOL_FOLLOW_OWN;
 }
 void chol_sched_opts_from_env(chol_sched_opts *o)
 {
@@ -143,6 +143,7 @@ void chol_sched_opts_from_env(chol_sched_opts *o)
   o->super_blocks = env_int("CHOLAMD_SUPER_BLOCKS", o->super_blocks);
   o->follow_tail = env_int("CHOLAMD_FOLLOW_TAIL", o->follow_tail);
   o->follow_tail_split = env_int("CHOLAMD_FOLLOW_TAIL_SPLIT", o->follow_tail_split);
+  o->follow_own = env_int("CHOLAMD_FOLLOW_OWN", o->follow_own);
   o->staged = !env_int("CHOLAMD_NO_STAGED", 0);
   o->fine_upd = !env_int("CHOLAMD_NO_FINE_UPD", 0);
   o->skyline = !env_int("CHOLAMD_NO_SKYLINE", 0);
@@ -1091,12 +1092,13 @@ static int **leaf_row_first(const plan_t *p)
  * triangle of the lim x lim target block at c_off, E = rows of the target in a source panel (off = row 0 in the first of k
  * columns).  They become ordinary update jobs on other CUs that wait for the sources' channel counters (the strips publish their
  * column tiles in order: the last column needed stands for all) and for the earlier update jobs into the panel; the follower
- * itself takes only the last column tiles of each source (follow_external) and sees these through its own tiles. */
+ * itself takes only the last column tiles of each source (follow_external) and sees these through its own tiles.  Returns 1 if it
+ * has emitted jobs (the follower then adds its own tiles last, option follow_own). */
 typedef struct { int64_t off; int ld, k, ctr, need; } early_src; /* ctr: the channel counter of the source's LAST early column tile (tiles before it: ctr - 1, ...) */
 #ifndef EARLY_CHUNK
 #define EARLY_CHUNK 2 /* column tiles per staged source of an early job (1 / 2 / 3 at follow_tail 3: 193.5 / 194.5 / 197.3 us on lapl_3375) */
 #endif
-static void emit_early_cells(pbuild *P, builder *B, const plan_t *p, int64_t c_off, int ldc, int lim, int blk, const early_src *es, int nes,
+static int emit_early_cells(pbuild *P, builder *B, const plan_t *p, int64_t c_off, int ldc, int lim, int blk, const early_src *es, int nes,
                              const int *c_upd, const int *c_updd, int *snap_upd, int *cnt_upd, int *cnt_updd)
 {
   chol_level_work *w = B->w;
@@ -1104,7 +1106,7 @@ static void emit_early_cells(pbuild *P, builder *B, const plan_t *p, int64_t c_o
    * in which the strips publish them, near enough); stage = position in this list + 1 */
   int nst = 0, maxch = 0;
   for (int q = 0; q < nes; q++) if (es[q].k > 0) { const int ch = ((es[q].k + CHOL_NB - 1) / CHOL_NB + EARLY_CHUNK - 1) / EARLY_CHUNK; nst += ch; if (ch > maxch) maxch = ch; }
-  if (nst == 0) return;
+  if (nst == 0) return 0;
   int *sc = malloc(nst * sizeof(int)), *sn = malloc(nst * sizeof(int)), *sq = malloc(nst * sizeof(int)), *sch = malloc(nst * sizeof(int));
   nst = 0;
   for (int c = 0; c < maxch; c++)
@@ -1140,6 +1142,7 @@ static void emit_early_cells(pbuild *P, builder *B, const plan_t *p, int64_t c_o
   snap_upd[col_sep] = cnt_upd[col_sep];
   emit_update_jobs(P, B, p, k0, c_upd, c_updd, snap_upd, cnt_upd, cnt_updd, sc, sn, nst, staged ? sq : NULL); /* sq: only "staged" (the stages are set) */
   free(sc); free(sn); free(sq); free(sch);
+  return w->n_task > k0;
 }
 
 /* the options as the program launch sees them: pivots up to CHOL_PROG_SPLIT_MIN columns whole unless split_min was set by the caller */
@@ -1242,8 +1245,9 @@ int chol_build_program(const plan_t *p, const chol_sched_opts *opts, chol_level_
     }
     est_start[p->tree[h]] = st0;
   }
-  /* POTRF job of block st of separator s; exts were added just before (ext_first .. n_ext) */
-  #define EMIT_POTRF(s_, st_, ext_first_)                                                                        \
+  /* POTRF job of block st of separator s; exts were added just before (ext_first .. n_ext); early_: early update jobs write its
+   * diagonal block.  mode = the place of a follower's own tiles among its items (option follow_own) */
+  #define EMIT_POTRF(s_, st_, ext_first_, early_)                                                                       \
     do {                                                                                                          \
       pblock *b_ = &pb[s_][st_];                                                                                  \
       const int ld_ = p->panel_ld[s_];                                                                            \
@@ -1261,6 +1265,9 @@ int chol_build_program(const plan_t *p, const chol_sched_opts *opts, chol_level_
       add_wait(P, c_updd[s_], cnt_updd[s_]);                                                                      \
       chol_job *j_ = add_job(P, 0, b_->potrf, 1, wf_);                                                            \
       j_->ext_first = (ext_first_); j_->n_ext = pg->n_ext - (ext_first_);                                         \
+      if (j_->n_ext > 0)                                                                                          \
+        j_->mode = j_->n_wait > 0 && (opts->follow_own == 2 || (opts->follow_own == 1 && (early_))) ? j_->n_ext   \
+                   : chol_follow_own_at(j_->n_ext, (b_->nb + CHOL_NB - 1) / CHOL_NB);                             \
       b_->emitted = 1;                                                                                            \
     } while (0)
 
@@ -1280,7 +1287,7 @@ int chol_build_program(const plan_t *p, const chol_sched_opts *opts, chol_level_
       /* (A) POTRF jobs of this step that no follower placement has emitted yet */
       for (int q = 0; q < nh; q++) {
         const int s = p->tree[hs[q]];
-        if (st < nblk_of[s] && !pb[s][st].emitted) EMIT_POTRF(s, st, pg->n_ext);
+        if (st < nblk_of[s] && !pb[s][st].emitted) EMIT_POTRF(s, st, pg->n_ext, 0);
       }
       /* (B) TRSM jobs: per pivot block the followed rows first (next column block of the pivot, rows of the parent's first
        *     column block), then everything else */
@@ -1354,15 +1361,16 @@ int chol_build_program(const plan_t *p, const chol_sched_opts *opts, chol_level_
           for (int i = (b->c0 + b->nb) / CHOL_NB; i * CHOL_NB < b->c0 + b->nb + nb1; i++) if (sky[s][i] < fmin) fmin = sky[s][i];
           if (fmin - b->c0 / CHOL_NB >= bt) bt = 0; /* (the tail items stay: they are cheap, and the follower's list must not be empty) */
         }
+        int early = 0;
         if (bt > 0) {
           const early_src es = { e_off, ld, bt * CHOL_NB, b->ch_below + bt - 1, b->ns_below };
-          emit_early_cells(P, B, p, p->panel_off[s] + (b->c0 + b->nb) + (int64_t)(b->c0 + b->nb) * ld, ld, nb1, BIDX(p, s, s), &es, 1, c_upd, c_updd, snap_upd, cnt_upd, cnt_updd);
+          early = emit_early_cells(P, B, p, p->panel_off[s] + (b->c0 + b->nb) + (int64_t)(b->c0 + b->nb) * ld, ld, nb1, BIDX(p, s, s), &es, 1, c_upd, c_updd, snap_upd, cnt_upd, cnt_updd);
         }
         const int ef = pg->n_ext;
         push_ext_items(&items, &nit, &capit, e_off, ld, b->nb, b->ch_below, b->ns_below, 0, bt);
         for (int i = 0; i < nit; i++) add_ext(P, items[i].x);
         free(items);
-        EMIT_POTRF(s, st + 1, ef);
+        EMIT_POTRF(s, st + 1, ef, early);
       }
       /* (D) trailing update of the step: columns right of the block in the pivot rows below it (lower triangle) and in the
        *     ancestor rows; the diagonal block of a following next column block is left out (follow_external does it) */
@@ -1529,16 +1537,17 @@ int chol_build_program(const plan_t *p, const chol_sched_opts *opts, chol_level_
             before += nt;
           }
         }
+        int early = 0;
         if (nes > 0) {
           const chol_block *Bp = &p->blk[BIDX(p, par, par)];
-          emit_early_cells(P, B, p, Bp->off, Bp->ld, lim, BIDX(p, par, par), es, nes, c_upd, c_updd, snap_upd, cnt_upd, cnt_updd);
+          early = emit_early_cells(P, B, p, Bp->off, Bp->ld, lim, BIDX(p, par, par), es, nes, c_upd, c_updd, snap_upd, cnt_upd, cnt_updd);
         }
         qsort(items, nit, sizeof(ext_item), cmp_ext_item);
         for (int i = 0; i < nit; i++) add_ext(P, items[i].x);
         free(items);
         if (pg->n_ext == ef) continue;
         follow_lim[BIDX(p, par, par)] = pb[par][0].nb;
-        EMIT_POTRF(par, 0, ef);
+        EMIT_POTRF(par, 0, ef, early);
       }
     /* (F) extend-add of the level (tuples in program order, grouped by target), without the followed cells */
     {
@@ -1716,6 +1725,11 @@ int chol_program_check_built(const plan_t *p, const chol_sched_opts *opts, int w
         if (val[wt->ctr] < wt->value) ok = 0;
       }
       if (rc) break;
+      if (jb->kind == 0 && jb->n_ext > 0) { /* the own tiles' place: in front of a round, or after the last item */
+        int at = 0;
+        while (at < jb->mode && at < jb->n_ext) at += chol_follow_round(at, jb->n_ext, (w.potrf[jb->first].n + CHOL_NB - 1) / CHOL_NB);
+        if (at != jb->mode) { chol_set_error("program job %d adds its own tiles at item %d of %d: not the start of a round", j, jb->mode, jb->n_ext); rc = CHOLAMD_ERR_ARG; break; }
+      }
       if (ok && jb->kind == 0)
         for (int x = 0; x < jb->n_ext && ok; x++) {
           const chol_ext *e = &g.ext[jb->ext_first + x];
@@ -1789,6 +1803,17 @@ int cholamd_plan_program_check_opts(const cholamd_plan *p, int follow_tail, int 
   if (split_nb >= 0) o.split_nb = split_nb;
   return chol_program_check(p, &o, workers);
 }
+int cholamd_plan_program_check_follow(const cholamd_plan *p, int follow_tail, int follow_tail_split, int follow_own, int split_min, int split_nb, int workers)
+{ /* ... and under other places of the followers' own tiles (option follow_own) */
+  chol_sched_opts o;
+  chol_sched_opts_from_env(&o);
+  if (follow_tail >= 0) o.follow_tail = follow_tail;
+  if (follow_tail_split >= 0) o.follow_tail_split = follow_tail_split;
+  if (follow_own >= 0) o.follow_own = follow_own;
+  if (split_min >= 0) o.split_min = split_min;
+  if (split_nb >= 0) o.split_nb = split_nb;
+  return chol_program_check(p, &o, workers);
+}
 int64_t cholamd_plan_program_jobs(const cholamd_plan *p, int follow, int64_t cap, int *out)
 { /* diagnostic: per job 8 ints: kind, separator (POTRF / TRSM: the pivot's label; update: target block's column label), target
    * block's row label (update) or column offset of the pivot block, first, n, sig0, sig1, n_wait; then the wait list as
@@ -1840,6 +1865,148 @@ int64_t cholamd_plan_program_followers(const cholamd_plan *p, int64_t cap, int *
   }
   chol_level_work_free(&w); chol_program_free(&g);
   return n;
+}
+int64_t cholamd_plan_program_follow_own(const cholamd_plan *p, int follow_tail, int follow_tail_split, int follow_own, int split_min, int split_nb, int64_t cap, int *out)
+{ /* per following POTRF job under the given options (negative: the default): job index, followed column tiles, column tiles of its pivot
+   * block, the item in front of whose round its own tiles are added (n_ext: after the last; the value the kernel takes), wait-list entries */
+  chol_sched_opts o;
+  chol_sched_opts_default(&o);
+  if (follow_tail >= 0) o.follow_tail = follow_tail;
+  if (follow_tail_split >= 0) o.follow_tail_split = follow_tail_split;
+  if (follow_own >= 0) o.follow_own = follow_own;
+  if (split_min >= 0) o.split_min = split_min;
+  if (split_nb >= 0) o.split_nb = split_nb;
+  chol_level_work w; chol_program g;
+  if (chol_build_program(p, &o, &w, &g)) return -1;
+  int64_t n = 0;
+  for (int j = 0; j < g.n_job; j++) {
+    const chol_job *jb = &g.job[j];
+    if (jb->kind != 0 || jb->n_ext <= 0) continue;
+    if (5 * n + 4 < cap) { out[5 * n] = j; out[5 * n + 1] = jb->n_ext; out[5 * n + 2] = (w.potrf[jb->first].n + CHOL_NB - 1) / CHOL_NB; out[5 * n + 3] = jb->mode; out[5 * n + 4] = jb->n_wait; }
+    n++;
+  }
+  chol_level_work_free(&w); chol_program_free(&g);
+  return n;
+}
+/* Write hazards between the update jobs of the program: two update jobs that write a common arena element must be ordered, the later one
+ * STARTING (its gating waits, chol_job.n_pre) only after the earlier one has completed.  What a wait guarantees is worked out from the counters'
+ * meaning, not from the order of the queue: a wait for `v` on counter c guarantees that signaller A of c has signalled iff the other signallers
+ * of c that can be among the contributions that take c to v without A having signalled -- A is not among what THEY are known to come after, and they
+ * do not themselves come after c >= v -- add up to less than v.  "Comes after" is the least fixed point over all waits of a job, the strips' wait
+ * for their pivot block's POTRF job and a follower's wait for its items.
+ * out: pairs of update jobs with a common element, pairs among them that are not ordered, the first such pair. */
+typedef struct { int job, add; } hz_sig;
+int cholamd_plan_program_hazards(const cholamd_plan *p, int follow_tail, int follow_tail_split, int follow_own, int split_min, int split_nb, int out[4])
+{
+  chol_sched_opts o;
+  chol_sched_opts_default(&o);
+  if (follow_tail >= 0) o.follow_tail = follow_tail;
+  if (follow_tail_split >= 0) o.follow_tail_split = follow_tail_split;
+  if (follow_own >= 0) o.follow_own = follow_own;
+  if (split_min >= 0) o.split_min = split_min;
+  if (split_nb >= 0) o.split_nb = split_nb;
+  chol_level_work w; chol_program g;
+  int rc = chol_build_program(p, &o, &w, &g);
+  if (rc) return rc;
+  const int nj = g.n_job, nw = (nj + 63) / 64;
+  /* signallers per counter */
+  int *ns = calloc(g.n_ctr + 1, sizeof(int)), *first = calloc(g.n_ctr + 2, sizeof(int));
+  hz_sig *sg = NULL;
+  for (int pass = 0; pass < 2; pass++) {
+    if (pass) { for (int c = 0; c < g.n_ctr; c++) { first[c + 1] = first[c] + ns[c]; ns[c] = 0; } sg = malloc((first[g.n_ctr] + 1) * sizeof(hz_sig)); }
+#define HZ_SIG(C_, J_, ADD_) do { if (pass) { hz_sig s_ = { J_, ADD_ }; sg[first[C_] + ns[C_]] = s_; } ns[C_]++; } while (0)
+    for (int j = 0; j < nj; j++) {
+      const chol_job *jb = &g.job[j];
+      if (jb->kind == 0) HZ_SIG(w.potrf[jb->first].ctr, j, g.ctr_total[w.potrf[jb->first].ctr]);
+      if (jb->kind == 1)
+        for (int t = 0; t < (w.trsm[jb->first].n + CHOL_NB - 1) / CHOL_NB; t++) { /* the strips of a job share pivot block and channel */
+          int add = 0;
+          for (int i = jb->first; i < jb->first + jb->n; i++) add += w.trsm[i].chan >= 0 && w.trsm[i].m > 0;
+          if (add > 0) HZ_SIG(w.trsm[jb->first].chan + t, j, add);
+        }
+      for (int q = 0; q < 2; q++) if (jb->sig[q] >= 0 && jb->sig_add > 0) HZ_SIG(jb->sig[q], j, jb->sig_add);
+    }
+#undef HZ_SIG
+  }
+  /* every wait of every job, the implied ones included: a strip job's for its pivot block's POTRF job, a follower's for its items */
+  int nwt = 0;
+  for (int j = 0; j < nj; j++) nwt += g.job[j].n_wait + (g.job[j].kind == 0 ? g.job[j].n_ext : g.job[j].kind == 1 ? 1 : 0);
+  typedef struct { int job, ctr, value, gating; } hz_wait;
+  hz_wait *wt = malloc((nwt + 1) * sizeof(hz_wait));
+  int *nwc = calloc(g.n_ctr + 1, sizeof(int)), *wfirst = calloc(g.n_ctr + 2, sizeof(int)), *wof = malloc((nwt + 1) * sizeof(int));
+  nwt = 0;
+  for (int j = 0; j < nj; j++) {
+    const chol_job *jb = &g.job[j];
+    for (int q = 0; q < jb->n_wait; q++) { hz_wait x = { j, g.wait[jb->wait_first + q].ctr, g.wait[jb->wait_first + q].value, jb->kind != 2 || q < jb->n_pre }; wt[nwt++] = x; }
+    if (jb->kind == 0) for (int q = 0; q < jb->n_ext; q++) { hz_wait x = { j, g.ext[jb->ext_first + q].ctr, g.ext[jb->ext_first + q].need, 1 }; wt[nwt++] = x; }
+    if (jb->kind == 1) { hz_wait x = { j, w.trsm[jb->first].flag, 1, 1 }; wt[nwt++] = x; }
+  }
+  for (int i = 0; i < nwt; i++) nwc[wt[i].ctr]++;
+  for (int c = 0; c < g.n_ctr; c++) { wfirst[c + 1] = wfirst[c] + nwc[c]; nwc[c] = 0; }
+  for (int i = 0; i < nwt; i++) wof[wfirst[wt[i].ctr] + nwc[wt[i].ctr]++] = i;
+  uint64_t *pre = calloc((size_t)nj * nw + 1, sizeof(uint64_t)), *start = calloc((size_t)nj * nw + 1, sizeof(uint64_t));
+  int *reqv = malloc((first[g.n_ctr] + 1) * sizeof(int));
+#define HZ_HAS(S_, J_, A_) ((S_[(size_t)(J_) * nw + (A_) / 64] >> ((A_) % 64)) & 1)
+  for (int changed = 1, sweep = 0; changed && sweep < 64; sweep++) {
+    changed = 0;
+    for (int c = 0; c < g.n_ctr; c++) {
+      /* the largest value of c that signaller Y is known to come after: its own waits for c and those of the jobs it comes after.  The
+       * contributions that take c to v for the FIRST time come from signallers that do not come after c >= v themselves */
+      for (int y = first[c]; y < first[c + 1]; y++) {
+        int m = 0;
+        for (int z = wfirst[c]; z < wfirst[c + 1]; z++) {
+          const hz_wait *x = &wt[wof[z]];
+          if (x->value > m && (x->job == sg[y].job || HZ_HAS(pre, sg[y].job, x->job))) m = x->value;
+        }
+        reqv[y] = m;
+      }
+      for (int z = wfirst[c]; z < wfirst[c + 1]; z++) {
+        const hz_wait *x = &wt[wof[z]];
+        uint64_t *pj = pre + (size_t)x->job * nw, *sj = start + (size_t)x->job * nw;
+        for (int a = first[c]; a < first[c + 1]; a++) {
+          const int A = sg[a].job;
+          if (HZ_HAS(pre, x->job, A) && (!x->gating || HZ_HAS(start, x->job, A))) continue;
+          int f = 0; /* what the others can add before c reaches x->value, without A */
+          for (int y = first[c]; y < first[c + 1] && f < x->value; y++) if (sg[y].job != A && reqv[y] < x->value && !HZ_HAS(pre, sg[y].job, A)) f += sg[y].add;
+          if (f >= x->value) continue;
+          const uint64_t *pa = pre + (size_t)A * nw;
+          for (int k = 0; k < nw; k++) {
+            const uint64_t add = pa[k] | (k == A / 64 ? (uint64_t)1 << (A % 64) : 0);
+            if (add & ~pj[k]) { pj[k] |= add; changed = 1; }
+            if (x->gating && (add & ~sj[k])) { sj[k] |= add; changed = 1; }
+          }
+        }
+      }
+    }
+  }
+  free(wt); free(nwc); free(wfirst); free(wof); free(reqv);
+  /* writers per arena element, in queue order: consecutive writers must be ordered (the order is transitive) */
+  int *last = malloc((size_t)(p->arena > 0 ? p->arena : 1) * sizeof(int));
+  for (int64_t e = 0; e < p->arena; e++) last[e] = -1;
+  uint64_t *seen = calloc((size_t)nj * nw + 1, sizeof(uint64_t));
+  out[0] = out[1] = 0; out[2] = out[3] = -1;
+  for (int j = 0; j < nj; j++) {
+    const chol_job *jb = &g.job[j];
+    if (jb->kind != 2) continue;
+    for (int t = jb->first; t < jb->first + jb->n; t++) {
+      const chol_upd_task *tk = &w.task[t];
+      for (int col = 0; col < tk->nv; col++)
+        for (int r = 0; r < tk->mv; r++) {
+          const int64_t e = tk->c_off + r + (int64_t)col * tk->ldc;
+          if (e < 0 || e >= p->arena) { chol_set_error("program task %d writes outside the arena", t); rc = CHOLAMD_ERR_ARG; continue; }
+          const int a = last[e];
+          last[e] = j;
+          if (a < 0 || a == j || HZ_HAS(seen, j, a)) continue;
+          seen[(size_t)j * nw + a / 64] |= (uint64_t)1 << (a % 64);
+          out[0]++;
+          if (!HZ_HAS(start, j, a)) { if (out[1]++ == 0) { out[2] = a; out[3] = j; } }
+        }
+    }
+  }
+#undef HZ_HAS
+  free(last); free(seen); free(pre); free(start); free(sg); free(ns); free(first);
+  chol_level_work_free(&w); chol_program_free(&g);
+  return rc;
 }
 int cholamd_plan_program_counts(const cholamd_plan *p, int follow, int out[6])
 { /* jobs, POTRF jobs that follow, update tasks, TRSM strips, counters, followed panels */

@@ -293,9 +293,28 @@ class Plan:
         """Host-side self-check of the one-launch program (raises CholamdError on a dead-lock or a mismatch)."""
         check(self.L.cholamd_plan_program_check(self.h, int(follow), int(workers)), "cholamd_plan_program_check")
 
-    def program_check_opts(self, follow_tail=-1, split_min=-1, split_nb=-1, workers=64):
-        """program_check under other follower tails / pivot splits (negative: the default)."""
-        check(self.L.cholamd_plan_program_check_opts(self.h, follow_tail, split_min, split_nb, int(workers)), "cholamd_plan_program_check_opts")
+    def program_check_opts(self, follow_tail=-1, split_min=-1, split_nb=-1, workers=64, follow_tail_split=-1, follow_own=-1):
+        """program_check under other follower tails / pivot splits / places of the followers' own tiles (negative: the default)."""
+        check(self.L.cholamd_plan_program_check_follow(self.h, follow_tail, follow_tail_split, follow_own, split_min, split_nb, int(workers)),
+              "cholamd_plan_program_check_follow")
+
+    def program_follow_own(self, follow_own=-1, follow_tail=-1, follow_tail_split=-1, split_min=-1, split_nb=-1):
+        """The following POTRF jobs of the one-launch program under the given options (negative: the default), one dict each: job, n_ext (followed
+        column tiles), T (column tiles of the block), own_at (the item in front of whose round the job adds its own tiles; n_ext: after the last
+        item -- the place the kernel takes from the job), n_wait (0: the job loads its own tiles first)."""
+        n = self.L.cholamd_plan_program_follow_own(self.h, follow_tail, follow_tail_split, follow_own, split_min, split_nb, 0, None)
+        if n < 0:
+            check(int(n), "cholamd_plan_program_follow_own")
+        buf = np.zeros(5 * n + 5, dtype=np.int32)
+        self.L.cholamd_plan_program_follow_own(self.h, follow_tail, follow_tail_split, follow_own, split_min, split_nb, buf.size, buf.ctypes.data)
+        return [dict(zip(("job", "n_ext", "T", "own_at", "n_wait"), (int(v) for v in buf[5 * i:5 * i + 5]))) for i in range(n)]
+
+    def program_hazards(self, follow_own=-1, follow_tail=-1, follow_tail_split=-1, split_min=-1, split_nb=-1):
+        """Write hazards between the update jobs of the one-launch program: (pairs of update jobs that write a common arena element, pairs among them
+        whose later job may start before the earlier one has completed, the first such pair or (-1, -1))."""
+        out = np.zeros(4, dtype=np.int32)
+        check(self.L.cholamd_plan_program_hazards(self.h, follow_tail, follow_tail_split, follow_own, split_min, split_nb, out.ctypes.data), "cholamd_plan_program_hazards")
+        return int(out[0]), int(out[1]), (int(out[2]), int(out[3]))
 
     def program_counts(self, follow=True):
         out = np.zeros(6, dtype=np.int32)

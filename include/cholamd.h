@@ -230,11 +230,20 @@ int cholamd_plan_program_check(const cholamd_plan *p, int follow, int workers);
 /* the same with followers under other values of the options "follow_tail", "split_min", "split_nb" (negative: the default); the other
  * switches as the environment sets them at the time of the call */
 int cholamd_plan_program_check_opts(const cholamd_plan *p, int follow_tail, int split_min, int split_nb, int workers);
+/* ... and under other values of "follow_tail_split" and "follow_own" (the place of the followers' own tiles) */
+int cholamd_plan_program_check_follow(const cholamd_plan *p, int follow_tail, int follow_tail_split, int follow_own, int split_min, int split_nb, int workers);
 int cholamd_plan_program_counts(const cholamd_plan *p, int follow, int out[6]);
 /* the rounds (of one or two followed column tiles) in which a following POTRF job of `tile_columns` column tiles consumes a list of n_ext items --
  * the kernel's own grouping, a function of the list alone; and the following jobs of a plan's program: (job, items, tile columns, waits) each */
 int cholamd_follow_rounds(int n_ext, int tile_columns, int cap, int *rounds_out, int *own_at_out);
 int64_t cholamd_plan_program_followers(const cholamd_plan *p, int64_t cap, int *out);
+/* the following jobs under given options (negative: the default), five ints each: job, items, tile columns, the item in front of whose round the
+ * job adds its own tiles (items: after the last one) -- the place the schedule has chosen (option "follow_own"), which the kernel takes from the job;
+ * cholamd_follow_rounds names the default place -- and wait-list entries (0: the job loads its own tiles first).  Returns the number of jobs. */
+int64_t cholamd_plan_program_follow_own(const cholamd_plan *p, int follow_tail, int follow_tail_split, int follow_own, int split_min, int split_nb, int64_t cap, int *out);
+/* write hazards between the update jobs of the program under given options (negative: the default): out = pairs of update jobs that write a common arena
+ * element, pairs among them whose later job may start before the earlier one has completed (worked out from what the counters guarantee), the first such pair */
+int cholamd_plan_program_hazards(const cholamd_plan *p, int follow_tail, int follow_tail_split, int follow_own, int split_min, int split_nb, int out[4]);
 int64_t cholamd_plan_program_jobs(const cholamd_plan *p, int follow, int64_t cap, int *out); /* diagnostic dump of the job queue (scripts/prog_trace.py) */ /* jobs, following POTRF jobs, update tasks, strips, counters, followed panels */
 /* dense N x N col-major image of an arena (zeros outside allocated blocks) and back */
 int cholamd_plan_arena_to_dense(const cholamd_plan *p, const double *arena, double *dense);
@@ -384,7 +393,9 @@ int cholamd_factor_info(cholamd_device *d, int *sep_out);
  * of a small problem as one launch; CHOLAMD_NO_PROGRAM), "follow" (its pivot blocks follow their children's TRSM strips;
  * CHOLAMD_NO_FOLLOW), "follow_tail" (followers of more than four tile columns take the last follow_tail column tiles of each source
  * themselves, update jobs bring the rest; 0 = they take everything; CHOLAMD_FOLLOW_TAIL; "follow_tail_split": the same for the next
- * column block of a split pivot), "staged" (the extend-add jobs of the
+ * column block of a split pivot), "follow_own" (where a follower that waits for update jobs adds its own tiles to the followed sums: 0 = in front
+ * of the round of its last two followed column tiles; 1, the default = after the last followed column tile where early update jobs write its diagonal
+ * block, as 0 elsewhere; 2 = after the last one for every such follower; the factor differs between the values by rounding; CHOLAMD_FOLLOW_OWN), "staged" (the extend-add jobs of the
  * program launch take their sources pivot block by pivot block as those are solved instead of waiting for all of them;
  * CHOLAMD_NO_STAGED), "fine_upd" (followed strips wait for the update jobs into their own rows' block only; CHOLAMD_NO_FINE_UPD),
  * (the program launch factors pivots up to 176 columns whole while "split_min" / "split_nb" are at their defaults: CHOL_PROG_SPLIT_MIN),

@@ -57,29 +57,31 @@ for j in range(len(jobs)):
         if c >= 0:
             sig_jobs.setdefault(int(c), []).append(j)
 heap_level = {int(plan.tree[h - 1]): h.bit_length() - 1 for h in range(1, plan.nsep + 1)}
-print("critical waits of the POTRF jobs (last signalling job of every counter waited for):")
+def reached(c, v):
+    """The job whose signal took counter c to the waited value v: the v-th signaller to end (jobs that signal later do not count towards the wait)."""
+    js = sorted(sig_jobs.get(int(c), []), key=lambda q: us[q, 2])
+    return js[min(int(v), len(js)) - 1] if js and v > 0 else None
+
+
+print("critical waits of the POTRF jobs (per counter waited for: the job whose signal took it to the waited value):")
 for j in range(len(jobs)):
     if jobs[j, 0] != 0:
         continue
     ws = waits[waits[:, 0] == j]
     worst = None
     for _, c, v in ws:
-        js = sig_jobs.get(int(c), [])
-        if js:
-            last = max(js, key=lambda q: us[q, 2])
-            if worst is None or us[last, 2] > us[worst, 2]:
-                worst = last
+        last = reached(c, v)
+        if last is not None and (worst is None or us[last, 2] > us[worst, 2]):
+            worst = last
     if worst is not None:
         print(f"  POTRF job {j} (sep {jobs[j, 1]} level {heap_level[int(jobs[j, 1])]} col0 {jobs[j, 2]}) start {us[j, 1]:6.1f}: last signal from job {worst} kind {jobs[worst, 0]} "
               f"target col-sep {jobs[worst, 1]} row-sep {jobs[worst, 2]}: drawn {us[worst, 0]:6.1f} start {us[worst, 1]:6.1f} end {us[worst, 2]:6.1f}")
         ws2 = waits[waits[:, 0] == worst]
         w2 = None
         for _, c, v in ws2:
-            js = sig_jobs.get(int(c), [])
-            if js:
-                last = max(js, key=lambda q: us[q, 2])
-                if w2 is None or us[last, 2] > us[w2, 2]:
-                    w2 = last
+            last = reached(c, v)
+            if last is not None and (w2 is None or us[last, 2] > us[w2, 2]):
+                w2 = last
         if w2 is not None:
             print(f"        ... which waited for job {w2} kind {jobs[w2, 0]} sep {jobs[w2, 1]} aux {jobs[w2, 2]}: drawn {us[w2, 0]:6.1f} start {us[w2, 1]:6.1f} end {us[w2, 2]:6.1f}")
 
@@ -180,3 +182,38 @@ if os.environ.get("TRACE_WAITS"):
             t = max((us[q, 2] for q in js), default=-1.0)
             line += f" c{c}>={v}@{t:.1f}"
         print(line)
+
+# followers: the four instants of a transition -- the last followed column tile on the channel, the wait for the own tiles over, the first column
+# started -- and where the own tiles go in (Plan.program_follow_own under the option given on the command line)
+own_opt = next((int(kv.split("=")[1]) for kv in sys.argv[2:] if kv.startswith("follow_own=")), -1)
+tail_opt = next((int(kv.split("=")[1]) for kv in sys.argv[2:] if kv.startswith("follow_tail=")), -1)
+place = {f["job"]: f for f in plan.program_follow_own(own_opt, follow_tail=tail_opt)}
+heap_of = {int(plan.tree[h - 1]): h for h in range(1, plan.nsep + 1)}
+fol = {}
+if os.path.exists(follow_file):
+    for ln in open(follow_file):
+        w = ln.split()
+        if len(w) >= 8 and w[2] == "kind" and w[3] == "0" and w[4] == "items":
+            fol[int(w[1])] = (float(w[7]), _stamps(ln, "rounds:"), _stamps(ln, "column started:"))
+print("followers (us): job, items, tile columns, own tiles at | last followed tile on the channel, last round taken, own-tiles wait over, first column started | wait over -> start")
+for j in sorted(fol):
+    if j not in place or place[j]["n_wait"] == 0:
+        continue
+    over, rounds, started = fol[j]
+    sep, col0 = int(jobs[j, 1]), int(jobs[j, 2])
+    # the sources: the strips of the block before (a later column block), of the children's rows of this separator (a first block); a block with two
+    # channels has the one to its own next block first
+    srcs = []
+    for (s2, c2, ch), js in seen.items():
+        chans = sorted(k[2] for k in seen if k[:2] == (s2, c2))
+        has_next = any(k[0] == s2 and k[1] > c2 for k in pot)
+        below = ch == chans[0] and has_next and (len(chans) == 2 or heap_of[s2] == 1)
+        if col0 > 0 and s2 == sep and below and c2 == max(k[1] for k in pot if k[0] == sep and k[1] < col0):
+            srcs += js
+        if col0 == 0 and heap_of[s2] // 2 == heap_of[sep] and not below:
+            srcs += js
+    on_chan = max((max(chn[q].values()) for q in srcs if chn.get(q)), default=float("nan"))
+    f = place[j]
+    start = started.get(0, float("nan"))
+    print(f"  job {j:4d} items {f['n_ext']:2d} T {f['T']:2d} own at {f['own_at']:2d}{' (last)' if f['own_at'] == f['n_ext'] else '':7s} | {on_chan:6.1f} {max(rounds.values(), default=float('nan')):6.1f} "
+          f"{over:6.1f} {start:6.1f} | {start - over:4.1f}   wait over {'after' if over > on_chan else 'before'} the last followed tile")
