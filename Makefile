@@ -9,11 +9,12 @@ BIN     := cholesky_amd/bin
 CFLAGS  := -O2 -fPIC -Wall -Wextra -std=gnu11 -Iinclude -I$(CSRC)
 HIPFLAGS:= -O3 -fPIC --offload-arch=$(ARCH) -Iinclude -I$(CSRC) -Wall
 # the TRSM strips' step loop (trsm_rr_body, up to 20 column tiles) must unroll completely: its register tiles are indexed by the step; beyond
-# LLVM's default pragma-unroll budget the loop stays rolled and the tiles go to scratch (160 B per lane)
-$(OUT)/chol_kernels.o: KERNFLAGS := -mllvm -pragma-unroll-threshold=100000
+# LLVM's default pragma-unroll budget the loop stays rolled and the tiles go to scratch (160 B per lane).  The streamed solve needs the flag as well:
+# without it the two k_solve_inv256 instances come out as different, shorter code
+$(OUT)/chol_kernels.o $(OUT)/chol_solve.o: KERNFLAGS := -mllvm -pragma-unroll-threshold=100000
 
-HOST_OBJS := $(OUT)/chol_ingest.o $(OUT)/chol_symbolic.o $(OUT)/chol_schedule.o $(OUT)/chol_generate.o $(OUT)/chol_lowrank_host.o
-KERNEL_OBJS := $(OUT)/chol_kernels.o $(OUT)/chol_kernels_f32.o $(OUT)/chol_solve_nrhs.o $(OUT)/chol_factor_query.o $(OUT)/chol_selinv.o $(OUT)/chol_schur.o $(OUT)/chol_multiply.o $(OUT)/chol_multiply_nrhs.o $(OUT)/chol_solve_det.o $(OUT)/chol_lowrank.o $(OUT)/chol_values_grad.o $(OUT)/chol_pcg.o
+HOST_OBJS := $(OUT)/chol_ingest.o $(OUT)/chol_symbolic.o $(OUT)/chol_schedule.o $(OUT)/chol_lists.o $(OUT)/chol_generate.o $(OUT)/chol_lowrank_host.o
+KERNEL_OBJS := $(OUT)/chol_kernels.o $(OUT)/chol_solve.o $(OUT)/chol_kernels_f32.o $(OUT)/chol_solve_nrhs.o $(OUT)/chol_factor_query.o $(OUT)/chol_selinv.o $(OUT)/chol_schur.o $(OUT)/chol_multiply.o $(OUT)/chol_multiply_nrhs.o $(OUT)/chol_solve_det.o $(OUT)/chol_lowrank.o $(OUT)/chol_values_grad.o $(OUT)/chol_pcg.o
 # the C-ABI glue: one file per family of entry points over the internal header chol_device.h
 GLUE      := chol_api chol_api_schur chol_api_blas chol_api_lowrank
 GLUE_HDRS := $(CSRC)/chol_device.h $(CSRC)/chol_devbuf.h $(CSRC)/chol_plan.h $(CSRC)/chol_kernels.h include/cholamd.h
@@ -29,6 +30,7 @@ $(OUT)/%.o: $(CSRC)/%.c $(CSRC)/chol_plan.h include/cholamd.h
 $(OUT)/%.o: $(CSRC)/%.hip $(CSRC)/chol_plan.h $(CSRC)/chol_kernels.h
 	@mkdir -p $(OUT)
 	$(HIPCC) $(HIPFLAGS) $(KERNFLAGS) -c $< -o $@
+$(OUT)/chol_kernels.o $(OUT)/chol_solve.o: $(CSRC)/chol_wave.h
 
 $(GLUE_OBJS): $(OUT)/%.o: $(CSRC)/%.cpp $(GLUE_HDRS)
 	@mkdir -p $(OUT)
@@ -55,7 +57,7 @@ clean:
 # cholesky_amd/lib/asan/libcholamd.so and runs the CPU test-suite of the host logic against it.
 ASAN_OUT := cholesky_amd/lib/asan
 SAN := -fsanitize=address,undefined -fno-omit-frame-pointer -g
-ASAN_HOST_OBJS := $(ASAN_OUT)/chol_ingest.o $(ASAN_OUT)/chol_symbolic.o $(ASAN_OUT)/chol_schedule.o $(ASAN_OUT)/chol_generate.o $(ASAN_OUT)/chol_lowrank_host.o
+ASAN_HOST_OBJS := $(ASAN_OUT)/chol_ingest.o $(ASAN_OUT)/chol_symbolic.o $(ASAN_OUT)/chol_schedule.o $(ASAN_OUT)/chol_lists.o $(ASAN_OUT)/chol_generate.o $(ASAN_OUT)/chol_lowrank_host.o
 $(ASAN_OUT)/%.o: $(CSRC)/%.c $(CSRC)/chol_plan.h include/cholamd.h
 	@mkdir -p $(ASAN_OUT)
 	$(CC) $(CFLAGS) -O1 $(SAN) -c $< -o $@

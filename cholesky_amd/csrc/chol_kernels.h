@@ -7,6 +7,7 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 #include "chol_plan.h"
+/* fp64 factor (chol_kernels.hip) */
 int chol_launch_scatter(double *arena, const int64_t *dst, const double *val, int64_t nnz, hipStream_t st);
 /* new values of A (cholamd_device_set_values): `parts` = CHOL_VALUES_STATUS (the four status words of the value array, which start at
  * { 0, INT64_MAX, 0, INT64_MAX }) | CHOL_VALUES_GATHER (a_val[e] = vals[a_src[e]], csr_val[k] = vals[csr_src[k]]) in one launch */
@@ -30,6 +31,7 @@ int chol_launch_dinv(const double *L, int n, int ldl, double *W, hipStream_t st)
 int chol_launch_trsm(double *base, const double *ws, const chol_trsm_desc *descs, int n, hipStream_t st);
 int chol_launch_update(double *base, const chol_upd_task *tasks, const chol_upd_src *srcs, int ntask, hipStream_t st);
 int chol_launch_update_mt(double *base, const chol_upd_task *tasks, const chol_upd_src *srcs, int ntask, int64_t arena_elems, hipStream_t st);
+/* streamed solve (chol_solve.hip) */
 int chol_launch_permute(const double *in, const int *perm, double *out, int n, int inverse, hipStream_t st);
 template <class TL> int chol_launch_solve_dinv(const TL *base, const chol_trsv_desc *descs, int n, int max_n, double *W, hipStream_t st);
 /* flags / gen: STEP flags of the device object (one int per separator of a top level, zero at allocation) and its launch counter (host) -- the step launches
@@ -44,15 +46,16 @@ template <class TL> int chol_launch_solve_offdiag(const TL *base, const chol_gem
 int chol_launch_trsv_fwd(const double *base, const chol_trsv_desc *descs, int n, double *y, hipStream_t st);
 int chol_launch_gemv_fwd(const double *base, const chol_gemv_desc *descs, const int *grp_start, const int *grp_rows, int ngroups, double *y, hipStream_t st);
 int chol_launch_bwd(const double *base, const chol_trsv_desc *descs, const chol_gemv_desc *gd, const int *gstart, int n, double *y, hipStream_t st);
-/* fp32 factor (chol_kernels_f32.hip) and the fp64 refinement helpers */
+/* the fp64 refinement helpers (chol_solve.hip): r = b - A x with the row blocks' sums of r^2 and b^2, x += dx */
+int chol_launch_residual(const int64_t *ptr, const int *col, const double *val, const double *b, const double *x, double *r, int n, double *partial, hipStream_t st);
+int chol_launch_axpy1(double *x, const double *dx, int n, hipStream_t st);
+/* fp32 factor (chol_kernels_f32.hip) */
 int chol_launch_scatter(float *arena, const int64_t *dst, const double *val, int64_t nnz, hipStream_t st);
 int chol_launch_potrf(float *base, float *ws, const chol_potrf_desc *descs, int n, int *info, hipStream_t st);
 int chol_launch_trsm(float *base, const float *ws, const chol_trsm_desc *descs, int n, hipStream_t st); /* (the fp32 schedule's kinds 1 and 4) */
 int chol_launch_trsm_wt(float *base, const float *ws, const chol_trsm_desc *descs, int n, hipStream_t st);
 int chol_launch_update(float *base, const chol_upd_task *tasks, const chol_upd_src *srcs, int ntask, hipStream_t st);
 int chol_launch_update_mt(float *base, const chol_upd_task *tasks, const chol_upd_src *srcs, int ntask, int64_t arena_elems, hipStream_t st);
-int chol_launch_residual(const int64_t *ptr, const int *col, const double *val, const double *b, const double *x, double *r, int n, double *partial, hipStream_t st);
-int chol_launch_axpy1(double *x, const double *dx, int n, hipStream_t st);
 /* block solve (chol_solve_nrhs.hip): right-hand sides in chunks of CHOL_NRHS_W columns in a permuted block Y (n x CHOL_NRHS_W, row-major); W16 / W256 as for
  * chol_launch_solve_trsv (W256 NULL: the substitution chain of the 16x16 inverses) */
 #define CHOL_NRHS_W 32
@@ -92,7 +95,7 @@ int chol_launch_schur_pack(const double *W, int64_t ldw, const double *XT, int64
 template <class TL> int chol_launch_multiply(const TL *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, const double *z, double *y, const int *perm, hipStream_t st);
 /* deterministic streamed solve (chol_solve_det.hip; chol_plan.h at chol_sdet_lists): the gather launch of one step, y[item] -= sum over the item's sources,
  * `items` = the step's first item, n_items of them, in permuted coordinates and in place (no source of a step is owned by an item of the step); one owner per
- * position, a fixed order, no atomics.  solve_span (chol_kernels.hip): the diagonal solve of the columns [col0, col0 + 256) of the n separators `descs`
+ * position, a fixed order, no atomics.  solve_span (chol_solve.hip): the diagonal solve of the columns [col0, col0 + 256) of the n separators `descs`
  * (those with fewer columns do nothing) with the 16x16 inverses W of chol_launch_solve_dinv, plain stores */
 template <class TL> int chol_launch_solve_det_gather(const TL *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, double *y, hipStream_t st);
 template <class TL> int chol_launch_solve_span(const TL *base, const chol_trsv_desc *descs, int n, const double *W, double *y, int col0, int backward, hipStream_t st);

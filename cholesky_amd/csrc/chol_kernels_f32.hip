@@ -627,37 +627,6 @@ __global__ __launch_bounds__(64 * T32_WAVES) void k32_trsm_wt(float *__restrict_
   }
 }
 
-// ------------------------------------------------------------------------------------------------
-// Iterative refinement helpers (fp64): r = b - A x with A as a symmetric CSR in original dof order, per-workgroup
-// partial sums of r^2 and b^2 (added on the host: deterministic), x += dx.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_residual_csr(const int64_t *__restrict__ ptr, const int *__restrict__ col, const double *__restrict__ val,
-                                                      const double *__restrict__ b, const double *__restrict__ x, double *__restrict__ r, int n, double *__restrict__ partial)
-{
-  __shared__ double s2[2][4];
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  double ri = 0.0, bi = 0.0;
-  if (i < n) {
-    bi = b[i];
-    double acc = bi;
-    for (int64_t e = ptr[i]; e < ptr[i + 1]; ++e) acc = fma(-val[e], x[col[e]], acc);
-    ri = acc;
-    if (r) r[i] = ri;
-  }
-  double a = ri * ri, c = bi * bi;
-  for (int o = 32; o > 0; o >>= 1) { a += __shfl_down(a, o, 64); c += __shfl_down(c, o, 64); }
-  if ((threadIdx.x & 63) == 0) { s2[0][threadIdx.x >> 6] = a; s2[1][threadIdx.x >> 6] = c; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    partial[2 * blockIdx.x] = ((s2[0][0] + s2[0][1]) + s2[0][2]) + s2[0][3];
-    partial[2 * blockIdx.x + 1] = ((s2[1][0] + s2[1][1]) + s2[1][2]) + s2[1][3];
-  }
-}
-__global__ void k_axpy1(double *__restrict__ x, const double *__restrict__ dx, int n)
-{
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) x[i] += dx[i];
-}
 
 int chol_launch_scatter(float *arena, const int64_t *dst, const double *val, int64_t nnz, hipStream_t st)
 {
@@ -700,17 +669,5 @@ int chol_launch_update_mt(float *base, const chol_upd_task *tasks, const chol_up
   if (ntask <= 0) return 0;
   const int per_xcd = (ntask + 7) / 8;
   hipLaunchKernelGGL(k32_update_mt, dim3(per_xcd * 8), dim3(256), 0, st, base, tasks, srcs, ntask, per_xcd, arena_elems);
-  return (int)hipGetLastError();
-}
-int chol_launch_residual(const int64_t *ptr, const int *col, const double *val, const double *b, const double *x, double *r, int n, double *partial, hipStream_t st)
-{
-  if (n <= 0) return 0;
-  hipLaunchKernelGGL(k_residual_csr, dim3((n + 255) / 256), dim3(256), 0, st, ptr, col, val, b, x, r, n, partial);
-  return (int)hipGetLastError();
-}
-int chol_launch_axpy1(double *x, const double *dx, int n, hipStream_t st)
-{
-  if (n <= 0) return 0;
-  hipLaunchKernelGGL(k_axpy1, dim3((n + 255) / 256), dim3(256), 0, st, x, dx, n);
   return (int)hipGetLastError();
 }

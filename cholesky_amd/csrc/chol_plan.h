@@ -364,6 +364,8 @@ struct cholamd_plan {
   int64_t nnz_tiles;  /* area of the filled tiles the schedule touches (>= nnz_l) */
   double fmin;        /* sum_j colcount_j^2, the lower bound F_min of SURVEY 8d */
 };
+typedef struct cholamd_plan plan_t; /* the host files' short name (chol_symbolic.c, chol_schedule.c, chol_lists.c) */
+#define BIDX(p, r, c) ((p)->blk_index[(size_t)(r) * ((p)->nsep + 1) + (c)])
 
 /* chol_symbolic.c */
 /* the plan rules of the values-gradient calls (include/cholamd.h at cholamd_values_grad_pairs): count == nz, no dropped and no duplicate entries; 0 or
@@ -385,7 +387,12 @@ int chol_build_level_work(const struct cholamd_plan *p, const chol_sched_opts *o
 void chol_level_work_free(chol_level_work *w);
 int chol_owner_of(const struct cholamd_plan *p, int label, int world); /* -1: shared top of the tree */
 int chol_split_level(int world);
-/* solve lists of one tree level; caller frees with chol_solve_level_free */
+/* the envelope of A in the LEAF panels (chol_schedule.c, at their definitions), shared with the list builders of chol_lists.c: per separator (index
+ * 1..nsep, NULL unless a leaf) the first non-zero column tile of every tile row of the pivot / the first non-zero column of every panel row */
+unsigned char **chol_leaf_skylines(const struct cholamd_plan *p);
+void chol_free_skylines(unsigned char **sky, int ns);
+int **chol_leaf_row_first(const struct cholamd_plan *p);
+/* solve lists of one tree level (this and the list builders below: chol_lists.c); caller frees with chol_solve_level_free */
 typedef struct {
   int n_trsv; chol_trsv_desc *trsv;                 /* one per separator of the level (forward and backward) */
   int n_fw; chol_gemv_desc *fw;                     /* forward sources, grouped by target row chunk */

@@ -1,7 +1,7 @@
 // The gathers of the deterministic streamed solve (option solve_deterministic; include/cholamd.h at "deterministic solve", lists: chol_plan.h at
 // chol_sdet_lists).  A sweep is a chain of STEPS, level by level: a level's lead step subtracts from the level's part of the permuted vector what reaches
 // it from outside its own diagonal blocks (FORWARD: the panels of the descendants; BACKWARD: the row runs into the ancestors); then, per 256-column span of
-// the level's separators, a step subtracts what reaches the span from inside the block and the span solvers of chol_kernels.hip (chol_launch_solve_span,
+// the level's separators, a step subtracts what reaches the span from inside the block and the span solvers of chol_solve.hip (chol_launch_solve_span,
 // plain stores) solve the span.  This kernel is the gather of either kind of step.  One workgroup per ITEM, an item owns at most 16 consecutive positions
 // and walks its sources in list order: one owner per position, a fixed summation order, no floating-point atomics -- two sweeps over one arena and one
 // right-hand side leave the same bits.  What a step reads of the vector was written by earlier launches on the stream (descendants and earlier spans in the

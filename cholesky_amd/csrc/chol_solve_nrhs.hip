@@ -19,7 +19,7 @@
 #include "chol_plan.h"
 
 #define NW CHOL_NRHS_W   // right-hand sides per chunk: two 16-column MFMA tiles
-#define NSPAN 256        // span of the diagonal solve (= SSPAN of chol_kernels.hip, the span of the explicit inverses)
+#define NSPAN 256        // span of the diagonal solve (= SSPAN of chol_solve.hip, the span of the explicit inverses)
 #define NT 16            // MFMA tile
 #define NPANEL_ROWS 256  // rows under a span per workgroup of k_nrhs_panel
 static_assert(NW == 32, "Y rows are two 16-column tiles");

@@ -19,10 +19,6 @@
 
 #include "chol_plan.h"
 
-typedef struct cholamd_plan plan_t;
-
-#define BIDX(p, r, c) ((p)->blk_index[(size_t)(r) * ((p)->nsep + 1) + (c)])
-
 static int ilog2(int v) { int l = 0; while ((1 << (l + 1)) <= v) l++; return l; }
 
 int chol_ntiles(const plan_t *p, int sep, int t)

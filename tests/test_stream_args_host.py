@@ -137,7 +137,7 @@ def test_the_scanner_sees_the_calls(scanned):
         by_kind[e[3]] = by_kind.get(e[3], 0) + 1
     assert by_kind.get("hipLaunchKernelGGL", 0) >= 100 and by_kind.get("hipMemcpyAsync", 0) >= 10 and by_kind.get("hipEventRecord", 0) >= 4, by_kind
     files = {e[0] for e in enq}
-    for fn in ("chol_kernels.hip", "chol_kernels_f32.hip", "chol_solve_nrhs.hip", "chol_solve_det.hip", "chol_pcg.hip", "chol_selinv.hip",
+    for fn in ("chol_kernels.hip", "chol_solve.hip", "chol_kernels_f32.hip", "chol_solve_nrhs.hip", "chol_solve_det.hip", "chol_pcg.hip", "chol_selinv.hip",
                "chol_multiply.hip", "chol_api.cpp", "chol_api_schur.cpp", "chol_api_lowrank.cpp", "chol_device.h"):
         assert fn in files, fn
     assert all(e[2] for e in enq) and all(b[2] for b in blk)
