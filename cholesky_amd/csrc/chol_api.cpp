@@ -214,10 +214,10 @@ extern "C" int cholamd_device_set_partition(cholamd_device *d, int rank, int wor
 }
 
 extern "C" int cholamd_device_bcast_phases(const cholamd_device *d)
-{ // broadcast phases (kind 6: top levels distributed by column blocks, option dist_top) in the device's per-level lists; > 0: the
+{ // broadcast phases (CHOL_PH_BCAST: top levels distributed by column blocks, option dist_top) in the device's per-level lists; > 0: the
   // factorisation needs a communicator (cholamd_factor_sharded / cholamd_factor_multi)
   int n = 0;
-  for (const level_dev &l : d->lv) for (const chol_phase &ph : l.phase) n += ph.kind == 6;
+  for (const level_dev &l : d->lv) for (const chol_phase &ph : l.phase) n += ph.kind == CHOL_PH_BCAST;
   return n;
 }
 extern "C" int cholamd_device_set_option(cholamd_device *d, const char *name, int value)
@@ -1974,7 +1974,7 @@ extern "C" int cholamd_exchange_volume(const cholamd_device *d, int64_t out[4])
   if (px.empty() && d->world > 1) out[0] = out[1] = 2 * count * (d->world - 1) / d->world;
   return 0;
 }
-// one rank's broadcasts of a phase of kind 6 (distributed top levels): every column block of the step travels from its owner to all
+// one rank's broadcasts of a CHOL_PH_BCAST phase (distributed top levels): every column block of the step travels from its owner to all
 // ranks, in place at the same arena offset; one RCCL group
 template <class T> static int bcast_rank_t(cholamd_device *d, const level_dev &l, const chol_phase &ph, T *d_arena, cholamd_comm *c, hipStream_t st)
 {
@@ -2008,19 +2008,28 @@ template <class T> static int device_fill(cholamd_device *d, T *d_arena, hipStre
 }
 extern "C" int cholamd_device_fill(cholamd_device *d, double *d_arena, void *stream) { return device_fill(d, d_arena, (hipStream_t)stream); }
 extern "C" int cholamd_device_fill_f32(cholamd_device *d, float *d_arena32, void *stream) { return device_fill(d, d_arena32, (hipStream_t)stream); }
+// the timing kind (cholamd_device_get_timing) a phase's launch is booked under: 0 potrf (+ fused trsm), 1 trsm, 2 update
+static int timing_kind_of(int phase_kind)
+{
+  switch (phase_kind) {
+    case CHOL_PH_POTRF: case CHOL_PH_FUSED: return 0;
+    case CHOL_PH_TRSM: case CHOL_PH_TRSM_W: case CHOL_PH_TRSM_WT: return 1;
+    default: return 2; // CHOL_PH_UPDATE, CHOL_PH_UPDATE_MT
+  }
+}
 template <class T> static int launch_phase(cholamd_device *d, const level_dev &l, const chol_phase &ph, T *d_arena, hipStream_t st)
 {
   constexpr bool F32 = sizeof(T) == 4;
   T *const ws = ws_of<T>(d);
-  const int kind = F32 && ph.kind == 4 ? 1 : ph.kind; // the one-wave strips of kind 4 are an fp64 kernel: the fp32 factor takes them like kind 1
-  if (kind == 0) HIPCHK((hipError_t)chol_launch_potrf(d_arena, ws, l.potrf + ph.first, ph.n, d->info, st));
-  else if (kind == 1) HIPCHK((hipError_t)chol_launch_trsm(d_arena, ws, l.trsm + ph.first, ph.n, st));
-  else if (kind == 7) HIPCHK((hipError_t)chol_launch_trsm_wt(d_arena, ws, l.trsm + ph.first, ph.n, st));
-  else if (kind == 2) HIPCHK((hipError_t)chol_launch_update(d_arena, l.task + ph.first, l.src, ph.n, st));
-  else if (kind == 3) HIPCHK((hipError_t)chol_launch_update_mt(d_arena, l.task_mt + ph.first, l.src, ph.n, (int64_t)d->plan->arena, st));
+  const int kind = F32 && ph.kind == CHOL_PH_TRSM_W ? CHOL_PH_TRSM : ph.kind; // the one-wave strips are an fp64 kernel: the fp32 factor takes them like CHOL_PH_TRSM
+  if (kind == CHOL_PH_POTRF) HIPCHK((hipError_t)chol_launch_potrf(d_arena, ws, l.potrf + ph.first, ph.n, d->info, st));
+  else if (kind == CHOL_PH_TRSM) HIPCHK((hipError_t)chol_launch_trsm(d_arena, ws, l.trsm + ph.first, ph.n, st));
+  else if (kind == CHOL_PH_TRSM_WT) HIPCHK((hipError_t)chol_launch_trsm_wt(d_arena, ws, l.trsm + ph.first, ph.n, st));
+  else if (kind == CHOL_PH_UPDATE) HIPCHK((hipError_t)chol_launch_update(d_arena, l.task + ph.first, l.src, ph.n, st));
+  else if (kind == CHOL_PH_UPDATE_MT) HIPCHK((hipError_t)chol_launch_update_mt(d_arena, l.task_mt + ph.first, l.src, ph.n, (int64_t)d->plan->arena, st));
   else if constexpr (F32) { chol_set_error("internal: phase kind %d in the fp32 schedule", ph.kind); return CHOLAMD_ERR_ARG; }
-  else if (kind == 4) HIPCHK((hipError_t)chol_launch_trsm_w(d_arena, ws, l.trsm + ph.first, ph.n, st));
-  else if (kind == 5) { // the fused launch (fp64 only)
+  else if (kind == CHOL_PH_TRSM_W) HIPCHK((hipError_t)chol_launch_trsm_w(d_arena, ws, l.trsm + ph.first, ph.n, st));
+  else if (kind == CHOL_PH_FUSED) { // the fused launch (fp64 only)
     // the progress words (epoch * 64 + columns) and the count of finished TRSM workgroups are monotonic across launches:
     // both start over, in stream order, long before either can wrap
     if (d->epoch >= (1 << 24) || d->done_total >= (1 << 30)) { HIPCHK(hipMemsetAsync(d->progress, 0, (size_t)(d->plan->nsep + 2) * sizeof(int), st)); d->epoch = 0; d->done_total = 0; }
@@ -2031,7 +2040,7 @@ template <class T> static int launch_phase(cholamd_device *d, const level_dev &l
   }
   return 0;
 }
-// levels [level_lo, level_hi] of one rank; a broadcast phase (kind 6: distributed top levels: the step's column blocks travel from their owners to every
+// levels [level_lo, level_hi] of one rank; a broadcast phase (CHOL_PH_BCAST: distributed top levels: the step's column blocks travel from their owners to every
 // rank) goes through `c`
 template <class T> static int factor_levels_comm(cholamd_device *d, T *d_arena, int level_hi, int level_lo, cholamd_comm *c, hipStream_t st)
 {
@@ -2045,13 +2054,13 @@ template <class T> static int factor_levels_comm(cholamd_device *d, T *d_arena, 
   for (int lvl = level_hi; lvl >= level_lo; lvl--) { // mmat.rg:1227
     const level_dev &l = levels_of<T>(d)[lvl];
     for (const chol_phase &ph : l.phase) {
-      if (ph.kind == 6) {
+      if (ph.kind == CHOL_PH_BCAST) {
         scoped_timer t(d, st, CHOL_TK_BCAST, ph.n > 0);
         int rc = bcast_rank_t<T>(d, l, ph, d_arena, c, st);
         if (rc) return rc;
         continue;
       }
-      scoped_timer t(d, st, ph.kind == 3 ? 2 : (ph.kind == 4 || ph.kind == 7) ? 1 : ph.kind == 5 ? 0 : ph.kind, ph.n > 0);
+      scoped_timer t(d, st, timing_kind_of(ph.kind), ph.n > 0);
       int rc = launch_phase<T>(d, l, ph, d_arena, st);
       if (rc) return rc;
     }
@@ -2193,7 +2202,7 @@ template <class T> static int factor_multi_t(cholamd_device *const *devs, T *con
       for (int g = 0; g < n; g++) {
         const level_dev &l = levels_of<T>(devs[g])[lvl];
         HIPCHK(hipSetDevice(devs[g]->dev));
-        while (cur[g] < l.phase.size() && l.phase[cur[g]].kind != 6) {
+        while (cur[g] < l.phase.size() && l.phase[cur[g]].kind != CHOL_PH_BCAST) {
           int rc = launch_phase(devs[g], l, l.phase[cur[g]], arenas[g], stream_of(streams, g));
           if (rc) return rc;
           cur[g]++;

@@ -2046,32 +2046,32 @@ __global__ __launch_bounds__(RR_THREADS) void k_program(double *__restrict__ bas
     // a strip job's column-tile flags (trsm_rr_body, FLAG form) are cleared here, ahead of the job's waits: the barrier behind the waits
     // (or the one in front of the strips, for a job without) is the one between the clearing and the first use
     int *const xflags = (int *)(smem + PROG_OFF_XFLAG);
-    if (jb.kind == 1 && tid < 3 * PROG_XFLAGS) xflags[tid] = 0;
+    if (jb.kind == CHOL_JOB_TRSM && tid < 3 * PROG_XFLAGS) xflags[tid] = 0;
     bool fenced = false;
     // ONE wave polls (hundreds of blocked workgroups are resident at a time: twelve polling waves each would sit on the L2 the
     // working jobs hand their data through); the others park at the barrier
     // A job is usually drawn long before it may run: what does not depend on the wait is fetched ahead of it -- the first
     // round's task descriptor and its source descriptors (immutable; scalar loads, kept warm in the scalar cache)
     chol_upd_task tpre;
-    if (jb.kind == 2) {
+    if (jb.kind == CHOL_JOB_UPDATE) {
       const int tk = jb.first + min(jb.mode == 0 ? wave : grp, jb.n - 1);
       tpre = tasks[tk];
       int touch = 0;
       for (int sx = tpre.src_begin; sx < tpre.src_end; ++sx) touch += srcs[sx].k;
       asm volatile("" :: "s"(touch));
     }
-    if (jb.n_pre > 0 && !(jb.kind == 0 && jb.n_ext > 0)) { // a follower looks at its waits itself (potrf_rr_body); an extend-add job's staged waits are its tasks' business
+    if (jb.n_pre > 0 && !(jb.kind == CHOL_JOB_POTRF && jb.n_ext > 0)) { // a follower looks at its waits itself (potrf_rr_body); an extend-add job's staged waits are its tasks' business
       if (wave == 0) wait_list(waits + jb.wait_first, jb.n_pre, ctr, ctr_total, epoch, lane, info);
       lds_barrier();
       fenced = true;
     }
     if (TR && trace && tid == 0) trace[4 * j + 1] = __builtin_amdgcn_s_memrealtime(); // a follower overwrites it when its followed columns are in
-    if (jb.kind == 0) {
+    if (jb.kind == CHOL_JOB_POTRF) {
       const chol_potrf_desc pd = pdescs[jb.first];
       follow_args fa;
       fa.ext = exts + jb.ext_first; fa.n_ext = jb.n_ext; fa.ctr = ctr; fa.ctr_total = ctr_total; fa.epoch = epoch; fa.wl = waits + jb.wait_first; fa.n_wl = jb.n_wait; fa.own_at = jb.mode; fa.stamp = TR && trace ? &trace[4 * j + 1] : nullptr; fa.xstamp = TR && trace ? &trace[4 * njobs + CHOL_TRACE_X * j] : nullptr;
       potrf_rr_body<true, true, TR>(base, ws, pd, info, ctr + pd.ctr, epoch * ctr_total[pd.ctr], smem, pdescs[jb.first].sky, fa, tid);
-    } else if (jb.kind == 1) {
+    } else if (jb.kind == CHOL_JOB_TRSM) {
       double (*sX)[RR_MAXT][TS * TS] = (double (*)[RR_MAXT][TS * TS])smem; // [group][column tile]: one slot per solved tile
       chol_trsm_desc d = tdescs[jb.first + min(grp, jb.n - 1)];
       if (grp >= jb.n) d.m = 0; // a placeholder group: the strips of a job are independent of each other (flag form), it leaves at once

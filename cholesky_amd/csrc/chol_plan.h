@@ -172,8 +172,9 @@ typedef struct {
  * Counters are monotonic across factorisations: a wait for `value` on counter c means  ctr[c] - epoch * total[c] >= value,
  * total[c] = what one factorisation adds to c. */
 typedef struct { int ctr, value; } chol_wait;
+enum chol_job_kind { CHOL_JOB_POTRF = 0, CHOL_JOB_TRSM = 1, CHOL_JOB_UPDATE = 2 }; /* chol_job.kind (a plain int: Python and the tests read the numbers) */
 typedef struct {
-  int kind;            /* 0 POTRF of one pivot block, 1 TRSM group (<= 3 strips of one pivot block), 2 update group (16x16 tasks of one target block) */
+  int kind;            /* chol_job_kind: POTRF of one pivot block, TRSM group (<= 3 strips of one pivot block), update group (16x16 tasks of one target block) */
   int first, n;        /* POTRF: descriptor index; TRSM: strips [first, first + n); update: tasks [first, first + n) */
   int wait_first, n_wait; /* chol_wait entries that must hold before the job touches its data */
   int sig[2], sig_add; /* counters raised by sig_add once the job's stores have completed (-1: none); POTRF jobs publish
@@ -227,12 +228,20 @@ typedef struct {
 } chol_program;
 
 /* one batched launch: descriptors [first, first + n) of the level's array of that kind */
+enum chol_phase_kind { /* chol_phase.kind (a plain int: Python and the tests read the numbers) */
+  CHOL_PH_POTRF = 0, CHOL_PH_TRSM = 1,
+  CHOL_PH_UPDATE = 2,    /* 16x16 tasks */
+  CHOL_PH_UPDATE_MT = 3, /* 64x64 macro-tile tasks */
+  CHOL_PH_TRSM_W = 4,    /* every strip's pivot block <= CHOL_TRSM_W_MAXN wide */
+  CHOL_PH_FUSED = 5,     /* potrf (first, n) + trsm (first2, n2) + 16x16 update tasks (first3, n3) */
+  CHOL_PH_BCAST = 6,     /* distributed top levels, see chol_bcast */
+  CHOL_PH_TRSM_WT = 7    /* throughput form, k_trsm_wt */
+};
 typedef struct {
-  int kind;  /* 0 potrf, 1 trsm, 2 update (16x16 tasks), 3 update (64x64 macro-tile tasks), 4 trsm (every strip's pivot block <= CHOL_TRSM_W_MAXN wide), 7 trsm (throughput form, k_trsm_wt),
-              * 5 fused potrf (first, n) + trsm (first2, n2) + 16x16 update tasks (first3, n3) */
+  int kind;  /* chol_phase_kind */
   int first, n, first2, n2, first3, n3;
 } chol_phase;
-/* kind 6 (distributed top levels): broadcast of the column blocks [first, first + n) of the level's bcast list: every rank receives
+/* CHOL_PH_BCAST (distributed top levels): broadcast of the column blocks [first, first + n) of the level's bcast list: every rank receives
  * `count` doubles at arena offset `off` from rank `owner` */
 typedef struct { int64_t off, count; int owner, heap; } chol_bcast; /* heap: heap index of the top separator the block belongs to */
 /* ranks whose copy of a column block of top separator `heap` (tree level < log2(world)) can be non-zero before the extend-add exchange: the ranks

@@ -157,19 +157,22 @@ static int pivot_block_width(const chol_sched_opts *o, int n) { const int nb = p
  * below it the 16x16 split-K workgroups are what fills the 256 CUs, above it their 4x operand
  * re-reads are what costs */
 
-static void push_phase_f(builder *B, int kind, int first, int n, int force);
-static void push_phase(builder *B, int kind, int first, int n) { push_phase_f(B, kind, first, n, 0); }
+static void push_phase_full(builder *B, chol_phase ph)
+{
+  chol_level_work *w = B->w;
+  if (w->n_phase == B->cap_ph) { B->cap_ph = B->cap_ph ? 2 * B->cap_ph : 16; w->phase = realloc(w->phase, B->cap_ph * sizeof(chol_phase)); }
+  w->phase[w->n_phase++] = ph;
+}
 /* force: an empty launch keeps its place in the sequence (distributed top levels: every rank walks the same phase sequence,
  * the broadcasts in it are collective) */
 static void push_phase_f(builder *B, int kind, int first, int n, int force)
 {
   if (n <= 0 && !force) return;
   if (n < 0) n = 0;
-  chol_level_work *w = B->w;
-  if (w->n_phase == B->cap_ph) { B->cap_ph = B->cap_ph ? 2 * B->cap_ph : 16; w->phase = realloc(w->phase, B->cap_ph * sizeof(chol_phase)); }
   chol_phase ph = { kind, first, n, 0, 0, 0, 0 };
-  w->phase[w->n_phase++] = ph;
+  push_phase_full(B, ph);
 }
+static void push_phase(builder *B, int kind, int first, int n) { push_phase_f(B, kind, first, n, 0); }
 /* The POTRF role's tables for one block, exactly what potrf_rr_body's prologue would build (and builds, for descriptors without one): the tile
  * of every (slot, wave), the first step with a non-zero update per slot (skyline), and per (step, wave) the slots that have work and the panel
  * tiles to solve. */
@@ -428,15 +431,13 @@ static int tuples_are_small(const chol_sched_opts *o, const upd_tuple *tu, int n
 /* filled row runs of the ancestor blocks of panel(s): (arena offset of the run's first row in column 0
  * of the panel, rows); tiles come in increasing row order and adjacent ones are merged */
 typedef struct { int64_t off; int m; int64_t pos; } row_run; /* pos: the run's first row in the panel's uncompacted row numbering (adjacency is decided there) */
-/* which: 0 = every ancestor, 1 = the parent only, 2 = every ancestor but the parent */
-static int ancestor_runs_of(const plan_t *p, int h, int which, int by_storage, const cholamd_filled *snap, const int64_t *first, const int *count, row_run **out)
+static int ancestor_runs(const plan_t *p, int h, int by_storage, const cholamd_filled *snap, const int64_t *first, const int *count, row_run **out)
 {
   const int s = p->tree[h];
   int cap = 16, n = 0;
   row_run *r = malloc(cap * sizeof(row_run));
   int64_t base = p->sep_size[s]; /* rows in front of the block in the uncompacted panel */
   for (int hp = h / 2; hp >= 1; base += p->sep_size[p->tree[hp]], hp /= 2) {
-    if ((which == 1 && hp != h / 2) || (which == 2 && hp == h / 2)) continue;
     const int b = BIDX(p, p->tree[hp], s);
     const chol_block *Bk = &p->blk[b];
     for (int q = 0; q < count[b]; q++) {
@@ -454,10 +455,6 @@ static int ancestor_runs_of(const plan_t *p, int h, int which, int by_storage, c
   *out = r;
   return n;
 }
-static int ancestor_runs(const plan_t *p, int h, int by_storage, const cholamd_filled *snap, const int64_t *first, const int *count, row_run **out)
-{
-  return ancestor_runs_of(p, h, 0, by_storage, snap, first, count, out);
-}
 
 /* smallest first-entry column over the panel rows [pr, pr + m) of a leaf */
 static int rows_first(const int *first, int pr, int m, int n)
@@ -466,234 +463,55 @@ static int rows_first(const int *first, int pr, int m, int n)
   for (int r = 0; r < m; r++) if (first[pr + r] < f) f = first[pr + r];
   return f;
 }
-int chol_build_level_work(const plan_t *p, const chol_sched_opts *opts, int level, int rank, int world, chol_level_work *w)
+/* a source out of a LEAF's panel (separator s) into an m x n target: it starts at the first column both row sets have entries from */
+static void leaf_trim_source(int **rfirst, const plan_t *p, chol_upd_src *sd, int s, int m, int n)
 {
-  chol_sched_opts dflt;
-  if (!opts) { chol_sched_opts_default(&dflt); opts = &dflt; }
-  memset(w, 0, sizeof *w);
-  w->level = level;
-  builder Bd; memset(&Bd, 0, sizeof Bd); Bd.w = w; Bd.o = opts;
-  builder *B = &Bd;
-  const int L = p->levels, lbl = L - 1 - level;
-  const int d = chol_split_level(world);
-  if (world < 1 || (1 << d) != world || d > L - 1 || rank < 0 || rank >= world) { chol_set_error("bad partition rank %d of %d", rank, world); return CHOLAMD_ERR_ARG; }
-  const int h0 = 1 << level, h1 = (1 << (level + 1)) - 1;
-  int64_t *first = malloc(p->nblk * sizeof(int64_t));
-  int *count = malloc(p->nblk * sizeof(int));
-  index_snapshot(p, lbl, first, count);
-  const cholamd_filled *snap = p->snap[lbl];
+  const int fa = rows_first(rfirst[s], (int)((sd->a_off - p->panel_off[s]) % sd->lda), m, sd->k);
+  const int fb = rows_first(rfirst[s], (int)((sd->b_off - p->panel_off[s]) % sd->ldb), n, sd->k);
+  int k0 = (fa > fb ? fa : fb) & ~15;
+  if (k0 > ((sd->k - 1) & ~15)) k0 = (sd->k - 1) & ~15; /* (at least the last sixteen columns: no empty source) */
+  if (k0 > 0) { sd->a_off += (int64_t)k0 * sd->lda; sd->b_off += (int64_t)k0 * sd->ldb; sd->k -= k0; }
+}
 
-  /* the separators of this level this rank works on */
-  int *hs = malloc((h1 - h0 + 1) * sizeof(int)), nh = 0, steps = 0;
-  for (int h = h0; h <= h1; h++) {
-    const int s = p->tree[h];
-    if (level >= d && chol_owner_of(p, s, world) != rank) continue;
-    if (count[BIDX(p, s, s)] == 0 || p->sep_size[s] == 0) continue;
-    hs[nh++] = h;
-    if (pivot_blocks(opts, p->sep_size[s]) > steps) steps = pivot_blocks(opts, p->sep_size[s]);
+/* the merged filled row runs of block b inside its rows [lo, hi), in increasing row order: block_runs_next yields (first row relative to the
+ * block, rows) until it returns 0 */
+typedef struct { const chol_block *Bk; const cholamd_filled *f; int n, q, lo, hi; } block_runs;
+static block_runs block_runs_of(const plan_t *p, int b, int lo, int hi, const cholamd_filled *snap, const int64_t *first, const int *count)
+{
+  block_runs it = { &p->blk[b], snap + first[b], count[b], 0, lo, hi };
+  return it;
+}
+static int block_runs_next(block_runs *it, int *row, int *rows)
+{
+  int run_lo = -1, run_hi = -1;
+  for (; it->q < it->n; it->q++) {
+    int a0 = it->f[it->q].lo_x - it->Bk->lo_x, a1 = it->f[it->q].hi_x - it->Bk->lo_x + 1;
+    if (a0 < it->lo) a0 = it->lo;
+    if (a1 > it->hi) a1 = it->hi;
+    if (a0 >= a1) continue;
+    if (run_lo < 0) { run_lo = a0; run_hi = a1; }
+    else if (run_hi == a0) run_hi = a1;
+    else break; /* the next run starts at this tile */
   }
-  if (steps == 0) steps = 1;
-  /* leaves: first entry of every panel row (leaf_envelope) */
-  int **rfirst = (level == L - 1 && L > 1 && opts->leaf_envelope && nh > 0) ? chol_leaf_row_first(p) : NULL;
-  /* ... their ancestor row runs in 64-row pieces where the level is throughput work (the generated grids); on a small problem (lapl_3375: 16 leaves, fused
-   * latency-bound launches) more runs are more padded strip groups: 210 -> 227 us */
-  int64_t level_rows = 0;
-  for (int q = 0; q < nh; q++) level_rows += p->panel_rows[p->tree[hs[q]]];
-  const int fine_pieces = level_rows >= 65536;
-  /* distributed top level (world > 1, option dist_top): column block `st` of separator s is factored and solved by its owner,
-   * broadcast, and every rank applies the updates into the column blocks IT owns (push_tasks / emit_cell_tasks cut and filter
-   * the targets); every rank walks the same phase sequence */
-  const int dist = world > 1 && level < d && (opts->dist_top == 1 || (opts->dist_top == 2 && p->sep_size[p->tree[1]] >= CHOL_DIST_MIN));
-  if (dist) { B->dist_world = world; B->dist_rank = rank; B->dist_plan = p; }
-  int fused_last = -1; /* the level's last fused launch, if nothing was launched after it */
-  int fuse = opts->fuse; /* POTRF + TRSM of a step in one launch, if every block fits its TRSM role */
-  for (int q = 0; q < nh; q++) if (pivot_block_width(opts, p->sep_size[p->tree[hs[q]]]) > CHOL_FUSE_MAXN) fuse = 0;
-  /* pivots: small ones whole in step 0; big ones in pivot_block_width()-column blocks, each step =
-   * POTRF of the diagonal block, TRSM of every row below it (rows of the pivot and filled ancestor rows
-   * alike), rank-nb update of the remaining columns of those rows */
-  for (int st = 0; st < steps; st++) {
-    const int p0 = w->n_potrf, t0 = w->n_trsm, k0 = w->n_task, km0 = w->n_task_mt, b0 = w->n_bcast;
-    /* a step with thousands of strips (the wide fronts of a large problem) is a throughput problem: POTRF launch, then the
-     * one-wave-per-strip TRSM with twelve strips per workgroup, instead of the fused launch's latency design */
-    int thru = 0;
-    if (fuse && opts->trsm_wt_min > 0) { /* (distributed top levels too: the owner's strips) */
-      int64_t est = 0; int fits = 1;
-      for (int q = 0; q < nh; q++) {
-        const int s = p->tree[hs[q]], n = p->sep_size[s], bw = pivot_block_width(opts, n), c0 = st * bw;
-        if (c0 >= n) continue;
-        const int nb = n - c0 < bw ? n - c0 : bw;
-        if (nb > CHOL_TRSM_WT_MAXN) fits = 0;
-        est += (p->panel_rows[s] - c0 - nb + CHOL_TRSM_ROWS - 1) / CHOL_TRSM_ROWS;
-      }
-      thru = fits && est >= opts->trsm_wt_min;
-    }
-    for (int q = 0; q < nh; q++) {
-      const int h = hs[q], s = p->tree[h], n = p->sep_size[s], ld = p->panel_ld[s];
-      const int bw = pivot_block_width(opts, n);
-      const int c0 = st * bw;
-      if (c0 >= n) continue;
-      const int nb = n - c0 < bw ? n - c0 : bw;
-      const int64_t diag = p->panel_off[s] + c0 + (int64_t)c0 * ld;          /* element (c0, c0) of the pivot */
-      const int64_t dinv = p->dinv_off[s] + (int64_t)(c0 / CHOL_NB) * CHOL_NB * CHOL_NB;
-      const int64_t colbase = (int64_t)c0 * ld;                              /* column c0 of the panel */
-      const int below = n - c0 - nb;                                         /* pivot rows under the diagonal block */
-      row_run *runs; const int nr_ = ancestor_runs(p, h, opts->merge_targets, snap, first, count, &runs);
-      const int mine = !dist || dist_owner(p, s, st, world) == rank;
-      /* a leaf: L(i, k) = 0 for i - k > band inside the diagonal block, and an ancestor row is zero in front of its first entry of A */
-      int band = n, *run_first = NULL;
-      int nr = nr_;
-      if (rfirst && rfirst[s]) {
-        band = 0;
-        for (int r = 0; r < n; r++) if (r - rfirst[s][r] > band) band = r - rfirst[s][r];
-        /* the ancestor row runs in pieces of 64 rows (a macro tile's height), each with the first entry of ITS rows: a run is live for a column block as a
-         * whole otherwise, though most of a face's rows start late */
-        const int ph = fine_pieces ? 64 : 1 << 30; /* piece height */
-        int np_ = 0;
-        for (int r = 0; r < nr_; r++) np_ += fine_pieces ? (runs[r].m + 63) / 64 : 1;
-        row_run *pieces = malloc((size_t)(np_ > 0 ? np_ : 1) * sizeof(row_run));
-        run_first = malloc((size_t)(np_ > 0 ? np_ : 1) * sizeof(int));
-        np_ = 0;
-        for (int r = 0; r < nr_; r++)
-          for (int r0 = 0; r0 < runs[r].m; r0 += ph) {
-            row_run pc = { runs[r].off + r0, runs[r].m - r0 < ph ? runs[r].m - r0 : ph, runs[r].pos + r0 };
-            run_first[np_] = rows_first(rfirst[s], (int)((pc.off - p->panel_off[s]) % ld), pc.m, n);
-            pieces[np_++] = pc;
-          }
-        free(runs); runs = pieces; nr = np_;
-      }
-#define RUN_LIVE(r_, col_end_) (!run_first || run_first[r_] < (col_end_)) /* the run has an entry in front of column col_end_ */
-      if (dist) { /* the column block travels from its owner to every rank once it is factored and solved */
-        if (w->n_bcast == B->cap_b) { B->cap_b = B->cap_b ? 2 * B->cap_b : 16; w->bcast = realloc(w->bcast, B->cap_b * sizeof(chol_bcast)); }
-        chol_bcast bc = { p->panel_off[s] + colbase, (int64_t)nb * ld, dist_owner(p, s, st, world), h };
-        w->bcast[w->n_bcast++] = bc;
-        B->tgt_sep = s;
-      }
-      if (mine) {
-        chol_potrf_desc pd = { diag, dinv, nb, ld, s, c0, 0, 0, { 0 } };
-        push_potrf(B, pd);
-        const int flag = w->n_potrf - 1 - p0; /* this block's POTRF descriptor within the step */
-        if (below > 0) push_trsm_run(B, diag, dinv, p->panel_off[s] + (c0 + nb) + colbase, nb, ld, below < band ? below : band, flag);
-        for (int r = 0; r < nr; r++) if (RUN_LIVE(r, c0 + nb)) push_trsm_run(B, diag, dinv, runs[r].off + colbase, nb, ld, runs[r].m, flag);
-        if (thru) pad_trsm_group(B, t0, CHOL_TRSM_WT_GROUP, diag, dinv, diag, nb, ld, flag);
-        else if (fuse) pad_trsm_group(B, t0, 3, diag, dinv, diag, nb, ld, flag);
-        else if (opts->trsm_group > 0) pad_trsm_group(B, t0, opts->trsm_group, diag, dinv, diag, nb, ld, flag);
-        else if (nb <= CHOL_TRSM_W_MAXN) pad_trsm_group(B, t0, 4, diag, dinv, diag, nb, ld, flag);
-      }
-      if (below > 0) {
-        /* Trailing update, in SUPER-BLOCKS of `super` column blocks: after a column block only the remaining columns of its
-         * own super-block receive its rank-nb update (they are factored next); the columns beyond wait for the end of the
-         * super-block and receive ONE update of rank (columns of the super-block) -- the same sums, but the bulk of the
-         * flops (the trailing matrix of a wide front) runs at K = super * nb instead of nb, where the macro-tile kernel is
-         * nearer its MFMA rate (35 TF/s at K = 144, 44 at K = 512, fp64).  Pivots of up to `super` blocks are unchanged. */
-        const int G = opts->super_blocks > 1 ? opts->super_blocks : 1;
-        const int sb0 = (st / G) * G;                                           /* first block of this super-block */
-        const int cs0 = sb0 * bw;                                               /* its first column */
-        const int cse = (sb0 + G) * bw < n ? (sb0 + G) * bw : n;                /* one past its last column */
-        const int last_in_sb = (st % G == G - 1) || c0 + nb >= n || c0 + nb >= cse;
-        /* (1) narrow: columns [c0+nb, cse) of the rows below, K = nb */
-        const int ncol = cse - (c0 + nb);
-        const int ncol_e = ncol < band ? ncol : band;                           /* (a leaf: the columns the block's band reaches) */
-        B->tgt_col0 = c0 + nb;
-        if (ncol > 0) {
-          const int64_t x_piv = p->panel_off[s] + (c0 + nb) + colbase;         /* solved pivot rows under the block, k = nb */
-          chol_upd_src sp = { x_piv, x_piv, ld, ld, nb, 0, 0, 0 };
-          const int sidx = push_src(B, sp);
-          push_tasks(B, p->panel_off[s] + (c0 + nb) + (int64_t)(c0 + nb) * ld, ld, ncol_e, ncol_e, 1, sidx, sidx + 1); /* rows inside the super-block: lower triangle */
-          const int beyond = below - ncol < band - ncol ? below - ncol : band - ncol; /* pivot rows beyond the super-block (inside the band) x its remaining columns */
-          if (beyond > 0) {
-            chol_upd_src sq = { x_piv + ncol, x_piv, ld, ld, nb, 0, 0, 0 };
-            const int si = push_src(B, sq);
-            push_tasks(B, p->panel_off[s] + cse + (int64_t)(c0 + nb) * ld, ld, beyond, ncol_e, 0, si, si + 1);
-          }
-          for (int r = 0; r < nr; r++) {
-            if (!RUN_LIVE(r, c0 + nb)) continue;
-            chol_upd_src sa = { runs[r].off + colbase, x_piv, ld, ld, nb, 0, 0, 0 };
-            const int si = push_src(B, sa);
-            push_tasks(B, runs[r].off + (int64_t)(c0 + nb) * ld, ld, runs[r].m, ncol_e, 0, si, si + 1);
-          }
-        }
-        /* (2) wide, at the end of the super-block: columns [cse, n), K = cse - cs0 */
-        B->tgt_col0 = cse;
-        if (last_in_sb && cse < n) {
-          /* (a leaf: only the last `band` columns of the super-block reach the columns beyond it, and only `band` of those) */
-          const int bk = (band + 15) / 16 * 16;
-          const int K = cse - cs0 < bk ? cse - cs0 : bk, ce0 = cse - K, rest = n - cse < band ? n - cse : band;
-          const int64_t x_sb = p->panel_off[s] + cse + (int64_t)ce0 * ld;      /* pivot rows beyond the super-block, its columns */
-          chol_upd_src sp = { x_sb, x_sb, ld, ld, K, 0, 0, 0 };
-          const int sidx = push_src(B, sp);
-          push_tasks(B, p->panel_off[s] + cse + (int64_t)cse * ld, ld, rest, rest, 1, sidx, sidx + 1);
-          for (int r = 0; r < nr; r++) {
-            if (!RUN_LIVE(r, cse)) continue;
-            int cr0 = ce0; /* (a leaf: the piece's rows are zero in front of their first entry) */
-            if (run_first && (run_first[r] & ~15) > cr0) cr0 = run_first[r] & ~15;
-            chol_upd_src sa = { runs[r].off + (int64_t)cr0 * ld, x_sb + (int64_t)(cr0 - ce0) * ld, ld, ld, cse - cr0, 0, 0, 0 };
-            const int si = push_src(B, sa);
-            push_tasks(B, runs[r].off + (int64_t)cse * ld, ld, runs[r].m, rest, 0, si, si + 1);
-          }
-        }
-      }
-#undef RUN_LIVE
-      free(run_first);
-      free(runs);
-    }
-    flush_targets(B);
-    if (dist) { /* owner's POTRF + TRSM, the broadcast of the step's column blocks (collective: the same list on every rank),
-                 * then this rank's share of the trailing update */
-      if (thru) {
-        push_phase(B, 0, p0, w->n_potrf - p0);
-        push_phase(B, 7, t0, w->n_trsm - t0);
-      } else if (fuse) {
-        if (w->n_phase == B->cap_ph) { B->cap_ph = B->cap_ph ? 2 * B->cap_ph : 16; w->phase = realloc(w->phase, B->cap_ph * sizeof(chol_phase)); }
-        chol_phase ph = { 5, p0, w->n_potrf - p0, t0, w->n_trsm - t0, k0, 0 };
-        if (ph.n > 0) w->phase[w->n_phase++] = ph;
-      } else {
-        push_phase(B, 0, p0, w->n_potrf - p0);
-        int wide = 0;
-        for (int i = t0; i < w->n_trsm; i++) if (w->trsm[i].n > CHOL_TRSM_W_MAXN) wide = 1;
-        push_phase(B, opts->trsm_group > 0 ? 7 : wide ? 1 : 4, t0, w->n_trsm - t0); /* (trsm_group: the fp32 schedule's throughput TRSM) */
-      }
-      push_phase_f(B, 6, b0, w->n_bcast - b0, 1);
-      push_phase(B, 2, k0, w->n_task - k0);
-      push_phase(B, 3, km0, w->n_task_mt - km0);
-      continue;
-    }
-    if (thru) {
-      push_phase(B, 0, p0, w->n_potrf - p0);
-      push_phase(B, 7, t0, w->n_trsm - t0);
-      push_phase(B, 2, k0, w->n_task - k0);
-      fused_last = -1;
-    } else if (fuse) { /* one launch: the strips follow their pivot's POTRF column by column, the 16x16 update tasks of the
-                 * step (trailing columns of a split pivot) wait for the strips inside the same launch */
-      if (w->n_phase == B->cap_ph) { B->cap_ph = B->cap_ph ? 2 * B->cap_ph : 16; w->phase = realloc(w->phase, B->cap_ph * sizeof(chol_phase)); }
-      const int ride = w->n_task - k0 <= opts->fuse_update_max;
-      chol_phase ph = { 5, p0, w->n_potrf - p0, t0, w->n_trsm - t0, k0, ride ? w->n_task - k0 : 0 };
-      fused_last = -1;
-      if (ph.n > 0) { fused_last = w->n_phase; w->phase[w->n_phase++] = ph; }
-      if (ph.n <= 0 || !ride) { if (w->n_task > k0) fused_last = -1; push_phase(B, 2, k0, w->n_task - k0); }
-    } else {
-      push_phase(B, 0, p0, w->n_potrf - p0);
-      /* strips whose pivot block is narrow enough take the one-wave-per-strip kernel */
-      int wide = 0;
-      for (int i = t0; i < w->n_trsm; i++) if (w->trsm[i].n > CHOL_TRSM_W_MAXN) wide = 1;
-      push_phase(B, opts->trsm_group > 0 ? 7 : wide ? 1 : 4, t0, w->n_trsm - t0);
-      push_phase(B, 2, k0, w->n_task - k0);
-    }
-    push_phase(B, 3, km0, w->n_task_mt - km0);
-  }
-  /* extend-add of the level: tuples in program order (par bottom-up, gp from par to the root, tiles i, j),
-   * grouped by target tile */
+  if (run_lo < 0) return 0;
+  *row = run_lo; *rows = run_hi - run_lo;
+  return 1;
+}
+
+/* extend-add of a level: tuples in program order (par bottom-up, gp from par to the root, tiles i, j) over the separators hs[0, nh),
+ * sorted by target tile.  The caller frees the list. */
+static upd_tuple *level_tuples(const plan_t *p, const int *hs, int nh, const cholamd_filled *snap, const int64_t *first, const int *count, int *ntu_out)
+{
   int cap_u = 256, ntu = 0;
   upd_tuple *tu = malloc(cap_u * sizeof(upd_tuple));
   int64_t seq = 0;
   for (int q = 0; q < nh; q++) {
     const int h = hs[q], s = p->tree[h], n = p->sep_size[s];
     for (int hp = h / 2; hp >= 1; hp /= 2) {
-      int par = p->tree[hp];
-      int bb = BIDX(p, par, s);
+      const int par = p->tree[hp], bb = BIDX(p, par, s);
       const chol_block *Bb = &p->blk[bb];
       for (int hg = hp; hg >= 1; hg /= 2) {
-        int gp = p->tree[hg];
-        int ba = BIDX(p, gp, s), bc = BIDX(p, gp, par);
+        const int gp = p->tree[hg], ba = BIDX(p, gp, s), bc = BIDX(p, gp, par);
         const chol_block *Ba = &p->blk[ba], *Bc = &p->blk[bc];
         for (int i = 0; i < count[ba]; i++) {
           const cholamd_filled *fa = &snap[first[ba] + i];
@@ -703,7 +521,7 @@ int chol_build_level_work(const plan_t *p, const chol_sched_opts *opts, int leve
             if (ntu == cap_u) { cap_u *= 2; tu = realloc(tu, cap_u * sizeof(upd_tuple)); }
             upd_tuple *u = &tu[ntu++];
             /* the C tile rectangle = rows of the A tile x rows of the B tile */
-            int crow = fa->lo_x - Bc->lo_x, ccol = fb_->lo_x - Bc->lo_y;
+            const int crow = fa->lo_x - Bc->lo_x, ccol = fb_->lo_x - Bc->lo_y;
             u->key = ((int64_t)bc << 40) | ((int64_t)crow << 20) | (int64_t)ccol;
             u->seq = seq++;
             u->c_off = chol_block_row(Bc, crow) + (int64_t)ccol * Bc->ld; u->ldc = Bc->ld;
@@ -718,108 +536,375 @@ int chol_build_level_work(const plan_t *p, const chol_sched_opts *opts, int leve
     }
   }
   qsort(tu, ntu, sizeof(upd_tuple), cmp_tuple);
-  {
-    const int k0 = w->n_task, km0 = w->n_task_mt;
-    if (tuples_are_small(opts, tu, ntu)) emit_cell_tasks(B, p, tu, ntu);
-    else {
-      /* One target per cluster-tile pair of the reference would leave the 64x64 macro tiles a quarter full where the cluster tiles are
-       * 32 rows (the generated problems: 54 % of the macro-tile work of 60^3 was 32 x 32 targets).  Targets of one block that are
-       * neighbours IN STORAGE -- in the target and, with the same shift, in every source (row compaction makes the kept tiles of a
-       * block consecutive) -- and receive the same sources in the same order are merged, along the columns first, then along the rows:
-       * every element keeps its sources and their order (bit-identical sums), the tiles fill up.  SYRK targets stay alone. */
-      int ng = 0;
-      tgt_group *G = malloc((size_t)(ntu > 0 ? ntu : 1) * sizeof(tgt_group));
-      for (int i = 0; i < ntu;) {
-        int e = i + 1;
-        while (e < ntu && tu[e].key == tu[i].key) e++;
-        tgt_group g = { i, e, tu[i].bc, tu[i].crow, tu[i].ccol, tu[i].m, tu[i].n, tu[i].syrk, tu[i].c_off, tu[i].ldc, 0 };
-        G[ng++] = g;
-        i = e;
+  *ntu_out = ntu;
+  return tu;
+}
+
+/* ---- chol_build_level_work: what is live across its steps */
+typedef struct {
+  const plan_t *p; const chol_sched_opts *o; chol_level_work *w; builder B;
+  int rank, world;
+  int dist;        /* distributed top level (world > 1, option dist_top): column block `st` of separator s is factored and solved by its owner, broadcast,
+                    * and every rank applies the updates into the column blocks IT owns (push_tasks / emit_cell_tasks cut and filter the targets); every
+                    * rank walks the same phase sequence */
+  const cholamd_filled *snap; int64_t *first; int *count; /* the level's fill snapshot and its index per block */
+  int *hs, nh, steps; /* heap indices of the level's separators this rank works on; most column blocks of one of them */
+  int **rfirst;    /* leaves: first entry of every panel row (leaf_envelope), else NULL */
+  int fine_pieces; /* ... their ancestor row runs in 64-row pieces where the level is throughput work (the generated grids); on a small problem (lapl_3375:
+                    * 16 leaves, fused latency-bound launches) more runs are more padded strip groups: 210 -> 227 us */
+  int fuse;        /* POTRF + TRSM of a step in one launch, if every block fits its TRSM role */
+  int fused_last;  /* the level's last fused launch, if nothing was launched after it */
+} level_ctx;
+static void level_ctx_init(level_ctx *c, const plan_t *p, const chol_sched_opts *opts, int level, int rank, int world, chol_level_work *w)
+{
+  memset(c, 0, sizeof *c);
+  c->p = p; c->o = opts; c->w = w; c->B.w = w; c->B.o = opts; c->rank = rank; c->world = world;
+  const int L = p->levels, lbl = L - 1 - level, d = chol_split_level(world);
+  const int h0 = 1 << level, h1 = (1 << (level + 1)) - 1;
+  c->first = malloc(p->nblk * sizeof(int64_t));
+  c->count = malloc(p->nblk * sizeof(int));
+  index_snapshot(p, lbl, c->first, c->count);
+  c->snap = p->snap[lbl];
+  c->hs = malloc((h1 - h0 + 1) * sizeof(int));
+  for (int h = h0; h <= h1; h++) {
+    const int s = p->tree[h];
+    if (level >= d && chol_owner_of(p, s, world) != rank) continue;
+    if (c->count[BIDX(p, s, s)] == 0 || p->sep_size[s] == 0) continue;
+    c->hs[c->nh++] = h;
+    if (pivot_blocks(opts, p->sep_size[s]) > c->steps) c->steps = pivot_blocks(opts, p->sep_size[s]);
+  }
+  if (c->steps == 0) c->steps = 1;
+  c->rfirst = (level == L - 1 && L > 1 && opts->leaf_envelope && c->nh > 0) ? chol_leaf_row_first(p) : NULL;
+  int64_t level_rows = 0;
+  for (int q = 0; q < c->nh; q++) level_rows += p->panel_rows[p->tree[c->hs[q]]];
+  c->fine_pieces = level_rows >= 65536;
+  c->dist = world > 1 && level < d && (opts->dist_top == 1 || (opts->dist_top == 2 && p->sep_size[p->tree[1]] >= CHOL_DIST_MIN));
+  if (c->dist) { c->B.dist_world = world; c->B.dist_rank = rank; c->B.dist_plan = p; }
+  c->fused_last = -1;
+  c->fuse = opts->fuse;
+  for (int q = 0; q < c->nh; q++) if (pivot_block_width(opts, p->sep_size[p->tree[c->hs[q]]]) > CHOL_FUSE_MAXN) c->fuse = 0;
+}
+static void level_ctx_free(level_ctx *c)
+{
+  if (c->rfirst) { for (int s = 1; s <= c->p->nsep; s++) free(c->rfirst[s]); free(c->rfirst); }
+  free(c->first); free(c->count); free(c->hs); free(c->B.pend);
+}
+/* a step with thousands of strips (the wide fronts of a large problem) is a throughput problem: POTRF launch, then the
+ * one-wave-per-strip TRSM with twelve strips per workgroup, instead of the fused launch's latency design */
+static int step_is_throughput(const level_ctx *c, int st)
+{
+  const plan_t *p = c->p;
+  if (!c->fuse || c->o->trsm_wt_min <= 0) return 0; /* (distributed top levels too: the owner's strips) */
+  int64_t est = 0; int fits = 1;
+  for (int q = 0; q < c->nh; q++) {
+    const int s = p->tree[c->hs[q]], n = p->sep_size[s], bw = pivot_block_width(c->o, n), c0 = st * bw;
+    if (c0 >= n) continue;
+    const int nb = n - c0 < bw ? n - c0 : bw;
+    if (nb > CHOL_TRSM_WT_MAXN) fits = 0;
+    est += (p->panel_rows[s] - c0 - nb + CHOL_TRSM_ROWS - 1) / CHOL_TRSM_ROWS;
+  }
+  return fits && est >= c->o->trsm_wt_min;
+}
+
+/* column block st of one pivot of the level: where it lies in the panel, and the filled ancestor row runs under it */
+typedef struct {
+  int h, s, n, ld, c0, nb;
+  int below;        /* pivot rows under the diagonal block */
+  int band;         /* a leaf: L(i, k) = 0 for i - k > band inside the diagonal block (else n) */
+  int64_t diag, dinv, colbase; /* element (c0, c0) of the pivot, its inverted diagonal blocks, column c0 of the panel */
+  row_run *runs; int nr;
+  int *run_first;   /* a leaf: an ancestor row is zero in front of its first entry of A: the smallest over each run, else NULL */
+} pivot_step;
+/* the run has an entry in front of column col_end */
+static inline int run_live(const int *run_first, int r, int col_end) { return !run_first || run_first[r] < col_end; }
+static int pivot_step_init(const level_ctx *c, int q, int st, pivot_step *ps) /* 0: the pivot has no column block st */
+{
+  const plan_t *p = c->p;
+  const int h = c->hs[q], s = p->tree[h], n = p->sep_size[s], ld = p->panel_ld[s];
+  const int bw = pivot_block_width(c->o, n), c0 = st * bw;
+  if (c0 >= n) return 0;
+  const int nb = n - c0 < bw ? n - c0 : bw;
+  ps->h = h; ps->s = s; ps->n = n; ps->ld = ld; ps->c0 = c0; ps->nb = nb;
+  ps->diag = p->panel_off[s] + c0 + (int64_t)c0 * ld;
+  ps->dinv = p->dinv_off[s] + (int64_t)(c0 / CHOL_NB) * CHOL_NB * CHOL_NB;
+  ps->colbase = (int64_t)c0 * ld;
+  ps->below = n - c0 - nb;
+  ps->band = n; ps->run_first = NULL;
+  const int nr_ = ancestor_runs(p, h, c->o->merge_targets, c->snap, c->first, c->count, &ps->runs);
+  ps->nr = nr_;
+  if (c->rfirst && c->rfirst[s]) {
+    const int *rf = c->rfirst[s];
+    ps->band = 0;
+    for (int r = 0; r < n; r++) if (r - rf[r] > ps->band) ps->band = r - rf[r];
+    /* the ancestor row runs in pieces of 64 rows (a macro tile's height), each with the first entry of ITS rows: a run is live for a column block as a
+     * whole otherwise, though most of a face's rows start late */
+    const int ph = c->fine_pieces ? 64 : 1 << 30; /* piece height */
+    int np_ = 0;
+    for (int r = 0; r < nr_; r++) np_ += c->fine_pieces ? (ps->runs[r].m + 63) / 64 : 1;
+    row_run *pieces = malloc((size_t)(np_ > 0 ? np_ : 1) * sizeof(row_run));
+    ps->run_first = malloc((size_t)(np_ > 0 ? np_ : 1) * sizeof(int));
+    np_ = 0;
+    for (int r = 0; r < nr_; r++)
+      for (int r0 = 0; r0 < ps->runs[r].m; r0 += ph) {
+        row_run pc = { ps->runs[r].off + r0, ps->runs[r].m - r0 < ph ? ps->runs[r].m - r0 : ph, ps->runs[r].pos + r0 };
+        ps->run_first[np_] = rows_first(rf, (int)((pc.off - p->panel_off[s]) % ld), pc.m, n);
+        pieces[np_++] = pc;
       }
-      if (opts->merge_targets) {
-        /* columns: the groups are sorted by (block, first row, first column) */
-        for (int a = 0; a < ng;) {
-          int b = a + 1;
-          while (b < ng && !G[a].syrk && !G[b].syrk && G[b].bc == G[a].bc && G[b].crow == G[a].crow && G[b].m == G[a].m && G[b].ccol == G[a].ccol + G[a].n &&
-                 same_sources(tu, &G[a], &G[b], 0, G[a].n)) { G[a].n += G[b].n; G[b].dead = 1; b++; }
-          a = b;
-        }
-        int nl = 0;
-        for (int a = 0; a < ng; a++) if (!G[a].dead) G[nl++] = G[a];
-        ng = nl;
-        /* rows: by (block, first column, columns, first row) */
-        qsort(G, ng, sizeof(tgt_group), cmp_group_rows);
-        for (int a = 0; a < ng;) {
-          int b = a + 1;
-          while (b < ng && !G[a].syrk && !G[b].syrk && G[b].bc == G[a].bc && G[b].ccol == G[a].ccol && G[b].n == G[a].n && G[b].c_off == G[a].c_off + G[a].m &&
-                 same_sources(tu, &G[a], &G[b], G[a].m, 0)) { G[a].m += G[b].m; G[b].dead = 1; b++; }
-          a = b;
-        }
-        nl = 0;
-        for (int a = 0; a < ng; a++) if (!G[a].dead) G[nl++] = G[a];
-        ng = nl;
-        qsort(G, ng, sizeof(tgt_group), cmp_group_first);
-      }
-      if (rfirst && !dist && !getenv("CHOLAMD_NO_LEAF_ORDER")) {
-        /* leaf level: every macro tile streams 2 x 64 x K operand entries out of its source leaf's panel, and in target order the tiles one leaf feeds are
-         * spread over the whole list -- 77 GB fetched for 3 GB of leaf panels at 100^3, the launch at 6.3 TB/s.  In source order the tiles of a leaf run
-         * on one XCD at about the same time and share its panel through the L2 (targets are independent: any order gives the same sums) */
-        qsort_r(G, ng, sizeof(tgt_group), cmp_group_source, tu);
-      }
-      for (int a = 0; a < ng; a++) {
-        if (rfirst && !dist && !G[a].syrk && rfirst[tu[G[a].i].src_sep]) {
-          /* sources out of LEAF panels: the target in 64 x 64 pieces (the macro tiles it would be cut into anyway, in the same 8 x 8 block order), every
-           * piece with its own sources, each starting at the first column both of the piece's row sets have entries from */
-          for (int rb = 0; rb < G[a].m; rb += 64 * MT_ORDER)
-          for (int cb = 0; cb < G[a].n; cb += 64 * MT_ORDER)
-          for (int r0 = rb; r0 < G[a].m && r0 < rb + 64 * MT_ORDER; r0 += 64)
-          for (int c0 = cb; c0 < G[a].n && c0 < cb + 64 * MT_ORDER; c0 += 64) {
-            const int mm = G[a].m - r0 < 64 ? G[a].m - r0 : 64, nn = G[a].n - c0 < 64 ? G[a].n - c0 : 64;
-            const int sb = w->n_src;
-            for (int q = G[a].i; q < G[a].e; q++) {
-              chol_upd_src sd = { tu[q].a_off + r0, tu[q].b_off + c0, tu[q].lda, tu[q].ldb, tu[q].k, 0, 0, 0 };
-              const int s_ = tu[q].src_sep;
-              const int fa_ = rows_first(rfirst[s_], (int)((sd.a_off - p->panel_off[s_]) % sd.lda), mm, sd.k);
-              const int fb_ = rows_first(rfirst[s_], (int)((sd.b_off - p->panel_off[s_]) % sd.ldb), nn, sd.k);
-              int k0_ = (fa_ > fb_ ? fa_ : fb_) & ~15;
-              if (k0_ > ((sd.k - 1) & ~15)) k0_ = (sd.k - 1) & ~15; /* (at least the last sixteen columns: no empty source) */
-              if (k0_ > 0) { sd.a_off += (int64_t)k0_ * sd.lda; sd.b_off += (int64_t)k0_ * sd.ldb; sd.k -= k0_; }
-              push_src(B, sd);
-            }
-            push_tasks(B, G[a].c_off + r0 + (int64_t)c0 * G[a].ldc, G[a].ldc, mm, nn, 0, sb, w->n_src);
-          }
-          continue;
-        }
+    free(ps->runs); ps->runs = pieces; ps->nr = np_;
+  }
+  return 1;
+}
+static void pivot_step_free(pivot_step *ps) { free(ps->run_first); free(ps->runs); }
+
+/* the block's descriptors: its broadcast entry (distributed top), and on the rank that factors it the POTRF descriptor and the TRSM strips of
+ * every row below it, padded to the group of the step's TRSM kernel.  p0 / t0: the step's first POTRF descriptor / strip */
+static void push_pivot_block(level_ctx *c, const pivot_step *ps, int st, int thru, int p0, int t0)
+{
+  const plan_t *p = c->p;
+  chol_level_work *w = c->w;
+  builder *B = &c->B;
+  const int s = ps->s, nb = ps->nb, ld = ps->ld, c0 = ps->c0;
+  if (c->dist) { /* the column block travels from its owner to every rank once it is factored and solved */
+    if (w->n_bcast == B->cap_b) { B->cap_b = B->cap_b ? 2 * B->cap_b : 16; w->bcast = realloc(w->bcast, B->cap_b * sizeof(chol_bcast)); }
+    chol_bcast bc = { p->panel_off[s] + ps->colbase, (int64_t)nb * ld, dist_owner(p, s, st, c->world), ps->h };
+    w->bcast[w->n_bcast++] = bc;
+    B->tgt_sep = s;
+  }
+  if (c->dist && dist_owner(p, s, st, c->world) != c->rank) return;
+  chol_potrf_desc pd = { ps->diag, ps->dinv, nb, ld, s, c0, 0, 0, { 0 } };
+  push_potrf(B, pd);
+  const int flag = w->n_potrf - 1 - p0; /* this block's POTRF descriptor within the step */
+  if (ps->below > 0) push_trsm_run(B, ps->diag, ps->dinv, p->panel_off[s] + (c0 + nb) + ps->colbase, nb, ld, ps->below < ps->band ? ps->below : ps->band, flag);
+  for (int r = 0; r < ps->nr; r++) if (run_live(ps->run_first, r, c0 + nb)) push_trsm_run(B, ps->diag, ps->dinv, ps->runs[r].off + ps->colbase, nb, ld, ps->runs[r].m, flag);
+  if (thru) pad_trsm_group(B, t0, CHOL_TRSM_WT_GROUP, ps->diag, ps->dinv, ps->diag, nb, ld, flag);
+  else if (c->fuse) pad_trsm_group(B, t0, 3, ps->diag, ps->dinv, ps->diag, nb, ld, flag);
+  else if (c->o->trsm_group > 0) pad_trsm_group(B, t0, c->o->trsm_group, ps->diag, ps->dinv, ps->diag, nb, ld, flag);
+  else if (nb <= CHOL_TRSM_W_MAXN) pad_trsm_group(B, t0, 4, ps->diag, ps->dinv, ps->diag, nb, ld, flag);
+}
+/* Trailing update of the block, in SUPER-BLOCKS of `super` column blocks: after a column block only the remaining columns of its
+ * own super-block receive its rank-nb update (they are factored next); the columns beyond wait for the end of the
+ * super-block and receive ONE update of rank (columns of the super-block) -- the same sums, but the bulk of the
+ * flops (the trailing matrix of a wide front) runs at K = super * nb instead of nb, where the macro-tile kernel is
+ * nearer its MFMA rate (35 TF/s at K = 144, 44 at K = 512, fp64).  Pivots of up to `super` blocks are unchanged. */
+static void push_trailing_update(level_ctx *c, const pivot_step *ps, int st)
+{
+  const plan_t *p = c->p;
+  builder *B = &c->B;
+  const int s = ps->s, n = ps->n, nb = ps->nb, ld = ps->ld, c0 = ps->c0, below = ps->below, band = ps->band, nr = ps->nr;
+  const row_run *runs = ps->runs;
+  const int64_t colbase = ps->colbase;
+  if (below <= 0) return;
+  const int G = c->o->super_blocks > 1 ? c->o->super_blocks : 1;
+  const int bw = pivot_block_width(c->o, n);
+  const int sb0 = (st / G) * G;                                           /* first block of this super-block */
+  const int cs0 = sb0 * bw;                                               /* its first column */
+  const int cse = (sb0 + G) * bw < n ? (sb0 + G) * bw : n;                /* one past its last column */
+  const int last_in_sb = (st % G == G - 1) || c0 + nb >= n || c0 + nb >= cse;
+  /* (1) narrow: columns [c0+nb, cse) of the rows below, K = nb */
+  const int ncol = cse - (c0 + nb);
+  const int ncol_e = ncol < band ? ncol : band;                           /* (a leaf: the columns the block's band reaches) */
+  B->tgt_col0 = c0 + nb;
+  if (ncol > 0) {
+    const int64_t x_piv = p->panel_off[s] + (c0 + nb) + colbase;         /* solved pivot rows under the block, k = nb */
+    chol_upd_src sp = { x_piv, x_piv, ld, ld, nb, 0, 0, 0 };
+    const int sidx = push_src(B, sp);
+    push_tasks(B, p->panel_off[s] + (c0 + nb) + (int64_t)(c0 + nb) * ld, ld, ncol_e, ncol_e, 1, sidx, sidx + 1); /* rows inside the super-block: lower triangle */
+    const int beyond = below - ncol < band - ncol ? below - ncol : band - ncol; /* pivot rows beyond the super-block (inside the band) x its remaining columns */
+    if (beyond > 0) {
+      chol_upd_src sq = { x_piv + ncol, x_piv, ld, ld, nb, 0, 0, 0 };
+      const int si = push_src(B, sq);
+      push_tasks(B, p->panel_off[s] + cse + (int64_t)(c0 + nb) * ld, ld, beyond, ncol_e, 0, si, si + 1);
+    }
+    for (int r = 0; r < nr; r++) {
+      if (!run_live(ps->run_first, r, c0 + nb)) continue;
+      chol_upd_src sa = { runs[r].off + colbase, x_piv, ld, ld, nb, 0, 0, 0 };
+      const int si = push_src(B, sa);
+      push_tasks(B, runs[r].off + (int64_t)(c0 + nb) * ld, ld, runs[r].m, ncol_e, 0, si, si + 1);
+    }
+  }
+  /* (2) wide, at the end of the super-block: columns [cse, n), K = cse - cs0 */
+  B->tgt_col0 = cse;
+  if (last_in_sb && cse < n) {
+    /* (a leaf: only the last `band` columns of the super-block reach the columns beyond it, and only `band` of those) */
+    const int bk = (band + 15) / 16 * 16;
+    const int K = cse - cs0 < bk ? cse - cs0 : bk, ce0 = cse - K, rest = n - cse < band ? n - cse : band;
+    const int64_t x_sb = p->panel_off[s] + cse + (int64_t)ce0 * ld;      /* pivot rows beyond the super-block, its columns */
+    chol_upd_src sp = { x_sb, x_sb, ld, ld, K, 0, 0, 0 };
+    const int sidx = push_src(B, sp);
+    push_tasks(B, p->panel_off[s] + cse + (int64_t)cse * ld, ld, rest, rest, 1, sidx, sidx + 1);
+    for (int r = 0; r < nr; r++) {
+      if (!run_live(ps->run_first, r, cse)) continue;
+      int cr0 = ce0; /* (a leaf: the piece's rows are zero in front of their first entry) */
+      if (ps->run_first && (ps->run_first[r] & ~15) > cr0) cr0 = ps->run_first[r] & ~15;
+      chol_upd_src sa = { runs[r].off + (int64_t)cr0 * ld, x_sb + (int64_t)(cr0 - ce0) * ld, ld, ld, cse - cr0, 0, 0, 0 };
+      const int si = push_src(B, sa);
+      push_tasks(B, runs[r].off + (int64_t)cse * ld, ld, runs[r].m, rest, 0, si, si + 1);
+    }
+  }
+}
+/* the launches of a step, whose lists start at p0 / t0 / k0 / km0 / b0.  thru: POTRF, throughput TRSM; fused: one launch, the strips follow
+ * their pivot's POTRF column by column and the 16x16 update tasks of the step (trailing columns of a split pivot) wait for the strips inside
+ * the same launch if they are few; else POTRF and the TRSM kernel the strips' widths allow.  Then the 16x16 tasks that did not ride in the fused
+ * launch and the macro tiles.  dist: the broadcast of the step's column blocks (collective: the same list on every rank) between the owner's
+ * POTRF + TRSM and this rank's share of the trailing update, which then never rides */
+static void push_step_phases(level_ctx *c, int dist, int thru, int p0, int t0, int k0, int km0, int b0)
+{
+  chol_level_work *w = c->w;
+  builder *B = &c->B;
+  int own_launch = 1; /* the step's 16x16 tasks get a launch of their own */
+  if (thru) {
+    push_phase(B, CHOL_PH_POTRF, p0, w->n_potrf - p0);
+    push_phase(B, CHOL_PH_TRSM_WT, t0, w->n_trsm - t0);
+    c->fused_last = -1;
+  } else if (c->fuse) {
+    const int ride = !dist && w->n_task - k0 <= c->o->fuse_update_max;
+    chol_phase ph = { CHOL_PH_FUSED, p0, w->n_potrf - p0, t0, w->n_trsm - t0, k0, ride ? w->n_task - k0 : 0 };
+    c->fused_last = -1;
+    if (ph.n > 0) { c->fused_last = w->n_phase; push_phase_full(B, ph); }
+    if (ph.n > 0 && ride) own_launch = 0;
+    else if (w->n_task > k0) c->fused_last = -1;
+  } else {
+    push_phase(B, CHOL_PH_POTRF, p0, w->n_potrf - p0);
+    /* strips whose pivot block is narrow enough take the one-wave-per-strip kernel */
+    int wide = 0;
+    for (int i = t0; i < w->n_trsm; i++) if (w->trsm[i].n > CHOL_TRSM_W_MAXN) wide = 1;
+    push_phase(B, c->o->trsm_group > 0 ? CHOL_PH_TRSM_WT : wide ? CHOL_PH_TRSM : CHOL_PH_TRSM_W, t0, w->n_trsm - t0); /* (trsm_group: the fp32 schedule's throughput TRSM) */
+  }
+  if (dist) push_phase_f(B, CHOL_PH_BCAST, b0, w->n_bcast - b0, 1);
+  if (own_launch) push_phase(B, CHOL_PH_UPDATE, k0, w->n_task - k0);
+  push_phase(B, CHOL_PH_UPDATE_MT, km0, w->n_task_mt - km0);
+}
+
+/* Extend-add targets of the level, tile by tile.  One target per cluster-tile pair of the reference would leave the 64x64 macro tiles a quarter
+ * full where the cluster tiles are 32 rows (the generated problems: 54 % of the macro-tile work of 60^3 was 32 x 32 targets).  Targets of one
+ * block that are neighbours IN STORAGE -- in the target and, with the same shift, in every source (row compaction makes the kept tiles of a
+ * block consecutive) -- and receive the same sources in the same order are merged, along the columns first, then along the rows:
+ * every element keeps its sources and their order (bit-identical sums), the tiles fill up.  SYRK targets stay alone. */
+static void push_extend_add_targets(level_ctx *c, const upd_tuple *tu, int ntu)
+{
+  const plan_t *p = c->p;
+  chol_level_work *w = c->w;
+  builder *B = &c->B;
+  int **rfirst = c->rfirst;
+  int ng = 0;
+  tgt_group *G = malloc((size_t)(ntu > 0 ? ntu : 1) * sizeof(tgt_group));
+  for (int i = 0; i < ntu;) {
+    int e = i + 1;
+    while (e < ntu && tu[e].key == tu[i].key) e++;
+    tgt_group g = { i, e, tu[i].bc, tu[i].crow, tu[i].ccol, tu[i].m, tu[i].n, tu[i].syrk, tu[i].c_off, tu[i].ldc, 0 };
+    G[ng++] = g;
+    i = e;
+  }
+  if (c->o->merge_targets) {
+    /* columns: the groups are sorted by (block, first row, first column) */
+    for (int a = 0; a < ng;) {
+      int b = a + 1;
+      while (b < ng && !G[a].syrk && !G[b].syrk && G[b].bc == G[a].bc && G[b].crow == G[a].crow && G[b].m == G[a].m && G[b].ccol == G[a].ccol + G[a].n &&
+             same_sources(tu, &G[a], &G[b], 0, G[a].n)) { G[a].n += G[b].n; G[b].dead = 1; b++; }
+      a = b;
+    }
+    int nl = 0;
+    for (int a = 0; a < ng; a++) if (!G[a].dead) G[nl++] = G[a];
+    ng = nl;
+    /* rows: by (block, first column, columns, first row) */
+    qsort(G, ng, sizeof(tgt_group), cmp_group_rows);
+    for (int a = 0; a < ng;) {
+      int b = a + 1;
+      while (b < ng && !G[a].syrk && !G[b].syrk && G[b].bc == G[a].bc && G[b].ccol == G[a].ccol && G[b].n == G[a].n && G[b].c_off == G[a].c_off + G[a].m &&
+             same_sources(tu, &G[a], &G[b], G[a].m, 0)) { G[a].m += G[b].m; G[b].dead = 1; b++; }
+      a = b;
+    }
+    nl = 0;
+    for (int a = 0; a < ng; a++) if (!G[a].dead) G[nl++] = G[a];
+    ng = nl;
+    qsort(G, ng, sizeof(tgt_group), cmp_group_first);
+  }
+  if (rfirst && !c->dist && !getenv("CHOLAMD_NO_LEAF_ORDER")) {
+    /* leaf level: every macro tile streams 2 x 64 x K operand entries out of its source leaf's panel, and in target order the tiles one leaf feeds are
+     * spread over the whole list -- 77 GB fetched for 3 GB of leaf panels at 100^3, the launch at 6.3 TB/s.  In source order the tiles of a leaf run
+     * on one XCD at about the same time and share its panel through the L2 (targets are independent: any order gives the same sums) */
+    qsort_r(G, ng, sizeof(tgt_group), cmp_group_source, (void *)tu);
+  }
+  for (int a = 0; a < ng; a++) {
+    if (rfirst && !c->dist && !G[a].syrk && rfirst[tu[G[a].i].src_sep]) {
+      /* sources out of LEAF panels: the target in 64 x 64 pieces (the macro tiles it would be cut into anyway, in the same 8 x 8 block order), every
+       * piece with its own sources, each trimmed to the piece's rows (leaf_trim_source) */
+      for (int rb = 0; rb < G[a].m; rb += 64 * MT_ORDER)
+      for (int cb = 0; cb < G[a].n; cb += 64 * MT_ORDER)
+      for (int r0 = rb; r0 < G[a].m && r0 < rb + 64 * MT_ORDER; r0 += 64)
+      for (int c0 = cb; c0 < G[a].n && c0 < cb + 64 * MT_ORDER; c0 += 64) {
+        const int mm = G[a].m - r0 < 64 ? G[a].m - r0 : 64, nn = G[a].n - c0 < 64 ? G[a].n - c0 : 64;
         const int sb = w->n_src;
         for (int q = G[a].i; q < G[a].e; q++) {
-          chol_upd_src sd = { tu[q].a_off, tu[q].b_off, tu[q].lda, tu[q].ldb, tu[q].k, 0, 0, 0 };
-          if (rfirst && rfirst[tu[q].src_sep]) { /* a leaf's panel: the source starts at the first column both row sets have entries from */
-            const int s_ = tu[q].src_sep;
-            const int fa_ = rows_first(rfirst[s_], (int)((tu[q].a_off - p->panel_off[s_]) % tu[q].lda), G[a].m, tu[q].k);
-            const int fb_ = rows_first(rfirst[s_], (int)((tu[q].b_off - p->panel_off[s_]) % tu[q].ldb), G[a].n, tu[q].k);
-            int k0_ = (fa_ > fb_ ? fa_ : fb_) & ~15;
-            if (k0_ > ((tu[q].k - 1) & ~15)) k0_ = (tu[q].k - 1) & ~15; /* (at least the last sixteen columns: no empty source) */
-            if (k0_ > 0) { sd.a_off += (int64_t)k0_ * sd.lda; sd.b_off += (int64_t)k0_ * sd.ldb; sd.k -= k0_; }
-          }
+          chol_upd_src sd = { tu[q].a_off + r0, tu[q].b_off + c0, tu[q].lda, tu[q].ldb, tu[q].k, 0, 0, 0 };
+          leaf_trim_source(rfirst, p, &sd, tu[q].src_sep, mm, nn);
           push_src(B, sd);
         }
-        if (dist) { B->tgt_sep = p->blk[G[a].bc].c; B->tgt_col0 = G[a].ccol; }
-        push_tasks(B, G[a].c_off, G[a].ldc, G[a].m, G[a].n, G[a].syrk, sb, w->n_src);
+        push_tasks(B, G[a].c_off + r0 + (int64_t)c0 * G[a].ldc, G[a].ldc, mm, nn, 0, sb, w->n_src);
       }
-      free(G);
+      continue;
     }
-    flush_targets(B);
-    if (dist) push_phase(B, 2, k0, w->n_task - k0); else
-    /* the 16x16 tasks of the extend-add ride in the level's last fused launch when that one carries no tasks of
-     * its own and nothing was launched after it */
-    if (fused_last >= 0 && fused_last == w->n_phase - 1 && w->phase[fused_last].n3 == 0 && w->n_task - k0 <= opts->fuse_update_max) {
-      w->phase[fused_last].first3 = k0;
-      w->phase[fused_last].n3 = w->n_task - k0;
-    } else push_phase(B, 2, k0, w->n_task - k0);
-    push_phase(B, 3, km0, w->n_task_mt - km0);
+    const int sb = w->n_src;
+    for (int q = G[a].i; q < G[a].e; q++) {
+      chol_upd_src sd = { tu[q].a_off, tu[q].b_off, tu[q].lda, tu[q].ldb, tu[q].k, 0, 0, 0 };
+      if (rfirst && rfirst[tu[q].src_sep]) leaf_trim_source(rfirst, p, &sd, tu[q].src_sep, G[a].m, G[a].n);
+      push_src(B, sd);
+    }
+    if (c->dist) { B->tgt_sep = p->blk[G[a].bc].c; B->tgt_col0 = G[a].ccol; }
+    push_tasks(B, G[a].c_off, G[a].ldc, G[a].m, G[a].n, G[a].syrk, sb, w->n_src);
   }
-  if (rfirst) { for (int s = 1; s <= p->nsep; s++) free(rfirst[s]); free(rfirst); }
-  free(tu); free(first); free(count); free(hs); free(B->pend); B->pend = NULL; B->cap_pend = 0;
+  free(G);
+}
+/* extend-add of the level, grouped by target tile: cell by cell where the phase is small, else tile by tile; its launches */
+static void push_level_extend_add(level_ctx *c)
+{
+  chol_level_work *w = c->w;
+  builder *B = &c->B;
+  int ntu;
+  upd_tuple *tu = level_tuples(c->p, c->hs, c->nh, c->snap, c->first, c->count, &ntu);
+  const int k0 = w->n_task, km0 = w->n_task_mt;
+  if (tuples_are_small(c->o, tu, ntu)) emit_cell_tasks(B, c->p, tu, ntu);
+  else push_extend_add_targets(c, tu, ntu);
+  flush_targets(B);
+  free(tu);
+  /* the 16x16 tasks of the extend-add ride in the level's last fused launch when that one carries no tasks of
+   * its own and nothing was launched after it */
+  const int fl = c->fused_last;
+  if (!c->dist && fl >= 0 && fl == w->n_phase - 1 && w->phase[fl].n3 == 0 && w->n_task - k0 <= c->o->fuse_update_max) {
+    w->phase[fl].first3 = k0;
+    w->phase[fl].n3 = w->n_task - k0;
+  } else push_phase(B, CHOL_PH_UPDATE, k0, w->n_task - k0);
+  push_phase(B, CHOL_PH_UPDATE_MT, km0, w->n_task_mt - km0);
+}
+
+/* The lists of one tree level for (rank, world).  Pivots: small ones whole in step 0; big ones in pivot_block_width()-column blocks, each step =
+ * POTRF of the diagonal block, TRSM of every row below it (rows of the pivot and filled ancestor rows alike), rank-nb update of the remaining
+ * columns of those rows; after the last step the extend-add of the level into its ancestors */
+int chol_build_level_work(const plan_t *p, const chol_sched_opts *opts, int level, int rank, int world, chol_level_work *w)
+{
+  chol_sched_opts dflt;
+  if (!opts) { chol_sched_opts_default(&dflt); opts = &dflt; }
+  memset(w, 0, sizeof *w);
+  w->level = level;
+  const int d = chol_split_level(world);
+  if (world < 1 || (1 << d) != world || d > p->levels - 1 || rank < 0 || rank >= world) { chol_set_error("bad partition rank %d of %d", rank, world); return CHOLAMD_ERR_ARG; }
+  level_ctx c;
+  level_ctx_init(&c, p, opts, level, rank, world, w);
+  for (int st = 0; st < c.steps; st++) {
+    const int p0 = w->n_potrf, t0 = w->n_trsm, k0 = w->n_task, km0 = w->n_task_mt, b0 = w->n_bcast;
+    const int thru = step_is_throughput(&c, st);
+    for (int q = 0; q < c.nh; q++) {
+      pivot_step ps;
+      if (!pivot_step_init(&c, q, st, &ps)) continue;
+      push_pivot_block(&c, &ps, st, thru, p0, t0);
+      push_trailing_update(&c, &ps, st);
+      pivot_step_free(&ps);
+    }
+    flush_targets(&c.B);
+    push_step_phases(&c, c.dist, thru, p0, t0, k0, km0, b0);
+  }
+  push_level_extend_add(&c);
+  level_ctx_free(&c);
   return 0;
 }
 
@@ -911,94 +996,118 @@ void chol_program_free(chol_program *g)
   free(g->job); free(g->wait); free(g->ext); free(g->ctr_total);
   memset(g, 0, sizeof *g);
 }
+/* ---- chol_build_program: what is live across its steps */
+typedef struct {
+  const plan_t *p; chol_sched_opts o; chol_level_work *w; chol_program *pg; builder B; pbuild P;
+  int follow;                /* pivot blocks follow their children's / predecessor's strips */
+  /* per separator (index 1 .. nsep) */
+  unsigned char **sky;       /* tile-level skyline of the leaf pivots (option skyline), else NULL entries */
+  int *bw_of, *band_of;      /* column-block width; band of a banded leaf factored as one block (0: dense) */
+  int *sw_of;                /* stage width of its extend-add sources: a banded leaf factored as one block is handed on in chunks of stage_chunk column
+                              * tiles (all its strips publish their column tiles); everything else block by block */
+  int *nblk_of; pblock **pb; /* its pivot blocks */
+  int *est_start;            /* expected position (in 16-column steps) at which its pivot chain starts: the longest chain below it; leaves start at 0.
+                              * A follower consumes its children's column tiles in the order of these positions */
+  int *c_upd, *c_updd;       /* counters of the update jobs into its panel / into its diagonal block */
+  int *cnt_upd, *cnt_updd;   /* ... and how many have been queued so far */
+  int *snap_upd;             /* cnt_upd at the start of the current update phase: what that phase's jobs wait for */
+  int *follow_lim;           /* per block: columns of a parent's diagonal block that its POTRF job takes from its children itself (current level) */
+  /* the current level */
+  int level; const cholamd_filled *snap; int64_t *first; int *count; /* its fill snapshot and its index per block */
+  int *hs, nh, steps;        /* heap indices of its separators; most pivot blocks of one of them */
+} prog_ctx;
+
 /* strips of the filled rows of block (anc, s) that lie in rows [lo, hi) of anc (relative to the block), for the column block
  * at column c0: appended to the TRSM list with `chan`; returns the number of strips */
-static int push_block_rows(builder *B, const plan_t *p, int anc, int s, int lo, int hi, const cholamd_filled *snap, const int64_t *first, const int *count,
-                           int64_t diag, int64_t dinv, int nb, int ld, int64_t colbase, int flag, int chan)
+static int push_block_rows(prog_ctx *c, int anc, int s, int lo, int hi, int64_t diag, int64_t dinv, int nb, int ld, int64_t colbase, int flag, int chan)
 {
-  chol_level_work *w = B->w;
-  const int b = BIDX(p, anc, s);
-  const chol_block *Bk = &p->blk[b];
-  const int t_before = w->n_trsm;
-  int run_lo = -1, run_hi = -1; /* current merged run, rows relative to the block */
-  for (int q = 0; q <= count[b]; q++) {
-    int a0 = -1, a1 = -1;
-    if (q < count[b]) {
-      const cholamd_filled *f = &snap[first[b] + q];
-      a0 = f->lo_x - Bk->lo_x; a1 = f->hi_x - Bk->lo_x + 1;
-      if (a0 < lo) a0 = lo;
-      if (a1 > hi) a1 = hi;
-      if (a0 >= a1) continue;
-      if (run_hi == a0) { run_hi = a1; continue; }
-    }
-    if (run_lo >= 0) {
-      push_trsm_run(B, diag, dinv, chol_block_row(Bk, run_lo) + colbase, nb, ld, run_hi - run_lo, flag);
-    }
-    run_lo = a0; run_hi = a1;
-  }
+  chol_level_work *w = c->w;
+  const int b = BIDX(c->p, anc, s), t_before = w->n_trsm;
+  block_runs it = block_runs_of(c->p, b, lo, hi, c->snap, c->first, c->count);
+  for (int row, rows; block_runs_next(&it, &row, &rows);) push_trsm_run(&c->B, diag, dinv, chol_block_row(it.Bk, row) + colbase, nb, ld, rows, flag);
   for (int i = t_before; i < w->n_trsm; i++) w->trsm[i].chan = chan;
   return w->n_trsm - t_before;
 }
-/* TRSM jobs over the strips [t0, n_trsm): groups of three, never mixing channels */
-static int emit_trsm_jobs(pbuild *P, builder *B, int t0, int c_upd, int need_upd, int c_strips,
-                          int ch_par, int c_updp, int need_updp, int ch_below, int c_updd, int need_updd)
-{ /* a job waits for the update jobs into the rows its strips solve: the followed strips of the parent's rows (channel ch_par) for
-   * those into the block (parent, separator), the followed strips of the pivot's next column block (ch_below) for those into the
-   * diagonal block, every other job for all the update jobs into the panel (ch_par / ch_below < 0: that for every job) */
-  chol_level_work *w = B->w;
+/* TRSM jobs over the strips [t0, n_trsm) of pivot block b of separator s: groups of three, never mixing channels.  A job waits for the update
+ * jobs into the rows its strips solve: the followed strips of the parent's rows (channel ch_par) for those into the block (parent, separator),
+ * the followed strips of the pivot's next column block (ch_below) for those into the diagonal block, every other job for all the update jobs
+ * into the panel (without option fine_upd: that for every job) */
+static int emit_trsm_jobs(prog_ctx *c, int s, const pblock *b, int t0)
+{
+  chol_level_work *w = c->w;
+  pbuild *P = &c->P;
   int njobs = 0;
   for (int i = t0; i < w->n_trsm;) {
     int e = i + 1;
     while (e < w->n_trsm && e - i < 3 && w->trsm[e].chan == w->trsm[i].chan) e++;
     const int wf = P->pg->n_wait;
     const int ch = w->trsm[i].chan;
-    if (ch >= 0 && ch == ch_par && c_updp >= 0) add_wait(P, c_updp, need_updp);
-    else if (ch >= 0 && ch == ch_below && ch_par >= -1 && c_updp >= 0) add_wait(P, c_updd, need_updd);
-    else add_wait(P, c_upd, need_upd);
-    chol_job *j = add_job(P, 1, i, e - i, wf);
-    j->sig[0] = c_strips; j->sig_add = 1;
+    if (ch >= 0 && ch == b->ch_par && P->c_updp) add_wait(P, P->c_updp[s], P->cnt_updp[s]);
+    else if (ch >= 0 && ch == b->ch_below && P->c_updp) add_wait(P, c->c_updd[s], c->cnt_updd[s]);
+    else add_wait(P, c->c_upd[s], c->cnt_upd[s]);
+    chol_job *j = add_job(P, CHOL_JOB_TRSM, i, e - i, wf);
+    j->sig[0] = b->c_strips; j->sig_add = 1;
     njobs++;
     i = e;
   }
   return njobs;
 }
-/* update jobs over the tasks [k0, n_task): consecutive tasks of one target block, at most PROG_JOB_TASKS each; every job waits
- * for the strips of its source pivot blocks (src_ctr / src_need pairs) and for the update jobs of earlier phases into its panel */
-static void emit_update_jobs(pbuild *P, builder *B, const plan_t *p, int k0, const int *c_upd, const int *c_updd, const int *snap_upd, int *cnt_upd, int *cnt_updd,
-                             const int *src_ctr, const int *src_need, int n_src_ctr, const int *stage_sep /* NULL: every wait gates the whole job */)
-{ /* stage_sep (extend-add of a level): src_ctr[i] is the strips counter of a pivot block of separator stage_sep[i], the list in the
-   * order the blocks are expected to finish.  Those waits are STAGED: the job starts as soon as the earlier update jobs into its
-   * panel are through, every task takes its sources in that order and looks at wait i only before the first source that needs it --
-   * what is left once the last source pivot has been solved is that pivot's contribution alone, not every descendant's */
-  chol_level_work *w = B->w;
-  for (int i = k0; i < w->n_task;) {
+/* what an update job waits for on the side of its sources: `need` on counter ctr.  Extend-add of a level: the strips counter of pivot block
+ * tag % 64 of separator tag / 64, expected to be complete at position est of the pivot chains */
+typedef struct { int ctr, need, tag, est; } wait_src;
+static void sort_wait_srcs(wait_src *a, int n) /* by est, stable (a few dozen entries) */
+{
+  for (int i = 1; i < n; i++) {
+    const wait_src x = a[i];
+    int b = i - 1;
+    while (b >= 0 && a[b].est > x.est) { a[b + 1] = a[b]; b--; }
+    a[b + 1] = x;
+  }
+}
+/* MFMA k-steps (of 4 columns) of a task over all its sources */
+static int task_steps(const chol_level_work *w, int t)
+{
+  int st = 0;
+  for (int q = w->task[t].src_begin; q < w->task[t].src_end; q++) st += (w->src[q].k + 3) / 4;
+  return st;
+}
+/* update jobs over the tasks [k0, k1): consecutive tasks of one target block, at most PROG_JOB_TASKS each; every job waits
+ * for the strips of its source pivot blocks (ws[0, nws)) and for the update jobs of earlier phases into its panel.
+ * staged: ws is in the order the source blocks are expected to finish and those waits are STAGED: the job starts as soon as the earlier
+ * update jobs into its panel are through, every task takes its sources in that order and looks at wait i only before the first source that
+ * needs it -- what is left once the last source pivot has been solved is that pivot's contribution alone, not every descendant's.  A source
+ * comes with its stage (> 0), or with the tag -(64 separator + block) - 1 of the pivot block it needs (emit_cell_tasks) */
+static void emit_update_jobs(prog_ctx *c, int k0, int k1, const wait_src *ws, int nws, int staged)
+{
+  const plan_t *p = c->p;
+  chol_level_work *w = c->w;
+  pbuild *P = &c->P;
+  for (int i = k0; i < k1;) {
     /* a task is heavy when its sources add up to PROG_HEAVY_STEPS MFMA k-steps or more (one wave would take them one memory
      * round trip after the other): heavy tasks go three to a job, four waves each; light ones twelve to a job, one wave each */
-#define TASK_STEPS(T_) ({ int st_ = 0; for (int q_ = w->task[T_].src_begin; q_ < w->task[T_].src_end; q_++) st_ += (w->src[q_].k + 3) / 4; st_; })
-    const int heavy = TASK_STEPS(i) >= PROG_HEAVY_STEPS;
+    const int heavy = task_steps(w, i) >= PROG_HEAVY_STEPS;
     const int lim = heavy ? 3 : PROG_JOB_TASKS;
     int e = i + 1;
-    while (e < w->n_task && e - i < lim && w->task[e].blk == w->task[i].blk && (TASK_STEPS(e) >= PROG_HEAVY_STEPS) == heavy) e++;
-#undef TASK_STEPS
+    while (e < k1 && e - i < lim && w->task[e].blk == w->task[i].blk && (task_steps(w, e) >= PROG_HEAVY_STEPS) == heavy) e++;
     const chol_block *Bc = &p->blk[w->task[i].blk];
     const int wf = P->pg->n_wait;
-    if (stage_sep) add_wait(P, c_upd[Bc->c], snap_upd[Bc->c]);
+    if (staged) add_wait(P, c->c_upd[Bc->c], c->snap_upd[Bc->c]);
     const int n_pre = P->pg->n_wait - wf;
-    for (int q = 0; q < n_src_ctr; q++) add_wait(P, src_ctr[q], src_need[q]);
-    if (!stage_sep) add_wait(P, c_upd[Bc->c], snap_upd[Bc->c]);
-    chol_job *j = add_job(P, 2, i, e - i, wf);
+    for (int q = 0; q < nws; q++) add_wait(P, ws[q].ctr, ws[q].need);
+    if (!staged) add_wait(P, c->c_upd[Bc->c], c->snap_upd[Bc->c]);
+    chol_job *j = add_job(P, CHOL_JOB_UPDATE, i, e - i, wf);
     j->mode = heavy;
-    if (stage_sep) {
+    if (staged) {
       j->n_pre = n_pre;
       for (int t = i; t < e; t++) {
         chol_upd_task *tk = &w->task[t];
         for (int q = tk->src_begin; q < tk->src_end; q++) { /* -(separator) - 1 -> number of staged waits that must hold: through its last pivot
                                                               * block; sub-tiles of one target share their sources: converted once */
           if (w->src[q].stage > 0) continue;
-          int st = n_src_ctr;
+          int st = nws;
           if (w->src[q].stage < 0) { /* tag 64 separator + block (block 63: the whole pivot): the last listed block of the separator up to that one */
             const int tag = -w->src[q].stage - 1;
-            for (int z = n_src_ctr - 1; z >= 0; z--) if (stage_sep[z] / 64 == tag / 64 && stage_sep[z] % 64 <= tag % 64) { st = z + 1; break; }
+            for (int z = nws - 1; z >= 0; z--) if (ws[z].tag / 64 == tag / 64 && ws[z].tag % 64 <= tag % 64) { st = z + 1; break; }
           }
           w->src[q].stage = st;
         }
@@ -1012,9 +1121,9 @@ static void emit_update_jobs(pbuild *P, builder *B, const plan_t *p, int k0, con
     } else for (int t = i; t < e; t++) for (int q = w->task[t].src_begin; q < w->task[t].src_end; q++) w->src[q].stage = 0;
     const int hpc = p->heap_of[Bc->c] / 2;
     const int is_par = P->c_updp && Bc->r != Bc->c && hpc >= 1 && Bc->r == p->tree[hpc];
-    j->sig[0] = c_upd[Bc->c]; j->sig[1] = Bc->r == Bc->c ? c_updd[Bc->c] : is_par ? P->c_updp[Bc->c] : -1; j->sig_add = 1;
-    cnt_upd[Bc->c]++;
-    if (Bc->r == Bc->c) cnt_updd[Bc->c]++;
+    j->sig[0] = c->c_upd[Bc->c]; j->sig[1] = Bc->r == Bc->c ? c->c_updd[Bc->c] : is_par ? P->c_updp[Bc->c] : -1; j->sig_add = 1;
+    c->cnt_upd[Bc->c]++;
+    if (Bc->r == Bc->c) c->cnt_updd[Bc->c]++;
     if (is_par) P->cnt_updp[Bc->c]++;
     i = e;
   }
@@ -1095,24 +1204,25 @@ typedef struct { int64_t off; int ld, k, ctr, need; } early_src; /* ctr: the cha
 #ifndef EARLY_CHUNK
 #define EARLY_CHUNK 2 /* column tiles per staged source of an early job (1 / 2 / 3 at follow_tail 3: 193.5 / 194.5 / 197.3 us on lapl_3375) */
 #endif
-static int emit_early_cells(pbuild *P, builder *B, const plan_t *p, int64_t c_off, int ldc, int lim, int blk, const early_src *es, int nes,
-                             const int *c_upd, const int *c_updd, int *snap_upd, int *cnt_upd, int *cnt_updd)
+static int emit_early_cells(prog_ctx *c, int64_t c_off, int ldc, int lim, int blk, const early_src *es, int nes)
 {
-  chol_level_work *w = B->w;
+  chol_level_work *w = c->w;
+  builder *B = &c->B;
   /* the staged waits of these jobs: the sources in chunks of EARLY_CHUNK column tiles, chunk by chunk over the sources (the order
    * in which the strips publish them, near enough); stage = position in this list + 1 */
   int nst = 0, maxch = 0;
   for (int q = 0; q < nes; q++) if (es[q].k > 0) { const int ch = ((es[q].k + CHOL_NB - 1) / CHOL_NB + EARLY_CHUNK - 1) / EARLY_CHUNK; nst += ch; if (ch > maxch) maxch = ch; }
   if (nst == 0) return 0;
-  int *sc = malloc(nst * sizeof(int)), *sn = malloc(nst * sizeof(int)), *sq = malloc(nst * sizeof(int)), *sch = malloc(nst * sizeof(int));
+  wait_src *ws = malloc(nst * sizeof(wait_src)); /* tag, est: here the source and its chunk */
   nst = 0;
-  for (int c = 0; c < maxch; c++)
+  for (int ch = 0; ch < maxch; ch++)
     for (int q = 0; q < nes; q++) {
       if (es[q].k <= 0) continue;
       const int et = (es[q].k + CHOL_NB - 1) / CHOL_NB;
-      if (c * EARLY_CHUNK >= et) continue;
-      const int last = (c + 1) * EARLY_CHUNK < et ? (c + 1) * EARLY_CHUNK - 1 : et - 1; /* last column tile of the chunk */
-      sc[nst] = es[q].ctr - (et - 1) + last; sn[nst] = es[q].need; sq[nst] = q; sch[nst] = c; nst++;
+      if (ch * EARLY_CHUNK >= et) continue;
+      const int last = (ch + 1) * EARLY_CHUNK < et ? (ch + 1) * EARLY_CHUNK - 1 : et - 1; /* last column tile of the chunk */
+      const wait_src x = { es[q].ctr - (et - 1) + last, es[q].need, q, ch };
+      ws[nst++] = x;
     }
   const int staged = B->o->staged;
   const int k0 = w->n_task, Tl = (lim + CHOL_NB - 1) / CHOL_NB;
@@ -1120,8 +1230,8 @@ static int emit_early_cells(pbuild *P, builder *B, const plan_t *p, int64_t c_of
     for (int J = 0; J <= I; J++) {
       const int sb = w->n_src;
       for (int z = 0; z < nst; z++) {
-        const early_src *e = &es[sq[z]];
-        const int col0 = sch[z] * EARLY_CHUNK * CHOL_NB, kc = e->k - col0 < EARLY_CHUNK * CHOL_NB ? e->k - col0 : EARLY_CHUNK * CHOL_NB;
+        const early_src *e = &es[ws[z].tag];
+        const int col0 = ws[z].est * EARLY_CHUNK * CHOL_NB, kc = e->k - col0 < EARLY_CHUNK * CHOL_NB ? e->k - col0 : EARLY_CHUNK * CHOL_NB;
         chol_upd_src sd = { e->off + CHOL_NB * I + (int64_t)col0 * e->ld, e->off + CHOL_NB * J + (int64_t)col0 * e->ld, e->ld, e->ld, kc, 0, staged ? z + 1 : 0, 0 };
         push_src(B, sd);
       }
@@ -1135,10 +1245,10 @@ static int emit_early_cells(pbuild *P, builder *B, const plan_t *p, int64_t c_of
       t->src_begin = sb; t->src_end = w->n_src;
       t->blk = blk;
     }
-  const int col_sep = p->blk[blk].c;
-  snap_upd[col_sep] = cnt_upd[col_sep];
-  emit_update_jobs(P, B, p, k0, c_upd, c_updd, snap_upd, cnt_upd, cnt_updd, sc, sn, nst, staged ? sq : NULL); /* sq: only "staged" (the stages are set) */
-  free(sc); free(sn); free(sq); free(sch);
+  const int col_sep = c->p->blk[blk].c;
+  c->snap_upd[col_sep] = c->cnt_upd[col_sep];
+  emit_update_jobs(c, k0, w->n_task, ws, nst, staged); /* (the stages are set) */
+  free(ws);
   return w->n_task > k0;
 }
 
@@ -1149,47 +1259,48 @@ static chol_sched_opts chol_program_opts(const chol_sched_opts *o)
   if (r.split_min == CHOL_SPLIT_MIN && r.split_nb == CHOL_SPLIT_NB) r.split_min = CHOL_PROG_SPLIT_MIN;
   return r;
 }
-int chol_build_program(const plan_t *p, const chol_sched_opts *opts, chol_level_work *w, chol_program *pg)
+static void prog_ctx_free(prog_ctx *c)
 {
-  memset(w, 0, sizeof *w);
-  memset(pg, 0, sizeof *pg);
-  w->level = -1;
-  chol_sched_opts dflt, prog;
-  if (!opts) { chol_sched_opts_default(&dflt); opts = &dflt; }
-  prog = chol_program_opts(opts); opts = &prog;
-  builder Bd; memset(&Bd, 0, sizeof Bd); Bd.w = w; Bd.o = opts; Bd.force_fine = 1;
-  builder *B = &Bd;
-  pbuild Pd; memset(&Pd, 0, sizeof Pd); Pd.pg = pg;
-  pbuild *P = &Pd;
+  const int ns = c->p->nsep;
+  free(c->P.c_updp); free(c->P.cnt_updp);
+  if (c->pb) for (int s = 1; s <= ns; s++) free(c->pb[s]);
+  chol_free_skylines(c->sky, ns); free(c->bw_of); free(c->band_of); free(c->sw_of);
+  free(c->est_start); free(c->pb); free(c->nblk_of); free(c->first); free(c->count); free(c->hs);
+  free(c->c_upd); free(c->c_updd); free(c->cnt_upd); free(c->cnt_updd); free(c->snap_upd); free(c->follow_lim);
+  free(c->B.pend);
+}
+/* block widths, eligibility, then the counters and pivot blocks of every separator; CHOLAMD_ERR_ARG: the problem does not qualify (prog_ctx_free
+ * in either case) */
+static int prog_ctx_init(prog_ctx *c, const plan_t *p, const chol_sched_opts *opts, chol_level_work *w, chol_program *pg)
+{
+  memset(c, 0, sizeof *c);
+  c->p = p; c->o = chol_program_opts(opts); c->w = w; c->pg = pg;
+  c->B.w = w; c->B.o = &c->o; c->B.force_fine = 1; c->P.pg = pg;
+  opts = &c->o;
+  pbuild *P = &c->P;
   const int L = p->levels, ns = p->nsep;
   int rc = 0;
   /* column-block width per separator.  A LEAF whose factor is banded at tile level (skyline: at most four tiles below the diagonal)
    * is factored as ONE block up to CHOL_RR_MAXN columns: its POTRF skips the zero tiles, so one CU keeps up with the pivot chain, and
    * its strips keep one L tile per step (trsm_rr_body, band form) -- no split, no transition between column blocks */
-  unsigned char **sky = opts->skyline ? chol_leaf_skylines(p) : calloc(ns + 1, sizeof(unsigned char *));
-  int *bw_of = malloc((ns + 1) * sizeof(int)), *band_of = calloc(ns + 1, sizeof(int));
+  c->sky = opts->skyline ? chol_leaf_skylines(p) : calloc(ns + 1, sizeof(unsigned char *));
+  c->bw_of = malloc((ns + 1) * sizeof(int)); c->band_of = calloc(ns + 1, sizeof(int)); c->sw_of = malloc((ns + 1) * sizeof(int));
   for (int s = 1; s <= ns; s++) {
     const int n = p->sep_size[s];
-    bw_of[s] = pivot_block_width(opts, n);
-    if (sky[s] && n > CHOL_FUSE_MAXN && n <= CHOL_RR_MAXN && pivot_blocks(opts, n) > 1) {
+    c->bw_of[s] = pivot_block_width(opts, n);
+    if (c->sky[s] && n > CHOL_FUSE_MAXN && n <= CHOL_RR_MAXN && pivot_blocks(opts, n) > 1) {
       int band = 1;
-      for (int i = 0; i * CHOL_NB < n; i++) if (i - sky[s][i] > band) band = i - sky[s][i];
-      if (band <= 4) { bw_of[s] = n; band_of[s] = band; }
+      for (int i = 0; i * CHOL_NB < n; i++) if (i - c->sky[s][i] > band) band = i - c->sky[s][i];
+      if (band <= 4) { c->bw_of[s] = n; c->band_of[s] = band; }
     }
+    c->sw_of[s] = c->bw_of[s];
+    if (c->band_of[s] && opts->staged && opts->stage_chunk > 0 && opts->stage_chunk * CHOL_NB < n) c->sw_of[s] = opts->stage_chunk * CHOL_NB;
   }
-  B->bw_of = bw_of;
-  /* stage width of a separator's extend-add sources: a banded leaf factored as one block is handed on in chunks of stage_chunk column
-   * tiles (all its strips publish their column tiles); everything else block by block */
-  int *sw_of = malloc((ns + 1) * sizeof(int));
-  for (int s = 1; s <= ns; s++) {
-    sw_of[s] = bw_of[s];
-    if (band_of[s] && opts->staged && opts->stage_chunk > 0 && opts->stage_chunk * CHOL_NB < p->sep_size[s]) sw_of[s] = opts->stage_chunk * CHOL_NB;
-  }
-  B->sw_of = sw_of;
+  c->B.bw_of = c->bw_of; c->B.sw_of = c->sw_of;
   /* eligibility: every pivot block fits both fused roles */
   for (int s = 1; s <= ns && !rc; s++) {
-    const int bw = bw_of[s];
-    if ((bw > CHOL_FUSE_MAXN && !band_of[s]) || bw > CHOL_RR_MAXN) { chol_set_error("program launch: pivot block of %d columns (separator %d) exceeds %d", bw, s, CHOL_FUSE_MAXN); rc = CHOLAMD_ERR_ARG; }
+    const int bw = c->bw_of[s];
+    if ((bw > CHOL_FUSE_MAXN && !c->band_of[s]) || bw > CHOL_RR_MAXN) { chol_set_error("program launch: pivot block of %d columns (separator %d) exceeds %d", bw, s, CHOL_FUSE_MAXN); rc = CHOLAMD_ERR_ARG; }
   }
   { /* cheap early refusal of large problems: 16x16 tiles of the trailing updates of split pivots, and of every panel once per
      * tree level below it (extend-add cells) */
@@ -1197,487 +1308,481 @@ int chol_build_program(const plan_t *p, const chol_sched_opts *opts, chol_level_
     for (int s = 1; s <= ns; s++) {
       const int n = p->sep_size[s], rows = p->panel_rows[s];
       if (n <= 0) continue;
-      const int bw = bw_of[s], nbk = (n + bw - 1) / bw;
+      const int bw = c->bw_of[s], nbk = (n + bw - 1) / bw;
       for (int st = 0; st + 1 < nbk; st++) est += (double)((rows - (st + 1) * bw) / 16 + 1) * ((n - (st + 1) * bw) / 16 + 1);
       est += (double)(rows / 16 + 1) * (n / 16 + 1) * (L - 1 - p->level_of[s]);
     }
     if (est > 2.0 * PROG_MAX_TASKS) { chol_set_error("program launch: about %.0f update tasks", est); rc = CHOLAMD_ERR_ARG; }
   }
-  if (rc) { chol_free_skylines(sky, ns); free(bw_of); free(band_of); free(sw_of); return rc; }
-  const int follow = opts->follow && opts->cells;
-  pg->follow = follow;
-  int64_t *first = malloc(p->nblk * sizeof(int64_t));
-  int *count = malloc(p->nblk * sizeof(int));
+  if (rc) return rc;
+  c->follow = opts->follow && opts->cells;
+  pg->follow = c->follow;
+  c->first = malloc(p->nblk * sizeof(int64_t));
+  c->count = malloc(p->nblk * sizeof(int));
+  c->hs = malloc(((size_t)1 << (L - 1)) * sizeof(int));
   /* per panel: counters and running counts of update jobs; per separator: its pivot blocks */
-  int *c_upd = malloc((ns + 1) * sizeof(int)), *c_updd = malloc((ns + 1) * sizeof(int));
+  c->c_upd = malloc((ns + 1) * sizeof(int)); c->c_updd = malloc((ns + 1) * sizeof(int));
   if (opts->fine_upd && opts->follow && opts->cells) { P->c_updp = malloc((ns + 1) * sizeof(int)); P->cnt_updp = calloc(ns + 1, sizeof(int)); }
-  int *cnt_upd = calloc(ns + 1, sizeof(int)), *cnt_updd = calloc(ns + 1, sizeof(int)), *snap_upd = calloc(ns + 1, sizeof(int));
-  int *nblk_of = calloc(ns + 1, sizeof(int));
-  pblock **pb = calloc(ns + 1, sizeof(pblock *));
-  int *follow_lim = calloc(p->nblk, sizeof(int));
+  c->cnt_upd = calloc(ns + 1, sizeof(int)); c->cnt_updd = calloc(ns + 1, sizeof(int)); c->snap_upd = calloc(ns + 1, sizeof(int));
+  c->nblk_of = calloc(ns + 1, sizeof(int));
+  c->pb = calloc(ns + 1, sizeof(pblock *));
+  c->follow_lim = calloc(p->nblk, sizeof(int));
   for (int s = 1; s <= ns; s++) {
-    c_upd[s] = new_ctr(P, 0); c_updd[s] = new_ctr(P, 0);
+    c->c_upd[s] = new_ctr(P, 0); c->c_updd[s] = new_ctr(P, 0);
     if (P->c_updp) P->c_updp[s] = new_ctr(P, 0);
     const int n = p->sep_size[s];
-    const int bw = bw_of[s], nbk = n > 0 ? (n + bw - 1) / bw : 0;
-    nblk_of[s] = nbk;
-    pb[s] = calloc(nbk > 0 ? nbk : 1, sizeof(pblock));
+    const int bw = c->bw_of[s], nbk = n > 0 ? (n + bw - 1) / bw : 0;
+    c->nblk_of[s] = nbk;
+    c->pb[s] = calloc(nbk > 0 ? nbk : 1, sizeof(pblock));
     for (int st = 0; st < nbk; st++) {
-      pblock *b = &pb[s][st];
+      pblock *b = &c->pb[s][st];
       b->c0 = st * bw; b->nb = n - b->c0 < bw ? n - b->c0 : bw;
       b->potrf = -1; b->ch_below = b->ch_par = b->ch_rest = -1;
       b->c_prog = new_ctr(P, (b->nb + CHOL_NB - 1) / CHOL_NB);
       b->c_strips = new_ctr(P, 0);
     }
   }
-  /* expected position (in 16-column steps) at which a separator's pivot chain starts: the longest chain below it; leaves start at 0.
-   * A follower consumes its children's column tiles in the order of these positions */
-  int *est_start = calloc(ns + 1, sizeof(int));
+  c->est_start = calloc(ns + 1, sizeof(int));
   for (int h = ns; h >= 1; h--) {
     int st0 = 0;
-    for (int c = 2 * h; c <= 2 * h + 1 && c <= ns; c++) {
-      const int k = p->tree[c];
-      const int end = est_start[k] + (p->sep_size[k] + CHOL_NB - 1) / CHOL_NB;
+    for (int k = 2 * h; k <= 2 * h + 1 && k <= ns; k++) {
+      const int kid = p->tree[k];
+      const int end = c->est_start[kid] + (p->sep_size[kid] + CHOL_NB - 1) / CHOL_NB;
       if (end > st0) st0 = end;
     }
-    est_start[p->tree[h]] = st0;
+    c->est_start[p->tree[h]] = st0;
   }
-  /* POTRF job of block st of separator s; exts were added just before (ext_first .. n_ext); early_: early update jobs write its
-   * diagonal block.  mode = the place of a follower's own tiles among its items (option follow_own) */
-  #define EMIT_POTRF(s_, st_, ext_first_, early_)                                                                       \
-    do {                                                                                                          \
-      pblock *b_ = &pb[s_][st_];                                                                                  \
-      const int ld_ = p->panel_ld[s_];                                                                            \
-      const int64_t diag_ = p->panel_off[s_] + b_->c0 + (int64_t)b_->c0 * ld_;                                    \
-      const int64_t dinv_ = p->dinv_off[s_] + (int64_t)(b_->c0 / CHOL_NB) * CHOL_NB * CHOL_NB;                    \
-      chol_potrf_desc pd_ = { diag_, dinv_, b_->nb, ld_, s_, b_->c0, b_->c_prog, 0, { 0 } };                      \
-      if (sky[s_]) /* the block's skyline, relative to its own first tile column */                              \
-        for (int i_ = 0; i_ * CHOL_NB < b_->nb && i_ < 24; i_++) {                                                \
-          const int f_ = sky[s_][b_->c0 / CHOL_NB + i_] - b_->c0 / CHOL_NB;                                       \
-          pd_.sky[i_] = (unsigned char)(f_ > 0 ? f_ : 0);                                                         \
-        }                                                                                                         \
-      push_potrf(B, pd_);                                                                                         \
-      b_->potrf = w->n_potrf - 1;                                                                                 \
-      const int wf_ = pg->n_wait;                                                                                 \
-      add_wait(P, c_updd[s_], cnt_updd[s_]);                                                                      \
-      chol_job *j_ = add_job(P, 0, b_->potrf, 1, wf_);                                                            \
-      j_->ext_first = (ext_first_); j_->n_ext = pg->n_ext - (ext_first_);                                         \
-      if (j_->n_ext > 0)                                                                                          \
-        j_->mode = j_->n_wait > 0 && (opts->follow_own == 2 || (opts->follow_own == 1 && (early_))) ? j_->n_ext   \
-                   : chol_follow_own_at(j_->n_ext, (b_->nb + CHOL_NB - 1) / CHOL_NB);                             \
-      b_->emitted = 1;                                                                                            \
-    } while (0)
+  return 0;
+}
+/* the level's fill snapshot and its separators with a pivot */
+static void prog_begin_level(prog_ctx *c, int level)
+{
+  const plan_t *p = c->p;
+  const int lbl = p->levels - 1 - level;
+  c->level = level;
+  index_snapshot(p, lbl, c->first, c->count);
+  c->snap = p->snap[lbl];
+  c->nh = c->steps = 0;
+  for (int h = 1 << level; h <= (1 << (level + 1)) - 1; h++) {
+    const int s = p->tree[h];
+    if (c->count[BIDX(p, s, s)] == 0 || p->sep_size[s] == 0) continue;
+    c->hs[c->nh++] = h;
+    if (c->nblk_of[s] > c->steps) c->steps = c->nblk_of[s];
+  }
+}
+/* POTRF job of block st of separator s; its followed items were added just before (ext_first .. n_ext); early: early update jobs write its
+ * diagonal block.  mode = the place of a follower's own tiles among its items (option follow_own) */
+static void emit_potrf_job(prog_ctx *c, int s, int st, int ext_first, int early)
+{
+  const plan_t *p = c->p;
+  chol_program *pg = c->pg;
+  pblock *b = &c->pb[s][st];
+  const int ld = p->panel_ld[s];
+  const int64_t diag = p->panel_off[s] + b->c0 + (int64_t)b->c0 * ld;
+  const int64_t dinv = p->dinv_off[s] + (int64_t)(b->c0 / CHOL_NB) * CHOL_NB * CHOL_NB;
+  chol_potrf_desc pd = { diag, dinv, b->nb, ld, s, b->c0, b->c_prog, 0, { 0 } };
+  if (c->sky[s]) /* the block's skyline, relative to its own first tile column */
+    for (int i = 0; i * CHOL_NB < b->nb && i < 24; i++) {
+      const int f = c->sky[s][b->c0 / CHOL_NB + i] - b->c0 / CHOL_NB;
+      pd.sky[i] = (unsigned char)(f > 0 ? f : 0);
+    }
+  push_potrf(&c->B, pd);
+  b->potrf = c->w->n_potrf - 1;
+  const int wf = pg->n_wait;
+  add_wait(&c->P, c->c_updd[s], c->cnt_updd[s]);
+  chol_job *j = add_job(&c->P, CHOL_JOB_POTRF, b->potrf, 1, wf);
+  j->ext_first = ext_first; j->n_ext = pg->n_ext - ext_first;
+  if (j->n_ext > 0)
+    j->mode = j->n_wait > 0 && (c->o.follow_own == 2 || (c->o.follow_own == 1 && early)) ? j->n_ext
+              : chol_follow_own_at(j->n_ext, (b->nb + CHOL_NB - 1) / CHOL_NB);
+  b->emitted = 1;
+}
+/* (A) POTRF jobs of this step that no follower placement has emitted yet */
+static void emit_plain_potrf_jobs(prog_ctx *c, int st)
+{
+  for (int q = 0; q < c->nh; q++) {
+    const int s = c->p->tree[c->hs[q]];
+    if (st < c->nblk_of[s] && !c->pb[s][st].emitted) emit_potrf_job(c, s, st, c->pg->n_ext, 0);
+  }
+}
+/* (B) TRSM jobs: per pivot block the followed rows first (next column block of the pivot, rows of the parent's first
+ *     column block), then everything else */
+static void emit_step_trsm_jobs(prog_ctx *c, int st)
+{
+  const plan_t *p = c->p;
+  chol_level_work *w = c->w;
+  builder *B = &c->B;
+  pbuild *P = &c->P;
+  for (int q = 0; q < c->nh; q++) {
+    const int h = c->hs[q], s = p->tree[h], n = p->sep_size[s], ld = p->panel_ld[s];
+    if (st >= c->nblk_of[s]) continue;
+    pblock *b = &c->pb[s][st];
+    const int c0 = b->c0, nb = b->nb, nt = (nb + CHOL_NB - 1) / CHOL_NB;
+    const int64_t diag = p->panel_off[s] + c0 + (int64_t)c0 * ld;
+    const int64_t dinv = p->dinv_off[s] + (int64_t)(c0 / CHOL_NB) * CHOL_NB * CHOL_NB;
+    const int64_t colbase = (int64_t)c0 * ld;
+    const int below = n - c0 - nb;
+    const int t0 = w->n_trsm;
+    B->cur_band = c->band_of[s]; /* strips of a banded leaf factored as one block */
+    /* rows of the next column block of this pivot */
+    int nb1 = 0;
+    if (below > 0) {
+      nb1 = c->pb[s][st + 1].nb;
+      const int fol = c->follow && (nb1 + CHOL_NB - 1) / CHOL_NB <= CHOL_FOLLOW_MAXT;
+      if (fol) { b->ns_below = (nb1 + CHOL_TRSM_ROWS - 1) / CHOL_TRSM_ROWS; b->ch_below = new_ctr(P, b->ns_below); for (int e = 1; e < nt; e++) new_ctr(P, b->ns_below); }
+      push_trsm_run(B, diag, dinv, p->panel_off[s] + (c0 + nb) + colbase, nb, ld, nb1, b->c_prog);
+      for (int i = w->n_trsm - (nb1 + CHOL_TRSM_ROWS - 1) / CHOL_TRSM_ROWS; i < w->n_trsm; i++) w->trsm[i].chan = fol ? b->ch_below : -1;
+    }
+    /* rows of the parent's first column block */
+    int par_lim = 0;
+    const int hp = h / 2;
+    if (hp >= 1 && c->follow) {
+      const int par = p->tree[hp];
+      if (c->nblk_of[par] > 0 && (c->pb[par][0].nb + CHOL_NB - 1) / CHOL_NB <= CHOL_FOLLOW_MAXT && c->count[BIDX(p, par, s)] > 0) {
+        par_lim = c->pb[par][0].nb;
+        const int tb = w->n_trsm;
+        const int nstr = push_block_rows(c, par, s, 0, par_lim, diag, dinv, nb, ld, colbase, b->c_prog, -2);
+        if (nstr > 0) {
+          b->ns_par = nstr; b->ch_par = new_ctr(P, nstr);
+          for (int e = 1; e < nt; e++) new_ctr(P, nstr);
+          for (int i = tb; i < w->n_trsm; i++) w->trsm[i].chan = b->ch_par;
+          b->par_off = p->blk[BIDX(p, par, s)].off + colbase; /* row 0 of the parent block in column c0 of the panel */
+        } else par_lim = 0;
+      }
+    }
+    /* the rest: remaining pivot rows, remaining parent rows, every other ancestor */
+    const int t_rest = w->n_trsm;
+    if (below - nb1 > 0) push_trsm_run(B, diag, dinv, p->panel_off[s] + (c0 + nb + nb1) + colbase, nb, ld, below - nb1, b->c_prog);
+    for (int ha = hp; ha >= 1; ha /= 2) {
+      const int anc = p->tree[ha];
+      if (BIDX(p, anc, s) < 0) continue;
+      push_block_rows(c, anc, s, ha == hp ? par_lim : 0, p->sep_size[anc], diag, dinv, nb, ld, colbase, b->c_prog, -1);
+    }
+    if (c->sw_of[s] < c->bw_of[s] && w->n_trsm > t_rest) { /* chunked: these strips publish their column tiles too */
+      b->ns_rest = w->n_trsm - t_rest; b->ch_rest = new_ctr(P, b->ns_rest);
+      for (int e = 1; e < nt; e++) new_ctr(P, b->ns_rest);
+      for (int i = t_rest; i < w->n_trsm; i++) w->trsm[i].chan = b->ch_rest;
+    }
+    B->cur_band = 0;
+    b->n_groups = emit_trsm_jobs(c, s, b, t0);
+    c->pg->ctr_total[b->c_strips] = b->n_groups;
+  }
+}
+/* (C) the next column block of a split pivot follows the strips of its own rows */
+static void emit_next_block_followers(prog_ctx *c, int st)
+{
+  const plan_t *p = c->p;
+  for (int q = 0; q < c->nh; q++) {
+    const int s = p->tree[c->hs[q]];
+    if (st + 1 >= c->nblk_of[s] || c->pb[s][st].ch_below < 0) continue;
+    const pblock *b = &c->pb[s][st];
+    const int ld = p->panel_ld[s];
+    ext_item *items = NULL; int nit = 0, capit = 0;
+    const int64_t e_off = p->panel_off[s] + (b->c0 + b->nb) + (int64_t)b->c0 * ld;
+    const int nb1 = c->pb[s][st + 1].nb, nt = (b->nb + CHOL_NB - 1) / CHOL_NB;
+    int bt = 0; /* column tiles of this block that reach the next block's diagonal block through early update jobs */
+    if (c->o.follow_tail_split > 0 && (nb1 + CHOL_NB - 1) / CHOL_NB > CHOL_FOLLOW_ALL_MAXT && nt > c->o.follow_tail_split) bt = nt - c->o.follow_tail_split;
+    if (bt > 0 && c->sky[s]) { /* a leaf: columns left of the next block's skyline bring nothing into its diagonal block */
+      int fmin = 1 << 20;
+      for (int i = (b->c0 + b->nb) / CHOL_NB; i * CHOL_NB < b->c0 + b->nb + nb1; i++) if (c->sky[s][i] < fmin) fmin = c->sky[s][i];
+      if (fmin - b->c0 / CHOL_NB >= bt) bt = 0; /* (the tail items stay: they are cheap, and the follower's list must not be empty) */
+    }
+    int early = 0;
+    if (bt > 0) {
+      const early_src es = { e_off, ld, bt * CHOL_NB, b->ch_below + bt - 1, b->ns_below };
+      early = emit_early_cells(c, p->panel_off[s] + (b->c0 + b->nb) + (int64_t)(b->c0 + b->nb) * ld, ld, nb1, BIDX(p, s, s), &es, 1);
+    }
+    const int ef = c->pg->n_ext;
+    push_ext_items(&items, &nit, &capit, e_off, ld, b->nb, b->ch_below, b->ns_below, 0, bt);
+    for (int i = 0; i < nit; i++) add_ext(&c->P, items[i].x);
+    free(items);
+    emit_potrf_job(c, s, st + 1, ef, early);
+  }
+}
+/* the fast part of a step's trailing update: (followed rows of the parent, block blk_par) x (columns of the NEXT column block) -- what that
+ * block's followed strips of the parent's rows wait for.  Its operands are channel strips on both sides (the parent-row strips, the strips of
+ * the next block's own rows), so these jobs wait for the channels' last column instead of every strip of the block, and are queued ahead of
+ * the rest of the step's trailing update.  plim: the followed rows; cols: the next block's columns */
+static void emit_fast_parent_update(prog_ctx *c, int s, const pblock *b, int blk_par, int plim, int cols)
+{
+  const plan_t *p = c->p;
+  chol_level_work *w = c->w;
+  builder *B = &c->B;
+  const int ld = p->panel_ld[s], c0 = b->c0, nb = b->nb, kf0 = w->n_task, ntl = (nb + CHOL_NB - 1) / CHOL_NB;
+  const int64_t colbase = (int64_t)c0 * ld, x_piv = p->panel_off[s] + (c0 + nb) + colbase;
+  B->cur_blk = blk_par;
+  block_runs it = block_runs_of(p, blk_par, 0, plim, c->snap, c->first, c->count);
+  for (int row, rows; block_runs_next(&it, &row, &rows);) { /* sources in chunks of EARLY_CHUNK column tiles, chunk ch behind the waits 2 ch, 2 ch + 1 (both channels) */
+    const int sb = w->n_src;
+    for (int ch = 0; ch * EARLY_CHUNK < ntl; ch++) {
+      const int col0 = ch * EARLY_CHUNK * CHOL_NB, kc = nb - col0 < EARLY_CHUNK * CHOL_NB ? nb - col0 : EARLY_CHUNK * CHOL_NB;
+      chol_upd_src sa = { chol_block_row(it.Bk, row) + colbase + (int64_t)col0 * ld, x_piv + (int64_t)col0 * ld, ld, ld, kc, 0, c->o.staged ? 2 * ch + 2 : 0, 0 };
+      push_src(B, sa);
+    }
+    push_tasks(B, chol_block_row(it.Bk, row) + (int64_t)(c0 + nb) * ld, ld, rows, cols, 0, sb, w->n_src);
+  }
+  flush_targets(B);
+  wait_src ws[2 * 32]; int nws = 0;
+  for (int ch = 0; ch * EARLY_CHUNK < ntl && nws < 62; ch++) {
+    const int last = (ch + 1) * EARLY_CHUNK < ntl ? (ch + 1) * EARLY_CHUNK - 1 : ntl - 1;
+    const wait_src x0 = { b->ch_par + last, b->ns_par, 0, 0 }, x1 = { b->ch_below + last, b->ns_below, 0, 0 };
+    ws[nws++] = x0; ws[nws++] = x1;
+  }
+  emit_update_jobs(c, kf0, w->n_task, ws, nws, c->o.staged); /* (the stages are set) */
+}
+/* (D) trailing update of the step: columns right of the block in the pivot rows below it (lower triangle) and in the
+ *     ancestor rows; the diagonal block of a following next column block is left out (follow_external does it) */
+static void emit_trailing_update(prog_ctx *c, int st)
+{
+  const plan_t *p = c->p;
+  chol_level_work *w = c->w;
+  builder *B = &c->B;
+  memcpy(c->snap_upd, c->cnt_upd, (p->nsep + 1) * sizeof(int));
+  for (int q = 0; q < c->nh; q++) {
+    const int h = c->hs[q], s = p->tree[h], n = p->sep_size[s], ld = p->panel_ld[s];
+    if (st >= c->nblk_of[s]) continue;
+    const pblock *b = &c->pb[s][st];
+    const int c0 = b->c0, nb = b->nb, below = n - c0 - nb;
+    if (below <= 0) continue;
+    const int64_t colbase = (int64_t)c0 * ld;
+    const int64_t x_piv = p->panel_off[s] + (c0 + nb) + colbase; /* solved pivot rows below the block, k = nb */
+    /* ancestor rows.  `blk` of these tasks: the true block for the followed rows of the parent (rows [0, par_lim) of block
+     * (parent, s): their update jobs are what the followed strips of the later column blocks wait for, counter updp), a
+     * non-parent, non-diagonal block of the panel for every other ancestor row (they raise the panel counter only) */
+    const int hpp = h / 2, hgp = h / 4;
+    const int par = hpp >= 1 ? p->tree[hpp] : -1;
+    const int blk_par = par >= 0 ? BIDX(p, par, s) : -1;
+    const int blk_rest = hgp >= 1 && BIDX(p, p->tree[hgp], s) >= 0 ? BIDX(p, p->tree[hgp], s) : blk_par;
+    const int fine = c->P.c_updp && b->ch_par >= 0 && blk_par >= 0 && c->count[blk_par] > 0;
+    const int par_lim = fine ? c->pb[par][0].nb : 0;
+    const int fast = fine && b->ch_below >= 0;
+    const int fast_cols = fast ? c->pb[s][st + 1].nb : 0; /* columns of the parent's followed rows the fast jobs cover */
+    if (fast) emit_fast_parent_update(c, s, b, blk_par, par_lim, fast_cols);
+    const int k0 = w->n_task;
+    B->cur_blk = BIDX(p, s, s);
+    if (b->ch_below >= 0) {
+      const int nb1 = c->pb[s][st + 1].nb, r2 = below - nb1;
+      if (r2 > 0) {
+        const int64_t x2 = x_piv + nb1;
+        chol_upd_src s1 = { x2, x_piv, ld, ld, nb, 0, 0, 0 }, s2 = { x2, x2, ld, ld, nb, 0, 0, 0 };
+        const int i1 = push_src(B, s1);
+        push_tasks(B, p->panel_off[s] + (c0 + nb + nb1) + (int64_t)(c0 + nb) * ld, ld, r2, nb1, 0, i1, i1 + 1);
+        const int i2 = push_src(B, s2);
+        push_tasks(B, p->panel_off[s] + (c0 + nb + nb1) + (int64_t)(c0 + nb + nb1) * ld, ld, r2, r2, 1, i2, i2 + 1);
+      }
+    } else {
+      chol_upd_src sp = { x_piv, x_piv, ld, ld, nb, 0, 0, 0 };
+      const int sidx = push_src(B, sp);
+      push_tasks(B, p->panel_off[s] + (c0 + nb) + (int64_t)(c0 + nb) * ld, ld, below, below, 1, sidx, sidx + 1);
+    }
+    if (fine && below > fast_cols) { /* followed parent rows: filled row runs of block (parent, s) within [0, par_lim), the columns beyond the fast part */
+      B->cur_blk = blk_par;
+      block_runs it = block_runs_of(p, blk_par, 0, par_lim, c->snap, c->first, c->count);
+      for (int row, rows; block_runs_next(&it, &row, &rows);) {
+        chol_upd_src sa = { chol_block_row(it.Bk, row) + colbase, x_piv + fast_cols, ld, ld, nb, 0, 0, 0 };
+        const int si = push_src(B, sa);
+        push_tasks(B, chol_block_row(it.Bk, row) + (int64_t)(c0 + nb + fast_cols) * ld, ld, rows, below - fast_cols, 0, si, si + 1);
+      }
+    }
+    B->cur_blk = blk_rest;
+    for (int ha = hpp; ha >= 1; ha /= 2) { /* every other ancestor row: the rest of the parent block, the other ancestors */
+      const int ba = BIDX(p, p->tree[ha], s);
+      if (ba < 0) continue;
+      block_runs it = block_runs_of(p, ba, (fine && ha == hpp) ? par_lim : 0, 1 << 30, c->snap, c->first, c->count);
+      for (int row, rows; block_runs_next(&it, &row, &rows);) {
+        chol_upd_src sa = { chol_block_row(it.Bk, row) + colbase, x_piv, ld, ld, nb, 0, 0, 0 };
+        const int si = push_src(B, sa);
+        push_tasks(B, chol_block_row(it.Bk, row) + (int64_t)(c0 + nb) * ld, ld, rows, below, 0, si, si + 1);
+      }
+    }
+    flush_targets(B);
+    const wait_src strips = { b->c_strips, b->n_groups, 0, 0 };
+    emit_update_jobs(c, k0, w->n_task, &strips, 1, 0);
+  }
+}
+/* (E) POTRF jobs of the parents' first column blocks: they follow their children's strips of the parent rows; children in
+ *     ascending pivot width (the one expected to finish last is consumed last), column blocks in order */
+static void emit_parent_followers(prog_ctx *c)
+{
+  const plan_t *p = c->p;
+  memset(c->follow_lim, 0, p->nblk * sizeof(int));
+  if (!c->follow) return;
+  for (int hp = (1 << c->level) / 2; hp <= ((1 << (c->level + 1)) - 1) / 2; hp++) {
+    const int par = p->tree[hp];
+    if (c->nblk_of[par] == 0 || c->pb[par][0].emitted || c->count[BIDX(p, par, par)] == 0) continue;
+    int kids[2] = { p->tree[2 * hp], p->tree[2 * hp + 1] };
+    if (p->sep_size[kids[0]] > p->sep_size[kids[1]]) { const int t = kids[0]; kids[0] = kids[1]; kids[1] = t; }
+    const int ef = c->pg->n_ext;
+    int all = 1; /* follow only if every contributing child has its channel (then the cells are left out of the extend-add) */
+    for (int k = 0; k < 2; k++)
+      for (int st = 0; st < c->nblk_of[kids[k]]; st++)
+        if (c->count[BIDX(p, par, kids[k])] > 0 && c->pb[kids[k]][st].ch_par < 0) all = 0;
+    if (!all) continue;
+    ext_item *items = NULL; int nit = 0, capit = 0;
+    const int lim = c->pb[par][0].nb, wide = c->o.follow_tail > 0 && (lim + CHOL_NB - 1) / CHOL_NB > CHOL_FOLLOW_ALL_MAXT;
+    early_src es[2 * 32]; int nes = 0;
+    for (int k = 0; k < 2; k++) {
+      int total = 0;
+      for (int st = 0; st < c->nblk_of[kids[k]]; st++) total += (c->pb[kids[k]][st].nb + CHOL_NB - 1) / CHOL_NB;
+      const int bt = wide && total > c->o.follow_tail ? total - c->o.follow_tail : 0; /* the child's leading column tiles that go the early way */
+      int before = 0; /* column tiles of the child's earlier blocks */
+      for (int st = 0; st < c->nblk_of[kids[k]]; st++) {
+        const pblock *b = &c->pb[kids[k]][st];
+        const int nt = (b->nb + CHOL_NB - 1) / CHOL_NB;
+        const int et = bt - before < 0 ? 0 : bt - before > nt ? nt : bt - before; /* early column tiles of this block */
+        if (b->ch_par >= 0) {
+          if (et > 0 && nes < 64) { const early_src e1 = { b->par_off, p->panel_ld[kids[k]], et * CHOL_NB < b->nb ? et * CHOL_NB : b->nb, b->ch_par + et - 1, b->ns_par }; es[nes++] = e1; }
+          push_ext_items(&items, &nit, &capit, b->par_off, p->panel_ld[kids[k]], b->nb, b->ch_par, b->ns_par, c->est_start[kids[k]] + before, et);
+        }
+        before += nt;
+      }
+    }
+    int early = 0;
+    if (nes > 0) {
+      const chol_block *Bp = &p->blk[BIDX(p, par, par)];
+      early = emit_early_cells(c, Bp->off, Bp->ld, lim, BIDX(p, par, par), es, nes);
+    }
+    qsort(items, nit, sizeof(ext_item), cmp_ext_item);
+    for (int i = 0; i < nit; i++) add_ext(&c->P, items[i].x);
+    free(items);
+    if (c->pg->n_ext == ef) continue;
+    c->follow_lim[BIDX(p, par, par)] = c->pb[par][0].nb;
+    emit_potrf_job(c, par, 0, ef, early);
+  }
+}
+/* the block ranges of the tasks [k0, n_task) by urgency: targets deepest in the tree first (their pivots are factored next), diagonal blocks
+ * before the rows below them; the order of the tasks in memory is irrelevant to the queue.  The caller frees the list */
+typedef struct { int i, e, prio; } blk_range;
+static blk_range *urgent_block_ranges(const prog_ctx *c, int k0, int *n_out)
+{
+  const plan_t *p = c->p;
+  const chol_level_work *w = c->w;
+  const int L = p->levels;
+  int nrg = 0, caprg = 64;
+  blk_range *rg = malloc(caprg * sizeof(blk_range));
+  for (int i = k0; i < w->n_task;) {
+    int e = i + 1;
+    while (e < w->n_task && w->task[e].blk == w->task[i].blk) e++;
+    const chol_block *Bc = &p->blk[w->task[i].blk];
+    if (nrg == caprg) { caprg *= 2; rg = realloc(rg, caprg * sizeof(blk_range)); }
+    rg[nrg].i = i; rg[nrg].e = e;
+    rg[nrg].prio = (L - p->level_of[Bc->c]) * 4 * L + (Bc->r == Bc->c ? 0 : 1 + (p->level_of[Bc->c] - p->level_of[Bc->r])); /* ascending = more urgent first */
+    nrg++;
+    i = e;
+  }
+  for (int a = 1; a < nrg; a++) { /* stable insertion sort (a few dozen ranges) */
+    blk_range t = rg[a];
+    int b = a - 1;
+    while (b >= 0 && rg[b].prio > t.prio) { rg[b + 1] = rg[b]; b--; }
+    rg[b + 1] = t;
+  }
+  *n_out = nrg;
+  return rg;
+}
+/* the wait list of the extend-add jobs into a panel of column separator col_sep: their sources are the separators of the current level under
+ * it: the strips counter of every pivot block of theirs (a chunked block: per chunk the channels' last column tile of the chunk), in expected
+ * order of completion.  The caller frees the list */
+static wait_src *target_wait_list(const prog_ctx *c, int col_sep, int *n_out)
+{
+  const plan_t *p = c->p;
+  const int hpar = p->heap_of[col_sep], dl = c->level - p->level_of[col_sep];
+  int n = 0, cap = 1;
+  for (int hh = hpar << dl; hh < ((hpar + 1) << dl); hh++) cap += c->nblk_of[p->tree[hh]] + 2 * ((p->sep_size[p->tree[hh]] + CHOL_NB - 1) / CHOL_NB);
+  wait_src *ws = malloc(cap * sizeof(wait_src));
+  for (int hh = hpar << dl; hh < ((hpar + 1) << dl); hh++) {
+    const int s = p->tree[hh];
+    int through = 0;
+    for (int st = 0; st < c->nblk_of[s]; st++) {
+      const pblock *b = &c->pb[s][st];
+      const int nt = (b->nb + CHOL_NB - 1) / CHOL_NB;
+      if (c->sw_of[s] < c->bw_of[s] && b->n_groups > 0) { /* chunked (one block) */
+        const int ct = c->sw_of[s] / CHOL_NB;
+        for (int ch = 0; ch * ct < nt; ch++) {
+          const int last = (ch + 1) * ct < nt ? (ch + 1) * ct - 1 : nt - 1;
+          const wait_src xp = { b->ch_par + last, b->ns_par, 64 * s + ch, c->est_start[s] + last + 1 }, xr = { b->ch_rest + last, b->ns_rest, 64 * s + ch, c->est_start[s] + last + 1 };
+          if (b->ch_par >= 0) ws[n++] = xp;
+          if (b->ch_rest >= 0) ws[n++] = xr;
+        }
+        through += nt;
+        continue;
+      }
+      through += nt;
+      const wait_src x = { b->c_strips, b->n_groups, 64 * s + st, c->est_start[s] + through };
+      if (b->n_groups > 0) ws[n++] = x;
+    }
+  }
+  sort_wait_srcs(ws, n);
+  *n_out = n;
+  return ws;
+}
+/* (F) extend-add of the level (tuples in program order, grouped by target), without the followed cells */
+static int emit_level_extend_add(prog_ctx *c)
+{
+  const plan_t *p = c->p;
+  chol_level_work *w = c->w;
+  builder *B = &c->B;
+  int ntu;
+  upd_tuple *tu = level_tuples(p, c->hs, c->nh, c->snap, c->first, c->count, &ntu);
+  const int k0 = w->n_task;
+  memcpy(c->snap_upd, c->cnt_upd, (p->nsep + 1) * sizeof(int));
+  int any_follow = 0;
+  for (int b = 0; b < p->nblk; b++) any_follow |= c->follow_lim[b] > 0;
+  const int small = tuples_are_small(&c->o, tu, ntu);
+  if (any_follow && !small) { free(tu); chol_set_error("program launch: followers need the grid-cell extend-add"); return CHOLAMD_ERR_ARG; }
+  if (small || any_follow) { B->follow_lim = c->follow_lim; emit_cell_tasks(B, p, tu, ntu); B->follow_lim = NULL; }
+  else {
+    for (int i = 0; i < ntu;) {
+      int e = i + 1;
+      while (e < ntu && tu[e].key == tu[i].key) e++;
+      const int sb = w->n_src;
+      for (int q = i; q < e; q++) { chol_upd_src sd = { tu[q].a_off, tu[q].b_off, tu[q].lda, tu[q].ldb, tu[q].k, 0, -(64 * tu[q].src_sep + 63) - 1, 0 }; push_src(B, sd); }
+      B->cur_blk = tu[i].bc;
+      push_tasks(B, tu[i].c_off, tu[i].ldc, tu[i].m, tu[i].n, tu[i].syrk, sb, w->n_src);
+      i = e;
+    }
+    flush_targets(B);
+  }
+  free(tu);
+  /* a job's sources are the separators of this level under its target's column separator: wait for all their strips */
+  int nrg;
+  blk_range *rg = urgent_block_ranges(c, k0, &nrg);
+  for (int q = 0; q < nrg; q++) {
+    int nws;
+    wait_src *ws = target_wait_list(c, p->blk[w->task[rg[q].i].blk].c, &nws);
+    emit_update_jobs(c, rg[q].i, rg[q].e, ws, nws, c->o.staged);
+    free(ws);
+  }
+  free(rg);
+  return 0;
+}
 
-  for (int level = L - 1; level >= 0 && !rc; level--) {
-    const int lbl = L - 1 - level;
-    index_snapshot(p, lbl, first, count);
-    const cholamd_filled *snap = p->snap[lbl];
-    const int h0 = 1 << level, h1 = (1 << (level + 1)) - 1;
-    int *hs = malloc((h1 - h0 + 1) * sizeof(int)), nh = 0, steps = 0;
-    for (int h = h0; h <= h1; h++) {
-      const int s = p->tree[h];
-      if (count[BIDX(p, s, s)] == 0 || p->sep_size[s] == 0) continue;
-      hs[nh++] = h;
-      if (nblk_of[s] > steps) steps = nblk_of[s];
+/* the queue order of the block comment at the head of this part ("Queue order per tree level ..."), step by step */
+int chol_build_program(const plan_t *p, const chol_sched_opts *opts, chol_level_work *w, chol_program *pg)
+{
+  memset(w, 0, sizeof *w);
+  memset(pg, 0, sizeof *pg);
+  w->level = -1;
+  chol_sched_opts dflt;
+  if (!opts) { chol_sched_opts_default(&dflt); opts = &dflt; }
+  prog_ctx c;
+  int rc = prog_ctx_init(&c, p, opts, w, pg);
+  for (int level = p->levels - 1; level >= 0 && !rc; level--) {
+    prog_begin_level(&c, level);
+    for (int st = 0; st < c.steps; st++) {
+      emit_plain_potrf_jobs(&c, st);
+      emit_step_trsm_jobs(&c, st);
+      emit_next_block_followers(&c, st);
+      emit_trailing_update(&c, st);
     }
-    for (int st = 0; st < steps; st++) {
-      /* (A) POTRF jobs of this step that no follower placement has emitted yet */
-      for (int q = 0; q < nh; q++) {
-        const int s = p->tree[hs[q]];
-        if (st < nblk_of[s] && !pb[s][st].emitted) EMIT_POTRF(s, st, pg->n_ext, 0);
-      }
-      /* (B) TRSM jobs: per pivot block the followed rows first (next column block of the pivot, rows of the parent's first
-       *     column block), then everything else */
-      for (int q = 0; q < nh; q++) {
-        const int h = hs[q], s = p->tree[h], n = p->sep_size[s], ld = p->panel_ld[s];
-        if (st >= nblk_of[s]) continue;
-        pblock *b = &pb[s][st];
-        const int c0 = b->c0, nb = b->nb;
-        const int64_t diag = p->panel_off[s] + c0 + (int64_t)c0 * ld;
-        const int64_t dinv = p->dinv_off[s] + (int64_t)(c0 / CHOL_NB) * CHOL_NB * CHOL_NB;
-        const int64_t colbase = (int64_t)c0 * ld;
-        const int below = n - c0 - nb;
-        const int t0 = w->n_trsm;
-        B->cur_band = band_of[s]; /* strips of a banded leaf factored as one block */
-        /* rows of the next column block of this pivot */
-        int nb1 = 0;
-        if (below > 0) {
-          nb1 = pb[s][st + 1].nb;
-          const int fol = follow && (nb1 + CHOL_NB - 1) / CHOL_NB <= CHOL_FOLLOW_MAXT;
-          if (fol) { b->ns_below = (nb1 + CHOL_TRSM_ROWS - 1) / CHOL_TRSM_ROWS; b->ch_below = new_ctr(P, b->ns_below); for (int e = 1; e < (nb + CHOL_NB - 1) / CHOL_NB; e++) new_ctr(P, b->ns_below); }
-          push_trsm_run(B, diag, dinv, p->panel_off[s] + (c0 + nb) + colbase, nb, ld, nb1, b->c_prog);
-          for (int i = w->n_trsm - (nb1 + CHOL_TRSM_ROWS - 1) / CHOL_TRSM_ROWS; i < w->n_trsm; i++) w->trsm[i].chan = fol ? b->ch_below : -1;
-        }
-        /* rows of the parent's first column block */
-        int par_lim = 0;
-        const int hp = h / 2;
-        if (hp >= 1 && follow) {
-          const int par = p->tree[hp];
-          if (nblk_of[par] > 0 && (pb[par][0].nb + CHOL_NB - 1) / CHOL_NB <= CHOL_FOLLOW_MAXT && count[BIDX(p, par, s)] > 0) {
-            par_lim = pb[par][0].nb;
-            const int tb = w->n_trsm;
-            const int nstr = push_block_rows(B, p, par, s, 0, par_lim, snap, first, count, diag, dinv, nb, ld, colbase, b->c_prog, -2);
-            if (nstr > 0) {
-              b->ns_par = nstr; b->ch_par = new_ctr(P, nstr);
-              for (int e = 1; e < (nb + CHOL_NB - 1) / CHOL_NB; e++) new_ctr(P, nstr);
-              for (int i = tb; i < w->n_trsm; i++) w->trsm[i].chan = b->ch_par;
-              b->par_off = p->blk[BIDX(p, par, s)].off + colbase; /* row 0 of the parent block in column c0 of the panel */
-            } else par_lim = 0;
-          }
-        }
-        /* the rest: remaining pivot rows, remaining parent rows, every other ancestor */
-        const int t_rest = w->n_trsm;
-        if (below - nb1 > 0) push_trsm_run(B, diag, dinv, p->panel_off[s] + (c0 + nb + nb1) + colbase, nb, ld, below - nb1, b->c_prog);
-        for (int ha = hp; ha >= 1; ha /= 2) {
-          const int anc = p->tree[ha];
-          if (BIDX(p, anc, s) < 0) continue;
-          push_block_rows(B, p, anc, s, ha == hp ? par_lim : 0, p->sep_size[anc], snap, first, count, diag, dinv, nb, ld, colbase, b->c_prog, -1);
-        }
-        if (sw_of[s] < bw_of[s] && w->n_trsm > t_rest) { /* chunked: these strips publish their column tiles too */
-          b->ns_rest = w->n_trsm - t_rest; b->ch_rest = new_ctr(P, b->ns_rest);
-          for (int e = 1; e < (nb + CHOL_NB - 1) / CHOL_NB; e++) new_ctr(P, b->ns_rest);
-          for (int i = t_rest; i < w->n_trsm; i++) w->trsm[i].chan = b->ch_rest;
-        }
-        B->cur_band = 0;
-        b->n_groups = emit_trsm_jobs(P, B, t0, c_upd[s], cnt_upd[s], b->c_strips, b->ch_par, P->c_updp ? P->c_updp[s] : -1, P->c_updp ? P->cnt_updp[s] : 0, b->ch_below, c_updd[s], cnt_updd[s]);
-        pg->ctr_total[b->c_strips] = b->n_groups;
-      }
-      /* (C) the next column block of a split pivot follows the strips of its own rows */
-      for (int q = 0; q < nh; q++) {
-        const int s = p->tree[hs[q]];
-        if (st + 1 >= nblk_of[s] || pb[s][st].ch_below < 0) continue;
-        const pblock *b = &pb[s][st];
-        const int ld = p->panel_ld[s];
-        ext_item *items = NULL; int nit = 0, capit = 0;
-        const int64_t e_off = p->panel_off[s] + (b->c0 + b->nb) + (int64_t)b->c0 * ld;
-        const int nb1 = pb[s][st + 1].nb, nt = (b->nb + CHOL_NB - 1) / CHOL_NB;
-        int bt = 0; /* column tiles of this block that reach the next block's diagonal block through early update jobs */
-        if (opts->follow_tail_split > 0 && (nb1 + CHOL_NB - 1) / CHOL_NB > CHOL_FOLLOW_ALL_MAXT && nt > opts->follow_tail_split) bt = nt - opts->follow_tail_split;
-        if (bt > 0 && sky[s]) { /* a leaf: columns left of the next block's skyline bring nothing into its diagonal block */
-          int fmin = 1 << 20;
-          for (int i = (b->c0 + b->nb) / CHOL_NB; i * CHOL_NB < b->c0 + b->nb + nb1; i++) if (sky[s][i] < fmin) fmin = sky[s][i];
-          if (fmin - b->c0 / CHOL_NB >= bt) bt = 0; /* (the tail items stay: they are cheap, and the follower's list must not be empty) */
-        }
-        int early = 0;
-        if (bt > 0) {
-          const early_src es = { e_off, ld, bt * CHOL_NB, b->ch_below + bt - 1, b->ns_below };
-          early = emit_early_cells(P, B, p, p->panel_off[s] + (b->c0 + b->nb) + (int64_t)(b->c0 + b->nb) * ld, ld, nb1, BIDX(p, s, s), &es, 1, c_upd, c_updd, snap_upd, cnt_upd, cnt_updd);
-        }
-        const int ef = pg->n_ext;
-        push_ext_items(&items, &nit, &capit, e_off, ld, b->nb, b->ch_below, b->ns_below, 0, bt);
-        for (int i = 0; i < nit; i++) add_ext(P, items[i].x);
-        free(items);
-        EMIT_POTRF(s, st + 1, ef, early);
-      }
-      /* (D) trailing update of the step: columns right of the block in the pivot rows below it (lower triangle) and in the
-       *     ancestor rows; the diagonal block of a following next column block is left out (follow_external does it) */
-      {
-        memcpy(snap_upd, cnt_upd, (ns + 1) * sizeof(int));
-        for (int q = 0; q < nh; q++) {
-          const int h = hs[q], s = p->tree[h], n = p->sep_size[s], ld = p->panel_ld[s];
-          if (st >= nblk_of[s]) continue;
-          const pblock *b = &pb[s][st];
-          const int c0 = b->c0, nb = b->nb, below = n - c0 - nb;
-          if (below <= 0) continue;
-          const int64_t colbase = (int64_t)c0 * ld;
-          const int64_t x_piv = p->panel_off[s] + (c0 + nb) + colbase; /* solved pivot rows below the block, k = nb */
-          /* fast part: (followed rows of the parent) x (columns of the NEXT column block) -- what that block's followed strips of
-           * the parent's rows wait for.  Its operands are channel strips on both sides (the parent-row strips, the strips of the next
-           * block's own rows), so these jobs wait for the channels' last column instead of every strip of the block, and are queued
-           * ahead of the rest of the step's trailing update */
-          const int hpp_ = h / 2, par_ = hpp_ >= 1 ? p->tree[hpp_] : -1, blkp_ = par_ >= 0 ? BIDX(p, par_, s) : -1;
-          const int fast = P->c_updp && b->ch_par >= 0 && b->ch_below >= 0 && blkp_ >= 0 && count[blkp_] > 0;
-          const int fast_cols = fast ? pb[s][st + 1].nb : 0; /* columns of the parent's followed rows the fast jobs cover */
-          if (fast) {
-            const chol_block *Bk = &p->blk[blkp_];
-            const int plim = pb[par_][0].nb, kf0 = w->n_task, ntl_ = (nb + CHOL_NB - 1) / CHOL_NB;
-            B->cur_blk = blkp_;
-            int run_lo = -1, run_hi = -1;
-            for (int q2 = 0; q2 <= count[blkp_]; q2++) {
-              int a0 = -1, a1 = -1;
-              if (q2 < count[blkp_]) {
-                const cholamd_filled *f = &snap[first[blkp_] + q2];
-                a0 = f->lo_x - Bk->lo_x; a1 = f->hi_x - Bk->lo_x + 1;
-                if (a1 > plim) a1 = plim;
-                if (a0 >= a1) continue;
-                if (run_hi == a0) { run_hi = a1; continue; }
-              }
-              if (run_lo >= 0) { /* sources in chunks of EARLY_CHUNK column tiles, chunk c behind the waits 2 c, 2 c + 1 (both channels) */
-                const int sb_ = w->n_src;
-                for (int c = 0; c * EARLY_CHUNK < ntl_; c++) {
-                  const int col0 = c * EARLY_CHUNK * CHOL_NB, kc = nb - col0 < EARLY_CHUNK * CHOL_NB ? nb - col0 : EARLY_CHUNK * CHOL_NB;
-                  chol_upd_src sa = { chol_block_row(Bk, run_lo) + colbase + (int64_t)col0 * ld, x_piv + (int64_t)col0 * ld, ld, ld, kc, 0, opts->staged ? 2 * c + 2 : 0, 0 };
-                  push_src(B, sa);
-                }
-                push_tasks(B, chol_block_row(Bk, run_lo) + (int64_t)(c0 + nb) * ld, ld, run_hi - run_lo, fast_cols, 0, sb_, w->n_src);
-              }
-              run_lo = a0; run_hi = a1;
-            }
-            flush_targets(B);
-            int scf[2 * 32], snf[2 * 32], nwf = 0;
-            for (int c = 0; c * EARLY_CHUNK < ntl_ && nwf < 62; c++) {
-              const int last = (c + 1) * EARLY_CHUNK < ntl_ ? (c + 1) * EARLY_CHUNK - 1 : ntl_ - 1;
-              scf[nwf] = b->ch_par + last; snf[nwf++] = b->ns_par;
-              scf[nwf] = b->ch_below + last; snf[nwf++] = b->ns_below;
-            }
-            emit_update_jobs(P, B, p, kf0, c_upd, c_updd, snap_upd, cnt_upd, cnt_updd, scf, snf, nwf, opts->staged ? scf : NULL); /* non-NULL: staged (the stages are set) */
-          }
-          const int k0 = w->n_task;
-          B->cur_blk = BIDX(p, s, s);
-          if (b->ch_below >= 0) {
-            const int nb1 = pb[s][st + 1].nb, r2 = below - nb1;
-            if (r2 > 0) {
-              const int64_t x2 = x_piv + nb1;
-              chol_upd_src s1 = { x2, x_piv, ld, ld, nb, 0, 0, 0 }, s2 = { x2, x2, ld, ld, nb, 0, 0, 0 };
-              const int i1 = push_src(B, s1);
-              push_tasks(B, p->panel_off[s] + (c0 + nb + nb1) + (int64_t)(c0 + nb) * ld, ld, r2, nb1, 0, i1, i1 + 1);
-              const int i2 = push_src(B, s2);
-              push_tasks(B, p->panel_off[s] + (c0 + nb + nb1) + (int64_t)(c0 + nb + nb1) * ld, ld, r2, r2, 1, i2, i2 + 1);
-            }
-          } else {
-            chol_upd_src sp = { x_piv, x_piv, ld, ld, nb, 0, 0, 0 };
-            const int sidx = push_src(B, sp);
-            push_tasks(B, p->panel_off[s] + (c0 + nb) + (int64_t)(c0 + nb) * ld, ld, below, below, 1, sidx, sidx + 1);
-          }
-          /* ancestor rows.  `blk` of these tasks: the true block for the followed rows of the parent (rows [0, par_lim) of block
-           * (parent, s): their update jobs are what the followed strips of the later column blocks wait for, counter updp), a
-           * non-parent, non-diagonal block of the panel for every other ancestor row (they raise the panel counter only) */
-          const int hpp = h / 2, hgp = h / 4;
-          const int par = hpp >= 1 ? p->tree[hpp] : -1;
-          const int blk_par = par >= 0 ? BIDX(p, par, s) : -1;
-          const int blk_rest = hgp >= 1 && BIDX(p, p->tree[hgp], s) >= 0 ? BIDX(p, p->tree[hgp], s) : blk_par;
-          const int fine = P->c_updp && b->ch_par >= 0 && blk_par >= 0 && count[blk_par] > 0;
-          const int par_lim = fine ? pb[par][0].nb : 0;
-          if (fine) { /* followed parent rows: filled row runs of block (parent, s) within [0, par_lim) */
-            const chol_block *Bk = &p->blk[blk_par];
-            B->cur_blk = blk_par;
-            int run_lo = -1, run_hi = -1;
-            for (int q2 = 0; q2 <= count[blk_par]; q2++) {
-              int a0 = -1, a1 = -1;
-              if (q2 < count[blk_par]) {
-                const cholamd_filled *f = &snap[first[blk_par] + q2];
-                a0 = f->lo_x - Bk->lo_x; a1 = f->hi_x - Bk->lo_x + 1;
-                if (a1 > par_lim) a1 = par_lim;
-                if (a0 >= a1) continue;
-                if (run_hi == a0) { run_hi = a1; continue; }
-              }
-              if (run_lo >= 0 && below > fast_cols) { /* the columns beyond the fast part */
-                chol_upd_src sa = { chol_block_row(Bk, run_lo) + colbase, x_piv + fast_cols, ld, ld, nb, 0, 0, 0 };
-                const int si = push_src(B, sa);
-                push_tasks(B, chol_block_row(Bk, run_lo) + (int64_t)(c0 + nb + fast_cols) * ld, ld, run_hi - run_lo, below - fast_cols, 0, si, si + 1);
-              }
-              run_lo = a0; run_hi = a1;
-            }
-          }
-          B->cur_blk = blk_rest;
-          for (int ha = hpp; ha >= 1; ha /= 2) { /* every other ancestor row: the rest of the parent block, the other ancestors */
-            const int anc = p->tree[ha], ba = BIDX(p, anc, s);
-            if (ba < 0) continue;
-            const chol_block *Bk = &p->blk[ba];
-            const int lo = (fine && ha == hpp) ? par_lim : 0;
-            int run_lo = -1, run_hi = -1;
-            for (int q2 = 0; q2 <= count[ba]; q2++) {
-              int a0 = -1, a1 = -1;
-              if (q2 < count[ba]) {
-                const cholamd_filled *f = &snap[first[ba] + q2];
-                a0 = f->lo_x - Bk->lo_x; a1 = f->hi_x - Bk->lo_x + 1;
-                if (a0 < lo) a0 = lo;
-                if (a0 >= a1) continue;
-                if (run_hi == a0) { run_hi = a1; continue; }
-              }
-              if (run_lo >= 0) {
-                chol_upd_src sa = { chol_block_row(Bk, run_lo) + colbase, x_piv, ld, ld, nb, 0, 0, 0 };
-                const int si = push_src(B, sa);
-                push_tasks(B, chol_block_row(Bk, run_lo) + (int64_t)(c0 + nb) * ld, ld, run_hi - run_lo, below, 0, si, si + 1);
-              }
-              run_lo = a0; run_hi = a1;
-            }
-          }
-          flush_targets(B);
-          const int sc[1] = { b->c_strips }, sn[1] = { b->n_groups };
-          emit_update_jobs(P, B, p, k0, c_upd, c_updd, snap_upd, cnt_upd, cnt_updd, sc, sn, 1, NULL);
-        }
-      }
-    }
-    if (level == 0) { free(hs); break; }
-    /* (E) POTRF jobs of the parents' first column blocks: they follow their children's strips of the parent rows; children in
-     *     ascending pivot width (the one expected to finish last is consumed last), column blocks in order */
-    memset(follow_lim, 0, p->nblk * sizeof(int));
-    if (follow)
-      for (int hp = h0 / 2; hp <= h1 / 2; hp++) {
-        const int par = p->tree[hp];
-        if (nblk_of[par] == 0 || pb[par][0].emitted || count[BIDX(p, par, par)] == 0) continue;
-        int kids[2] = { p->tree[2 * hp], p->tree[2 * hp + 1] };
-        if (p->sep_size[kids[0]] > p->sep_size[kids[1]]) { const int t = kids[0]; kids[0] = kids[1]; kids[1] = t; }
-        const int ef = pg->n_ext;
-        int all = 1; /* follow only if every contributing child has its channel (then the cells are left out of the extend-add) */
-        for (int c = 0; c < 2; c++)
-          for (int st = 0; st < nblk_of[kids[c]]; st++)
-            if (count[BIDX(p, par, kids[c])] > 0 && pb[kids[c]][st].ch_par < 0) all = 0;
-        if (!all) continue;
-        ext_item *items = NULL; int nit = 0, capit = 0;
-        const int lim = pb[par][0].nb, wide = opts->follow_tail > 0 && (lim + CHOL_NB - 1) / CHOL_NB > CHOL_FOLLOW_ALL_MAXT;
-        early_src es[2 * 32]; int nes = 0;
-        for (int c = 0; c < 2; c++) {
-          int total = 0;
-          for (int st = 0; st < nblk_of[kids[c]]; st++) total += (pb[kids[c]][st].nb + CHOL_NB - 1) / CHOL_NB;
-          const int bt = wide && total > opts->follow_tail ? total - opts->follow_tail : 0; /* the child's leading column tiles that go the early way */
-          int before = 0; /* column tiles of the child's earlier blocks */
-          for (int st = 0; st < nblk_of[kids[c]]; st++) {
-            const pblock *b = &pb[kids[c]][st];
-            const int nt = (b->nb + CHOL_NB - 1) / CHOL_NB;
-            const int et = bt - before < 0 ? 0 : bt - before > nt ? nt : bt - before; /* early column tiles of this block */
-            if (b->ch_par >= 0) {
-              if (et > 0 && nes < 64) { const early_src e1 = { b->par_off, p->panel_ld[kids[c]], et * CHOL_NB < b->nb ? et * CHOL_NB : b->nb, b->ch_par + et - 1, b->ns_par }; es[nes++] = e1; }
-              push_ext_items(&items, &nit, &capit, b->par_off, p->panel_ld[kids[c]], b->nb, b->ch_par, b->ns_par, est_start[kids[c]] + before, et);
-            }
-            before += nt;
-          }
-        }
-        int early = 0;
-        if (nes > 0) {
-          const chol_block *Bp = &p->blk[BIDX(p, par, par)];
-          early = emit_early_cells(P, B, p, Bp->off, Bp->ld, lim, BIDX(p, par, par), es, nes, c_upd, c_updd, snap_upd, cnt_upd, cnt_updd);
-        }
-        qsort(items, nit, sizeof(ext_item), cmp_ext_item);
-        for (int i = 0; i < nit; i++) add_ext(P, items[i].x);
-        free(items);
-        if (pg->n_ext == ef) continue;
-        follow_lim[BIDX(p, par, par)] = pb[par][0].nb;
-        EMIT_POTRF(par, 0, ef, early);
-      }
-    /* (F) extend-add of the level (tuples in program order, grouped by target), without the followed cells */
-    {
-      int cap_u = 256, ntu = 0;
-      upd_tuple *tu = malloc(cap_u * sizeof(upd_tuple));
-      int64_t seq = 0;
-      for (int q = 0; q < nh; q++) {
-        const int h = hs[q], s = p->tree[h], n = p->sep_size[s];
-        for (int hp = h / 2; hp >= 1; hp /= 2) {
-          const int par = p->tree[hp], bb = BIDX(p, par, s);
-          const chol_block *Bb = &p->blk[bb];
-          for (int hg = hp; hg >= 1; hg /= 2) {
-            const int gp = p->tree[hg], ba = BIDX(p, gp, s), bc = BIDX(p, gp, par);
-            const chol_block *Ba = &p->blk[ba], *Bc = &p->blk[bc];
-            for (int i = 0; i < count[ba]; i++) {
-              const cholamd_filled *fa = &snap[first[ba] + i];
-              for (int j = 0; j < count[bb]; j++) {
-                const cholamd_filled *fb_ = &snap[first[bb] + j];
-                if (gp == par && fb_->cluster > fa->cluster) continue; /* col > row skipped, blas.rg:396-431 */
-                if (ntu == cap_u) { cap_u *= 2; tu = realloc(tu, cap_u * sizeof(upd_tuple)); }
-                upd_tuple *u = &tu[ntu++];
-                const int crow = fa->lo_x - Bc->lo_x, ccol = fb_->lo_x - Bc->lo_y;
-                u->key = ((int64_t)bc << 40) | ((int64_t)crow << 20) | (int64_t)ccol;
-                u->seq = seq++;
-                u->c_off = chol_block_row(Bc, crow) + (int64_t)ccol * Bc->ld; u->ldc = Bc->ld;
-                u->a_off = chol_block_row(Ba, fa->lo_x - Ba->lo_x); u->lda = Ba->ld;
-                u->b_off = chol_block_row(Bb, fb_->lo_x - Bb->lo_x); u->ldb = Bb->ld;
-                u->m = fa->hi_x - fa->lo_x + 1; u->n = fb_->hi_x - fb_->lo_x + 1; u->k = n;
-                u->syrk = (gp == par && fb_->cluster == fa->cluster);
-                u->bc = bc; u->crow = crow; u->ccol = ccol; u->src_sep = s;
-              }
-            }
-          }
-        }
-      }
-      qsort(tu, ntu, sizeof(upd_tuple), cmp_tuple);
-      const int k0 = w->n_task;
-      memcpy(snap_upd, cnt_upd, (ns + 1) * sizeof(int));
-      int any_follow = 0;
-      for (int b = 0; b < p->nblk; b++) any_follow |= follow_lim[b] > 0;
-      if (any_follow && !tuples_are_small(opts, tu, ntu)) { chol_set_error("program launch: followers need the grid-cell extend-add"); rc = CHOLAMD_ERR_ARG; }
-      if (!rc) {
-        if (tuples_are_small(opts, tu, ntu) || any_follow) { B->follow_lim = follow_lim; emit_cell_tasks(B, p, tu, ntu); B->follow_lim = NULL; }
-        else {
-          for (int i = 0; i < ntu;) {
-            int e = i + 1;
-            while (e < ntu && tu[e].key == tu[i].key) e++;
-            const int sb = w->n_src;
-            for (int q = i; q < e; q++) { chol_upd_src sd = { tu[q].a_off, tu[q].b_off, tu[q].lda, tu[q].ldb, tu[q].k, 0, -(64 * tu[q].src_sep + 63) - 1, 0 }; push_src(B, sd); }
-            B->cur_blk = tu[i].bc;
-            push_tasks(B, tu[i].c_off, tu[i].ldc, tu[i].m, tu[i].n, tu[i].syrk, sb, w->n_src);
-            i = e;
-          }
-          flush_targets(B);
-        }
-        /* a job's sources are the separators of this level under its target's column separator: wait for all their strips.
-         * Jobs are queued by urgency: targets deepest in the tree first (their pivots are factored next), diagonal blocks
-         * before the rows below them; the order of the tasks in memory is irrelevant to the queue */
-        typedef struct { int i, e, prio; } blk_range;
-        int nrg = 0, caprg = 64;
-        blk_range *rg = malloc(caprg * sizeof(blk_range));
-        for (int i = k0; i < w->n_task;) {
-          int e = i + 1;
-          while (e < w->n_task && w->task[e].blk == w->task[i].blk) e++;
-          const chol_block *Bc = &p->blk[w->task[i].blk];
-          if (nrg == caprg) { caprg *= 2; rg = realloc(rg, caprg * sizeof(blk_range)); }
-          rg[nrg].i = i; rg[nrg].e = e;
-          rg[nrg].prio = (L - p->level_of[Bc->c]) * 4 * L + (Bc->r == Bc->c ? 0 : 1 + (p->level_of[Bc->c] - p->level_of[Bc->r])); /* ascending = more urgent first */
-          nrg++;
-          i = e;
-        }
-        for (int a = 1; a < nrg; a++) { /* stable insertion sort (a few dozen ranges) */
-          blk_range t = rg[a];
-          int b = a - 1;
-          while (b >= 0 && rg[b].prio > t.prio) { rg[b + 1] = rg[b]; b--; }
-          rg[b + 1] = t;
-        }
-        for (int q = 0; q < nrg; q++) {
-          const int i = rg[q].i, e = rg[q].e;
-          const chol_block *Bc = &p->blk[w->task[i].blk];
-          const int hpar = p->heap_of[Bc->c], dl = level - p->level_of[Bc->c];
-          int nsc = 0, capsc = 1;
-          for (int hh = hpar << dl; hh < ((hpar + 1) << dl); hh++) capsc += nblk_of[p->tree[hh]] + 2 * ((p->sep_size[p->tree[hh]] + CHOL_NB - 1) / CHOL_NB);
-          int *sc = malloc(capsc * sizeof(int)), *sn = malloc(capsc * sizeof(int)), *ssep = malloc(capsc * sizeof(int)), *sest = malloc(capsc * sizeof(int));
-          for (int hh = hpar << dl; hh < ((hpar + 1) << dl); hh++) {
-            const int s = p->tree[hh];
-            int through = 0;
-            for (int st = 0; st < nblk_of[s]; st++) {
-              const pblock *b = &pb[s][st];
-              if (sw_of[s] < bw_of[s] && b->n_groups > 0) { /* chunked (one block): per chunk the channels' last column tile of the chunk */
-                const int nt = (b->nb + CHOL_NB - 1) / CHOL_NB, ct = sw_of[s] / CHOL_NB;
-                for (int c = 0; c * ct < nt; c++) {
-                  const int last = (c + 1) * ct < nt ? (c + 1) * ct - 1 : nt - 1;
-                  if (b->ch_par >= 0) { sc[nsc] = b->ch_par + last; sn[nsc] = b->ns_par; ssep[nsc] = 64 * s + c; sest[nsc] = est_start[s] + last + 1; nsc++; }
-                  if (b->ch_rest >= 0) { sc[nsc] = b->ch_rest + last; sn[nsc] = b->ns_rest; ssep[nsc] = 64 * s + c; sest[nsc] = est_start[s] + last + 1; nsc++; }
-                }
-                through += nt;
-                continue;
-              }
-              through += (b->nb + CHOL_NB - 1) / CHOL_NB;
-              if (b->n_groups > 0) { sc[nsc] = b->c_strips; sn[nsc] = b->n_groups; ssep[nsc] = 64 * s + st; sest[nsc] = est_start[s] + through; nsc++; }
-            }
-          }
-          for (int a = 1; a < nsc; a++) { /* expected order of completion (stable) */
-            const int c0_ = sc[a], n0_ = sn[a], s0_ = ssep[a], e0_ = sest[a];
-            int b = a - 1;
-            while (b >= 0 && sest[b] > e0_) { sc[b + 1] = sc[b]; sn[b + 1] = sn[b]; ssep[b + 1] = ssep[b]; sest[b + 1] = sest[b]; b--; }
-            sc[b + 1] = c0_; sn[b + 1] = n0_; ssep[b + 1] = s0_; sest[b + 1] = e0_;
-          }
-          /* emit_update_jobs walks [i, n_task): hand it exactly this block's tasks */
-          const int keep = w->n_task;
-          w->n_task = e;
-          emit_update_jobs(P, B, p, i, c_upd, c_updd, snap_upd, cnt_upd, cnt_updd, sc, sn, nsc, opts->staged ? ssep : NULL);
-          w->n_task = keep;
-          free(ssep); free(sest);
-          free(sc); free(sn);
-        }
-        free(rg);
-      }
-      free(tu);
-    }
-    free(hs);
+    if (level == 0) break;
+    emit_parent_followers(&c);
+    rc = emit_level_extend_add(&c);
     if (w->n_task > PROG_MAX_TASKS && !rc) { chol_set_error("program launch: more than %d update tasks", PROG_MAX_TASKS); rc = CHOLAMD_ERR_ARG; }
   }
-  #undef EMIT_POTRF
   if (!rc && w->n_task_mt > 0) { chol_set_error("program launch: macro-tile update phases"); rc = CHOLAMD_ERR_ARG; }
   if (!rc && w->n_task > PROG_MAX_TASKS) { chol_set_error("program launch: %d update tasks", w->n_task); rc = CHOLAMD_ERR_ARG; }
-  for (int s = 1; s <= ns; s++) { pg->ctr_total[c_upd[s]] = cnt_upd[s]; pg->ctr_total[c_updd[s]] = cnt_updd[s]; if (P->c_updp) pg->ctr_total[P->c_updp[s]] = P->cnt_updp[s]; }
-  free(P->c_updp); free(P->cnt_updp); P->c_updp = P->cnt_updp = NULL;
-  for (int s = 1; s <= ns; s++) free(pb[s]);
-  chol_free_skylines(sky, ns); free(bw_of); free(band_of); free(sw_of);
-  free(est_start); free(pb); free(nblk_of); free(first); free(count); free(c_upd); free(c_updd); free(cnt_upd); free(cnt_updd); free(snap_upd); free(follow_lim);
-  free(B->pend);
+  if (!rc) for (int s = 1; s <= p->nsep; s++) { pg->ctr_total[c.c_upd[s]] = c.cnt_upd[s]; pg->ctr_total[c.c_updd[s]] = c.cnt_updd[s]; if (c.P.c_updp) pg->ctr_total[c.P.c_updp[s]] = c.P.cnt_updp[s]; }
+  prog_ctx_free(&c);
   if (rc) { chol_level_work_free(w); chol_program_free(pg); }
   return rc;
 }
@@ -1722,21 +1827,21 @@ int chol_program_check_built(const plan_t *p, const chol_sched_opts *opts, int w
         if (val[wt->ctr] < wt->value) ok = 0;
       }
       if (rc) break;
-      if (jb->kind == 0 && jb->n_ext > 0) { /* the own tiles' place: in front of a round, or after the last item */
+      if (jb->kind == CHOL_JOB_POTRF && jb->n_ext > 0) { /* the own tiles' place: in front of a round, or after the last item */
         int at = 0;
         while (at < jb->mode && at < jb->n_ext) at += chol_follow_round(at, jb->n_ext, (w.potrf[jb->first].n + CHOL_NB - 1) / CHOL_NB);
         if (at != jb->mode) { chol_set_error("program job %d adds its own tiles at item %d of %d: not the start of a round", j, jb->mode, jb->n_ext); rc = CHOLAMD_ERR_ARG; break; }
       }
-      if (ok && jb->kind == 0)
+      if (ok && jb->kind == CHOL_JOB_POTRF)
         for (int x = 0; x < jb->n_ext && ok; x++) {
           const chol_ext *e = &g.ext[jb->ext_first + x];
           if (val[e->ctr] < e->need) ok = 0;
         }
-      if (ok && jb->kind == 1 && val[w.trsm[jb->first].flag] < g.ctr_total[w.trsm[jb->first].flag]) ok = 0; /* its pivot block is factored */
+      if (ok && jb->kind == CHOL_JOB_TRSM && val[w.trsm[jb->first].flag] < g.ctr_total[w.trsm[jb->first].flag]) ok = 0; /* its pivot block is factored */
       if (!ok) continue;
       /* complete */
-      if (jb->kind == 0) val[w.potrf[jb->first].ctr] = g.ctr_total[w.potrf[jb->first].ctr];
-      if (jb->kind == 1)
+      if (jb->kind == CHOL_JOB_POTRF) val[w.potrf[jb->first].ctr] = g.ctr_total[w.potrf[jb->first].ctr];
+      if (jb->kind == CHOL_JOB_TRSM)
         for (int i = jb->first; i < jb->first + jb->n; i++)
           if (w.trsm[i].chan >= 0 && w.trsm[i].m > 0)
             for (int t = 0; t < (w.trsm[i].n + CHOL_NB - 1) / CHOL_NB; t++) val[w.trsm[i].chan + t]++;
@@ -1826,10 +1931,10 @@ int64_t cholamd_plan_program_jobs(const cholamd_plan *p, int follow, int64_t cap
     for (int j = 0; j < g.n_job; j++) {
       const chol_job *jb = &g.job[j];
       int a = 0, b = 0;
-      if (jb->kind == 0) { a = w.potrf[jb->first].sep; b = w.potrf[jb->first].col0; }
-      else if (jb->kind == 1) { for (int i = 0; i < w.n_potrf; i++) if (w.potrf[i].ctr == w.trsm[jb->first].flag) { a = w.potrf[i].sep; b = w.potrf[i].col0; } }
+      if (jb->kind == CHOL_JOB_POTRF) { a = w.potrf[jb->first].sep; b = w.potrf[jb->first].col0; }
+      else if (jb->kind == CHOL_JOB_TRSM) { for (int i = 0; i < w.n_potrf; i++) if (w.potrf[i].ctr == w.trsm[jb->first].flag) { a = w.potrf[i].sep; b = w.potrf[i].col0; } }
       else { a = p->blk[w.task[jb->first].blk].c; b = p->blk[w.task[jb->first].blk].r; }
-      out[k++] = jb->kind; out[k++] = a; out[k++] = b; out[k++] = jb->first; out[k++] = jb->n; out[k++] = jb->sig[0]; out[k++] = jb->kind == 1 ? w.trsm[jb->first].chan : jb->sig[1]; out[k++] = jb->n_wait;
+      out[k++] = jb->kind; out[k++] = a; out[k++] = b; out[k++] = jb->first; out[k++] = jb->n; out[k++] = jb->sig[0]; out[k++] = jb->kind == CHOL_JOB_TRSM ? w.trsm[jb->first].chan : jb->sig[1]; out[k++] = jb->n_wait;
     }
     for (int j = 0; j < g.n_job; j++)
       for (int q = 0; q < g.job[j].n_wait; q++) { out[k++] = j; out[k++] = g.wait[g.job[j].wait_first + q].ctr; out[k++] = g.wait[g.job[j].wait_first + q].value; }
@@ -1856,7 +1961,7 @@ int64_t cholamd_plan_program_followers(const cholamd_plan *p, int64_t cap, int *
   int64_t n = 0;
   for (int j = 0; j < g.n_job; j++) {
     const chol_job *jb = &g.job[j];
-    if (jb->kind != 0 || jb->n_ext <= 0) continue;
+    if (jb->kind != CHOL_JOB_POTRF || jb->n_ext <= 0) continue;
     if (4 * n + 3 < cap) { out[4 * n] = j; out[4 * n + 1] = jb->n_ext; out[4 * n + 2] = (w.potrf[jb->first].n + CHOL_NB - 1) / CHOL_NB; out[4 * n + 3] = jb->n_wait; }
     n++;
   }
@@ -1878,7 +1983,7 @@ int64_t cholamd_plan_program_follow_own(const cholamd_plan *p, int follow_tail, 
   int64_t n = 0;
   for (int j = 0; j < g.n_job; j++) {
     const chol_job *jb = &g.job[j];
-    if (jb->kind != 0 || jb->n_ext <= 0) continue;
+    if (jb->kind != CHOL_JOB_POTRF || jb->n_ext <= 0) continue;
     if (5 * n + 4 < cap) { out[5 * n] = j; out[5 * n + 1] = jb->n_ext; out[5 * n + 2] = (w.potrf[jb->first].n + CHOL_NB - 1) / CHOL_NB; out[5 * n + 3] = jb->mode; out[5 * n + 4] = jb->n_wait; }
     n++;
   }
@@ -1914,8 +2019,8 @@ int cholamd_plan_program_hazards(const cholamd_plan *p, int follow_tail, int fol
 #define HZ_SIG(C_, J_, ADD_) do { if (pass) { hz_sig s_ = { J_, ADD_ }; sg[first[C_] + ns[C_]] = s_; } ns[C_]++; } while (0)
     for (int j = 0; j < nj; j++) {
       const chol_job *jb = &g.job[j];
-      if (jb->kind == 0) HZ_SIG(w.potrf[jb->first].ctr, j, g.ctr_total[w.potrf[jb->first].ctr]);
-      if (jb->kind == 1)
+      if (jb->kind == CHOL_JOB_POTRF) HZ_SIG(w.potrf[jb->first].ctr, j, g.ctr_total[w.potrf[jb->first].ctr]);
+      if (jb->kind == CHOL_JOB_TRSM)
         for (int t = 0; t < (w.trsm[jb->first].n + CHOL_NB - 1) / CHOL_NB; t++) { /* the strips of a job share pivot block and channel */
           int add = 0;
           for (int i = jb->first; i < jb->first + jb->n; i++) add += w.trsm[i].chan >= 0 && w.trsm[i].m > 0;
@@ -1927,16 +2032,16 @@ int cholamd_plan_program_hazards(const cholamd_plan *p, int follow_tail, int fol
   }
   /* every wait of every job, the implied ones included: a strip job's for its pivot block's POTRF job, a follower's for its items */
   int nwt = 0;
-  for (int j = 0; j < nj; j++) nwt += g.job[j].n_wait + (g.job[j].kind == 0 ? g.job[j].n_ext : g.job[j].kind == 1 ? 1 : 0);
+  for (int j = 0; j < nj; j++) nwt += g.job[j].n_wait + (g.job[j].kind == CHOL_JOB_POTRF ? g.job[j].n_ext : g.job[j].kind == CHOL_JOB_TRSM ? 1 : 0);
   typedef struct { int job, ctr, value, gating; } hz_wait;
   hz_wait *wt = malloc((nwt + 1) * sizeof(hz_wait));
   int *nwc = calloc(g.n_ctr + 1, sizeof(int)), *wfirst = calloc(g.n_ctr + 2, sizeof(int)), *wof = malloc((nwt + 1) * sizeof(int));
   nwt = 0;
   for (int j = 0; j < nj; j++) {
     const chol_job *jb = &g.job[j];
-    for (int q = 0; q < jb->n_wait; q++) { hz_wait x = { j, g.wait[jb->wait_first + q].ctr, g.wait[jb->wait_first + q].value, jb->kind != 2 || q < jb->n_pre }; wt[nwt++] = x; }
-    if (jb->kind == 0) for (int q = 0; q < jb->n_ext; q++) { hz_wait x = { j, g.ext[jb->ext_first + q].ctr, g.ext[jb->ext_first + q].need, 1 }; wt[nwt++] = x; }
-    if (jb->kind == 1) { hz_wait x = { j, w.trsm[jb->first].flag, 1, 1 }; wt[nwt++] = x; }
+    for (int q = 0; q < jb->n_wait; q++) { hz_wait x = { j, g.wait[jb->wait_first + q].ctr, g.wait[jb->wait_first + q].value, jb->kind != CHOL_JOB_UPDATE || q < jb->n_pre }; wt[nwt++] = x; }
+    if (jb->kind == CHOL_JOB_POTRF) for (int q = 0; q < jb->n_ext; q++) { hz_wait x = { j, g.ext[jb->ext_first + q].ctr, g.ext[jb->ext_first + q].need, 1 }; wt[nwt++] = x; }
+    if (jb->kind == CHOL_JOB_TRSM) { hz_wait x = { j, w.trsm[jb->first].flag, 1, 1 }; wt[nwt++] = x; }
   }
   for (int i = 0; i < nwt; i++) nwc[wt[i].ctr]++;
   for (int c = 0; c < g.n_ctr; c++) { wfirst[c + 1] = wfirst[c] + nwc[c]; nwc[c] = 0; }
@@ -1984,7 +2089,7 @@ int cholamd_plan_program_hazards(const cholamd_plan *p, int follow_tail, int fol
   out[0] = out[1] = 0; out[2] = out[3] = -1;
   for (int j = 0; j < nj; j++) {
     const chol_job *jb = &g.job[j];
-    if (jb->kind != 2) continue;
+    if (jb->kind != CHOL_JOB_UPDATE) continue;
     for (int t = jb->first; t < jb->first + jb->n; t++) {
       const chol_upd_task *tk = &w.task[t];
       for (int col = 0; col < tk->nv; col++)
@@ -2014,7 +2119,7 @@ int cholamd_plan_program_counts(const cholamd_plan *p, int follow, int out[6])
   int rc = chol_build_program(p, &o, &w, &g);
   if (rc) return rc;
   int nf = 0;
-  for (int j = 0; j < g.n_job; j++) nf += g.job[j].kind == 0 && g.job[j].n_ext > 0;
+  for (int j = 0; j < g.n_job; j++) nf += g.job[j].kind == CHOL_JOB_POTRF && g.job[j].n_ext > 0;
   out[0] = g.n_job; out[1] = nf; out[2] = w.n_task; out[3] = w.n_trsm; out[4] = g.n_ctr; out[5] = g.n_ext;
   chol_level_work_free(&w); chol_program_free(&g);
   return 0;
@@ -2049,7 +2154,7 @@ static int level_work_volume(const cholamd_plan *p, const chol_sched_opts *o, in
   out[3] = w.n_bcast;
   for (int i = 0; i < w.n_bcast; i++) { out[4] += w.bcast[i].count; out[5] = (int64_t)((uint64_t)out[5] * 1000003u + (uint64_t)w.bcast[i].off * 31u + (uint64_t)w.bcast[i].owner + 7u * (uint64_t)w.bcast[i].count); /* a hash of the sequence: wraps (unsigned) */ }
   int nb6 = 0;
-  for (int i = 0; i < w.n_phase; i++) if (w.phase[i].kind == 6) nb6 += w.phase[i].n;
+  for (int i = 0; i < w.n_phase; i++) if (w.phase[i].kind == CHOL_PH_BCAST) nb6 += w.phase[i].n;
   if (nb6 != w.n_bcast) { chol_set_error("internal: %d broadcast entries, %d in phases", w.n_bcast, nb6); rc = CHOLAMD_ERR_ARG; }
   chol_level_work_free(&w);
   return rc;
@@ -2170,7 +2275,7 @@ int cholamd_plan_level_mt_fill(const cholamd_plan *p, int level, int64_t out[4])
   out[0] = w.n_task_mt; out[1] = out[2] = out[3] = 0;
   if (getenv("CHOLAMD_PRINT_PHASES"))
     for (int i = 0; i < w.n_phase; i++)
-      if (w.phase[i].kind == 3) {
+      if (w.phase[i].kind == CHOL_PH_UPDATE_MT) {
         double work = 0; int64_t nsrc = 0, kmax = 0;
         for (int q = w.phase[i].first; q < w.phase[i].first + w.phase[i].n; q++) {
           const chol_upd_task *t = &w.task_mt[q];
