@@ -13,10 +13,10 @@ HIPFLAGS:= -O3 -fPIC --offload-arch=$(ARCH) -Iinclude -I$(CSRC) -Wall
 # without it the two k_solve_inv256 instances come out as different, shorter code
 $(OUT)/chol_kernels.o $(OUT)/chol_solve.o: KERNFLAGS := -mllvm -pragma-unroll-threshold=100000
 
-HOST_OBJS := $(OUT)/chol_ingest.o $(OUT)/chol_symbolic.o $(OUT)/chol_schedule.o $(OUT)/chol_lists.o $(OUT)/chol_generate.o $(OUT)/chol_lowrank_host.o
-KERNEL_OBJS := $(OUT)/chol_kernels.o $(OUT)/chol_solve.o $(OUT)/chol_kernels_f32.o $(OUT)/chol_solve_nrhs.o $(OUT)/chol_factor_query.o $(OUT)/chol_selinv.o $(OUT)/chol_schur.o $(OUT)/chol_multiply.o $(OUT)/chol_multiply_nrhs.o $(OUT)/chol_solve_det.o $(OUT)/chol_lowrank.o $(OUT)/chol_values_grad.o $(OUT)/chol_pcg.o
+HOST_OBJS := $(OUT)/chol_ingest.o $(OUT)/chol_symbolic.o $(OUT)/chol_schedule.o $(OUT)/chol_lists.o $(OUT)/chol_generate.o $(OUT)/chol_lowrank_host.o $(OUT)/chol_lists_sparse.o
+KERNEL_OBJS := $(OUT)/chol_kernels.o $(OUT)/chol_solve.o $(OUT)/chol_kernels_f32.o $(OUT)/chol_solve_nrhs.o $(OUT)/chol_factor_query.o $(OUT)/chol_selinv.o $(OUT)/chol_schur.o $(OUT)/chol_multiply.o $(OUT)/chol_multiply_nrhs.o $(OUT)/chol_solve_det.o $(OUT)/chol_lowrank.o $(OUT)/chol_values_grad.o $(OUT)/chol_pcg.o $(OUT)/chol_sparse.o
 # the C-ABI glue: one file per family of entry points over the internal header chol_device.h
-GLUE      := chol_api chol_api_schur chol_api_blas chol_api_lowrank
+GLUE      := chol_api chol_api_schur chol_api_blas chol_api_lowrank chol_api_sparse
 GLUE_HDRS := $(CSRC)/chol_device.h $(CSRC)/chol_devbuf.h $(CSRC)/chol_plan.h $(CSRC)/chol_kernels.h include/cholamd.h
 GLUE_OBJS := $(GLUE:%=$(OUT)/%.o)
 HIP_OBJS  := $(KERNEL_OBJS) $(GLUE_OBJS)
@@ -57,7 +57,7 @@ clean:
 # cholesky_amd/lib/asan/libcholamd.so and runs the CPU test-suite of the host logic against it.
 ASAN_OUT := cholesky_amd/lib/asan
 SAN := -fsanitize=address,undefined -fno-omit-frame-pointer -g
-ASAN_HOST_OBJS := $(ASAN_OUT)/chol_ingest.o $(ASAN_OUT)/chol_symbolic.o $(ASAN_OUT)/chol_schedule.o $(ASAN_OUT)/chol_lists.o $(ASAN_OUT)/chol_generate.o $(ASAN_OUT)/chol_lowrank_host.o
+ASAN_HOST_OBJS := $(ASAN_OUT)/chol_ingest.o $(ASAN_OUT)/chol_symbolic.o $(ASAN_OUT)/chol_schedule.o $(ASAN_OUT)/chol_lists.o $(ASAN_OUT)/chol_generate.o $(ASAN_OUT)/chol_lowrank_host.o $(ASAN_OUT)/chol_lists_sparse.o
 $(ASAN_OUT)/%.o: $(CSRC)/%.c $(CSRC)/chol_plan.h include/cholamd.h
 	@mkdir -p $(ASAN_OUT)
 	$(CC) $(CFLAGS) -O1 $(SAN) -c $< -o $@
@@ -72,7 +72,7 @@ $(ASAN_OUT)/libcholamd.so: $(ASAN_HOST_OBJS) $(GLUE:%=$(ASAN_OUT)/%.o) $(KERNEL_
 # frame, hide) the library's, so that run keeps detect_leaks=0.
 G := tests/golden
 # every tests/native/*.c program links against the sanitized library in the same way
-NATIVE_PROGS := host_leak schur_host multiply_host multiply_nrhs_host solve_det_host solve_det_nrhs_host schur_solve_host lowrank_host values_grad_host pcg_host
+NATIVE_PROGS := host_leak schur_host multiply_host multiply_nrhs_host solve_det_host solve_det_nrhs_host schur_solve_host lowrank_host values_grad_host pcg_host sparse_solve_host
 $(NATIVE_PROGS:%=$(ASAN_OUT)/%): $(ASAN_OUT)/%: tests/native/%.c $(ASAN_OUT)/libcholamd.so
 	$(HIPCC) -x c -O1 -Iinclude $(SAN) -fno-sanitize=function -o $@ $< -L$(ASAN_OUT) -lcholamd -Wl,-rpath,$(abspath $(ASAN_OUT)) -lm
 # the owning device buffers of the glue over a host allocator that can be told to fail (tests/native/devbuf_host.cpp): no library, no HIP runtime
@@ -126,3 +126,9 @@ pcg_host: $(ASAN_OUT)/pcg_host
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 LSAN_OPTIONS=suppressions=$(abspath scripts/lsan.supp):print_suppressions=0 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
 	$(ASAN_OUT)/pcg_host
 .PHONY: pcg_host
+# the pruned step lists of the sparse solve and their host walk (chol_lists_sparse.c) under the sanitizers, in a process of its own
+# (tests/native/sparse_solve_host.c: it generates its input): `make sparse_solve_host` builds and runs this program alone
+sparse_solve_host: $(ASAN_OUT)/sparse_solve_host
+	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 LSAN_OPTIONS=suppressions=$(abspath scripts/lsan.supp):print_suppressions=0 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 \
+	$(ASAN_OUT)/sparse_solve_host
+.PHONY: sparse_solve_host

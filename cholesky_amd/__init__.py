@@ -10,7 +10,8 @@ from ._lib import CholamdError, Filled, Op, Region, load  # noqa: F401
 from .plan import Plan, Problem  # noqa: F401
 from .device import HALF_BACKWARD, HALF_FORWARD, Comm, Device  # noqa: F401
 from .lowrank import LowRank  # noqa: F401
+from .sparse import SparseSolve  # noqa: F401
 from .autograd import Factorization, factorize  # noqa: F401
 from . import blas  # noqa: F401
 
-__all__ = ["Plan", "Problem", "Device", "Comm", "LowRank", "Factorization", "factorize", "blas", "CholamdError", "Filled", "Op", "Region", "load", "HALF_FORWARD", "HALF_BACKWARD"]
+__all__ = ["Plan", "Problem", "Device", "Comm", "LowRank", "SparseSolve", "Factorization", "factorize", "blas", "CholamdError", "Filled", "Op", "Region", "load", "HALF_FORWARD", "HALF_BACKWARD"]

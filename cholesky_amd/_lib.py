@@ -277,6 +277,15 @@ def load():
     L.cholamd_lowrank_slabs.argtypes = [i64, vp, i64]
     L.cholamd_lowrank_tprod_host.argtypes = [i64, ci, ci, vp, i64, vp, i64, vp, i64]
     L.cholamd_lowrank_rprod_host.argtypes = [i64, ci, ci, cd, cd, vp, i64, vp, i64, vp, i64]
+    L.cholamd_sparse_create.argtypes = [vp, vp, ci, vp, ci, C.POINTER(vp)]
+    L.cholamd_sparse_destroy.argtypes = [vp]
+    L.cholamd_sparse_destroy.restype = None
+    L.cholamd_sparse_counts.argtypes = [vp, vp]
+    L.cholamd_sparse_solve_nrhs.argtypes = [vp, vp, vp, i64, vp, i64, ci, ci, vp]
+    L.cholamd_sparse_solve_nrhs_f32.argtypes = [vp, vp, vp, i64, vp, i64, ci, ci, vp]
+    L.cholamd_plan_sparse_solve_host_nrhs.argtypes = [vp, vp, vp, ci, vp, ci, ci, vp, i64, vp, i64, ci]
+    L.cholamd_plan_sparse_counts.argtypes = [vp, vp, ci, vp, ci, vp]
+    L.cholamd_plan_sparse_lists.argtypes = [vp, vp, ci, vp, ci, ci, vp, vp, vp]
     _lib = L
     return L
 

@@ -106,6 +106,11 @@ template <class TL> int chol_launch_solve_span(const TL *base, const chol_trsv_d
  * alone, plain stores */
 template <class TL> int chol_launch_solve_det_gather_nrhs(const TL *base, const chol_mul_item *items, int n_items, const chol_mul_src *srcs, int backward, double *Yp, hipStream_t st);
 template <class TL> int chol_nrhs_launch_span(const TL *base, const chol_trsv_desc *descs, int n_descs, const double *W16, double *Y, int col0, int backward, hipStream_t st);
+/* sparse solves (chol_sparse.hip): a chunk's way into and out of the ACTIVE rows of the permuted row-major block Y.  load: row r of the list, position
+ * act_pos[r], takes the chunk's columns of row act_in[r] of Bs (column-major, ldb) or, act_in[r] < 0, zeros; all 32 columns of each of the n_pos rows are
+ * written, no other row of Y is touched.  store: Xs[i + (c0 + j) ldx] = Y[pos_out[i] 32 + j], j < cols */
+int chol_launch_sparse_load(const double *Bs, int64_t ldb, const int *act_pos, const int *act_in, int64_t n_pos, int c0, int cols, double *Y, hipStream_t st);
+int chol_launch_sparse_store(const double *Y, const int *pos_out, int64_t n_out, double *Xs, int64_t ldx, int c0, int cols, hipStream_t st);
 /* block form (chol_multiply_nrhs.hip): the same items on a chunk of CHOL_NRHS_W columns, Zp the permuted row-major block of chol_nrhs_launch_permute.
  * perm != NULL (the last stage of a call): Y[perm[pos] + (c0 + j) ldy] for the chunk's columns j < cols; perm == NULL (the first stage of the full product):
  * Y is a second permuted block, all 32 columns written */

@@ -996,57 +996,64 @@ int cholamd_plan_solve_det_host(const cholamd_plan *p, const double *arena_host,
  * order and subtracted from the owner's value.  A span is solved by substitution inside its own lower triangle, column by column of the block, as
  * sdet_host_sweep does (the device's span kernel sums in another order: the host walk does not return the device's bits).  Every column of the block
  * goes through its own scalar operations: no column's result depends on another's. */
-static void sdet_host_block_sweep(const plan_t *p, const chol_sdet_lists *w, int which, const double *arena, double *yp)
+void chol_sdet_host_block_gather(const chol_sdet_lists *w, int which, const chol_sdet_step *st, const double *arena, double *yp)
 {
   enum { T = CHOL_MUL_TILE, W = 32 };
   double acc[CHOL_MULN_WAVES][T][W];
+  for (int i = st->item_first; i < st->item_end; i++) {
+    const chol_mul_item *it = &w->item[which][i];
+    memset(acc, 0, sizeof acc);
+    for (int s = it->src_first; s < it->src_end; s++) {
+      const chol_mul_src *q = &w->src[which][s];
+      for (int c = 0; c * CHOL_MULN_KSTEP < q->len; c++) {
+        double (*a)[W] = acc[chol_muln_wave(s - it->src_first, c)];
+        for (int k = c * CHOL_MULN_KSTEP; k < (c + 1) * CHOL_MULN_KSTEP; k++)
+          for (int l = 0; l < T; l++) {
+            int meant;
+            const double v = arena[chol_muln_elem(q, which, it->nv, l, k, &meant)]; /* read whether meant or not: the clamp keeps it inside the strip */
+            if (!meant) continue;
+            const double *zr = yp + (int64_t)(q->z_off + k) * W;
+            for (int j = 0; j < W; j++) a[l][j] += v * zr[j];
+          }
+      }
+    }
+    for (int l = 0; l < it->nv; l++)
+      for (int j = 0; j < W; j++) {
+        double sum = acc[0][l][j];
+        for (int wv = 1; wv < CHOL_MULN_WAVES; wv++) sum += acc[wv][l][j];
+        yp[(int64_t)(it->y_off + l) * W + j] -= sum;
+      }
+  }
+}
+void chol_sdet_host_block_span(const plan_t *p, int s, int col0, int which, const double *arena, double *yp)
+{
+  enum { W = 32 };
+  const int n = p->sep_size[s], ld = p->panel_ld[s];
+  if (n <= col0) return;
+  const int n1 = n < col0 + CHOL_SDET_SPAN ? n : col0 + CHOL_SDET_SPAN;
+  const double *Lm = arena + p->panel_off[s];
+  double *x = yp + (int64_t)p->sep_off[s] * W;
+  for (int c = 0; c < W; c++)
+    if (which == CHOLAMD_HALF_FORWARD)
+      for (int i = col0; i < n1; i++) {
+        double v = x[(int64_t)i * W + c];
+        for (int j = col0; j < i; j++) v -= Lm[i + (int64_t)j * ld] * x[(int64_t)j * W + c];
+        x[(int64_t)i * W + c] = v / Lm[i + (int64_t)i * ld];
+      }
+    else
+      for (int i = n1 - 1; i >= col0; i--) {
+        double v = x[(int64_t)i * W + c];
+        for (int j = i + 1; j < n1; j++) v -= Lm[j + (int64_t)i * ld] * x[(int64_t)j * W + c];
+        x[(int64_t)i * W + c] = v / Lm[i + (int64_t)i * ld];
+      }
+}
+static void sdet_host_block_sweep(const plan_t *p, const chol_sdet_lists *w, int which, const double *arena, double *yp)
+{
   for (int t = 0; t < w->n_step[which]; t++) {
     const chol_sdet_step *st = &w->step[which][t];
-    for (int i = st->item_first; i < st->item_end; i++) {
-      const chol_mul_item *it = &w->item[which][i];
-      memset(acc, 0, sizeof acc);
-      for (int s = it->src_first; s < it->src_end; s++) {
-        const chol_mul_src *q = &w->src[which][s];
-        for (int c = 0; c * CHOL_MULN_KSTEP < q->len; c++) {
-          double (*a)[W] = acc[chol_muln_wave(s - it->src_first, c)];
-          for (int k = c * CHOL_MULN_KSTEP; k < (c + 1) * CHOL_MULN_KSTEP; k++)
-            for (int l = 0; l < T; l++) {
-              int meant;
-              const double v = arena[chol_muln_elem(q, which, it->nv, l, k, &meant)]; /* read whether meant or not: the clamp keeps it inside the strip */
-              if (!meant) continue;
-              const double *zr = yp + (int64_t)(q->z_off + k) * W;
-              for (int j = 0; j < W; j++) a[l][j] += v * zr[j];
-            }
-        }
-      }
-      for (int l = 0; l < it->nv; l++)
-        for (int j = 0; j < W; j++) {
-          double sum = acc[0][l][j];
-          for (int wv = 1; wv < CHOL_MULN_WAVES; wv++) sum += acc[wv][l][j];
-          yp[(int64_t)(it->y_off + l) * W + j] -= sum;
-        }
-    }
+    chol_sdet_host_block_gather(w, which, st, arena, yp);
     if (st->col0 < 0) continue; /* the level's outside gather: no span */
-    for (int h = 1 << st->level; h < (1 << (st->level + 1)) && h <= p->nsep; h++) {
-      const int s = p->tree[h], n = p->sep_size[s], ld = p->panel_ld[s];
-      if (n <= st->col0) continue;
-      const int n1 = n < st->col0 + CHOL_SDET_SPAN ? n : st->col0 + CHOL_SDET_SPAN;
-      const double *Lm = arena + p->panel_off[s];
-      double *x = yp + (int64_t)p->sep_off[s] * W;
-      for (int c = 0; c < W; c++)
-        if (which == CHOLAMD_HALF_FORWARD)
-          for (int i = st->col0; i < n1; i++) {
-            double v = x[(int64_t)i * W + c];
-            for (int j = st->col0; j < i; j++) v -= Lm[i + (int64_t)j * ld] * x[(int64_t)j * W + c];
-            x[(int64_t)i * W + c] = v / Lm[i + (int64_t)i * ld];
-          }
-        else
-          for (int i = n1 - 1; i >= st->col0; i--) {
-            double v = x[(int64_t)i * W + c];
-            for (int j = i + 1; j < n1; j++) v -= Lm[j + (int64_t)i * ld] * x[(int64_t)j * W + c];
-            x[(int64_t)i * W + c] = v / Lm[i + (int64_t)i * ld];
-          }
-    }
+    for (int h = 1 << st->level; h < (1 << (st->level + 1)) && h <= p->nsep; h++) chol_sdet_host_block_span(p, p->tree[h], st->col0, which, arena, yp);
   }
 }
 int cholamd_plan_solve_det_host_nrhs(const cholamd_plan *p, const double *arena_host, int which, const double *B, int64_t ldb, double *X, int64_t ldx, int nrhs)

@@ -525,6 +525,34 @@ void chol_sdet_lists_free(chol_sdet_lists *w);
  * the steps of the levels levels - 1 .. k and one KEPT LEAD step (level = -1, col0 = -1: the lead-step sources of the kept chunks that read positions under
  * the cut), BACKWARD the steps of the levels k .. levels - 1.  Checks its own invariants as chol_build_solve_det does. */
 int chol_build_schur_det(const struct cholamd_plan *p, int k, chol_sdet_lists *out);
+/* The same lists PRUNED to a set of separators per direction for the sparse solve (cholamd_sparse_*; chol_lists_sparse.c).  act_fw / act_bw
+ * are indexed by separator label (1 .. nsep) and closed under "parent" (chol_sparse_masks closes them).  Derived from the full lists, in their order:
+ *   FORWARD   an item stays iff the separator of its y_off is in act_fw, a source of it iff the separator of its z_off is (a dropped source multiplies
+ *             positions that are exactly zero); an item left without sources goes
+ *   BACKWARD  an item stays iff its separator is in act_bw; its sources lie in ancestors, hence in act_bw (checked)
+ *   a span step (col0 >= 0) stays iff an active separator of its level is wider than col0, with or without items; a lead step stays iff it has items -- or had
+ *   none in the full lists either and its level holds an active separator (it launches nothing; with both masks all ones the output is the full lists)
+ * trsv[q]: the chol_trsv_desc of the active separators (q = 0, 1: of the direction; 2: of the union, the 16x16 inverses of a whole solve), level by level in
+ * the order of chol_solve_level.trsv: level l = [lvl_first[q][l], lvl_first[q][l + 1]), the widest of them lvl_max_n[q][l] columns.  range: the positions of
+ * the union's separators as n_range ascending (pos0, len) pairs, neighbours merged; n_pos of them in all.  Checks its own invariants (CHOLAMD_ERR_INVARIANT):
+ * over a sweep every active position is solved exactly once, no source reads a position that is inactive for its direction or not solved yet, no item owns
+ * an inactive position, every source strip lies inside the arena. */
+typedef struct {
+  chol_sdet_lists w;
+  int n_act[3]; chol_trsv_desc *trsv[3]; int *lvl_first[3], *lvl_max_n[3];
+  int n_range; int *range; int64_t n_pos;
+} chol_sparse_lists;
+int chol_build_sparse_det(const struct cholamd_plan *p, const unsigned char *act_fw, const unsigned char *act_bw, chol_sparse_lists *out);
+void chol_sparse_lists_free(chol_sparse_lists *w);
+void chol_sparse_counts(const struct cholamd_plan *p, const chol_sparse_lists *w, int64_t out[12]); /* the layout of cholamd_plan_sparse_counts */
+/* the masks of a pair of dof lists (original order): act_fw = up(in), act_bw = up(out), nsep + 1 bytes each; pos_in / pos_out (may be NULL): the dofs'
+ * permuted positions.  CHOLAMD_ERR_ARG with the first offender named: a NULL, a count < 1, a dof outside [0, n), a duplicate inside either list */
+int chol_sparse_masks(const struct cholamd_plan *p, const char *what, const int *in_dofs, int n_in, const int *out_dofs, int n_out, unsigned char *act_fw, unsigned char *act_bw,
+                      int *pos_in, int *pos_out);
+/* the two halves of a step of the block host walk (chol_lists.c at sdet_host_block_sweep): the gather of the step's items with the kernel's partition, and
+ * the substitution inside the span [col0, col0 + CHOL_SDET_SPAN) of ONE separator; yp = the permuted row-major block (n x 32) */
+void chol_sdet_host_block_gather(const chol_sdet_lists *w, int which, const chol_sdet_step *st, const double *arena, double *yp);
+void chol_sdet_host_block_span(const struct cholamd_plan *p, int sep, int col0, int which, const double *arena, double *yp);
 
 /* ---- block form of the products (cholamd_multiply_half_nrhs; chol_multiply_nrhs.hip): the same items and sources on a chunk of 32 columns.  The reduction
  * range of a source is cut into CHUNKS of CHOL_MULN_KSTEP steps; chunk c of the s-th source of an item (s counted from the item's first) belongs to wave

@@ -17,6 +17,10 @@
  *        --lowrank FILE K [--lowrank-mode update|downdate|constraint] (FILE: a Matrix-Market dense `array` n x K, the columns of U; after the factorisation
  *        cholamd_lowrank_set on device 0; the solve of -b becomes the corrected solve of A + U U^T (update, the default), A - U U^T (downdate) or of A under
  *        U^T x = 0 (constraint); with --logdet one more line "logdet C: %.17g" after the logdet line: log det(A +- U U^T) = logdet + logdet C; fp64 only),
+ *        --inverse-block DOFS.txt FILE (DOFS.txt: one 0-based dof per line, m of them; after the factorisation the block A^-1[S, S] of those dofs by a sparse
+ *        solve of the identity -- cholamd_sparse_create + cholamd_sparse_solve_nrhs: the sweeps touch the separators of the dofs and their ancestors only --
+ *        written dense in write_matrix's format: the banner, "m m m*m", then "i j value" lines, 1-based indices into the list, row by row, %0.8g or %.17g
+ *        under --full-precision; fp64 factor only),
  *        --pcg (needs -b: the solve of either --precision goes through cholamd_solve_pcg / _f32 -- conjugate gradients preconditioned with the factor, 30
  *        iterations, 1e-14 -- and one stderr line "[cholamd] pcg: %d iterations, ||b - A x|| / ||b|| = %.3e", and one more with the status where that is not 0; not with --lowrank or --gpus > 1).
  * Unknown flags (the reference passes -fflow/-ll:cpu/-fcuda/-ll:csize through to Legion) are ignored.
@@ -43,7 +47,7 @@ static double now_s(void)
 int main(int argc, char **argv)
 {
   const char *matrix_file = "", *separator_file = "", *clusters_file = "", *b_file = "", *solution_file = "", *factor_file = "",
-             *permuted_file = "", *debug_path = "", *invdiag_file = "", *schur_file = "", *lowrank_file = "", *lowrank_mode = "update";
+             *permuted_file = "", *debug_path = "", *invdiag_file = "", *invblock_dofs = "", *invblock_file = "", *schur_file = "", *lowrank_file = "", *lowrank_mode = "update";
   int debug = 0, iterations = 1, gpu = 0, full = 0, gpus = 1, want_logdet = 0, want_check = 0, schur_k = 0, det_solve = 0, lowrank_k = 0, pcg = 0;
   const char *precision = "fp64";
   for (int i = 0; i < argc; i++) {
@@ -67,6 +71,7 @@ int main(int argc, char **argv)
     else if (!strcmp(argv[i], "--deterministic-solve")) det_solve = 1; /* device option solve_deterministic for the solve of -b: the same bits in every run */
     else if (!strcmp(argv[i], "--pcg")) pcg = 1;
     else if (!strcmp(argv[i], "--invdiag")) invdiag_file = next;
+    else if (!strcmp(argv[i], "--inverse-block")) { invblock_dofs = next; invblock_file = i + 2 < argc ? argv[i + 2] : ""; if (!*invblock_dofs || !*invblock_file) DIE("--inverse-block DOFS.txt FILE"); }
     else if (!strcmp(argv[i], "--schur")) { schur_k = atoi(next); schur_file = i + 2 < argc ? argv[i + 2] : ""; if (!*schur_file) DIE("--schur K FILE"); }
     else if (!strcmp(argv[i], "--lowrank")) { lowrank_file = next; lowrank_k = i + 2 < argc ? atoi(argv[i + 2]) : 0; if (!*lowrank_file || lowrank_k < 1) DIE("--lowrank FILE K"); }
     else if (!strcmp(argv[i], "--lowrank-mode")) lowrank_mode = next;
@@ -103,6 +108,18 @@ int main(int argc, char **argv)
   if (mixed && gpus > 1) DIE("--precision mixed is a single-GPU path");
   if (want_check && !*b_file) DIE("--check takes the right-hand side as its probe: it needs -b");
   if (mixed && *invdiag_file) DIE("--invdiag needs the fp64 factor (--precision fp64)");
+  if (mixed && *invblock_file) DIE("--inverse-block needs the fp64 factor (--precision fp64)");
+  int *invblock_list = NULL, invblock_m = 0;
+  if (*invblock_file) { /* the list is read before any device work; the library names a dof that is out of range or listed twice */
+    FILE *fd = fopen(invblock_dofs, "r");
+    if (!fd) DIE("cannot read %s", invblock_dofs);
+    int v = 0, more = 0;
+    invblock_list = malloc((size_t)(n > 0 ? n : 1) * sizeof(int));
+    if (!invblock_list) DIE("out of memory");
+    while (fscanf(fd, "%d", &v) == 1) { if (invblock_m < n) invblock_list[invblock_m++] = v; else more = 1; }
+    fclose(fd);
+    if (invblock_m < 1 || more) DIE("--inverse-block: %s holds %s", invblock_dofs, more ? "more dofs than the matrix has" : "no dof");
+  }
   if (*schur_file && (mixed || gpus > 1)) DIE("--schur is a single-GPU fp64 path");
   if (*schur_file && cholamd_plan_schur_size(plan, schur_k) < 0) DIE("--schur: %s", cholamd_last_error());
   const int lr_mode = !strcmp(lowrank_mode, "update") ? CHOLAMD_LOWRANK_UPDATE : !strcmp(lowrank_mode, "downdate") ? CHOLAMD_LOWRANK_DOWNDATE : CHOLAMD_LOWRANK_CONSTRAINT;
@@ -198,6 +215,28 @@ int main(int argc, char **argv)
     if (cholamd_write_solution(invdiag_file, diag, n, full)) DIE("%s", cholamd_last_error());
     cholamd_device_free(dev, d_z); cholamd_device_free(dev, d_diag);
     free(diag);
+  }
+  if (*invblock_file) { /* the complete factor is on device 0; the identity is solved in place */
+    const int m = invblock_m;
+    int *dofs = invblock_list;
+    const int64_t mm = (int64_t)m * m;
+    double *Z = calloc((size_t)mm, sizeof(double)), *d_Z = NULL;
+    if (!Z) DIE("out of memory");
+    for (int i = 0; i < m; i++) Z[i + (size_t)i * m] = 1.0;
+    cholamd_sparse *sp = NULL;
+    if (cholamd_sparse_create(dev, dofs, m, dofs, m, &sp)) DIE("inverse-block: %s", cholamd_last_error());
+    if (cholamd_device_alloc(dev, mm, &d_Z) || cholamd_device_upload(dev, d_Z, Z, mm, NULL)) DIE("%s", cholamd_last_error());
+    if (cholamd_sparse_solve_nrhs(sp, d_arena, d_Z, m, d_Z, m, m, -1, NULL) || cholamd_device_download(dev, Z, d_Z, mm, NULL)) DIE("inverse-block: %s", cholamd_last_error());
+    printf("Saving inverse block (%d dofs) to: %s\n", m, invblock_file);
+    FILE *fz = fopen(invblock_file, "w");
+    if (!fz) DIE("cannot write %s", invblock_file);
+    fprintf(fz, "%%%%MatrixMarket matrix coordinate real general\n%d %d %lld\n", m, m, (long long)mm);
+    for (int i = 0; i < m; i++)
+      for (int j = 0; j < m; j++) fprintf(fz, full ? "%d %d %.17g\n" : "%d %d %0.8g\n", i + 1, j + 1, Z[i + (size_t)j * m]);
+    if (fclose(fz)) DIE("cannot write %s", invblock_file);
+    cholamd_sparse_destroy(sp);
+    cholamd_device_free(dev, d_Z);
+    free(Z); free(dofs);
   }
   if (*schur_file) { /* a second arena, filled again and eliminated down to level K only: its kept blocks hold S */
     const int m = cholamd_plan_schur_size(plan, schur_k);

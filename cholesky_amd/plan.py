@@ -527,6 +527,61 @@ class Plan:
         check(self.L.cholamd_plan_solve_det_lists(self.h, int(which), steps.ctypes.data, items.ctypes.data, srcs.ctypes.data), "cholamd_plan_solve_det_lists")
         return steps[:c["steps"]], items[:c["items"]], srcs[:c["sources"]]
 
+    @staticmethod
+    def _dofs(dofs, what):
+        """A dof list as the int32 array the library takes (not validated here: the library names the first offender)."""
+        a = np.ascontiguousarray(np.asarray(dofs).reshape(-1), dtype=np.int32)
+        if np.asarray(dofs).size and not np.array_equal(a, np.asarray(dofs).reshape(-1)):
+            raise ValueError(f"{what} must be integers that fit 32 bits")
+        return a
+
+    SPARSE_COUNT_KEYS = ("separators", "steps", "items", "sources", "entries")
+
+    @classmethod
+    def _sparse_counts_dict(cls, out):
+        c = {w: {k: int(out[5 * i + j]) for j, k in enumerate(cls.SPARSE_COUNT_KEYS)} for i, w in enumerate(("forward", "backward"))}
+        c["positions"], c["ranges"] = int(out[10]), int(out[11])
+        return c
+
+    def sparse_counts(self, in_dofs, out_dofs):
+        """Sizes of the step lists of the sparse solve pruned to up(in_dofs) (forward) and up(out_dofs) (backward) (cholamd_plan_sparse_counts): per
+        direction the active separators, steps, items, sources and entries of L read -- comparable with solve_det_counts -- and the active positions
+        of the union with the ranges they form."""
+        i, o = self._dofs(in_dofs, "in_dofs"), self._dofs(out_dofs, "out_dofs")
+        out = np.zeros(12, dtype=np.int64)
+        check(self.L.cholamd_plan_sparse_counts(self.h, i.ctypes.data, i.size, o.ctypes.data, o.size, out.ctypes.data), "cholamd_plan_sparse_counts")
+        return self._sparse_counts_dict(out)
+
+    def sparse_lists(self, in_dofs, out_dofs, which):
+        """The pruned lists of one direction (cholamd_plan_sparse_lists) in the formats of solve_det_lists."""
+        i, o = self._dofs(in_dofs, "in_dofs"), self._dofs(out_dofs, "out_dofs")
+        c = self.sparse_counts(i, o)["forward" if which == 0 else "backward"]
+        steps = np.zeros((max(c["steps"], 1), 4), dtype=np.int64)
+        items = np.zeros((max(c["items"], 1), 4), dtype=np.int64)
+        srcs = np.zeros((max(c["sources"], 1), 5), dtype=np.int64)
+        check(self.L.cholamd_plan_sparse_lists(self.h, i.ctypes.data, i.size, o.ctypes.data, o.size, int(which), steps.ctypes.data, items.ctypes.data, srcs.ctypes.data),
+              "cholamd_plan_sparse_lists")
+        return steps[:c["steps"]], items[:c["items"]], srcs[:c["sources"]]
+
+    def sparse_solve_host_nrhs(self, arena, in_dofs, out_dofs, which, Bs, ldb=None, ldx=None):
+        """Rows out_dofs of A^-1 b (which = -1), M^-1 b (0) or M^-T b (1) on the CPU for the columns of Bs (len(in_dofs) x k: b is Bs on in_dofs and zero
+        elsewhere) with the pruned step lists (cholamd_plan_sparse_solve_host_nrhs).  ldb / ldx: leading dimensions of the column-major copies handed
+        to the library (defaults: the row counts); the padding rows of the result are checked to be untouched.  Returns len(out_dofs) x k."""
+        arena = np.ascontiguousarray(arena, dtype=np.float64)
+        assert arena.size == self.arena_doubles
+        i, o = self._dofs(in_dofs, "in_dofs"), self._dofs(out_dofs, "out_dofs")
+        Bs = np.asarray(Bs, dtype=np.float64)
+        assert Bs.ndim == 2 and Bs.shape[0] == i.size
+        k = Bs.shape[1]
+        ldb, ldx = int(ldb or max(i.size, 1)), int(ldx or max(o.size, 1))
+        bb = np.full((max(k, 1), max(ldb, i.size, 1)), -3.0)     # row j of the buffer = column j of Bs
+        bb[:k, :i.size] = Bs.T
+        xb = np.full((max(k, 1), max(ldx, o.size, 1)), np.nan)
+        check(self.L.cholamd_plan_sparse_solve_host_nrhs(self.h, arena.ctypes.data, i.ctypes.data, i.size, o.ctypes.data, o.size, int(which), bb.ctypes.data, ldb,
+                                                         xb.ctypes.data, ldx, k), "cholamd_plan_sparse_solve_host_nrhs")
+        assert np.isnan(xb[:, o.size:]).all(), "rows n_out .. ldx - 1 of Xs were written"
+        return xb[:k, :o.size].T.copy()
+
     def arena_to_dense(self, arena):
         arena = np.ascontiguousarray(arena, dtype=np.float64)
         assert arena.size == self.arena_doubles

@@ -1069,6 +1069,47 @@ int  cholamd_lowrank_slabs(int64_t n, int64_t *first_row, int64_t cap);
 int  cholamd_lowrank_tprod_host(int64_t n, int k, int m, const double *P, int64_t ldp, const double *Q, int64_t ldq, double *T, int64_t ldt);
 int  cholamd_lowrank_rprod_host(int64_t n, int k, int m, double alpha, double beta, const double *V, int64_t ldv, const double *T, int64_t ldt, double *X, int64_t ldx);
 
+/* ---- sparse solves: a right-hand side that is non-zero on a few dofs, a solution wanted on a few dofs (CHOLMOD's solve2 with Bset / Xset; DESIGN.md
+ * section 19).  L^-1 P b is non-zero only on the separators that hold a non-zero of b and on their ancestors, up(in); x on a dof set needs the backward
+ * sweep only on the separators of those dofs and their ancestors, up(out).  The handle owns the step lists of the deterministic block solve PRUNED to these
+ * sets (steps, items and sources of the full lists, in their order; per level the descriptors of the active separators), built and uploaded at
+ * cholamd_sparse_create: a warm cholamd_sparse_solve_nrhs allocates nothing and only enqueues on `stream`.  The sweeps are the block kernels of option
+ * "solve_deterministic_block" on those lists; two small kernels (chol_sparse.hip) load and store the few rows.  NOTHING outside the active rows of the
+ * device object's permuted block, and no entry of the arena outside the listed strips and the active separators' diagonal blocks, is read or written.
+ * ARGUMENTS: dofs in original order, 0-based.  Bs is n_in x nrhs column-major, ldb >= n_in: row i is the value at in_dofs[i], b is zero everywhere else
+ * (an explicit 0.0 is fine; all columns share the pattern).  Xs is n_out x nrhs, ldx >= n_out: row i is x[out_dofs[i]].  which = -1: x = A^-1 b;
+ * CHOLAMD_HALF_FORWARD: M^-1 b -- the sweep runs on up(in), an output dof outside it is exactly +0.0; CHOLAMD_HALF_BACKWARD: M^-T b -- the sweep runs on
+ * up(out), an input dof outside it cannot reach a wanted output and does not.  The whole solve: up(in), then up(out).  nrhs = 0 returns 0 and touches nothing.
+ * REFUSED with CHOLAMD_ERR_ARG, the message naming the first offender, nothing written: a NULL; n_in < 1 or n_out < 1; a dof outside [0, n); a duplicate
+ * inside either list; ldb < n_in or ldx < n_out; nrhs < 0; a `which` other than the three; a device object that is another rank of a partition.
+ * The handle borrows the device object's permuted block and its workspace of 16x16 inverses: one stream of work per device object covers it.  It forms the
+ * inverses of its active separators at every call and does not read or change keep_inverses or any solve_* / schur_* option: it always takes the step
+ * kernels.  It needs the COMPLETE factor in the arena, as cholamd_solve_nrhs does, and refers to d: destroy it first.
+ * THE CONTRACT:
+ *  (a) the same bits from call to call, from one handle to another on the same dof lists, on a device object created under CHOLAMD_POISON=1, and whatever an
+ *      earlier call left in the device object's block;
+ *  (b) the bits of column j of Xs depend on the arena and on column j of Bs alone;
+ *  (c) with in_dofs = out_dofs = 0 .. n - 1 the bits of cholamd_solve_nrhs / cholamd_solve_half_nrhs under "solve_deterministic" + "solve_deterministic_block"
+ *      (the pruned lists are then the full ones, element for element);
+ *  (d) otherwise it agrees with those to rounding only: dropping sources moves the remaining ones between the four partial sums of a gather;
+ *  (e) rows n_in .. ldb - 1 of Bs, rows n_out .. ldx - 1 of Xs and columns >= nrhs are never read or written; Bs is not modified unless Xs aliases it, which
+ *      is allowed only with n_in == n_out and ldb == ldx.
+ * cholamd_sparse_counts / cholamd_plan_sparse_counts: out[5 d + 0 .. 4] = active separators, steps, items, sources and entries of L read of direction d
+ * (counted as cholamd_plan_solve_det_counts counts them), out[10] = active positions of up(in) | up(out), out[11] = the ranges they form.
+ * cholamd_plan_sparse_lists: the pruned lists of one direction in the row formats of cholamd_plan_solve_det_lists, sized by the counts.
+ * cholamd_plan_sparse_solve_host_nrhs: the same walk on the HOST over a host arena (the gather with the kernel's own partition, a span by substitution:
+ * deterministic, not the device's bits); rows of its block outside the active ranges hold NaN, so a read of one shows. */
+typedef struct cholamd_sparse cholamd_sparse;
+int  cholamd_sparse_create(cholamd_device *d, const int *in_dofs, int n_in, const int *out_dofs, int n_out, cholamd_sparse **out);
+void cholamd_sparse_destroy(cholamd_sparse *s);
+int  cholamd_sparse_counts(const cholamd_sparse *s, int64_t out[12]);
+int  cholamd_sparse_solve_nrhs(cholamd_sparse *s, const double *d_arena, const double *d_Bs, int64_t ldb, double *d_Xs, int64_t ldx, int nrhs, int which, void *stream);
+int  cholamd_sparse_solve_nrhs_f32(cholamd_sparse *s, const float *d_arena32, const double *d_Bs, int64_t ldb, double *d_Xs, int64_t ldx, int nrhs, int which, void *stream);
+int  cholamd_plan_sparse_solve_host_nrhs(const cholamd_plan *p, const double *arena_host, const int *in_dofs, int n_in, const int *out_dofs, int n_out, int which,
+                                         const double *Bs, int64_t ldb, double *Xs, int64_t ldx, int nrhs);
+int  cholamd_plan_sparse_counts(const cholamd_plan *p, const int *in_dofs, int n_in, const int *out_dofs, int n_out, int64_t out[12]);
+int  cholamd_plan_sparse_lists(const cholamd_plan *p, const int *in_dofs, int n_in, const int *out_dofs, int n_out, int which, int64_t *steps, int64_t *items, int64_t *srcs);
+
 #ifdef __cplusplus
 }
 #endif
