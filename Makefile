@@ -16,7 +16,7 @@ $(OUT)/chol_kernels.o $(OUT)/chol_solve.o: KERNFLAGS := -mllvm -pragma-unroll-th
 HOST_OBJS := $(OUT)/chol_ingest.o $(OUT)/chol_symbolic.o $(OUT)/chol_schedule.o $(OUT)/chol_lists.o $(OUT)/chol_generate.o $(OUT)/chol_lowrank_host.o $(OUT)/chol_lists_sparse.o
 KERNEL_OBJS := $(OUT)/chol_kernels.o $(OUT)/chol_solve.o $(OUT)/chol_kernels_f32.o $(OUT)/chol_solve_nrhs.o $(OUT)/chol_factor_query.o $(OUT)/chol_selinv.o $(OUT)/chol_schur.o $(OUT)/chol_multiply.o $(OUT)/chol_multiply_nrhs.o $(OUT)/chol_solve_det.o $(OUT)/chol_lowrank.o $(OUT)/chol_values_grad.o $(OUT)/chol_pcg.o $(OUT)/chol_sparse.o
 # the C-ABI glue: one file per family of entry points over the internal header chol_device.h
-GLUE      := chol_api chol_api_schur chol_api_blas chol_api_lowrank chol_api_sparse
+GLUE      := chol_api chol_api_factor chol_api_solve chol_api_query chol_api_pcg chol_api_schur chol_api_blas chol_api_lowrank chol_api_sparse
 GLUE_HDRS := $(CSRC)/chol_device.h $(CSRC)/chol_devbuf.h $(CSRC)/chol_plan.h $(CSRC)/chol_kernels.h include/cholamd.h
 GLUE_OBJS := $(GLUE:%=$(OUT)/%.o)
 HIP_OBJS  := $(KERNEL_OBJS) $(GLUE_OBJS)

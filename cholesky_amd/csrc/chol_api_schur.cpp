@@ -1,5 +1,5 @@
 // C ABI glue of libcholamd, the Schur complement on the top levels of the tree: the partial factor, the gather of S, condense and expand for one
-// vector and for blocks, atomic or deterministic.  Compiled with hipcc like chol_api.cpp, whose sweep helpers it composes (chol_device.h).
+// vector and for blocks, atomic or deterministic.  Compiled with hipcc like chol_api.cpp; it composes the sweep helpers of chol_api_solve.cpp (chol_device.h).
 #include "chol_device.h"
 
 // ---------------------------------------------------------------------------------------------

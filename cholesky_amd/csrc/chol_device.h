@@ -75,6 +75,10 @@ struct schur_dev { dev_buf<chol_schur_desc> desc; int64_t n = -1; }; // n < 0: n
 // deterministic step lists (chol_sdet_lists: the whole tree's, or those of condense / expand cut at k kept levels) on the device; the steps stay on the
 // host: they are the launch sequence
 struct sdet_dev { dev_buf<chol_mul_item> item[2]; dev_buf<chol_mul_src> src[2]; std::vector<chol_sdet_step> step[2]; bool ready = false; };
+// kinds: 0 potrf (+ fused trsm), 1 trsm, 2 update, 3 program launch, 4 extend-add exchange (RCCL), 5 broadcasts of the distributed top levels
+#define CHOL_TIMING_KINDS 8
+#define CHOL_TK_EXCHANGE 4
+#define CHOL_TK_BCAST 5
 struct timed_launch { hipEvent_t a, b; int kind; };
 
 struct cholamd_device {
@@ -206,17 +210,34 @@ struct keep_restore { // keep_inverses for the chunks of one call, the caller's 
 // records the measurement behind the value.
 template <class TL> static constexpr int half_nrhs_min_block() { return sizeof(TL) == sizeof(double) ? 4 : 6; }
 
-#pragma GCC visibility push(hidden) // helpers that cross glue files, all defined in chol_api.cpp: none of them enters the library's dynamic symbol table
+#pragma GCC visibility push(hidden) // helpers that cross glue files, by the file that defines them: none of them enters the library's dynamic symbol table
+// chol_api.cpp
 hipEvent_t get_event(cholamd_device *d);
 int no_device_error();
 bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb);
+void free_solve_lists(cholamd_device *d);
+int upload_level(level_dev &l, const chol_level_work &w, bool with_tables = true);
+int clear_owned(cholamd_device *d, void *arena, size_t elem, hipStream_t st);
+int f32_range_ok(cholamd_device *d, hipStream_t st);
+int ensure_csr(cholamd_device *d);
+int ensure_refine(cholamd_device *d);
+// chol_api_factor.cpp
+int comm_matches(const cholamd_device *d, const cholamd_comm *c);
+int multi_sum_vec(cholamd_device *const *devs, cholamd_comm *const *comms, int n, void *const *streams, int64_t off, int64_t count);
+// chol_api_solve.cpp
 int build_solve(cholamd_device *d, int rank = 0, int world = 1);
 int upload_sdet(sdet_dev &q, const chol_sdet_lists &w);
+hipStream_t stream_of(void *const *streams, int g);
+int half_which_ok(int which, const char *what);
+int block_check(cholamd_device *d, bool with_arena, const void *arena, const double *B, int64_t ldb, const double *X, int64_t ldx, int nrhs, const char *what, const char *in,
+                const char *out);
 int nrhs_check(cholamd_device *d, const void *arena, const double *B, int64_t ldb, const double *X, int64_t ldx, int nrhs, const char *what, const char *in = "B", const char *out = "X");
-// (the templates: instantiated in chol_api.cpp for double and float)
+// (the templates: instantiated in chol_api_solve.cpp for double and float)
 template <class TL> int form_inverses(cholamd_device *d, const TL *d_arena, int lvl_lo, bool with_spans, hipStream_t st);
 template <class TL> int sweep_levels(cholamd_device *d, const TL *d_arena, sweep_rhs rhs, bool backward, int lvl_lo, int lvl_hi, int64_t *count, hipStream_t st);
 template <class TL> int sweep_steps(cholamd_device *d, const TL *d_arena, const sdet_dev &c, int q, sweep_rhs rhs, int64_t *counts, hipStream_t st);
+template <class TL> int solve_any(cholamd_device *d, const TL *d_arena, const double *d_b, double *d_x, int which, hipStream_t st);
+template <class TL> int solve_nrhs_any(cholamd_device *d, const TL *d_arena, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, int cols, bool half, int which, hipStream_t st);
 #pragma GCC visibility pop
 
 struct scoped_timer {

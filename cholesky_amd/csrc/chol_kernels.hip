@@ -2403,7 +2403,7 @@ __global__ __launch_bounds__(256) void k_trsm_big(double *__restrict__ base, con
 }
 
 // ------------------------------------------------------------------------------------------------
-// launchers (chol_kernels.h, called from chol_api.cpp)
+// launchers (chol_kernels.h, called from the glue: chol_api.cpp, chol_api_factor.cpp, chol_api_blas.cpp)
 // ------------------------------------------------------------------------------------------------
 int chol_launch_scatter(double *arena, const int64_t *dst, const double *val, int64_t nnz, hipStream_t st)
 {

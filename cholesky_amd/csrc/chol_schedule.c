@@ -2182,7 +2182,7 @@ int cholamd_plan_level_work_volume_opts(const cholamd_plan *p, int level, int me
  * sent, out[2] the tail, out[3] column-block pieces (0: replicated top levels, one all-reduce of the tail -- a ring moves
  * 2 (world - 1) / world of it each way).  Distributed top levels: a rank sends the column blocks it does not own of the top separators ON ITS
  * OWN ROOT PATH once, to their owners (rank 0: of every top separator -- it holds A's entries), and receives, for every block it owns, one copy
- * from each other rank under the block's separator and from rank 0 (chol_top_contributors; chol_api.cpp, exchange_owned). */
+ * from each other rank under the block's separator and from rank 0 (chol_top_contributors; chol_api_factor.cpp, exchange_owned). */
 int cholamd_plan_exchange_volume(const cholamd_plan *p, int rank, int world, int dist_top, int64_t out[4])
 {
   chol_sched_opts o;

@@ -12,7 +12,7 @@ build and upload).
 With NRHS the block form is timed too (multiply_half_nrhs both ways, multiply_nrhs), all in the same process: the single product (the unchanged k_multiply),
 NRHS single calls in a loop, the block call of NRHS columns on the default path, with every chunk forced onto the block kernel (option multiply_nrhs_min
 = 1) and forced column by column (= 33), a forced block chunk of 32 columns and one of 1 column; bytes of L per time for the 32-column chunk (one pass), and
-min = ceil(T_chunk(32 columns) / T_single), the threshold multiply_nrhs_min_block of chol_api.cpp takes at gen:60:8."""
+min = ceil(T_chunk(32 columns) / T_single), the threshold multiply_nrhs_min_block of chol_api_query.cpp takes at gen:60:8."""
 import os
 import statistics
 import sys

@@ -1,5 +1,5 @@
 """The three single-vector refinement entry points -- cholamd_solve_refine, cholamd_solve_refine_sharded and cholamd_solve_refine_multi -- run ONE loop
-(refine_loop, chol_api.cpp).  Pinned here through each door on an unpartitioned device object (the sharded door at world 1 returns before it reads
+(refine_loop, chol_api_solve.cpp).  Pinned here through each door on an unpartitioned device object (the sharded door at world 1 returns before it reads
 its communicator; the multi door takes a one-element device list), at n = 25 (one residual workgroup, every separator under one span) and n = 400.
 
 The solves underneath add with fp64 atomics: the doors are compared by residual and against the golden x, never bit for bit.  The residual kernel has no

@@ -33,8 +33,8 @@ BLOCKING_ALLOWED = {
     ("chol_api.cpp", "chol_dev_copy_in"): "dev_buf::upload at creation and first use: a blocking copy from pageable host memory",
     ("chol_api.cpp", "cholamd_device_destroy"): "destroy waits for the work in flight before it frees",
     ("chol_api.cpp", "cholamd_device_free_arena"): "a rank arena is unmapped only when the device is idle",
-    ("chol_api.cpp", "cholamd_device_program_trace"): "diagnostic: reads the job stamps back after synchronising the stream",
-    ("chol_api.cpp", "cholamd_factor_info"): "documented: called after the stream has been synchronised, reads two ints back",
+    ("chol_api_factor.cpp", "cholamd_device_program_trace"): "diagnostic: reads the job stamps back after synchronising the stream",
+    ("chol_api_factor.cpp", "cholamd_factor_info"): "documented: called after the stream has been synchronised, reads two ints back",
     ("chol_api.cpp", "f32_range_ok"): "the fp32 range verdict's refusal: the offending value read back for the error text, on the way to CHOLAMD_ERR_ARG",
     ("chol_api_blas.cpp", "debug_dump"): "cholamd_factor_debug: the arena read back for the dump files",
     ("chol_api_blas.cpp", "cholamd_factor_debug"): "cholamd_factor_debug: a failed pivot's info written where cholamd_factor_info reads it",
@@ -138,7 +138,8 @@ def test_the_scanner_sees_the_calls(scanned):
     assert by_kind.get("hipLaunchKernelGGL", 0) >= 100 and by_kind.get("hipMemcpyAsync", 0) >= 10 and by_kind.get("hipEventRecord", 0) >= 4, by_kind
     files = {e[0] for e in enq}
     for fn in ("chol_kernels.hip", "chol_solve.hip", "chol_kernels_f32.hip", "chol_solve_nrhs.hip", "chol_solve_det.hip", "chol_pcg.hip", "chol_selinv.hip",
-               "chol_multiply.hip", "chol_api.cpp", "chol_api_schur.cpp", "chol_api_lowrank.cpp", "chol_device.h"):
+               "chol_multiply.hip", "chol_api.cpp", "chol_api_factor.cpp", "chol_api_solve.cpp", "chol_api_query.cpp", "chol_api_pcg.cpp", "chol_api_schur.cpp",
+               "chol_api_blas.cpp", "chol_api_lowrank.cpp", "chol_device.h"):
         assert fn in files, fn
     assert all(e[2] for e in enq) and all(b[2] for b in blk)
 
