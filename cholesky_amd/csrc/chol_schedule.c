@@ -2296,6 +2296,60 @@ int cholamd_plan_level_mt_fill(const cholamd_plan *p, int level, int64_t out[4])
   return 0;
 }
 
+/* what the macro-tile kernels meet on one level's lists (include/cholamd.h names the counts).  The edge-tile predicate restates the bound check of
+ * update_mt_body (chol_kernels.hip) and k32_update_mt (chol_kernels_f32.hip): both tile 64 x 64 (MT, M32) over 16-deep chunks (MKB, M32_KB), and
+ * both get plan->arena as the arena's length in elements (chol_api_factor.cpp) */
+int cholamd_plan_level_mt_classes(const cholamd_plan *p, int level, int merge_targets, int mt_min_tiles, int f32, int rank, int world, int dist_top,
+                                  int64_t out[CHOLAMD_MT_CLASSES])
+{
+  enum { TILE = 64, CHUNK = 16, BATCH = 32 /* MT_SRC_BATCH, M32_SRC_BATCH */ };
+  chol_sched_opts o;
+  chol_sched_opts_default(&o);
+  o.program = 0;
+  o.merge_targets = merge_targets != 0;
+  o.dist_top = dist_top;
+  if (mt_min_tiles >= 0) o.mt_min_tiles = mt_min_tiles;
+  if (f32) { o.split_min = CHOL32_MAXN; o.split_nb = CHOL32_MAXN; o.fuse = 0; o.fuse_update_max = 0; o.trsm_group = CHOL32_TRSM_GROUP; } /* ensure_f32 (chol_api_factor.cpp) */
+  chol_level_work w;
+  int rc = chol_build_level_work(p, &o, level, rank, world, &w);
+  if (rc) return rc;
+  const int64_t arena_elems = p->arena;
+  memset(out, 0, CHOLAMD_MT_CLASSES * sizeof(int64_t));
+  out[CHOLAMD_MT_TASKS] = w.n_task_mt; out[CHOLAMD_MT_DMA_SLACK] = -1;
+  for (int i = 0; i < w.n_task_mt; i++) {
+    const chol_upd_task *t = &w.task_mt[i];
+    const int ns = t->src_end - t->src_begin;
+    const int full = t->mv == TILE && t->nv == TILE;
+    int ok = 1, late = 0, chunks = 0;
+    int64_t reach = -1; /* the furthest element the DMA of this tile's whole chunks touches */
+    for (int s = t->src_begin; s < t->src_end; s++) {
+      const chol_upd_src *sd = &w.src[s];
+      const int kf = (sd->k / CHUNK) * CHUNK;
+      if (kf > 0) { /* 64 rows of the last whole chunk's last column, both operands */
+        const int64_t ra = sd->a_off + t->ar + (TILE - 1) + (int64_t)(kf - 1) * sd->lda, rb = sd->b_off + t->br + (TILE - 1) + (int64_t)(kf - 1) * sd->ldb;
+        if (ra >= arena_elems || rb >= arena_elems) ok = 0;
+        if (ra > reach) reach = ra;
+        if (rb > reach) reach = rb;
+      }
+      chunks += kf > 0;
+      late |= kf > 0 && s - t->src_begin >= BATCH;
+      out[sd->k < CHUNK ? CHOLAMD_MT_K_SHORT : sd->k % CHUNK == 0 ? CHOLAMD_MT_K_CHUNKS : sd->k % CHUNK == 1 ? CHOLAMD_MT_K_CHUNKS_1 : CHOLAMD_MT_K_OTHER]++;
+      out[CHOLAMD_MT_ODD_ORIGIN] += ((sd->a_off + t->ar) | (sd->b_off + t->br)) & 1;
+    }
+    out[CHOLAMD_MT_FULL] += full;
+    if (!full) out[ok ? CHOLAMD_MT_EDGE_DMA : CHOLAMD_MT_EDGE_STAGED]++;
+    out[CHOLAMD_MT_LOWER] += t->lower != 0; out[CHOLAMD_MT_LOWER_AR] += t->lower && t->ar != 0; out[CHOLAMD_MT_LOWER_AR_CUT] += t->lower && t->ar % TILE != 0;
+    out[CHOLAMD_MT_MV1] += t->mv == 1; out[CHOLAMD_MT_NV1] += t->nv == 1;
+    if (ns > out[CHOLAMD_MT_MAX_SOURCES]) out[CHOLAMD_MT_MAX_SOURCES] = ns;
+    out[CHOLAMD_MT_SOURCES_32] += ns == BATCH; out[CHOLAMD_MT_SOURCES_33_63] += ns > BATCH && ns < 2 * BATCH; out[CHOLAMD_MT_SOURCES_64] += ns >= 2 * BATCH;
+    out[CHOLAMD_MT_LATE_CHUNKS] += late;
+    out[CHOLAMD_MT_EMPTY_RING] += (full || ok) && chunks == 0;
+    if (!full && ok && reach >= 0 && (out[CHOLAMD_MT_DMA_SLACK] < 0 || arena_elems - 1 - reach < out[CHOLAMD_MT_DMA_SLACK])) out[CHOLAMD_MT_DMA_SLACK] = arena_elems - 1 - reach;
+  }
+  chol_level_work_free(&w);
+  return 0;
+}
+
 int cholamd_plan_level_work_counts(const cholamd_plan *p, int level, int rank, int world, int out[4])
 {
   chol_level_work w;

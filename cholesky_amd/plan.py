@@ -289,6 +289,20 @@ class Plan:
         check(self.L.cholamd_plan_level_mt_fill(self.h, level, out.ctypes.data), "cholamd_plan_level_mt_fill")
         return tuple(int(v) for v in out)
 
+    MT_CLASSES = ("tasks", "full", "edge_dma", "edge_staged", "lower", "lower_ar", "mv1", "nv1", "max_sources", "sources_32", "sources_33_63",
+                  "sources_64", "k_short", "k_chunks", "k_chunks_1", "k_other", "odd_origin", "late_chunks", "lower_ar_cut", "empty_ring", "dma_slack")
+
+    def level_mt_classes(self, level, merge_targets=1, mt_min_tiles=-1, f32=False, rank=0, world=1, dist_top=2):
+        """What the macro-tile update kernels meet on one level's lists (cholamd_plan_level_mt_classes): a dict of counts by MT_CLASSES -- tasks,
+        full 64 x 64 tiles, edge tiles served by LDS-DMA / staged through registers, `lower` tiles (and those with ar != 0), tiles of one valid
+        row / column, the most sources of a task and the tasks with 32, 33 .. 63 and >= 64, sources by depth (k < 16, whole chunks, one column
+        over, other), sources of odd operand origin, tasks whose ring issues chunks in a second descriptor batch, `lower` tiles with ar % 64 != 0 (cut at a column block),
+        DMA-served tiles with no whole chunk, the least distance between an edge tile's furthest DMA element and the arena's end (-1: none)."""
+        out = np.zeros(len(self.MT_CLASSES), dtype=np.int64)
+        check(self.L.cholamd_plan_level_mt_classes(self.h, level, int(merge_targets), int(mt_min_tiles), int(bool(f32)), rank, world, dist_top,
+                                                   out.ctypes.data), "cholamd_plan_level_mt_classes")
+        return dict(zip(self.MT_CLASSES, (int(v) for v in out)))
+
     def program_check(self, follow=True, workers=64):
         """Host-side self-check of the one-launch program (raises CholamdError on a dead-lock or a mismatch)."""
         check(self.L.cholamd_plan_program_check(self.h, int(follow), int(workers)), "cholamd_plan_program_check")

@@ -209,6 +209,35 @@ int cholamd_plan_level_work_volume_opts(const cholamd_plan *p, int level, int me
 /* how full the 64 x 64 macro-tile update tasks of a level are (single GPU): out = { tasks, tasks with all 64 x 64 elements valid,
  * sum of valid elements x depth, sum of tile elements x depth } */
 int cholamd_plan_level_mt_fill(const cholamd_plan *p, int level, int64_t out[4]);
+/* what the macro-tile update kernels (k_update_mt, k32_update_mt) meet on a level's lists for (rank, world), built as the device builds them
+ * under options merge_targets, mt_min_tiles (< 0: default) and dist_top; f32 != 0: the fp32 schedule (pivot blocks of at most 128 columns).
+ * out[] is indexed by the constants below (Plan.MT_CLASSES names them in the same order); sources are counted once per task that reads them */
+enum {
+  CHOLAMD_MT_TASKS,          /* macro-tile tasks */
+  CHOLAMD_MT_FULL,           /* ... with mv == nv == 64 */
+  CHOLAMD_MT_EDGE_DMA,       /* edge tasks the kernel serves by LDS-DMA (its bound check against the arena's length holds) */
+  CHOLAMD_MT_EDGE_STAGED,    /* edge tasks it stages through registers (the check fails) */
+  CHOLAMD_MT_LOWER,          /* `lower` tasks */
+  CHOLAMD_MT_LOWER_AR,       /* `lower` tasks with ar != 0 */
+  CHOLAMD_MT_MV1,            /* tasks with mv == 1 */
+  CHOLAMD_MT_NV1,            /* tasks with nv == 1 */
+  CHOLAMD_MT_MAX_SOURCES,    /* most sources of one task */
+  CHOLAMD_MT_SOURCES_32,     /* tasks with exactly 32 sources */
+  CHOLAMD_MT_SOURCES_33_63,  /* ... with 33 .. 63 */
+  CHOLAMD_MT_SOURCES_64,     /* ... with 64 or more */
+  CHOLAMD_MT_K_SHORT,        /* sources with k < 16 */
+  CHOLAMD_MT_K_CHUNKS,       /* k >= 16 and k % 16 == 0 */
+  CHOLAMD_MT_K_CHUNKS_1,     /* k >= 16 and k % 16 == 1 */
+  CHOLAMD_MT_K_OTHER,        /* other k */
+  CHOLAMD_MT_ODD_ORIGIN,     /* sources with an odd operand origin (a_off + ar or b_off + br) */
+  CHOLAMD_MT_LATE_CHUNKS,    /* tasks of more than 32 sources with a source of k >= 16 behind the 32nd (the ring issues chunks in a later descriptor batch) */
+  CHOLAMD_MT_LOWER_AR_CUT,   /* `lower` tasks with ar % 64 != 0 (a SYRK target cut at a column block of the distributed top) */
+  CHOLAMD_MT_EMPTY_RING,     /* DMA-served tasks (full or edge) all of whose sources have k < 16 */
+  CHOLAMD_MT_DMA_SLACK,      /* the least distance, over the DMA-served edge tasks, between the furthest element their DMA touches and the arena's last element (-1: none) */
+  CHOLAMD_MT_CLASSES
+};
+int cholamd_plan_level_mt_classes(const cholamd_plan *p, int level, int merge_targets, int mt_min_tiles, int f32, int rank, int world, int dist_top,
+                                  int64_t out[CHOLAMD_MT_CLASSES]);
 /* volumes of the same lists with the top levels replicated (dist_top = 0) or distributed by column blocks (1; 2 = automatic):
  * POTRF columns, TRSM elements, update volume (target elements x source depth), broadcast entries, broadcast doubles, checksum
  * of the broadcast list (the same on every rank) */

@@ -1,4 +1,4 @@
-/* Leak check of libcholamd's HOST code (ingest, symbolic phase, schedules, program builder + self-check, generator) without an
+/* Leak check of libcholamd's HOST code (ingest, symbolic phase, schedules and the views of their lists, program builder + self-check, generator) without an
  * interpreter in the process: `make asan` builds this against the sanitizer build and runs it with LeakSanitizer on and NO
  * suppressions that could hide the library's own allocations.  No GPU call is made (device entry points need a HIP device). */
 #include <stdio.h>
@@ -16,6 +16,12 @@ static int run_plan(cholamd_plan *p)
         if (cholamd_plan_level_work_counts(p, lvl, r, world, out4)) return 1;
         if (cholamd_plan_level_work_volume(p, lvl, r, world, 1, vol)) return 1;
       }
+  int64_t mt[CHOLAMD_MT_CLASSES];
+  for (int world = 1; world <= 2 && (world == 1 || L > 3); world *= 2)
+    for (int r = 0; r < world; r++)
+      for (int lvl = 0; lvl < L; lvl++)
+        for (int v = 0; v < 8; v++) /* merge_targets x macro tiles forced / default x fp64 / fp32 schedule */
+          if (cholamd_plan_level_mt_classes(p, lvl, v & 1, v & 2 ? 1 : -1, (v >> 2) & 1, r, world, 1, mt)) return 1;
   for (int workers = 4; workers <= 256; workers *= 8) (void)cholamd_plan_program_check(p, 1, workers); /* may refuse large problems: also a path to check */
   (void)cholamd_plan_program_check(p, 0, 16);
   (void)cholamd_plan_program_counts(p, 1, out6);

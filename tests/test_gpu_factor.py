@@ -283,6 +283,8 @@ LAUNCH_PATHS = [
     {"cells": 0},                                      # extend-add by the reference's cluster tiles instead of grid cells (no followers)
     {"program": 0, "cells": 0},
     {"solve_reference_shape": 1},                      # the per-call (deterministic) solve kernels
+    {"program": 0, "mt_min_tiles": 1, "merge_targets": 0}, # every target of more than 16 rows or columns on 64x64 macro tiles (k_update_mt), unmerged
+    {"program": 0, "mt_min_tiles": 1, "merge_targets": 1}, # ... with neighbouring targets merged
 ]
 
 

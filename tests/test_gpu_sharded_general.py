@@ -288,14 +288,35 @@ def test_gathered_factor_serves_rank_zero(name, world, f32, spd):
 # ------------------------------------------------------------------------------------------------
 # e. kernel-path switches under the distributed top
 # ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("opts", [{"trsm_wt_min": 1}, {"fuse": 0}, {"super_blocks": 1}], ids=_ids)
+def _assert_macro_tiles(S, world, f32):
+    """Every rank's lists hold macro-tile tasks under mt_min_tiles = 1 (Plan.level_mt_classes, summed over the levels)."""
+    for r in range(world):
+        n = sum(S.plan.level_mt_classes(lvl, 1, 1, f32, r, world, 1)["tasks"] for lvl in range(S.plan.levels))
+        assert n > 0, (world, r, f32)
+
+
+@pytest.mark.parametrize("opts", [{"trsm_wt_min": 1}, {"fuse": 0}, {"super_blocks": 1}, {"mt_min_tiles": 1}], ids=_ids)
 def test_kernel_path_switches_under_the_distributed_top(opts, spd):
-    """tree_top at world 4, fp64: the owners' strips through the throughput TRSM, POTRF and TRSM as launches of their own, and rank-nb trailing
-    updates instead of super-blocks -- each with the column blocks of the top spread over the ranks."""
+    """tree_top at world 4, fp64: the owners' strips through the throughput TRSM, POTRF and TRSM as launches of their own, rank-nb trailing
+    updates instead of super-blocks, and the updates on 64 x 64 macro tiles -- each with the column blocks of the top spread over the ranks."""
     S = spd("tree_top")
+    if "mt_min_tiles" in opts:
+        _assert_macro_tiles(S, 4, False)
     with _ranks(S, 4, 1, False, opts) as (devs, arenas):
         _factor(devs, arenas, False)
         _check_factor(S, devs, arenas, False, f"tree_top w4 dist_top=1 fp64 {_ids(opts)}")
+
+
+@pytest.mark.parametrize("f32", PRECISIONS, ids=PIDS)
+@pytest.mark.parametrize("world", [2, 4])
+def test_macro_tiles_under_the_distributed_top(world, f32, spd):
+    """tree_top with mt_min_tiles = 1 at worlds 2 and 4, fp64 and fp32: SYRK targets cut at the top separators' column blocks reach the macro-tile
+    kernels with an origin of their own (ar, br no multiples of 64; tests/test_update_mt_host.py counts them)."""
+    S = spd("tree_top")
+    _assert_macro_tiles(S, world, f32)
+    with _ranks(S, world, 1, f32, {"mt_min_tiles": 1}) as (devs, arenas):
+        _factor(devs, arenas, f32)
+        _check_factor(S, devs, arenas, f32, f"tree_top w{world} dist_top=1 {'fp32' if f32 else 'fp64'} mt_min_tiles=1")
 
 
 # ------------------------------------------------------------------------------------------------

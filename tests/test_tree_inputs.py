@@ -7,7 +7,7 @@ import pytest
 import spd_inputs as si
 import tree_inputs as ti
 
-ALL = ti.NAMED + ti.SINGLE + ti.TOP
+ALL = ti.NAMED + ti.SINGLE + ti.TOP + ti.DEEP
 
 
 @pytest.fixture(scope="module")
@@ -16,7 +16,7 @@ def spd(tmp_path_factory):
 
 
 def test_named_trees_are_the_suites_inputs():
-    assert si.NAMES[-len(ti.NAMED):] == ti.NAMED and not set(ti.SINGLE + ti.TOP) & set(si.NAMES)
+    assert si.NAMES[-len(ti.NAMED):] == ti.NAMED and not set(ti.SINGLE + ti.TOP + ti.DEEP) & set(si.NAMES)
     assert si.NAMES.index("g7_ragged") == 9             # the inputs before the trees keep their places, and so their seeds
 
 
@@ -188,4 +188,48 @@ def test_a_dropped_tile_contribution_fails_the_measures(spd):
     assert S.row_error(S.Ld) == 0.0
     row, rec = S.row_error(L), S.reconstruction(L)
     print(f"dropped tile: row_error = {row:.3g} (tol {S.tol_factor():.3g}), reconstruction = {rec:.3g} (tol {S.tol_reconstruction():.3g})")
+    assert row > 1e3 * S.tol_factor() and rec > 1e3 * S.tol_reconstruction()
+
+
+def test_tree_deep_is_seven_levels_of_dense_couplings(spd):
+    """What tree_deep is for: 127 separators on seven levels (the separator file's level field is still one digit), every one coupled to every
+    ancestor, three in four leaves to all 80 rows of the root and every fourth to its first 48 only -- so the root's tile pairs collect 64 and 48
+    sources from the leaf level (tests/test_update_mt_host.py counts the lists)."""
+    S = spd("tree_deep")
+    T, P = S.tree, S.plan
+    assert (P.levels, P.nsep, S.n) == (7, 127, 1634) and T.heap_sizes[:3] == [80, 40, 33]
+    assert open(S.ord).readline().split() == ["7", "127"]
+    assert all(T.kinds[c >> j, c] != "none" for c in range(2, 128) for j in range(1, c.bit_length()))
+    rows = [T.kinds[1, c] for c in range(64, 128)]
+    assert rows.count(("rows", 48)) == 16 and rows.count(("random", 0.5)) == 48
+    root = P.sep_offsets[P.tree[0] - 1]
+    for c in (64, 67):
+        lo, w = int(P.sep_offsets[P.tree[c - 1] - 1]), T.heap_sizes[c - 1]
+        panel = S.PAP[root:root + 80, lo:lo + w]
+        assert panel[:48].any() and panel[48:].any() == (c % 4 != 3)
+
+
+def test_a_dropped_tile_contribution_into_the_root_of_tree_deep_fails_the_measures(spd):
+    """The argument of test_a_dropped_tile_contribution_fails_the_measures for tree_deep's root, which collects a contribution from each of its 126
+    descendants: the root's pivot recomputed from a Schur complement that lacks ONE 16 x 16 product of ONE leaf's panel (the last 16 columns of
+    heap index 64, 16 rows of the root) exceeds the fp64 tolerances on row error and reconstruction by more than 1e3 -- a macro-tile kernel that
+    lost one source at the restart between two descriptor batches could not pass."""
+    S = spd("tree_deep")
+    P = S.plan
+    root = int(P.tree[0])
+    off, m = int(P.sep_offsets[root - 1]), int(P.sep_sizes[root - 1])
+    leaf = int(P.tree[63])
+    lo, w = int(P.sep_offsets[leaf - 1]), int(P.sep_sizes[leaf - 1])
+    assert m == 80 and 16 <= w <= 21
+    panel = S.Ld[off:off + m, lo:lo + w]
+    I = next(t for t in range(m // 16) if panel[16 * t:16 * t + 16, w - 16:].all())
+    X = panel[16 * I:16 * I + 16, w - 16:]
+    D = S.Ld[off:off + m, off:off + m]
+    C = D @ D.T
+    C[16 * I:16 * I + 16, 16 * I:16 * I + 16] += X @ X.T
+    L = S.Ld.copy()
+    L[off:off + m, off:off + m] = np.linalg.cholesky(C)
+    row, rec = S.row_error(L), S.reconstruction(L)
+    print(f"dropped tile, tree_deep: row_error = {row:.3g} (tol {S.tol_factor():.3g}), reconstruction = {rec:.3g} (tol {S.tol_reconstruction():.3g}); "
+          f"fp32 tol {S.tol_factor(si.U32):.3g}")
     assert row > 1e3 * S.tol_factor() and rec > 1e3 * S.tol_reconstruction()

@@ -4,7 +4,7 @@ Every other input of the suite is a grid: its separators are planes of a box, so
 its grandparent always come in the same ratios.  A tree input names the size of every separator, so a pivot of exactly 145, 177, 193, 257 or 273
 columns can be a leaf, a middle separator or a root.  A spec is a dict:
 
-  levels     1 .. 6 (the separator file holds one digit)
+  levels     1 .. 7 (the separator file holds one digit)
   sizes      one size >= 1 per node of the complete binary tree in heap order (root first; label of heap index h = nsep - (h - 1))
   tile       interval-0 cluster tiles of about `tile` dofs as the generator cuts them, or "random": a seeded strictly increasing boundary list with
              1-dof tiles that is not aligned to 16.  A separator at tree level l has the intervals 0 .. max(0, levels - 2 - l), later intervals
@@ -12,9 +12,9 @@ columns can be a leaf, a middle separator or a root.  A spec is a dict:
   leaf       internal pattern of the leaves, cycled in heap order: ("band", w) | "dense" | ("random", p) | "arrow" (a chain plus 16 dense last rows)
   inner      internal pattern of the other separators, cycled: "dense" | ("random", p)
   coupling   pattern of the block (ancestor r, separator c), cycled over the pairs in the order c = 2, 3, ...; r = parent, grandparent, ...:
-             "dense" | ("random", p) | "tiles" | "none".  "tiles": only a seeded subset of r's 16-row tiles is touched, all columns of c, and the
-             two children of a node take disjoint subsets (row compaction, block_tile_map).  "none" applies above the parent only; for the parent
-             the next kind of the cycle is taken
+             "dense" | ("random", p) | "tiles" | ("rows", m) | "none".  ("rows", m): the first m rows of r, all columns of c.  "tiles": only a
+             seeded subset of r's 16-row tiles is touched, all columns of c, and the two children of a node take disjoint subsets (row
+             compaction, block_tile_map).  "none" applies above the parent only; for the parent the next kind of the cycle is taken
   seed       of the permutation, the boundaries and the patterns (the values have the seed of spd_inputs.SPD)
 
 An entry couples a separator with itself or with an ancestor only, so the ordering drops nothing (plan.dropped == 0).  `build()` writes the separator
@@ -27,6 +27,24 @@ import numpy as np
 
 SWEEP_SIZES = [1, 15, 16, 17, 63, 64, 65, 127, 128, 129, 143, 144, 145, 159, 160, 161, 175, 176, 177, 191, 192, 193, 255, 256, 257, 271, 272, 273,
                287, 288, 289, 511, 512, 513]
+
+def _deep_sizes():
+    """tree_deep: 80, 40, 33 on the top two levels, 60 separators of 3 .. 7 columns below them and 64 leaves of 16 .. 21 (n = 1634)."""
+    rng = np.random.default_rng(3)
+    return [80, 40, 33] + [int(v) for v in rng.integers(3, 8, 60)] + [int(v) for v in rng.integers(16, 22, 64)]
+
+
+def _deep_coupling():
+    """tree_deep: dense, dense, ("random", 0.5) cycled over the pairs (so every separator reaches every ancestor), but every fourth leaf touches
+    the first 48 rows of the root only: the root's tile pairs inside those rows collect a source from each of the 64 leaves, the others from 48."""
+    cycle, out = ["dense", "dense", ("random", 0.5)], []
+    for c in range(2, 128):
+        r = c // 2
+        while r >= 1:
+            out.append(("rows", 48) if c >= 64 and c % 4 == 3 and r == 1 else cycle[len(out) % 3])
+            r //= 2
+    return out
+
 
 # the named trees: the first four join spd_inputs.INPUTS, the others are single-purpose
 TREES = {
@@ -48,9 +66,13 @@ TREES = {
     "tree_top": dict(levels=3, sizes=[433, 289, 1, 65, 17, 33, 129], tile="random",
                      leaf=["dense", ("band", 17), "arrow", ("random", 0.3)], inner=["dense", ("random", 0.5)],
                      coupling=["tiles", "dense", ("random", 0.3)], seed=17),
+    # seven levels with dense couplings to every ancestor: a 64 x 64 target tile of the upper separators collects a source from each descendant, so
+    # the macro-tile update kernels read their source descriptors in more than one batch of 32 (tests/test_update_mt_host.py counts them)
+    "tree_deep": dict(levels=7, sizes=_deep_sizes(), tile=16, leaf=["dense", ("band", 5)], inner=["dense"], coupling=_deep_coupling(), seed=80),
 }
 NAMED = ["tree_over", "tree_at", "tree_skew", "tree_tiny"]
 SINGLE = ["tree_single", "tree_two"]
+DEEP = ["tree_deep"]                                     # the macro-tile update tests' own input (tests/test_gpu_update_mt.py)
 TOP = ["tree_top"]                                       # the multi-rank tests' own input (tests/test_gpu_sharded_general.py)
 WITH_TILES = ["tree_over", "tree_at", "tree_skew"]       # "tiles" couplings above the parent with more than one 16-row tile to choose from
 
@@ -118,7 +140,7 @@ class Tree:
     def __init__(self, spec):
         levels, sizes = spec["levels"], list(spec["sizes"])
         ns = (1 << levels) - 1
-        assert 1 <= levels <= 6 and len(sizes) == ns and min(sizes) >= 1
+        assert 1 <= levels <= 7 and len(sizes) == ns and min(sizes) >= 1
         rng = np.random.default_rng(spec["seed"])
         self.levels, self.nsep, self.n = levels, ns, int(sum(sizes))
         self.heap_sizes = sizes
@@ -177,6 +199,9 @@ class Tree:
                     keep = np.zeros((mr, mc), dtype=bool)
                     keep[np.isin(np.arange(mr) // 16, mine), :] = True
                     self.untouched_tiles += nt - len(mine)
+                elif kind[0] == "rows":
+                    keep = np.zeros((mr, mc), dtype=bool)
+                    keep[:kind[1], :] = True
                 else:
                     assert kind[0] == "random", kind
                     keep = rng.random((mr, mc)) < kind[1]
